@@ -21,6 +21,8 @@ Output (rank 0, stdout): the compact headline object (< 4 KB: metric, value, roo
 scalars lifted from the extra workloads) is printed as soon as it is known, the extra workloads follow as ONE line
 {"extra": ...} (also written to bench_extra.json), and the compact headline -- now with the extras' scalars -- is
 printed again as the LAST line.  README.md ("Reading the bench line") explains every field; no prose travels in the line.
+`--dump-outputs DIR` also writes what the last timed step computed as DIR/*.npy (dump_outputs); the synthetic inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -78,7 +80,15 @@ def parse():
     ap.add_argument("--cpu-sample-genomes", type=int, default=0, help="0 = 1024 (SURVEY 8d: >= 1k genomes)")
     ap.add_argument("--cpu-sample-sketches", type=int, default=8000)
     ap.add_argument("--extra-json", default=os.path.join(ROOT, "bench_extra.json"), help="where the full extras object is also written")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned -- the forest's edge.mst records, every sketch's "
+                         "size and a fixed sample of the sketch rows -- as DIR/<name>.npy (float64), for comparing two builds")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.only:
+        ap.error("--dump-outputs writes the headline path's outputs; --only runs an extra workload instead")
+    return args
 
 
 def respawn_under_torchrun(args):
@@ -1019,6 +1029,33 @@ def emit(obj):
     print(json.dumps(sanitize(obj)), flush=True)
 
 
+DUMP_SAMPLE_ROWS = 1024          # sketch rows written by --dump-outputs, drawn with a fixed seed
+DUMP_SAMPLE_BYTES = 48 << 20     # ... and at most this many bytes of them
+
+
+def dump_outputs(dirname, pipe):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files (every value exact in float64):
+    the forest (pipe.last_mst, edge.mst records: mst_pre_node, mst_suf_node, mst_dist), every genome's sketch size
+    (sketch_len) and the sketch rows of a seeded sample of genomes (sketch_sample_rows; their hashes concatenated in row
+    order, split into the high and low 32 bits: sketch_sample_hash_hi / _lo)."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    mst, sk = pipe.last_mst, pipe.last_sketches
+    start = sk.start.cpu().numpy().astype(np.int64)
+    lens = sk.len.cpu().numpy().astype(np.int64)
+    rows = np.sort(np.random.default_rng(0).choice(sk.n, size=min(sk.n, DUMP_SAMPLE_ROWS), replace=False))
+    rows = rows[np.cumsum(lens[rows]) * 16 <= DUMP_SAMPLE_BYTES]
+    np_dt = np.uint64 if sk.width == 8 else np.uint32
+    parts = [sk.hashes[int(start[r]):int(start[r] + lens[r])] for r in rows]
+    hashes = (torch.cat(parts).cpu().numpy().view(np_dt) if parts else np.zeros(0, dtype=np_dt)).astype(np.uint64)
+    out = {"mst_pre_node": mst["preNode"], "mst_suf_node": mst["sufNode"], "mst_dist": mst["dist"], "sketch_len": lens,
+           "sketch_sample_rows": rows, "sketch_sample_hash_hi": hashes >> np.uint64(32),
+           "sketch_sample_hash_lo": hashes & np.uint64(0xFFFFFFFF)}
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1137,6 +1174,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=ctx.device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, pipe)
 
     pairs = n_total * (n_total - 1) // 2
     bases_total = float(n_total) * length

@@ -12,9 +12,11 @@ Two kinds of fixtures, labelled in MANIFEST.json:
 """
 import ctypes as C
 import gzip
+import hashlib
 import json
 import os
 import sys
+import tempfile
 
 import numpy as np
 
@@ -49,6 +51,64 @@ def write_fasta_inputs():
     return sorted(list(files) + ["plain.fa.gz"])
 
 
+def _kseq_dump(ref, path):
+    need = ref.ref_kseq_dump(path.encode(), None, 0)
+    if need < 0:
+        return None
+    buf = C.create_string_buffer(max(need, 1))
+    ref.ref_kseq_dump(path.encode(), buf, need)
+    return buf.raw[:need]
+
+
+def write_kseq_random(ref):
+    """kseq_random.npz: 20 random FASTA texts (headers of odd characters, CR/LF, blank lines, empty records) and one gzip
+    member of five long records, with what the reference's kseq reads from each (the gzip layouts: SHA-256 and length of
+    the dump; -1 where kseq reports an error)."""
+    rng = np.random.default_rng(9)
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for t in range(20):
+            parts = []
+            for r in range(int(rng.integers(0, 5))):
+                hdr = ">" + "".join(rng.choice(list("abcXYZ_ \t|.:"), size=int(rng.integers(0, 20))))
+                eol = "\r\n" if rng.random() < 0.3 else "\n"
+                parts.append(hdr + eol)
+                for _ in range(int(rng.integers(0, 4))):
+                    parts.append("".join(rng.choice(list("ACGTNacgt"), size=int(rng.integers(0, 90)))) + eol)
+                    if rng.random() < 0.2:
+                        parts.append(eol)
+            text = "".join(parts).encode()
+            p = os.path.join(tmp, f"r{t}.fa")
+            open(p, "wb").write(text)
+            want = _kseq_dump(ref, p)
+            out[f"rand{t}_in"] = np.frombuffer(text, dtype=np.uint8)
+            out[f"rand{t}_want"] = np.frombuffer(want if want is not None else b"", dtype=np.uint8)
+            out[f"rand{t}_ok"] = np.array(want is not None)
+        body = "".join(">rec%d some text\n" % r + "\n".join("".join(rng.choice(list("ACGTNacgt"), size=70)) for _ in range(400)) + "\n"
+                       for r in range(5)).encode()
+        one = gzip.compress(body, 6, mtime=0)
+        out["gz_one"] = np.frombuffer(one, dtype=np.uint8)
+        # the layouts the test builds from the stored member: one member, two members, many small members (bgzip style),
+        # a file cut short, bytes behind the last member, an empty member
+        cases = {
+            "one.fa.gz": one,
+            "two.fa.gz": gzip.compress(body[:70_000], 6) + gzip.compress(body[70_000:], 1),
+            "many.fa.gz": b"".join(gzip.compress(body[i:i + 9_000], 4) for i in range(0, len(body), 9_000)),
+            "cut.fa.gz": one[:-1500],
+            "trail.fa.gz": one + b"trailing bytes that are no gzip member",
+            "hole.fa.gz": gzip.compress(body[:50_000], 6) + gzip.compress(b"", 6) + gzip.compress(body[50_000:], 6),
+        }
+        for name, data in cases.items():
+            p = os.path.join(tmp, name)
+            open(p, "wb").write(data)
+            want = _kseq_dump(ref, p)
+            key = name.split(".")[0]
+            out[f"gz_{key}_len"] = np.array(-1 if want is None else len(want), dtype=np.int64)
+            out[f"gz_{key}_sha256"] = np.array(hashlib.sha256(want or b"").hexdigest())
+    np.savez_compressed(os.path.join(HERE, "kseq_random.npz"), **out)
+    return {"kind": "reference", "source": "kseq.h via oracle/ref_harness.cpp on 20 random FASTA texts and 6 gzip layouts"}
+
+
 def main():
     manifest = {}
     names = write_fasta_inputs()
@@ -56,6 +116,7 @@ def main():
         raise SystemExit("oracle/_ref/libref_harness.so missing: run `make -C oracle` where /root/reference exists")
     ref = C.CDLL(REF)
     ref.ref_kseq_dump.restype = C.c_long
+    manifest["kseq_random.npz"] = write_kseq_random(ref)
     for n in names:
         p = os.path.join(HERE, "fasta", n).encode()
         need = ref.ref_kseq_dump(p, None, 0)

@@ -53,3 +53,45 @@ def test_north_star_genomes_do_not_depend_on_the_rank_count():
         parts = [bench.north_star_descs(api, "minhash", r * n_local, (r + 1) * n_local) for r in range(world)]
         assert np.array_equal(np.concatenate(parts), whole[: n_local * world])
     assert not np.array_equal(bench.north_star_descs(api, "kssd", 0, 10), whole[:10])
+
+
+def test_dump_outputs_writes_the_last_step_exactly(tmp_path):
+    """--dump-outputs, host logic only: the forest and the sketches of a stand-in pipeline come back from the float64 .npy
+    files bit for bit (64-bit hashes as two 32-bit halves), the sampled rows are the same from run to run, and the
+    sample stays inside its byte budget"""
+    import types
+    import numpy as np
+    import bench
+    from rabbittclust_amd import api
+    rng = np.random.default_rng(3)
+    for width, n in ((8, 3000), (4, 50)):
+        dt = np.uint64 if width == 8 else np.uint32
+        sketches = [np.sort(rng.integers(0, np.iinfo(dt).max, size=int(rng.integers(0, 40)), dtype=dt, endpoint=True))
+                    for _ in range(n)]
+        mst = np.zeros(n - 1, dtype=api.EDGE_DT)
+        mst["preNode"], mst["sufNode"] = rng.integers(0, n, size=n - 1), rng.integers(0, n, size=n - 1)
+        mst["dist"] = rng.random(n - 1) / 3
+        pipe = types.SimpleNamespace(last_mst=mst, last_sketches=api.SketchSet.from_host(sketches, "cpu", width=width))
+        outs = []
+        for run in range(2):
+            d = tmp_path / f"w{width}_{run}"
+            bench.dump_outputs(str(d), pipe)
+            got = {f.stem: np.load(f) for f in d.glob("*.npy")}
+            assert all(a.dtype == np.float64 for a in got.values())
+            outs.append(got)
+        a, b = outs
+        assert set(a) == {"mst_pre_node", "mst_suf_node", "mst_dist", "sketch_len", "sketch_sample_rows",
+                          "sketch_sample_hash_hi", "sketch_sample_hash_lo"}
+        assert all(np.array_equal(a[k], b[k]) for k in a)
+        assert np.array_equal(a["mst_pre_node"], mst["preNode"]) and np.array_equal(a["mst_suf_node"], mst["sufNode"])
+        assert np.array_equal(a["mst_dist"], mst["dist"])
+        assert np.array_equal(a["sketch_len"], [len(s) for s in sketches])
+        rows = a["sketch_sample_rows"].astype(np.int64)
+        assert len(rows) == min(n, bench.DUMP_SAMPLE_ROWS) and np.all(np.diff(rows) > 0)
+        h = a["sketch_sample_hash_hi"].astype(np.uint64) << np.uint64(32) | a["sketch_sample_hash_lo"].astype(np.uint64)
+        assert np.array_equal(h, np.concatenate([sketches[r] for r in rows]).astype(np.uint64))
+    big = types.SimpleNamespace(last_mst=np.zeros(0, dtype=api.EDGE_DT),
+                                last_sketches=api.SketchSet.from_host([np.arange(40_000, dtype=np.uint64)] * 200, "cpu"))
+    bench.dump_outputs(str(tmp_path / "big"), big)
+    rows = np.load(tmp_path / "big" / "sketch_sample_rows.npy")
+    assert 0 < len(rows) < 200 and len(rows) * 40_000 * 16 <= bench.DUMP_SAMPLE_BYTES

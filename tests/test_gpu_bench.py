@@ -126,3 +126,37 @@ def test_bench_strong_scaling_one_rank_small(tmp_path):
     assert k.returncode == 0, k.stderr[-2000:]
     kl, _, _ = check_lines(k.stdout)
     assert kl["dtype"] == "u32" and kl["roofline"]["kernel"] == "sketch_kssd_packed_kernel" and kl["mst_edges"] > 500
+
+
+def test_bench_dump_outputs_are_the_timed_steps_and_repeat(oracle, tmp_path):
+    """--dump-outputs on a small one-GPU run: the forest the line reports, sampled sketch rows equal to the CPU oracle's
+    sketches of the same synthetic genomes, and the same files from a second run with the same arguments"""
+    import numpy as np
+    from rabbittclust_amd import api
+    n, L = 200, 100_000
+    args = ["--steps", "2", "--warmup", "1", "--genomes", str(n), "--length", str(L), "--no-cpu-baseline", "--no-extra",
+            "--extra-json", str(tmp_path / "x.json")]
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line, _, _ = check_lines(r.stdout)
+        assert line["steps"] == 2 and line["config"]["genomes_total"] == n
+        got = {f.stem: np.load(f) for f in d.glob("*.npy")}
+        assert got and all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+        runs.append((line, got))
+    (line, a), (_, b) = runs
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert len(a["mst_dist"]) == line["mst_edges"] and n - int(np.count_nonzero(a["mst_dist"] <= 0.05)) == line["clusters"]
+    assert np.array_equal(a["sketch_len"], np.full(n, 1000))
+    rows = a["sketch_sample_rows"].astype(np.int64)
+    assert len(rows) == n
+    h = (a["sketch_sample_hash_hi"].astype(np.uint64) << np.uint64(32)) | a["sketch_sample_hash_lo"].astype(np.uint64)
+    desc = api.synth_family_descs(n // 10, 10, global_seed=42)
+    off = np.array([0, L], dtype=np.uint64)
+    for g in (0, 1, 57, n - 1):
+        d = desc[g]
+        seq = oracle.synth_genome(int(d["fam_seed"]), int(d["mut_seed"]), int(d["mut_thr"]), L, int(d["n_every"]))
+        assert np.array_equal(h[g * 1000:(g + 1) * 1000], oracle.sketch_minhash_batch(seq, off, 21, 1000)[0]), g
