@@ -177,7 +177,8 @@ int rtc_pair_mash_dev(rtc_ctx* ctx, const void* d_hashes, int width, const uint6
 typedef struct { uint32_t i, j, common; } rtc_cedge; /* i > j */
 /* Scans the common matrix produced above and appends every pair the reference would turn into
  * an EdgeInfo: j < i, common > 0, both sketches non-empty, max(|A|,|B|) <= radio*min(|A|,|B|)
- * (src/MST.cpp:1468-1487; radio = (int)(2*exp(threshold*(k-1))-1), :1292).  d_count is a u64
+ * (src/MST.cpp:1468-1487; radio = floor(2*exp(threshold*(k-1))-1), :1292, saturated at INT32_MAX), the
+ * product taken exactly in 64 bits (the reference's int product wraps: DESIGN 5).  d_count is a u64
  * counter the caller zeroes; edges beyond `cap` are counted but not stored. */
 int rtc_extract_edges_dev(rtc_ctx* ctx, const uint32_t* d_common, uint64_t ld, uint32_t row0,
                           uint32_t row1, uint32_t col0, uint32_t col1, const uint32_t* d_len,

@@ -499,9 +499,13 @@ extern "C" uint32_t orc_common_u32(const uint32_t* a, uint32_t na, const uint32_
   return common_sorted(a, na, b, nb);
 }
 
-// src/MST.cpp:26-37 calr(), :1292 "int radio = calr(threshold, kmer_size-1)"
+// src/MST.cpp:26-37 calr(), :1292 "int radio = calr(threshold, kmer_size-1)".  Deliberate divergence from the
+// reference: its int conversion is undefined once calr leaves int's range and its "radio * min_size" (:1484) is an int
+// product that wraps, which drops pairs at any threshold past ~0.695 (k = 21, s = 1000).  Here radio saturates at INT32_MAX
+// and mst_row takes the product in 64 bits: a pair is kept iff max <= radio * min exactly.
 extern "C" int orc_mst_radio(double threshold, int kmer_size) {
-  return (int)(2.0 * std::exp(threshold * (kmer_size - 1)) - 1.0);
+  const double r = 2.0 * std::exp(threshold * (kmer_size - 1)) - 1.0;
+  return r < 2147483647.0 ? (int)r : INT32_MAX;
 }
 
 // src/MST.cpp:1295 inv_kmer_size, :1489-1515
@@ -679,7 +683,7 @@ static void mst_row(const Sketches& S, const InvIndex& idx, Counter& C, uint32_t
     int size1 = (int)S.len[j];
     if (size1 == 0) continue;                                         // :1477
     int mn = size0 < size1 ? size0 : size1, mx = size0 > size1 ? size0 : size1;
-    if (mx > radio * mn) continue;                                    // :1481-1484
+    if ((int64_t)mx > (int64_t)radio * mn) continue;                  // :1481-1484, exact (orc_mst_radio)
     outv.push_back(orc_edge{(int)i, j, orc_mst_distance(common, size0, size1, kmer_size, is_containment)});
   }
 }

@@ -81,7 +81,8 @@ uint32_t orc_common_u64(const uint64_t* a, uint32_t na, const uint64_t* b, uint3
 uint32_t orc_common_u32(const uint32_t* a, uint32_t na, const uint32_t* b, uint32_t nb);
 /* src/MST.cpp:1489-1503 (Jaccard -> Mash) and :1504-1515 (containment -> AAF); no >1 clamp */
 double orc_mst_distance(int common, int size0, int size1, int kmer_size, int is_containment);
-/* radio filter src/MST.cpp:1292,1481-1484: (int)(2*exp(thr*(k-1))-1) */
+/* radio filter src/MST.cpp:1292,1481-1484: floor(2*exp(thr*(k-1))-1) saturated at INT32_MAX; the filter keeps a pair
+ * iff max <= radio * min in exact (64-bit) arithmetic, where the reference's int product wraps */
 int orc_mst_radio(double threshold, int kmer_size);
 /* greedy slow path src/greedy.cpp:1240-1282 (Mash formula on containment, clamped to 1) */
 double orc_greedy_distance(int common, int size_ref, int size_qry, int kmer_size, int rep_is_containment);

@@ -558,9 +558,17 @@ class Comm:
 
 
 # ---- host-side arithmetic shared by CLI-equivalent flows (reference expression order) -------------
+RADIO_MAX = 0x7FFFFFFF
+
+
 def mst_radio(threshold, kmer_size):
-    """src/MST.cpp:26-37,1292: (int)(2*exp(thr*(k-1)) - 1)."""
-    return int(2.0 * math.exp(threshold * (kmer_size - 1)) - 1.0)
+    """src/MST.cpp:26-37,1292: floor(2*exp(thr*(k-1)) - 1), saturated at INT32_MAX (rtc_size_radio in csrc/rtc_internal.h):
+    the value crosses the C ABI as an int, and a saturated radio keeps every pair."""
+    try:
+        r = 2.0 * math.exp(threshold * (kmer_size - 1)) - 1.0
+    except OverflowError:  # where C's exp gives +inf
+        return RADIO_MAX
+    return int(r) if r < RADIO_MAX else RADIO_MAX
 
 
 def mst_distance(common, size0, size1, kmer_size, is_containment):

@@ -1,6 +1,7 @@
 // rtc_internal.h -- shared host-side plumbing for the HIP translation units (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,6 +35,15 @@ struct rtc_options {
   double comm_timeout_s = 120.0;   // RTC_COMM_TIMEOUT_S (<= 0: forever)
 };
 void rtc_options_from_env(rtc_options* o);
+
+// The size-ratio bound of the MST's candidate filter: calr (src/MST.cpp:26-37) as the reference stores it, "int radio =
+// calr(threshold, k - 1)" (:1292), i.e. floor(2 e^(threshold (k-1)) - 1) for threshold >= 0 -- but saturated at INT32_MAX where
+// the reference's conversion is undefined.  The kernels keep a pair iff max <= radio * min with the product in 64 bits, so a
+// saturated radio keeps every pair; the reference's int product wraps there instead (a deliberate divergence).
+static inline int rtc_size_radio(double threshold, int kmer_size) {
+  const double r = 2.0 * exp(threshold * (kmer_size - 1)) - 1.0;
+  return r < 2147483647.0 ? (int)r : 2147483647;
+}
 
 struct rtc_ctx {
   int device = 0;

@@ -680,7 +680,7 @@ int rtc_candidate_edges_device(rtc_ctx* ctx, const void* d_hashes, int width, co
                                const uint32_t* d_len, uint32_t n, uint32_t row0, uint32_t row1, int kmer_size,
                                int is_containment, double threshold, uint32_t s_fixed, rtc_edge_list* el,
                                const rtc_edge_observer* obs) {
-  const int radio = (int)(2.0 * exp(threshold * (kmer_size - 1)) - 1.0);  // src/MST.cpp:26-37,1292
+  const int radio = rtc_size_radio(threshold, kmer_size);  // src/MST.cpp:26-37,1292, saturated (rtc_internal.h)
   uint64_t budget = (uint64_t)256 << 20;  // edges (3 GiB)
   if (ctx->opt.edge_budget) budget = ctx->opt.edge_budget;  // tests of the dense path
   budget = std::max<uint64_t>(budget, 66ull * n + 1024);  // a 64-row block on top of a contracted list always fits

@@ -4,8 +4,9 @@
 
 Two kinds of fixtures, labelled in MANIFEST.json:
   * "reference": outputs of the reference's own code run here -- oracle/_ref/libref_harness.so is
-    compiled from /root/reference/src/{kseq.h,UnionFind.h} where they lie (oracle/Makefile).
-    They pin the host FASTA reader and the union-find used by Kruskal.
+    compiled from the reference's src/{kseq.h,UnionFind.h} where they lie, oracle/_ref/libref_fns.so from its
+    self-contained distance-half functions (oracle/Makefile, REF_FNS).  They pin the host FASTA reader, the
+    union-find, the size-ratio bound, the KSSD greedy distance, Kruskal + the forest cut and the KSSD shuffle table.
   * "oracle": outputs of oracle/ (the CPU restatement).  They let the GPU box check the HIP path
     without regenerating expectations, and freeze the oracle against accidental edits.  The MinHash
     ones are NOT pinned against upstream RabbitSketch (see oracle/rtc_oracle.h).
@@ -14,6 +15,7 @@ import ctypes as C
 import gzip
 import hashlib
 import json
+import math
 import os
 import sys
 import tempfile
@@ -26,6 +28,136 @@ sys.path.insert(0, ROOT)
 from oracle import pyoracle as O  # noqa: E402
 
 REF = os.path.join(ROOT, "oracle", "_ref", "libref_harness.so")
+REF_FNS = os.path.join(ROOT, "oracle", "_ref", "libref_fns.so")
+EDGE_DT = np.dtype([("preNode", np.int32), ("sufNode", np.int32), ("dist", np.float64)])  # the reference's EdgeInfo
+SHUFFLE_HALF_SUBK = (6, 7)  # half_subk = 6 for --drlevel 0..4, drlevel + 2 = 7 for 5; 8 would overflow 1 << 4 * half_subk
+
+
+def ref_fns_lib(path=REF_FNS):
+    """oracle/_ref/libref_fns.so: the reference's distance-half functions behind oracle/ref_fns_shims.inc"""
+    L = C.CDLL(path)
+    L.ref_calr.restype = L.ref_calculate_max_size_ratio.restype = L.ref_mash_distance_fast.restype = C.c_double
+    L.ref_calr.argtypes = L.ref_calculate_max_size_ratio.argtypes = [C.c_double, C.c_int]
+    L.ref_mash_distance_fast.argtypes = [C.c_int] * 4
+    L.ref_kruskal_forest.restype = C.c_uint64
+    L.ref_kruskal_forest.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
+    L.ref_generate_shuffle_dim.restype = C.c_int
+    L.ref_generate_shuffle_dim.argtypes = [C.c_int, C.c_void_p]
+    return L
+
+
+def ref_kruskal_forest(L, edges, n, thr):
+    """(tree, forest) of kruskalAlgorithm + generateForest over edges (EDGE_DT, sorted by dist)"""
+    edges = np.ascontiguousarray(edges, dtype=EDGE_DT)
+    tree = np.zeros(max(n, 1), dtype=EDGE_DT)
+    forest = np.zeros(max(n, 1), dtype=EDGE_DT)
+    tm = C.c_uint64()
+    fm = L.ref_kruskal_forest(edges.ctypes.data, len(edges), n, thr, tree.ctypes.data, C.byref(tm), forest.ctypes.data)
+    return tree[:tm.value], forest[:fm]
+
+
+def ref_shuffle_dim(L, half_subk):
+    out = np.empty(1 << 4 * half_subk, dtype=np.int32)
+    assert L.ref_generate_shuffle_dim(half_subk, out.ctypes.data) == len(out)
+    return out
+
+
+def shuffle_sample_positions(half_subk):
+    """the table positions a fixture stores: the first 64 and 4096 seeded ones"""
+    n = 1 << 4 * half_subk
+    return np.concatenate([np.arange(64), np.random.default_rng(half_subk).integers(0, n, size=4096)]).astype(np.int64)
+
+
+def radio_grid():
+    """(d, k) points of the calr / calculateMaxSizeRatio table: d on a 0..1 grid and, for every k, where
+    2 e^(d (k-1)) - 1 crosses 2^31 - 1, 2^31 and 2^32 (and one ulp either side), plus the thresholds the tests use"""
+    ds, ks = [], []
+    for k in range(1, 33):
+        pts = list(np.linspace(0.0, 1.0, 101)) + [0.05, 0.62, 0.6931471805862327, 0.7, 0.8]
+        if k > 1:
+            for v in (2.0 ** 31 - 1, 2.0 ** 31, 2.0 ** 32):
+                x = math.log((v + 1.0) / 2.0) / (k - 1)
+                pts += [np.nextafter(x, -1.0), x, np.nextafter(x, 2.0)]
+        pts = sorted(set(float(p) for p in pts if 0.0 <= p <= 1.0))
+        ds += pts
+        ks += [k] * len(pts)
+    return np.array(ds, dtype=np.float64), np.array(ks, dtype=np.int32)
+
+
+def mash_grid():
+    """(common, size0, size1, k) points of calculate_mash_distance_fast: zeros, denominator 0, common = size, j = 1/s (the
+    tuning's max distance), distances past 1 (clamped), large sizes (size0 + size1 below 2^31: the reference's int sum)"""
+    rng = np.random.default_rng(11)
+    pts = []
+    for k in (1, 2, 5, 12, 16, 19, 21, 22, 24, 31, 32):
+        for s0, s1 in [(0, 0), (0, 7), (7, 0), (1, 1), (1, 1000), (1000, 1000), (997, 1003), (1, 100000), (60000, 60000),
+                       (5_000_000, 3), (1 << 29, 1 << 29), ((1 << 30) - 1, 1 << 30)]:
+            for c in {0, 1, 2, min(s0, s1), max(min(s0, s1) - 1, 0), min(s0, s1) // 2, s0 + s1}:
+                if s0 + s1 - c < (1 << 31):
+                    pts.append((c, s0, s1, k))
+        for s in (100, 1000, 5000, 10000, 60000, 100000):  # tune_parameters: maxDist at minJaccard = 1/sketchSize
+            pts.append((1, 1, s, k))
+        for _ in range(40):
+            s0, s1 = (int(x) for x in rng.integers(1, 200_000, size=2))
+            pts.append((int(rng.integers(0, min(s0, s1) + 1)), s0, s1, k))
+    return np.array(sorted(set(pts)), dtype=np.int32)
+
+
+def kruskal_cases():
+    """seeded edge lists sorted by distance (stable), many equal distances; thresholds on an edge's distance and one ulp
+    either side"""
+    cases = []
+    for seed, n, m, levels in [(1, 30, 80, 6), (2, 200, 900, 12), (3, 500, 3000, 40), (4, 64, 2016, 3), (5, 1, 0, 1),
+                               (6, 2, 1, 1), (7, 300, 200, 1000)]:
+        rng = np.random.default_rng(100 + seed)
+        pre = rng.integers(0, n, size=m).astype(np.int32)
+        suf = rng.integers(0, n, size=m).astype(np.int32)
+        dist = (rng.integers(0, levels, size=m) / levels * 0.3).astype(np.float64)
+        e = np.zeros(m, dtype=EDGE_DT)
+        e["preNode"], e["sufNode"], e["dist"] = pre, suf, dist
+        e = e[np.argsort(e["dist"], kind="stable")]
+        thr = [0.0, 0.05, 1.0]
+        for d in (e["dist"][m // 3:m // 3 + 1].tolist() + e["dist"][m // 2:m // 2 + 1].tolist() if m else []):
+            thr += [np.nextafter(d, -1.0), d, np.nextafter(d, 2.0)]
+        cases.append((n, e, np.array(thr, dtype=np.float64)))
+    return cases
+
+
+def write_ref_distance_half(L):
+    """ref_distance_half.npz: the reference's own calr / calculateMaxSizeRatio, calculate_mash_distance_fast,
+    kruskalAlgorithm + generateForest and generate_shuffle_dim, evaluated here on fixed grids"""
+    out = {}
+    d, k = radio_grid()
+    out["radio_d"], out["radio_k"] = d, k
+    out["calr"] = np.array([L.ref_calr(a, b - 1) for a, b in zip(d, k)], dtype=np.float64)  # calr(threshold, k - 1)
+    out["max_size_ratio"] = np.array([L.ref_calculate_max_size_ratio(a, b) for a, b in zip(d, k)], dtype=np.float64)
+    g = mash_grid()
+    out["mash_args"] = g
+    out["mash_dist"] = np.array([L.ref_mash_distance_fast(*map(int, r)) for r in g], dtype=np.float64)
+    for i, (n, e, thr) in enumerate(kruskal_cases()):
+        out[f"kr{i}_n"] = np.array(n, dtype=np.int32)
+        out[f"kr{i}_edges"] = e
+        out[f"kr{i}_thr"] = thr
+        tree = None
+        for t, th in enumerate(thr):
+            tree, forest = ref_kruskal_forest(L, e, n, th)
+            out[f"kr{i}_forest{t}"] = forest
+        out[f"kr{i}_tree"] = tree
+    for hs in SHUFFLE_HALF_SUBK:
+        t = ref_shuffle_dim(L, hs)
+        pos = shuffle_sample_positions(hs)
+        out[f"shuffle{hs}_sha256"] = np.array(hashlib.sha256(t.tobytes()).hexdigest())
+        out[f"shuffle{hs}_pos"], out[f"shuffle{hs}_val"] = pos, t[pos]
+        del t
+    np.savez_compressed(os.path.join(HERE, "ref_distance_half.npz"), **out)
+    return {"kind": "reference", "source": "calr, calculateMaxSizeRatio, calculate_mash_distance_fast, EdgeInfo, kruskalAlgorithm, "
+            "generateForest, shuffle/shuffleN/generate_shuffle_dim via oracle/ref_fns_shims.inc: (d, k) and (common, size0, "
+            "size1, k) grids, 7 sorted edge lists with thresholds on an edge and one ulp either side, SHA-256 + 4160 entries "
+            "of the shuffle tables at half_subk 6 and 7",
+            "pins": "reference-pinned: KSSD shuffle table, size-ratio radio, kruskalAlgorithm + generateForest cut, KSSD greedy "
+            "distance, tune_parameters' max distance; still restated: the MinHash k-mer hash and the MST loop's inline distance",
+            "filter": "deliberate divergence: a pair is kept iff max <= R * min in exact (64-bit) integers, R = floor(calr) saturated "
+            "at INT32_MAX; the reference's int conversion and int product overflow past 2^31 (DESIGN 5)"}
 
 
 def write_fasta_inputs():
@@ -137,13 +269,19 @@ def main():
     np.savez(os.path.join(HERE, "unionfind.npz"), xs=xs, ys=ys, roots=roots, size=size.value)
     manifest["unionfind.npz"] = {"kind": "reference", "source": "UnionFind.h via oracle/ref_harness.cpp"}
 
-    # ---- oracle fixtures ----
-    sd = O.kssd_shuffle_dim(6)
+    # ---- the reference's distance half ----
+    if not os.path.exists(REF_FNS):
+        raise SystemExit("oracle/_ref/libref_fns.so missing: run `make -C oracle` where the reference tree exists")
+    fns = ref_fns_lib()
+    manifest["ref_distance_half.npz"] = write_ref_distance_half(fns)
+    sd = ref_shuffle_dim(fns, 6)
     kept = np.nonzero(sd < 4096)[0].astype(np.uint32)
     np.savez_compressed(os.path.join(HERE, "kssd_shuffle_hs6.npz"), dim_id=kept, rank=sd[kept].astype(np.uint16),
                         head=sd[:64].astype(np.int32))
-    manifest["kssd_shuffle_hs6.npz"] = {"kind": "oracle", "source": "glibc srand/rand via orc_kssd_shuffle_dim(6); "
-                                        "4096 surviving (dim_id, rank) pairs + first 64 table entries"}
+    manifest["kssd_shuffle_hs6.npz"] = {"kind": "reference", "source": "generate_shuffle_dim(6) via oracle/ref_fns_shims.inc "
+                                        "(glibc srand/rand); 4096 surviving (dim_id, rank) pairs + first 64 table entries"}
+
+    # ---- oracle fixtures ----
     L = 60_000
     descs = [(11, 0, 0, 0), (11, 5, 300, 0), (11, 6, 900, 0), (12, 0, 0, 0), (12, 9, 500, 7000), (13, 0, 0, 0)]
     genomes = [O.synth_genome(f, m_, t, L, ne) for (f, m_, t, ne) in descs]

@@ -589,3 +589,27 @@ def test_repdb_stats_reads_reference_layout(tmp_path):
     assert "  Unique hashes:          %d\n" % len(index) in r.stdout
     r = subprocess.run([binp, "--fast", "--db", mh, "--stats"], capture_output=True, text=True, timeout=60)
     assert r.returncode != 0 and "Invalid RepDB file (bad magic)" in r.stderr
+
+
+def test_shuffle_dim_and_tune_bound_equal_reference(host):
+    """rtch_shuffle_dim against the reference's generate_shuffle_dim at every half_subk the command lines use (6 for
+    --drlevel 0..4, 7 for 5), and tune_parameters' maxDist against calculate_mash_distance_fast(1, 1, s, k): a threshold on
+    it is accepted, one ulp above is refused (tests/golden/ref_distance_half.npz)"""
+    import hashlib
+    fx = np.load(os.path.join(GOLD, "ref_distance_half.npz"))
+    for hs in (6, 7):
+        out = np.zeros(1 << 4 * hs, dtype=np.int32)
+        assert host.rtch_shuffle_dim(hs, out.ctypes.data_as(C.c_void_p)) == 1 << 4 * hs
+        assert hashlib.sha256(out.tobytes()).hexdigest() == str(fx[f"shuffle{hs}_sha256"]), hs
+        assert np.array_equal(out[fx[f"shuffle{hs}_pos"]], fx[f"shuffle{hs}_val"]), hs
+        del out
+    n = 0
+    for (c, s0, s1, k), d in zip(fx["mash_args"].tolist(), fx["mash_dist"]):
+        if (c, s0) != (1, 1) or not 15 <= k <= 21 or s1 < 100:
+            continue
+        for thr, ok in ((float(d), 1), (float(np.nextafter(d, 2.0)), 0)):
+            kk, cc, ic = C.c_int(), C.c_int(), C.c_int()
+            assert host.rtch_tune(0, 1, 0, 1, k, thr, 1000, s1, 5062520, 5062520, 5062520, C.byref(kk), C.byref(cc), C.byref(ic)) == ok, (s1, k, thr)
+            assert kk.value == k
+        n += 1
+    assert n >= 6

@@ -373,3 +373,193 @@ def test_sketch_threshold_test_word_bounds():
             for lo1, lo2 in ((int(rng.integers(0, 1 << 32)), int(rng.integers(0, 1 << 32))), (M32, M32), (0, 0), (M32, 1)):
                 seen.add(check((h1 << 32 | lo1) * Cinv & M64, (h2 << 32 | lo2) * Cinv & M64))
     assert seen == {0, 1, 2}
+
+
+# ---- the distance half against the reference's own functions (tests/golden/ref_distance_half.npz) -----------------------
+INT32_MAX = 2 ** 31 - 1
+
+
+def _ref_fixture():
+    return np.load(os.path.join(GOLD, "ref_distance_half.npz"))
+
+
+def _make_golden():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(GOLD, "make_golden.py"))
+    mg = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mg)
+    return mg
+
+
+def _saturated_radio(calr):
+    """the filter's bound: floor of the reference's calr, saturated at INT32_MAX"""
+    return int(calr) if calr < INT32_MAX else INT32_MAX
+
+
+def test_radio_is_the_reference_calr_saturated(oracle):
+    from rabbittclust_amd import api
+    fx = _ref_fixture()
+    L = oracle.lib()
+    seen = set()
+    for d, k, calr, msr in zip(fx["radio_d"], fx["radio_k"], fx["calr"], fx["max_size_ratio"]):
+        d, k = float(d), int(k)
+        # calculateMaxSizeRatio(d, k) is calr(d, k) (the KSSD greedy's double bound, host/main.cpp, test_gpu_cli.py)
+        assert msr == 2.0 * math.exp(d * k) - 1.0, (d, k)
+        if k == 1:
+            assert math.isnan(calr)  # calr(d, 0) throws in the reference; the k-mer sizes here are >= 2
+            continue
+        want = _saturated_radio(float(calr))
+        assert L.orc_mst_radio(d, k) == want, (d, k, calr)
+        assert api.mst_radio(d, k) == want, (d, k, calr)
+        seen.add("saturated" if want == INT32_MAX else "exact")
+        if 2 ** 31 <= calr < 2 ** 32:
+            seen.add("past 2^31")
+        if calr >= 2 ** 32:
+            seen.add("past 2^32")  # where a modulo-2^32 conversion (ctypes c_int) would give a small radio
+    assert seen == {"saturated", "exact", "past 2^31", "past 2^32"}
+    assert api.mst_radio(0.6931471805862327, 32) == INT32_MAX  # calr = 4 294 967 298: c_int would pass 2
+    assert api.mst_radio(1e6, 21) == INT32_MAX and L.orc_mst_radio(1e6, 21) == INT32_MAX  # exp overflows to +inf
+
+
+def test_mash_distance_fast_equals_reference(oracle):
+    """orc_kssd_greedy_distance is calculate_mash_distance_fast; the MST distance (api.mst_distance, orc_mst_distance) is the
+    same expression without the clamp at 1"""
+    from rabbittclust_amd import api
+    fx = _ref_fixture()
+    L = oracle.lib()
+    got = np.array([L.orc_kssd_greedy_distance(*map(int, a)) for a in fx["mash_args"]])
+    assert np.array_equal(got.view(np.uint64), fx["mash_dist"].view(np.uint64))
+    for (c, s0, s1, k), want in zip(fx["mash_args"].tolist(), fx["mash_dist"]):
+        if c > min(s0, s1):  # no intersection is larger than a set (the grid pins the reference there too)
+            continue
+        for d in (api.mst_distance(c, s0, s1, k, False), L.orc_mst_distance(c, s0, s1, k, 0)):
+            assert min(d, 1.0) == want, (c, s0, s1, k)
+    assert {0.0, 1.0} <= set(fx["mash_dist"].tolist()) and ((fx["mash_dist"] > 0) & (fx["mash_dist"] < 1)).sum() > 100
+
+
+def test_tune_max_distance_is_the_reference_expression(oracle):
+    """tune_parameters' maxDist at minJaccard = 1/sketchSize is calculate_mash_distance_fast(1, 1, sketchSize, k)"""
+    fx = _ref_fixture()
+    n = 0
+    for (c, s0, s1, k), want in zip(fx["mash_args"].tolist(), fx["mash_dist"]):
+        if (c, s0) != (1, 1) or not 15 <= k <= 21 or s1 < 100:
+            continue
+        r = oracle.tune_parameters(0, 1, 0, 1, k, 0.01, 1000, s1, 5062520, 5062520, 5062520)
+        assert r.kmer_size == k and r.max_dist == want, (s1, k)
+        n += 1
+    assert n >= 6
+
+
+def _edges_as_oracle(oracle, e):
+    out = np.zeros(len(e), dtype=oracle.EDGE_DT)
+    out["pre"], out["suf"], out["dist"] = e["preNode"], e["sufNode"], e["dist"]
+    return out
+
+
+def _partition_of(edges, n):
+    from oracle.brute import partition
+    return partition(zip(edges["dist"], edges["pre"], edges["suf"]), n)
+
+
+def test_kruskal_and_forest_cut_equal_reference(oracle):
+    """orc_kruskal is kruskalAlgorithm (record for record, ties and self-loops included); orc_forest_clusters cuts at
+    dist <= threshold like generateForest, with the threshold on an edge's distance and one ulp either side"""
+    fx = _ref_fixture()
+    cases = 0
+    while f"kr{cases}_n" in fx:
+        i = cases
+        n, e, tree = int(fx[f"kr{i}_n"]), _edges_as_oracle(oracle, fx[f"kr{i}_edges"]), _edges_as_oracle(oracle, fx[f"kr{i}_tree"])
+        out = np.zeros(max(len(e), 1), dtype=oracle.EDGE_DT)
+        m = oracle.lib().orc_kruskal(e.ctypes.data_as(C.c_void_p), C.c_uint64(len(e)), C.c_int(n), out.ctypes.data_as(C.c_void_p))
+        assert np.array_equal(out[:m], tree), i
+        for t, thr in enumerate(fx[f"kr{i}_thr"]):
+            forest = _edges_as_oracle(oracle, fx[f"kr{i}_forest{t}"])
+            assert np.array_equal(forest, tree[tree["dist"] <= thr]), (i, thr)
+            got = sorted(tuple(sorted(c)) for c in oracle.forest_clusters(tree, float(thr), n))
+            assert got == _partition_of(forest, n), (i, thr)
+        cases += 1
+    assert cases == 7
+    # the thresholds on an edge cut differently from one ulp below
+    thr = fx["kr2_thr"]
+    tree = fx["kr2_tree"]
+    assert (tree["dist"] <= thr[4]).sum() > (tree["dist"] <= thr[3]).sum()
+
+
+def test_shuffle_table_equals_reference(oracle):
+    import hashlib
+    fx = _ref_fixture()
+    sd = oracle.kssd_shuffle_dim(6)
+    assert hashlib.sha256(sd.astype(np.int32).tobytes()).hexdigest() == str(fx["shuffle6_sha256"])
+    assert np.array_equal(sd[fx["shuffle6_pos"]], fx["shuffle6_val"])
+    hs6 = np.load(os.path.join(GOLD, "kssd_shuffle_hs6.npz"))
+    assert np.array_equal(sd[:64], hs6["head"]) and np.array_equal(sd[hs6["dim_id"]], hs6["rank"])
+    # half_subk 7 (--drlevel 5): 2^28 entries, hashed in place and freed rather than cached like the hs6 table
+    ptr = oracle.lib().orc_kssd_shuffle_dim(7)
+    try:
+        t7 = np.ctypeslib.as_array(ptr, shape=(1 << 28,))
+        assert hashlib.sha256(memoryview(t7)).hexdigest() == str(fx["shuffle7_sha256"])
+        assert np.array_equal(t7[fx["shuffle7_pos"]], fx["shuffle7_val"])
+        del t7
+    finally:
+        C.CDLL(None).free(C.cast(ptr, C.c_void_p))
+
+
+def test_reference_functions_live_against_fixture(oracle):
+    """The stored grids are what make_golden.py's generators produce.  Where oracle/_ref is built (a checkout beside the
+    reference tree), the reference's functions also run again on them; elsewhere that half has nothing to run and says so
+    with a warning, like the kseq test, while the fixture itself is checked by the tests above."""
+    import warnings
+    mg = _make_golden()
+    fx = _ref_fixture()
+    d, k = mg.radio_grid()
+    assert np.array_equal(d, fx["radio_d"]) and np.array_equal(k, fx["radio_k"])
+    assert np.array_equal(mg.mash_grid(), fx["mash_args"])
+    if not os.path.exists(mg.REF_FNS):
+        warnings.warn("oracle/_ref/libref_fns.so is not built: the reference's functions were not re-run")
+        return
+    L = mg.ref_fns_lib()
+    calr = np.array([L.ref_calr(a, b - 1) for a, b in zip(d, k)])
+    assert np.array_equal(calr.view(np.uint64), fx["calr"].view(np.uint64))
+    msr = np.array([L.ref_calculate_max_size_ratio(a, b) for a, b in zip(d, k)])
+    assert np.array_equal(msr.view(np.uint64), fx["max_size_ratio"].view(np.uint64))
+    md = np.array([L.ref_mash_distance_fast(*map(int, r)) for r in fx["mash_args"]])
+    assert np.array_equal(md.view(np.uint64), fx["mash_dist"].view(np.uint64))
+    for i, (n, e, thr) in enumerate(mg.kruskal_cases()):
+        assert np.array_equal(e, fx[f"kr{i}_edges"]) and np.array_equal(thr, fx[f"kr{i}_thr"])
+        for t, th in enumerate(thr):
+            tree, forest = mg.ref_kruskal_forest(L, e, n, th)
+            assert np.array_equal(tree, fx[f"kr{i}_tree"]) and np.array_equal(forest, fx[f"kr{i}_forest{t}"]), (i, t)
+    t6 = mg.ref_shuffle_dim(L, 6)
+    assert np.array_equal(t6, oracle.kssd_shuffle_dim(6))
+
+
+def _overflow_sets():
+    """MinHash-like u64 sets that share hashes: four of s = 1000, two containment-sized (5.0e4, 5.2e4), one of 6.0e5 and
+    sketches of 1 and 3 hashes inside it"""
+    rng = np.random.default_rng(77)
+    pool = np.unique(rng.integers(1, 1 << 62, size=700_000, dtype=np.uint64))
+    rng.shuffle(pool)
+    big = np.sort(pool[:600_000])
+    sets = [np.sort(np.concatenate([pool[:200], pool[1000 + 800 * i:1000 + 800 * (i + 1)]])) for i in range(4)]
+    sets += [np.sort(pool[100:50_100]), np.sort(pool[150:52_150]), big, np.sort(pool[:1]), np.sort(pool[5:8])]
+    return sets
+
+
+@pytest.mark.parametrize("containment", [False, True])
+@pytest.mark.parametrize("thr", [0.62, 0.7, 0.8])
+def test_oracle_mst_size_filter_past_32_bits(oracle, thr, containment):
+    """R * min past 2^31 (d = 0.7: R = 2 405 207, R * 1000 wraps negative in the reference's int product; d = 0.8: wraps
+    positive; d = 0.62: control, R * 1000 fits but R * 6e5 / R * 1 decides one pair).  The oracle must equal the exact filter."""
+    sets = _overflow_sets()
+    flat, start, lens = oracle.to_csr(sets)
+    from oracle.brute import mst_forest, partition
+    cand, forest = mst_forest(sets, 21, containment, thr)
+    got = oracle.mst(flat, start, lens, 21, containment, thr, threads=1)
+    assert len(got) == len(forest)
+    assert np.array_equal(np.sort(got["dist"]).view(np.uint64), np.sort(np.array([f[0] for f in forest])).view(np.uint64))
+    want_part = partition(forest, len(sets))
+    assert sorted(tuple(sorted(c)) for c in oracle.forest_clusters(got, 1.0, len(sets))) == want_part
+    # the 1-hash sketch and the 6e5 one: ratio 600 000 -- above R = 485 601 at 0.62, below R at 0.7 and 0.8
+    pair = any(i == 7 and j == 6 for _, i, j in cand)
+    assert pair == (thr > 0.62)
+    assert len(cand) >= 30

@@ -7,7 +7,6 @@ gather, triangle row ranges, per-round all-reduce + device union (rtc_mst_sharde
 driven with one rank (RTC_COMM_FORCE_RCCL=1): ncclAllReduce and the grouped in-place ncclBroadcast."""
 import os
 import subprocess
-import threading
 
 import numpy as np
 import pytest
@@ -25,22 +24,8 @@ BIN = os.path.join(ROOT, "rabbittclust_amd", "bin")
 
 
 def _threads(fns):
-    err, out = [], [None] * len(fns)
-
-    def run(i):
-        try:
-            out[i] = fns[i]()
-        except BaseException as e:  # noqa: BLE001 -- reported to the main thread
-            err.append(e)
-    ts = [threading.Thread(target=run, args=(i,)) for i in range(len(fns))]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join(300)
-    assert not any(t.is_alive() for t in ts), "a rank hung"
-    if err:
-        raise err[0]
-    return out
+    from oracle.brute import run_ranks
+    return run_ranks(fns)
 
 
 @pytest.mark.parametrize("world", [2, 3])
