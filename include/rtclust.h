@@ -406,6 +406,24 @@ int rtc_greedy_mash(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_
                     uint32_t n, int kmer_size, int is_containment, uint32_t sketch_size, double threshold,
                     int32_t* h_rep_of, uint32_t* h_n_clusters);
 
+/* ---- clust-mst post-processing ----------------------------------------------------------- */
+/* The --dedup-dist representatives: build_dedup_candidates_per_cluster_core (src/cluster_postprocess.cpp:60-156).  The forest
+ * edges with dist <= dedup_dist (h_edges[0..m), EdgeInfo records; those edges must form a forest over n nodes) are joined into
+ * groups; every group's representative is its tree medoid, the member with the smallest sum of tree distances to the other
+ * members -- ties to the longer sequence (h_seq_len[n], may be NULL), then to the smaller id.  h_node_to_rep[n] receives the
+ * representative of every node (itself in a group of one; every node when dedup_dist <= 0, the reference's no-op).  The sums
+ * carry the reference's rounding: each distance accumulated outward from the candidate, one add per edge, the members summed
+ * in ascending id.  Groups below a measured size are done on the host (rtc_ctx_set_host_threads), the larger ones on the GPU,
+ * one wave per candidate; RTC_DEDUP_GPU=0 keeps every group on the host, =2 sends every group of two or more to the GPU.
+ * Synchronous. */
+int rtc_tree_medoids(rtc_ctx* ctx, uint32_t n, const rtc_edge* h_edges, uint64_t m, double dedup_dist, const uint64_t* h_seq_len,
+                     int32_t* h_node_to_rep);
+/* Where the last rtc_tree_medoids of this context computed its sums: 0 nowhere (no group of two or more), 1 host only,
+ * 2 GPU only, 3 both (tests and measurement). */
+int rtc_dedup_last_path(const rtc_ctx* ctx);
+/* Host threads of the context's host-side work (rtc_tree_medoids' small groups); default 1. */
+int rtc_ctx_set_host_threads(rtc_ctx* ctx, int threads);
+
 #ifdef __cplusplus
 }
 #endif

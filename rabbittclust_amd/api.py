@@ -498,6 +498,25 @@ class Context:
                                        _np_ptr(rep), C.byref(nc)))
         return int(nc.value), rep[:n].copy()
 
+    def tree_medoids(self, n, edges, dedup_dist, seq_len=None, threads=None):
+        """--dedup-dist representatives (build_dedup_candidates_per_cluster_core): node_to_rep[n] (int32) from forest edges
+        (EDGE_DT records) -- each group of edges with dist <= dedup_dist represented by its tree medoid.  threads: host
+        threads of the small groups (rtc_ctx_set_host_threads).  RTC_DEDUP_GPU picks the path (see dedup_last_path)."""
+        e = np.ascontiguousarray(np.asarray(edges, dtype=EDGE_DT))
+        lens = None if seq_len is None else np.ascontiguousarray(np.asarray(seq_len, dtype=np.uint64))
+        if lens is not None and lens.shape[0] != n:
+            raise ValueError("seq_len must hold n values")
+        if threads is not None:
+            self.check(self.lib.rtc_ctx_set_host_threads(self.h, int(threads)))
+        out = np.zeros(max(int(n), 1), dtype=np.int32)
+        self.check(self.lib.rtc_tree_medoids(self.h, int(n), _np_ptr(e) if len(e) else None, len(e), float(dedup_dist),
+                                             _np_ptr(lens) if lens is not None else None, _np_ptr(out)))
+        return out[:n].copy()
+
+    def dedup_last_path(self):
+        """Where the last tree_medoids call computed its sums: 0 nowhere, 1 host, 2 GPU, 3 both."""
+        return int(self.lib.rtc_dedup_last_path(self.h))
+
 
 class Comm:
     """One rtc_comm (RCCL communicator of one GPU / context).  Ranks are processes (init_rank, the id

@@ -97,6 +97,7 @@ void rtc_options_from_env(rtc_options* o) {
   o->sketch_t0_factor = getenv("RTC_SKETCH_T0_FACTOR") ? (int)std::max<long long>(0, num("RTC_SKETCH_T0_FACTOR", 0)) : -1;
   o->comm_force_rccl = flag("RTC_COMM_FORCE_RCCL");
   if (const char* e = getenv("RTC_COMM_TIMEOUT_S")) o->comm_timeout_s = atof(e);
+  o->dedup_gpu = (int)num("RTC_DEDUP_GPU", 1);
 }
 
 extern "C" {

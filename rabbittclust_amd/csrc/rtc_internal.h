@@ -33,6 +33,7 @@ struct rtc_options {
   int sketch_t0_factor = -1;       // RTC_SKETCH_T0_FACTOR (-1: by rule)
   int comm_force_rccl = 0;         // RTC_COMM_FORCE_RCCL
   double comm_timeout_s = 120.0;   // RTC_COMM_TIMEOUT_S (<= 0: forever)
+  int dedup_gpu = 1;               // RTC_DEDUP_GPU: 0 never, 1 groups from the measured cutoff up, 2 every group of two or more
 };
 void rtc_options_from_env(rtc_options* o);
 
@@ -73,6 +74,8 @@ struct rtc_ctx {
   // launches (the row-chunk loop of the dense candidate-edge path).
   int quiet = 0;           // rtc_warmup's context: no RTC_VERBOSE lines
   int pair_last_path = 0;  // rtc_pair_last_path
+  int dedup_last_path = 0;  // rtc_dedup_last_path
+  int host_threads = 1;     // rtc_ctx_set_host_threads: the host side of rtc_tree_medoids
   // rtc_diag_counters: [0] pair tiles the join took, [1] tiled-kernel tiles, [2] merge-kernel tiles, [3] candidate lists contracted
   // to their forest, [4] greedy runs replayed from ONE global join, [5] greedy query blocks of the block loop, [6] estimates handed
   // back instead of a launch (rtc_pair_edges_dev's overflow protocol)

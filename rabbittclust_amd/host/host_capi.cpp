@@ -123,4 +123,30 @@ int rtch_read_genome_packed(const char* path, unsigned char* out, long cap_bases
   for (size_t i = 0; i < runs.size() && (long)i < runs_cap; i++) runs_out[i] = runs[i];
   return st;
 }
+
+// clust-mst --fast --dedup-dist / --reps-per-cluster on the host (src/sub_command.cpp:2089-2103): the clusters of the forest
+// (generate_cluster_with_bfs), node_to_rep[n], the candidates and the representatives of every cluster as flat lists with
+// offsets (cand_off / reps_off: clusters + 1 entries, at most n + 1; the lists at most n ids).  Returns the cluster count,
+// -1 if the edges with dist <= dedup_dist are not a forest.
+int rtch_dedup_reps(int n, const rtc_edge* forest, long m, const uint64_t* seq_len, double dedup_dist, int k, int threads,
+                    int* node_to_rep, int* cand, int* cand_off, int* reps, int* reps_off) {
+  const std::vector<rtc_edge> f(forest, forest + m);
+  const std::vector<uint64_t> lens(seq_len, seq_len + n);
+  std::vector<int> rep;
+  if (!tree_medoids_host(n, f, dedup_dist, lens, rep, threads)) return -1;
+  const std::vector<std::vector<int>> cl = generate_cluster_with_bfs(f, n);
+  const std::vector<std::vector<int>> cd = dedup_candidates(cl, rep, dedup_dist);
+  const std::vector<std::vector<int>> rp = select_k_reps(cl, cd, f, n, rep, k);
+  for (int i = 0; i < n; i++) node_to_rep[i] = rep[i];
+  auto flat = [](const std::vector<std::vector<int>>& v, int* ids, int* off) {
+    off[0] = 0;
+    for (size_t i = 0; i < v.size(); i++) {
+      for (size_t j = 0; j < v[i].size(); j++) ids[off[i] + j] = v[i][j];
+      off[i + 1] = off[i] + (int)v[i].size();
+    }
+  };
+  flat(cd, cand, cand_off);
+  flat(rp, reps, reps_off);
+  return (int)cl.size();
+}
 }

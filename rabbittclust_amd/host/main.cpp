@@ -856,6 +856,11 @@ struct Options {
   int kmerSize = 19, sketchSize = 1000, containCompress = 1000, drlevel = 3;
   uint64_t minLen = 10000;
   bool useIndex = true;  // --inverted-index=false: the dense estimator loops (modifyMST / greedyCluster) instead of the index path
+  // clust-mst post-processing (src/main.cpp:205-209): the MST edge-length analysis, its stability, the near-duplicate groups
+  // and the representatives per cluster.  Each acts in the flows where the reference honours it and is accepted elsewhere.
+  bool autoThreshold = false, stability = false;
+  double dedupDist = -1.0;
+  int repsPerCluster = 0;
   string gpus;  // --gpus / RTC_GPUS: "all" (default), a count, or a comma list of device ordinals
 };
 
@@ -907,6 +912,10 @@ static Options parse(int argc, char** argv) {
     }
 #ifndef GREEDY_CLUST
     else if (a == "--premsted") { o.folder_path = need(i); o.has_premsted = true; }
+    else if (a == "--auto-threshold") o.autoThreshold = true;
+    else if (a == "--stability") o.stability = true;
+    else if (a == "--dedup-dist") o.dedupDist = atof(need(i));
+    else if (a == "--reps-per-cluster") o.repsPerCluster = atoi(need(i));
 #endif
     else if (a == "-h" || a == "--help") {
 #ifdef GREEDY_CLUST
@@ -919,7 +928,8 @@ static Options parse(int argc, char** argv) {
            "  --presketched DIR  --fast  --drlevel N  --gpus all|N|i,j,.. (default all visible MI355X)\n"
            "  --inverted-index=false (MinHash: the dense loops modifyMST / greedyCluster with MinHash::distance())"
 #ifndef GREEDY_CLUST
-           "  --premsted DIR  --append LIST (with --presketched/--premsted DIR)"
+           "  --premsted DIR  --append LIST (with --presketched/--premsted DIR)\n"
+           "  --auto-threshold  --stability  --dedup-dist D  --reps-per-cluster K (with --fast: <output>.dedup / .reps)"
 #else
            "  --append LIST (with --presketched DIR)  --save-rep (cluster_state.bin beside the sketches)\n"
            "  [--fast] --db FILE --build|--query|--assign|--append LIST|--stats [--top-k N] (representative database)"
@@ -931,11 +941,10 @@ static Options parse(int argc, char** argv) {
 #ifndef GREEDY_CLUST
              a == "--db" || a == "--build" || a == "--query" || a == "--assign" || a == "--stats" || a == "--top-k" || a == "--save-rep" ||
 #else
-             a == "--dense" ||
+             a == "--dense" || a == "--auto-threshold" || a == "--stability" || a == "--dedup-dist" || a == "--reps-per-cluster" ||
 #endif
               a == "--newick-tree" || a == "--phylip-tree" ||
-             a == "--nexus-tree" || a == "--linkage-matrix" || a == "--auto-threshold" || a == "--stability" ||
-             a == "--dedup-dist" || a == "--reps-per-cluster" || a == "--buildDB")
+             a == "--nexus-tree" || a == "--linkage-matrix" || a == "--buildDB")
       unsupported(a.c_str());
     else { fprintf(stderr, "ERROR: unknown option %s\n", a.c_str()); exit(1); }
   }
@@ -943,10 +952,13 @@ static Options parse(int argc, char** argv) {
 }
 
 [[maybe_unused]] static void cluster_from_mst(const vector<rtc_edge>& mst, const vector<GenomeInfo>& genomes, bool sketchByFile,
-                             const string& outputFile, double threshold) {
+                             const string& outputFile, double threshold, vector<rtc_edge>* forest_out = nullptr,
+                             vector<vector<int>>* clusters_out = nullptr) {
   vector<rtc_edge> forest = generate_forest(mst, threshold);
   vector<vector<int>> cl = generate_cluster_with_bfs(forest, (int)genomes.size());
   print_result(cl, genomes, sketchByFile, outputFile, threshold);
+  if (forest_out) *forest_out = forest;
+  if (clusters_out) *clusters_out = cl;
   cerr << "-----write the cluster result into: " << outputFile << endl;
   cerr << "-----the cluster number of: " << outputFile << " is: " << cl.size() << endl;
   g_metrics.num("clusters", (double)cl.size());
@@ -957,7 +969,8 @@ static void write_trees(const Options& o, const vector<GenomeInfo>& genomes, con
 
 // --dense noise removal (src/sub_command.cpp:3071-3103): drop the forest edges of low-density nodes, cluster again
 [[maybe_unused]] static void remove_noise_and_print(const vector<rtc_edge>& mst, const vector<GenomeInfo>& genomes, bool sketchByFile,
-                                                    const string& outputFile, double threshold, const vector<int32_t>& dense, int span) {
+                                                    const string& outputFile, double threshold, const vector<int32_t>& dense, int span,
+                                                    vector<rtc_edge>* forest_out = nullptr, vector<vector<int>>* clusters_out = nullptr) {
   vector<rtc_edge> forest = generate_forest(mst, threshold);
   vector<vector<int>> cl = generate_cluster_with_bfs(forest, (int)genomes.size());
   vector<int> noise = noise_nodes(cl, dense, span, (int)genomes.size(), threshold);
@@ -968,6 +981,39 @@ static void write_trees(const Options& o, const vector<GenomeInfo>& genomes, con
   print_result(cluster, genomes, sketchByFile, outputFileNew);
   cerr << "-----write the cluster without noise into: " << outputFileNew << endl;
   cerr << "-----the cluster number of: " << outputFileNew << " is: " << cluster.size() << endl;
+  if (forest_out) *forest_out = forest;
+  if (clusters_out) *clusters_out = cluster;
+}
+
+// --dedup-dist / --reps-per-cluster after a clustering (src/sub_command.cpp:2089-2103, :2130-2144, :2583-2597, :2624-2638):
+// <base>.dedup holds every cluster's representatives of its near-duplicate groups, <base>.reps up to K of them chosen
+// farthest-first on the forest's tree metric.  The groups' tree medoids come from rtc_tree_medoids (large groups on the GPU).
+[[maybe_unused]] static void dedup_and_reps(rtc_ctx* ctx, double dedup_dist, int reps_per_cluster, int threads, const vector<rtc_edge>& forest,
+                                            const vector<vector<int>>& clusters, const vector<GenomeInfo>& genomes, bool sketchByFile,
+                                            const string& base) {
+  if (!(dedup_dist > 0) && !(reps_per_cluster > 0)) return;
+  const int n = (int)genomes.size();
+  vector<int> node_to_rep(n);
+  for (int i = 0; i < n; i++) node_to_rep[i] = i;
+  if (dedup_dist > 0) {
+    vector<uint64_t> lens(n);  // get_seq_len (src/cluster_postprocess.cpp:13-19): the medoid ties go to the longer sequence
+    for (int i = 0; i < n; i++) lens[i] = sketchByFile ? genomes[i].totalSeqLength : (uint64_t)genomes[i].seq0.length;
+    vector<int32_t> rep(n);
+    CHECK(ctx, rtc_ctx_set_host_threads(ctx, threads));
+    CHECK(ctx, rtc_tree_medoids(ctx, (uint32_t)n, forest.data(), forest.size(), dedup_dist, lens.data(), rep.data()));
+    for (int i = 0; i < n; i++) node_to_rep[i] = rep[i];
+  }
+  const vector<vector<int>> candidates = dedup_candidates(clusters, node_to_rep, dedup_dist);
+  if (dedup_dist > 0) {
+    const string f = base + ".dedup";
+    print_result(candidates, genomes, sketchByFile, f);
+    cerr << "-----write the deduped cluster result into: " << f << endl;
+  }
+  if (reps_per_cluster > 0) {
+    const string f = base + ".reps";
+    print_result(select_k_reps(clusters, candidates, forest, n, node_to_rep, reps_per_cluster), genomes, sketchByFile, f);
+    cerr << "-----write the reps-per-cluster result into: " << f << endl;
+  }
 }
 
 [[maybe_unused]] static vector<vector<int>> clusters_from_rep_of(const vector<int32_t>& rep_of) {
@@ -1740,6 +1786,10 @@ int main(int argc, char** argv) {
     if (!load_genome_info(o.folder_path, "mst", genomes, o.is_fast, byFile)) return 1;
     if (!load_mst(o.folder_path, mst)) return 1;
     write_trees(o, genomes, mst, byFile);
+    // clust_from_mst (src/sub_command.cpp:1852-1893) runs the edge-length analysis; clust_from_mst_fast (--fast, :1760-1822)
+    // has none, so there the two flags have no effect
+    if (!o.is_fast && o.autoThreshold) auto_threshold_report(mst, (int)genomes.size(), o.outputFile, 0.05, o.stability);
+    else if (!o.is_fast && o.stability) stability_report(mst, (int)genomes.size(), o.threshold);
     cluster_from_mst(mst, genomes, byFile, o.outputFile, o.threshold);
     if (o.dense) {  // clust_from_mst with !no_dense: the stored mst.dense drives the noise pass (src/sub_command.cpp:1795-1822)
       vector<int32_t> dense; int span = 0, gn = 0;
@@ -2070,10 +2120,25 @@ int main(int argc, char** argv) {
     g_metrics.num("saveMST_s", get_sec() - t3);
   }
   write_trees(o, genomes, mst, sketchByFile);
-  cluster_from_mst(mst, genomes, sketchByFile, o.outputFile, o.threshold);
+  // the edge-length analysis: compute_kssd_clusters (--fast from genomes, src/sub_command.cpp:2032-2073) with --stability, the
+  // --presketched flows (clust_from_sketch_fast :2549-2566, clust_from_sketches :2786-2803) with min_gap_ratio 0.1 and without
+  // it; compute_clusters (MinHash from genomes) has it switched off (:3031-3032)
+  if (o.is_fast && !from_sketches) {
+    if (o.autoThreshold) auto_threshold_report(mst, (int)genomes.size(), o.outputFile, 0.05, o.stability);
+    else if (o.stability) stability_report(mst, (int)genomes.size(), o.threshold);
+  } else if (from_sketches && o.autoThreshold) {
+    auto_threshold_report(mst, (int)genomes.size(), o.outputFile, 0.1, false);
+  }
+  vector<rtc_edge> forest;
+  vector<vector<int>> clusters;
+  cluster_from_mst(mst, genomes, sketchByFile, o.outputFile, o.threshold, &forest, &clusters);
+  // --dedup-dist / --reps-per-cluster: the KSSD flows only (compute_kssd_clusters, clust_from_sketch_fast)
+  if (o.is_fast) dedup_and_reps(ctx, o.dedupDist, o.repsPerCluster, o.threads, forest, clusters, genomes, sketchByFile, o.outputFile);
   if (o.dense) {
     if (!o.noSave && !from_sketches) { save_ani(folder_path, ani); save_dense(folder_path, dense, DENSE_SPAN, (int)genomes.size()); }
-    remove_noise_and_print(mst, genomes, sketchByFile, o.outputFile, o.threshold, dense, DENSE_SPAN);
+    remove_noise_and_print(mst, genomes, sketchByFile, o.outputFile, o.threshold, dense, DENSE_SPAN, &forest, &clusters);
+    if (o.is_fast)
+      dedup_and_reps(ctx, o.dedupDist, o.repsPerCluster, o.threads, forest, clusters, genomes, sketchByFile, o.outputFile + ".removeNoise");
   }
 #endif
   const double t_end = get_sec();

@@ -1,5 +1,6 @@
 // rtc_host.cpp -- host side of the drop-in (see rtc_host.h).  Plain C++17 + zlib; no GPU code.
 #include "rtc_host.h"
+#include "../csrc/rtc_tree_medoid.h"
 
 #include <ctype.h>
 #include <dlfcn.h>
@@ -26,6 +27,7 @@
 #include <fstream>
 #include <iomanip>
 #include <iostream>
+#include <limits>
 #include <queue>
 
 namespace rtc {
@@ -1849,6 +1851,391 @@ void print_result(const std::vector<std::vector<int>>& cluster, const std::vecto
     fprintf(fp, "\n");
   }
   fclose(fp);
+}
+
+// ---- --auto-threshold / --stability (src/MST.cpp:1743-2376) ----
+EdgeLengthStats edge_length_stats(const std::vector<rtc_edge>& mst) {  // analyzeEdgeLengthDistribution, :1742-1816
+  EdgeLengthStats s;
+  for (const rtc_edge& e : mst) if (e.dist > 1e-10) s.sorted_distances.push_back(e.dist);  // zero edges (identical genomes) left out
+  std::vector<double>& d = s.sorted_distances;
+  std::sort(d.begin(), d.end());
+  const int n = (int)d.size();
+  if (n == 0) return s;
+  s.min_dist = d[0];
+  s.max_dist = d[n - 1];
+  if (n == 1) { s.median_dist = s.mean_dist = s.q1_dist = s.q3_dist = d[0]; return s; }
+  s.median_dist = n % 2 == 0 ? (d[n / 2 - 1] + d[n / 2]) / 2.0 : d[n / 2];
+  s.q1_dist = d[std::max(0, n / 4)];
+  s.q3_dist = d[std::min(n - 1, 3 * n / 4)];
+  double sum = 0.0;
+  for (double x : d) sum += x;
+  s.mean_dist = sum / n;
+  double var = 0.0;
+  for (double x : d) { const double dx = x - s.mean_dist; var += dx * dx; }
+  s.std_dev = sqrt(var / n);
+  return s;
+}
+
+StabilityResult threshold_stability(const std::vector<rtc_edge>& mst, double threshold, int num_vertices, double epsilon,
+                                    int num_samples, int min_near_edges) {  // computeThresholdStability, :1827-1955
+  StabilityResult r;
+  if (num_vertices <= 0 || mst.empty()) return r;
+  // the window [threshold - eps, threshold + eps] grows by 1.5x until it holds min_near_edges edges or eps passes threshold / 2
+  double lo = std::max(0.0, threshold - epsilon), hi = threshold + epsilon;
+  const double eps_max = threshold * 0.5;
+  std::vector<double> near;
+  for (double eps = epsilon; near.size() < (size_t)min_near_edges && eps <= eps_max;) {
+    lo = std::max(0.0, threshold - eps);
+    hi = threshold + eps;
+    near.clear();
+    for (const rtc_edge& e : mst) if (e.dist >= lo && e.dist <= hi) near.push_back(e.dist);
+    if (near.size() < (size_t)min_near_edges) eps *= 1.5;
+  }
+  r.near_edge_count = (int)near.size();
+  if (near.empty()) { r.overall = r.split = r.merge = 1.0; return r; }
+  std::sort(near.begin(), near.end());
+  const double step = num_samples > 1 ? (hi - lo) / (num_samples - 1) : 0.0;
+  double all = 0.0, split = 0.0, merge = 0.0;
+  int n_all = 0, n_split = 0, n_merge = 0;
+  for (int k = 0; k < num_samples; k++) {
+    const double t = lo + k * step;
+    if (t < 0.0) continue;
+    // consistency = share of the near edges that stay on their side: those in (min(t, threshold), max(t, threshold)] flip
+    double c = 1.0;
+    if (!(fabs(t - threshold) < 1e-10)) {
+      const auto a = std::upper_bound(near.begin(), near.end(), std::min(threshold, t));
+      const auto b = std::upper_bound(near.begin(), near.end(), std::max(threshold, t));
+      c = (double)((int)near.size() - (int)(b - a)) / near.size();
+    }
+    all += c; n_all++;
+    if (t < threshold) { split += c; n_split++; }
+    else if (t > threshold) { merge += c; n_merge++; }
+  }
+  if (n_all > 0) r.overall = all / n_all;
+  if (n_split > 0) r.split = split / n_split;
+  if (n_merge > 0) r.merge = merge / n_merge;
+  r.overall = std::min(r.split, r.merge);
+  return r;
+}
+
+namespace {
+const char* gap_level(double t) {  // :2063-2077 (and the percentile candidates, :2137-2151)
+  return t < 0.001 ? "identical/near-identical" : t < 0.005 ? "strain/subspecies" : t < 0.01 ? "strain" : t < 0.03 ? "species"
+       : t < 0.1 ? "genus" : t < 0.2 ? "family" : "higher";
+}
+// the stability fields and the cluster count of a candidate (:2088-2105): cluster count whenever the vertex count is known
+void fill_candidate(ThresholdCandidate& c, const std::vector<rtc_edge>& mst, bool enable_stability, int num_vertices) {
+  if (num_vertices <= 0) return;
+  if (enable_stability) {
+    const StabilityResult s = threshold_stability(mst, c.threshold, num_vertices, 0.01, 5, 100);
+    c.stability_score = s.overall; c.stability_split = s.split; c.stability_merge = s.merge; c.near_edge_count = s.near_edge_count;
+  }
+  c.cluster_count = (int)generate_cluster_with_bfs(generate_forest(mst, c.threshold), num_vertices).size();
+}
+}  // namespace
+
+std::vector<ThresholdCandidate> threshold_candidates(const std::vector<rtc_edge>& mst, int max_candidates, double min_gap_ratio,
+                                                     bool enable_stability, int num_vertices) {  // findThresholdCandidates, :1957-2178
+  std::vector<ThresholdCandidate> out;
+  if (mst.size() < 2) return out;
+  const EdgeLengthStats st = edge_length_stats(mst);
+  const std::vector<double>& d = st.sorted_distances;
+  const int n = (int)d.size();
+  const double range = st.max_dist - st.min_dist;
+  if (range <= 1e-10) {  // one distance only: the median, with the coarser level scale of :1990-1998
+    ThresholdCandidate c;
+    c.threshold = st.median_dist;
+    c.confidence = 0.5;
+    c.level = c.threshold < 0.01 ? "strain" : c.threshold < 0.03 ? "species" : c.threshold < 0.1 ? "genus" : "higher";
+    fill_candidate(c, mst, enable_stability, num_vertices);
+    out.push_back(c);
+    return out;
+  }
+  const double min_gap = range * min_gap_ratio;
+  std::vector<std::pair<double, int>> gaps;  // (gap, index of the larger distance)
+  for (int i = 1; i < n; i++) {
+    const double gap = d[i] - d[i - 1];
+    if (gap > min_gap) gaps.push_back({gap, i});
+  }
+  // largest first; equal gaps in the order std::sort leaves them, as in the reference (:2040-2043)
+  std::sort(gaps.begin(), gaps.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first > b.first; });
+  for (int i = 0; i < std::min(max_candidates, (int)gaps.size()); i++) {
+    ThresholdCandidate c;
+    c.edge_index = gaps[i].second;
+    c.threshold = d[c.edge_index];
+    c.gap_score = gaps[i].first;
+    c.confidence = std::min(1.0, gaps[i].first / range * 10.0);
+    c.level = gap_level(c.threshold);
+    fill_candidate(c, mst, enable_stability, num_vertices);
+    out.push_back(c);
+  }
+  // Q1 (unless below 0.001), median and Q3 where they lie strictly inside the range and not within min_gap / 2 of a candidate
+  std::vector<double> pct;
+  if (st.q1_dist >= 0.001) pct.push_back(st.q1_dist);
+  pct.push_back(st.median_dist);
+  pct.push_back(st.q3_dist);
+  for (double t : pct) {
+    if (t < 0.001) continue;
+    bool close = false;
+    for (const ThresholdCandidate& c : out) if (fabs(c.threshold - t) < min_gap * 0.5) { close = true; break; }
+    if (close || !(t > st.min_dist && t < st.max_dist)) continue;
+    ThresholdCandidate c;
+    c.threshold = t;
+    c.confidence = 0.4;
+    c.level = gap_level(t);
+    fill_candidate(c, mst, enable_stability, num_vertices);
+    out.push_back(c);
+  }
+  std::sort(out.begin(), out.end(), [](const ThresholdCandidate& a, const ThresholdCandidate& b) { return a.threshold < b.threshold; });
+  return out;
+}
+
+// selectOptimalThreshold, :2180-2269.  Where the reference leaves fields of its result uninitialised (the empty list, the
+// fallback when no candidate reaches 0.001) they hold ThresholdCandidate's defaults here: no gap, edge index -1, stability
+// 0.5, no cluster count.
+ThresholdCandidate select_optimal_threshold(const std::vector<ThresholdCandidate>& candidates, const std::vector<rtc_edge>& mst) {
+  ThresholdCandidate opt;
+  if (candidates.empty()) { opt.threshold = 0.05; opt.confidence = 0.0; opt.level = "unknown"; return opt; }
+  double best = -1.0;
+  bool in_range = false;
+  for (const ThresholdCandidate& c : candidates) {
+    if (c.threshold < 0.001) continue;
+    double score = c.confidence;
+    if (c.threshold >= 0.01 && c.threshold <= 0.1) { score *= 2.0; in_range = true; }
+    else if (c.threshold >= 0.001 && c.threshold < 0.01) score *= 1.2;
+    else if (c.threshold > 0.1 && c.threshold <= 0.2) score *= 1.1;
+    if (c.gap_score > 0.0) score += c.gap_score * 20.0;
+    if (score > best) { best = score; opt = c; }
+  }
+  if (!in_range && best < 0) {
+    const double med = edge_length_stats(mst).median_dist;
+    if (med >= 0.01 && med <= 0.2) {
+      opt.threshold = med; opt.confidence = 0.4;
+      opt.level = med < 0.03 ? "species" : med < 0.1 ? "genus" : "family";
+    } else {
+      opt.threshold = 0.05; opt.confidence = 0.3; opt.level = "genus";
+    }
+    opt.gap_score = 0.0; opt.edge_index = -1;
+  }
+  return opt;
+}
+
+void print_threshold_analysis(const std::vector<rtc_edge>& mst, const EdgeLengthStats& st, const std::vector<ThresholdCandidate>& cands,
+                              const ThresholdCandidate& opt, const std::string& file) {  // printThresholdAnalysis, :2271-2376
+  FILE* fp = fopen(file.c_str(), "w");
+  if (!fp) { std::cerr << "ERROR: printThresholdAnalysis(), cannot write file: " << file << std::endl; return; }
+  fprintf(fp, "# Automatic Threshold Selection Analysis\n# Based on MST Edge Length Distribution\n# ===========================================\n\n");
+  fprintf(fp, "## Edge Length Statistics\n");
+  fprintf(fp, "Total edges: %zu\n", mst.size());
+  fprintf(fp, "Min distance: %.6f\n", st.min_dist);
+  fprintf(fp, "Max distance: %.6f\n", st.max_dist);
+  fprintf(fp, "Mean distance: %.6f\n", st.mean_dist);
+  fprintf(fp, "Median distance: %.6f\n", st.median_dist);
+  fprintf(fp, "Q1 (25%%): %.6f\n", st.q1_dist);
+  fprintf(fp, "Q3 (75%%): %.6f\n", st.q3_dist);
+  fprintf(fp, "Standard deviation: %.6f\n", st.std_dev);
+  fprintf(fp, "Range: %.6f\n\n", st.max_dist - st.min_dist);
+  fprintf(fp, "## Optimal Threshold (Recommended)\n");
+  fprintf(fp, "Threshold: %.6f\n", opt.threshold);
+  fprintf(fp, "Confidence: %.3f\n", opt.confidence);
+  if (opt.cluster_count > 0 || opt.stability_score != 0.5) {
+    fprintf(fp, "Stability (overall): %.3f\n", opt.stability_score);
+    if (opt.stability_split != 0.5 || opt.stability_merge != 0.5) {
+      fprintf(fp, "  - Split sensitivity: %.3f (stability when threshold decreases)\n", opt.stability_split);
+      fprintf(fp, "  - Merge sensitivity: %.3f (stability when threshold increases)\n", opt.stability_merge);
+    }
+    if (opt.near_edge_count > 0) fprintf(fp, "  - Near edges evaluated: %d\n", opt.near_edge_count);
+    fprintf(fp, "Number of clusters: %d\n", opt.cluster_count);
+  }
+  fprintf(fp, "Suggested level: %s\n", opt.level.c_str());
+  if (opt.edge_index >= 0) {
+    fprintf(fp, "Edge index: %d\nGap score: %.6f\n", opt.edge_index, opt.gap_score);
+    fprintf(fp, "Source: gap-based detection (natural breakpoint in edge distribution)\n");
+  } else {
+    fprintf(fp, "Source: percentile-based (median/quartile, no significant gap detected)\n");
+    fprintf(fp, "Note: This threshold is based on distribution statistics, not natural breakpoints.\n");
+    fprintf(fp, "      Consider manual adjustment (e.g., 0.01-0.05 for species/genus level) if needed.\n");
+  }
+  fprintf(fp, "\n## All Candidate Thresholds\n");
+  bool wide = false;  // stability columns once any candidate carries a cluster count or a stability score
+  for (const ThresholdCandidate& c : cands) if (c.cluster_count > 0 || c.stability_score != 0.5) { wide = true; break; }
+  if (wide) {
+    fprintf(fp, "# Threshold\tConfidence\tStability_Overall\tStability_Split\tStability_Merge\tNear_Edges\tClusters\tLevel\tGap_Score\tEdge_Index\n");
+    for (const ThresholdCandidate& c : cands)
+      fprintf(fp, "%.6f\t%.3f\t%.3f\t%.3f\t%.3f\t%d\t%d\t%s\t%.6f\t%d\n", c.threshold, c.confidence, c.stability_score, c.stability_split,
+              c.stability_merge, c.near_edge_count, c.cluster_count, c.level.c_str(), c.gap_score, c.edge_index);
+  } else {
+    fprintf(fp, "# Threshold\tConfidence\tLevel\tGap_Score\tEdge_Index\n");
+    for (const ThresholdCandidate& c : cands)
+      fprintf(fp, "%.6f\t%.3f\t%s\t%.6f\t%d\n", c.threshold, c.confidence, c.level.c_str(), c.gap_score, c.edge_index);
+  }
+  fprintf(fp, "\n## Edge Length Distribution (sorted)\n# Index\tDistance\n");
+  for (size_t i = 0; i < st.sorted_distances.size(); i++) fprintf(fp, "%zu\t%.6f\n", i, st.sorted_distances[i]);
+  fclose(fp);
+  std::cerr << "-----write threshold analysis into: " << file << std::endl;
+}
+
+// src/sub_command.cpp:1852-1879 (clust_from_mst), :2032-2059 (compute_kssd_clusters), :2549-2566 / :2786-2803 (--presketched)
+void auto_threshold_report(const std::vector<rtc_edge>& mst, int num_vertices, const std::string& outputFile, double min_gap_ratio,
+                           bool stability) {
+  if (mst.empty()) { std::cerr << "-----WARNING: MST is empty, cannot perform automatic threshold selection" << std::endl; return; }
+  if (mst.size() < 2) {
+    std::cerr << "-----WARNING: MST has only " << mst.size() << " edge(s), cannot perform automatic threshold selection" << std::endl;
+    return;
+  }
+  std::cerr << "-----analyzing MST edge length distribution for automatic threshold selection..." << std::endl;
+  if (stability) std::cerr << "-----stability evaluation enabled (this may take longer)..." << std::endl;
+  const EdgeLengthStats st = edge_length_stats(mst);
+  const std::vector<ThresholdCandidate> cands = threshold_candidates(mst, 5, min_gap_ratio, stability, num_vertices);
+  const ThresholdCandidate opt = select_optimal_threshold(cands, mst);
+  const std::string file = outputFile + ".threshold_analysis.txt";
+  print_threshold_analysis(mst, st, cands, opt, file);
+  std::cerr << "-----optimal threshold: " << opt.threshold << " (confidence: " << opt.confidence << ", suggested level: " << opt.level << ")"
+            << std::endl;
+  if (stability) {
+    std::cerr << "-----stability: " << opt.stability_score << " (split: " << opt.stability_split << ", merge: " << opt.stability_merge << ")"
+              << std::endl;
+    std::cerr << "-----near edges: " << opt.near_edge_count << ", clusters: " << opt.cluster_count << std::endl;
+  }
+  std::cerr << "-----threshold analysis written to: " << file << std::endl;
+}
+
+// src/sub_command.cpp:1880-1892, :2060-2072: --stability without --auto-threshold, at the user's threshold
+void stability_report(const std::vector<rtc_edge>& mst, int num_vertices, double threshold) {
+  if (mst.empty()) { std::cerr << "-----WARNING: MST is empty, cannot evaluate threshold stability" << std::endl; return; }
+  std::cerr << "-----evaluating stability for threshold: " << threshold << "..." << std::endl;
+  const StabilityResult s = threshold_stability(mst, threshold, num_vertices, 0.01, 5, 100);
+  const size_t nc = generate_cluster_with_bfs(generate_forest(mst, threshold), num_vertices).size();
+  std::cerr << "-----threshold stability: " << s.overall << " (split: " << s.split << ", merge: " << s.merge << ")" << std::endl;
+  std::cerr << "-----near edges evaluated: " << s.near_edge_count << ", clusters: " << nc << std::endl;
+}
+
+// ---- --dedup-dist / --reps-per-cluster (src/cluster_postprocess.cpp) ----
+bool tree_medoids_host(int n, const std::vector<rtc_edge>& forest, double dedup_dist, const std::vector<uint64_t>& seq_len,
+                       std::vector<int>& node_to_rep, int threads) {
+  node_to_rep.resize(n);
+  if (!(dedup_dist > 0)) { for (int i = 0; i < n; i++) node_to_rep[i] = i; return true; }
+  rtc_tm::Groups G;
+  if (!rtc_tm::build_groups(n, forest.data(), forest.size(), dedup_dist, G)) return false;
+  std::vector<uint32_t> all(G.count());
+  for (size_t g = 0; g < all.size(); g++) all[g] = (uint32_t)g;
+  std::vector<double> tot(G.mem.size());
+  rtc_tm::totals_host(G, all, tot.data(), threads);
+  rtc_tm::assign(G, n, tot.data(), seq_len.empty() ? nullptr : seq_len.data(), node_to_rep.data());
+  return true;
+}
+
+std::vector<std::vector<int>> dedup_candidates(const std::vector<std::vector<int>>& clusters, const std::vector<int>& node_to_rep,
+                                               double dedup_dist) {
+  if (!(dedup_dist > 0)) return clusters;
+  const int n = (int)node_to_rep.size();
+  std::vector<std::vector<int>> out;
+  out.reserve(clusters.size());
+  for (const std::vector<int>& cl : clusters) {
+    std::vector<int> c;
+    for (int v : cl) {
+      if (v < 0 || v >= n) continue;
+      c.push_back(node_to_rep[v] < 0 ? v : node_to_rep[v]);
+    }
+    std::sort(c.begin(), c.end());
+    c.erase(std::unique(c.begin(), c.end()), c.end());
+    out.push_back(std::move(c));
+  }
+  return out;
+}
+
+namespace {
+// tree distances from `s` over a component's local adjacency (-1: not reached); the stack walk of distances_from, :33-54
+void tree_dist(int s, const std::vector<std::vector<std::pair<int, double>>>& adj, std::vector<double>& dist, std::vector<int>& parent,
+               std::vector<int>& stack) {
+  dist.assign(adj.size(), -1.0);
+  parent.assign(adj.size(), -1);
+  stack.clear();
+  dist[s] = 0.0; parent[s] = s;
+  stack.push_back(s);
+  while (!stack.empty()) {
+    const int u = stack.back();
+    stack.pop_back();
+    for (const auto& vw : adj[u]) {
+      if (vw.first == parent[u]) continue;
+      parent[vw.first] = u;
+      dist[vw.first] = dist[u] + vw.second;
+      stack.push_back(vw.first);
+    }
+  }
+}
+}  // namespace
+
+std::vector<std::vector<int>> select_k_reps(const std::vector<std::vector<int>>& clusters, const std::vector<std::vector<int>>& candidates,
+                                            const std::vector<rtc_edge>& forest, int n, const std::vector<int>& node_to_rep, int k) {
+  std::vector<std::vector<int>> reps(clusters.size());
+  if (k <= 0) return reps;
+  std::vector<std::vector<std::pair<int, double>>> adj(n);
+  for (const rtc_edge& e : forest) {
+    if (e.preNode < 0 || e.preNode >= n || e.sufNode < 0 || e.sufNode >= n) continue;
+    adj[e.preNode].push_back({e.sufNode, e.dist});
+    adj[e.sufNode].push_back({e.preNode, e.dist});
+  }
+  std::vector<int> local(n, -1);  // node -> position in the current cluster
+  std::vector<double> dist;
+  std::vector<int> parent, stack;
+  for (size_t ci = 0; ci < clusters.size(); ci++) {
+    const std::vector<int>& comp = clusters[ci];
+    const std::vector<int>& cand = candidates[ci];
+    if (cand.empty()) continue;
+    if ((int)cand.size() <= k) { reps[ci] = cand; continue; }
+    const int m = (int)comp.size();
+    for (int i = 0; i < m; i++) local[comp[i]] = i;
+    std::vector<std::vector<std::pair<int, double>>> ladj(m);
+    for (int i = 0; i < m; i++)
+      for (const auto& vw : adj[comp[i]]) if (local[vw.first] >= 0) ladj[i].push_back({local[vw.first], vw.second});
+    auto farthest = [&](int s) {  // first of the largest distances (:166-178)
+      tree_dist(s, ladj, dist, parent, stack);
+      int far = s; double best = -1.0;
+      for (int i = 0; i < m; i++) if (dist[i] > best) { best = dist[i]; far = i; }
+      return far;
+    };
+    const int u = farthest(0), v = farthest(u);  // the diameter's ends (:234-237)
+    std::vector<int> cand_sorted(cand);
+    std::sort(cand_sorted.begin(), cand_sorted.end());
+    auto is_cand = [&](int x) { return std::binary_search(cand_sorted.begin(), cand_sorted.end(), x); };
+    auto to_cand = [&](int node) {  // map_to_candidate, :244-249
+      const int r = node >= 0 && node < (int)node_to_rep.size() ? node_to_rep[node] : node;
+      if (is_cand(r)) return r;
+      if (is_cand(node)) return node;
+      return cand[0];
+    };
+    std::vector<int> chosen;
+    auto taken = [&](int x) { return std::find(chosen.begin(), chosen.end(), x) != chosen.end(); };
+    const int r1 = to_cand(comp[u]);
+    chosen.push_back(r1);
+    if ((int)chosen.size() < k) { const int r2 = to_cand(comp[v]); if (!taken(r2)) chosen.push_back(r2); }
+    std::vector<double> min_dist(m, std::numeric_limits<double>::infinity());
+    auto add = [&](int rep) {
+      if (rep < 0 || rep >= n || local[rep] < 0) return;
+      tree_dist(local[rep], ladj, dist, parent, stack);
+      for (int i = 0; i < m; i++) if (dist[i] >= 0.0 && dist[i] < min_dist[i]) min_dist[i] = dist[i];
+    };
+    for (int r : chosen) add(r);
+    std::vector<int> cand_local;
+    for (int c : cand) if (c >= 0 && c < n && local[c] >= 0) cand_local.push_back(local[c]);
+    while ((int)chosen.size() < k) {  // farthest-first: the candidate farthest from every chosen one (:280-298)
+      int best_i = -1; double best = -1.0;
+      for (int li : cand_local) {
+        if (taken(to_cand(comp[li]))) continue;
+        if (min_dist[li] > best) { best = min_dist[li]; best_i = li; }
+      }
+      if (best_i < 0) break;
+      const int next = to_cand(comp[best_i]);
+      if (taken(next)) break;
+      chosen.push_back(next);
+      add(next);
+    }
+    for (int i = 0; i < m; i++) local[comp[i]] = -1;
+    std::sort(chosen.begin(), chosen.end());
+    reps[ci] = std::move(chosen);
+  }
+  return reps;
 }
 
 std::string current_date_time() {

@@ -169,6 +169,47 @@ void print_phylip_tree(const std::vector<GenomeInfo>& g, const std::vector<rtc_e
 void print_nexus_tree(const std::vector<GenomeInfo>& g, const std::vector<rtc_edge>& mst, bool sketchByFile, const std::string& output);
 void print_linkage_matrix(int n, const std::vector<rtc_edge>& mst, const std::string& output);  // c1 \t c2 \t dist \t size
 
+// ---- clust-mst --auto-threshold / --stability: the MST edge-length analysis (src/MST.cpp:1743-2376, structs src/MST.h:77-100) ----
+struct EdgeLengthStats {
+  double min_dist = 0, max_dist = 0, median_dist = 0, q1_dist = 0, q3_dist = 0, mean_dist = 0, std_dev = 0;
+  std::vector<double> sorted_distances;  // the distances above 1e-10, ascending
+};
+struct ThresholdCandidate {
+  double threshold = 0, gap_score = 0.0;
+  int edge_index = -1;
+  double confidence = 0;
+  std::string level;
+  double stability_score = 0.5, stability_split = 0.5, stability_merge = 0.5;
+  int cluster_count = 0, near_edge_count = 0;
+};
+struct StabilityResult { double overall = 0.5, split = 0.5, merge = 0.5; int near_edge_count = 0; };
+EdgeLengthStats edge_length_stats(const std::vector<rtc_edge>& mst);
+StabilityResult threshold_stability(const std::vector<rtc_edge>& mst, double threshold, int num_vertices, double epsilon = 0.01,
+                                    int num_samples = 5, int min_near_edges = 100);
+std::vector<ThresholdCandidate> threshold_candidates(const std::vector<rtc_edge>& mst, int max_candidates, double min_gap_ratio,
+                                                     bool enable_stability, int num_vertices);
+ThresholdCandidate select_optimal_threshold(const std::vector<ThresholdCandidate>& candidates, const std::vector<rtc_edge>& mst);
+void print_threshold_analysis(const std::vector<rtc_edge>& mst, const EdgeLengthStats& stats,
+                              const std::vector<ThresholdCandidate>& candidates, const ThresholdCandidate& optimal, const std::string& file);
+// The call-site blocks: --auto-threshold (<output>.threshold_analysis.txt and the stderr lines; min_gap_ratio 0.05 with
+// --stability honoured in clust_from_mst / compute_kssd_clusters, 0.1 without it in the --presketched flows) and --stability
+// alone (stderr only).  Neither changes the clustering threshold.
+void auto_threshold_report(const std::vector<rtc_edge>& mst, int num_vertices, const std::string& outputFile, double min_gap_ratio,
+                           bool stability);
+void stability_report(const std::vector<rtc_edge>& mst, int num_vertices, double threshold);
+
+// ---- clust-mst --fast --dedup-dist / --reps-per-cluster (src/cluster_postprocess.cpp) ----
+// The host path of rtc_tree_medoids (the same code: csrc/rtc_tree_medoid.h) on `threads` threads; false if the edges with
+// dist <= dedup_dist are not a forest.
+bool tree_medoids_host(int n, const std::vector<rtc_edge>& forest, double dedup_dist, const std::vector<uint64_t>& seq_len,
+                       std::vector<int>& node_to_rep, int threads);
+// the candidates of every cluster: its members' representatives, unique, ascending (:143-155); dedup_dist <= 0: the clusters
+std::vector<std::vector<int>> dedup_candidates(const std::vector<std::vector<int>>& clusters, const std::vector<int>& node_to_rep,
+                                               double dedup_dist);
+// select_k_reps_per_cluster_tree (:192-329): farthest-first over the forest's tree metric, up to k per cluster
+std::vector<std::vector<int>> select_k_reps(const std::vector<std::vector<int>>& clusters, const std::vector<std::vector<int>>& candidates,
+                                            const std::vector<rtc_edge>& forest, int n, const std::vector<int>& node_to_rep, int k);
+
 std::string current_date_time();  // src/common.hpp:36-44
 
 // Time the parser threads spent inside gzip decompression (libdeflate or zlib), summed over threads, and the bytes it produced
