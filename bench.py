@@ -17,10 +17,15 @@ command lines' 2-bit staging format (--staging packed, north_star's "packed sequ
 `python bench.py --gpus N` with N > 1 and no torchrun environment re-launches itself under torch.distributed.run with N
 ranks (one per GPU, backend nccl = RCCL); `n_gpus` in the output is the world size the process group reports.
 
-Output (rank 0, stdout): the compact headline object (< 4 KB: metric, value, roofline, cpu_baseline, phase_ms and the
-scalars lifted from the extra workloads) is printed as soon as it is known, the extra workloads follow as ONE line
-{"extra": ...} (also written to bench_extra.json), and the compact headline -- now with the extras' scalars -- is
-printed again as the LAST line.  README.md ("Reading the bench line") explains every field; no prose travels in the line.
+A plain run sets up, warms up, times the steps and prints its result.  `--full` adds everything else the benchmark measures,
+after the timed region: the CPU baseline on a bounded sample and, at N=1, the extra workloads (the other BASELINE shapes,
+the dense regime, the north-star jobs on one GPU, the command lines from FASTA files).
+
+Output (rank 0, stdout): a plain run prints ONE line {"headline": ...} with the full headline object, then the compact
+headline (< 4 KB: metric, value, roofline, cpu_baseline, phase_ms) as the LAST line.  With --full the compact headline is
+printed first, as soon as it is known, the extra workloads follow in the {"headline": ..., "extra": ...} line (also written
+to bench_extra.json), and the compact headline -- now with the extras' scalars -- is printed again as the LAST line.
+README.md ("Reading the bench line") explains every field; no prose travels in the line.
 `--dump-outputs DIR` also writes what the last timed step computed as DIR/*.npy (dump_outputs); the synthetic inputs are
 seeded, so two builds run with the same arguments can be compared output for output.
 """
@@ -68,9 +73,11 @@ def parse():
     ap.add_argument("--comm", choices=("native", "torch"), default="native",
                     help="N>1 collectives: the C ABI's own RCCL communicator (rtc_comm_*, what the C++ hosts use) "
                          "or torch.distributed's; both are RCCL over xGMI (strong scaling is native only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the CPU baseline and (N=1) the extra workloads; a plain run does neither")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extra", action="store_true",
-                    help="N=1 only: skip the extra workloads timed after the headline region")
+                    help="--full, N=1 only: skip the extra workloads timed after the headline region")
     ap.add_argument("--extra-steps", type=int, default=3)
     ap.add_argument("--only", choices=tuple(n for n, _ in EXTRAS), default=None,
                     help="run ONE of the extra workloads alone and print {\"extra\": {...}} (the profile collection's driver)")
@@ -79,7 +86,7 @@ def parse():
                     help="extra.cli: one more MinHash run of the command line on this many genomes when /dev/shm has the room (0: skip)")
     ap.add_argument("--cpu-sample-genomes", type=int, default=0, help="0 = 1024 (SURVEY 8d: >= 1k genomes)")
     ap.add_argument("--cpu-sample-sketches", type=int, default=8000)
-    ap.add_argument("--extra-json", default=os.path.join(ROOT, "bench_extra.json"), help="where the full extras object is also written")
+    ap.add_argument("--extra-json", default=os.path.join(ROOT, "bench_extra.json"), help="--full: where the full extras object is also written")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one returned -- the forest's edge.mst records, every sketch's "
                          "size and a fixed sample of the sketch rows -- as DIR/<name>.npy (float64), for comparing two builds")
@@ -1088,6 +1095,7 @@ def main():
     mode = args.mode
     scaling = args.scaling or ("strong" if world > 1 else "weak")
     packed = args.staging == "packed"
+    want_cpu = args.full and not args.no_cpu_baseline
     length = args.length or NORTH_STAR[mode]["L"]
     shuffled = None
     if mode == "kssd":
@@ -1146,9 +1154,10 @@ def main():
         seq = ctx.synth_genomes(desc, off)
         ctx.sync()
         ns_cpu = min(args.cpu_sample_genomes or 1024, n_local)
-        cpu_seq, cpu_off = seq, off
+        cpu_seq, cpu_off = (seq, off) if want_cpu else (None, None)
         if packed:  # the batch as the command lines hand it over; packing is the host parser's work, outside the timed region
-            cpu_seq = seq[: ns_cpu * length].clone()  # the characters of the CPU baseline's sample
+            if want_cpu:
+                cpu_seq = seq[: ns_cpu * length].clone()  # the characters of the CPU baseline's sample
             pb = api.pack_staging(seq, int(off[-1]))
             del seq
             seq = [(pb, off)] if isinstance(comm, pipeline.NativeComm) else pb  # behind the C ABI: the sharded packed entry points
@@ -1259,7 +1268,7 @@ def main():
                 "phase_ms_max": {k: max(r[k] for r in ranks_ph) for k in keys},
                 "boruvka_rounds": rounds,
                 "all_reduce_bytes_per_step": rounds * n_total * (8 if s_fixed else 16)}
-        if not args.no_cpu_baseline:
+        if want_cpu:
             try:
                 if cpu_seq is None:  # strong scaling: rank 0's first genomes again as characters
                     ns_cpu = min(args.cpu_sample_genomes or 1024, n_local)
@@ -1276,9 +1285,12 @@ def main():
             except Exception as e:  # the baseline is a reported extra; never lose the GPU line
                 line["cpu_baseline"] = {"value": None, "error": repr(e)}
         del cpu_seq
-        # ---- the evidence: the compact headline at once, the extras after it, the compact headline again as the LAST line ----
-        emit(compact_line(line))
-        want_extra = world == 1 and dist is None and not args.no_extra and mode == "minhash" and not args.genomes and not args.length and scaling == "weak"
+        # ---- the evidence.  --full: the compact headline at once and the extras after it; then (every run) the full object and
+        # the compact headline -- with the extras' scalars, if any -- as the LAST line ----
+        if args.full:
+            emit(compact_line(line))
+        want_extra = (args.full and world == 1 and dist is None and not args.no_extra and mode == "minhash" and not args.genomes
+                      and not args.length and scaling == "weak")
         extras = None
         if want_extra:
             seq = batches = pb = None
@@ -1294,11 +1306,12 @@ def main():
             extras = extra_workloads(args, ctx, api, pipeline)
         full = sanitize({"headline": line, "extra": extras} if extras is not None else {"headline": line})
         emit(full)
-        try:
-            with open(args.extra_json, "w") as f:
-                json.dump(full, f, indent=1)
-        except OSError as e:
-            print(f"bench.py: could not write {args.extra_json}: {e}", file=sys.stderr)
+        if args.full:
+            try:
+                with open(args.extra_json, "w") as f:
+                    json.dump(full, f, indent=1)
+            except OSError as e:
+                print(f"bench.py: could not write {args.extra_json}: {e}", file=sys.stderr)
         emit(compact_line(line, extras))
     if dist is not None:
         dist.barrier()

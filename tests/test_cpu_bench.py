@@ -95,3 +95,13 @@ def test_dump_outputs_writes_the_last_step_exactly(tmp_path):
     bench.dump_outputs(str(tmp_path / "big"), big)
     rows = np.load(tmp_path / "big" / "sketch_sample_rows.npy")
     assert 0 < len(rows) < 200 and len(rows) * 40_000 * 16 <= bench.DUMP_SAMPLE_BYTES
+
+
+def test_full_is_off_by_default(monkeypatch):
+    """a plain `bench.py --gpus 1 --steps N --warmup W` runs no CPU baseline and no extra workload: both wait for --full"""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = bench.parse()
+    assert not a.full and (a.gpus, a.steps, a.warmup) == (1, 20, 5)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert bench.parse().full

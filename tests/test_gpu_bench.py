@@ -1,9 +1,9 @@
 """bench.py end to end on the GPU box.  The driver reads ONE thing of a round: the last stdout line of `bench.py`.  So the
 tests here are about the shape of the evidence as much as about its content: the last line parses, is the compact headline
 (< 4 096 bytes) with `roofline` and `cpu_baseline`, no string anywhere in any printed line is long or looks like an array
-that slipped into an f-string, every extra workload ran WITHOUT an error entry (an extra that breaks is reported as
-{"error": ...} so that it never costs the headline -- which also means nobody notices unless a test looks), and the
-headline is printed before the extras start."""
+that slipped into an f-string, a plain run does nothing but its timed steps, and under --full every extra workload ran
+WITHOUT an error entry (an extra that breaks is reported as {"error": ...} so that it never costs the headline -- which also
+means nobody notices unless a test looks) and the headline is printed before the extras start."""
 import json
 import os
 import re
@@ -52,14 +52,35 @@ def check_lines(stdout):
     return head, full, objs
 
 
-def test_bench_default_line_has_every_extra_without_error(ctx, tmp_path):
+def test_bench_plain_run_times_the_headline_only(ctx, tmp_path):
+    """`bench.py --steps N --warmup W` without --full: the default workload's timed steps and nothing after them -- no CPU
+    baseline, no extra workload, no extras file -- the full headline object, then the compact headline as the last line"""
+    import gc
+    import torch
+    gc.collect()
+    torch.cuda.empty_cache()
+    env = {k: v for k, v in os.environ.items() if not k.startswith("RTC_PAIR")}
+    xj = tmp_path / "bench_extra.json"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--extra-json", str(xj)],
+                       capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line, full, objs = check_lines(r.stdout)
+    assert len(objs) == 2 and list(full) == ["headline"] and full["headline"]["value"] == pytest.approx(line["value"], rel=1e-5)
+    assert line["n_gpus"] == 1 and line["steps"] == 1 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["config"]["genomes_total"] == 10000 and line["config"]["genome_length"] == 5_000_000 and line["config"]["staging"] == "packed"
+    assert line["roofline"]["kernel"].startswith("sketch_minhash_packed_kernel") and line["roofline"]["frac"] > 0
+    assert line["cpu_baseline"]["value"] is None and "extra_scalars" not in line and "extra_errors" not in line
+    assert not xj.exists()
+
+
+def test_bench_full_line_has_every_extra_without_error(ctx, tmp_path):
     import gc
     import torch
     gc.collect()
     torch.cuda.empty_cache()  # the child needs ~130 GB for the north-star extras: nothing cached by earlier tests of this process may stay
     env = {k: v for k, v in os.environ.items() if not k.startswith("RTC_PAIR")}
     xj = str(tmp_path / "bench_extra.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--extra-steps", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "0", "--extra-steps", "1",
                         "--cli-genomes", "64", "--cli-genomes-large", "128", "--cpu-sample-genomes", "32", "--cpu-sample-sketches", "2000",
                         "--extra-json", xj],
                        capture_output=True, text=True, timeout=1500, env=env)

@@ -454,7 +454,7 @@ def test_bench_kssd_mode_small(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--mode", "kssd", "--steps", "1", "--warmup", "0",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--mode", "kssd", "--steps", "1", "--warmup", "0",
                         "--genomes", "300", "--length", "300000", "--cpu-sample-genomes", "32"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]

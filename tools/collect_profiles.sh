@@ -37,16 +37,16 @@ run_section() {
 for S in $SECTIONS; do
   case $S in
     minhash)   # the judged line: BASELINE config[1], batch resident in the 2-bit staging format, every extra
-      run_section minhash --steps 5 --warmup 2 -- --steps 3 --warmup 1 --no-cpu-baseline --no-extra -- --steps 1 --warmup 0 --no-cpu-baseline --no-extra
+      run_section minhash --full --steps 5 --warmup 2 -- --steps 3 --warmup 1 --no-cpu-baseline --no-extra -- --steps 1 --warmup 0 --no-cpu-baseline --no-extra
       python $R/tools/make_pmc_json.py $OUT/minhash $TAG minhash 10000 5000000 packed > $OUT/${TAG}_pmc_traffic.json;;
     minhash_ascii)   # the same batch resident as characters
-      run_section minhash_ascii --staging ascii --steps 5 --warmup 2 --no-extra -- --staging ascii --steps 3 --warmup 1 --no-cpu-baseline --no-extra -- --staging ascii --steps 1 --warmup 0 --no-cpu-baseline --no-extra
+      run_section minhash_ascii --full --staging ascii --steps 5 --warmup 2 --no-extra -- --staging ascii --steps 3 --warmup 1 --no-cpu-baseline --no-extra -- --staging ascii --steps 1 --warmup 0 --no-cpu-baseline --no-extra
       python $R/tools/make_pmc_json.py $OUT/minhash_ascii ${TAG}_minhash_ascii minhash 10000 5000000 > $OUT/${TAG}_minhash_ascii_pmc_traffic.json;;
     kssd)
-      run_section kssd --mode kssd --staging ascii --steps 3 --warmup 1 -- --mode kssd --staging ascii --steps 3 --warmup 1 --no-cpu-baseline -- --mode kssd --staging ascii --steps 1 --warmup 0 --no-cpu-baseline
+      run_section kssd --full --mode kssd --staging ascii --steps 3 --warmup 1 -- --mode kssd --staging ascii --steps 3 --warmup 1 --no-cpu-baseline -- --mode kssd --staging ascii --steps 1 --warmup 0 --no-cpu-baseline
       python $R/tools/make_pmc_json.py $OUT/kssd ${TAG}_kssd kssd 25000 2000000 > $OUT/${TAG}_kssd_pmc_traffic.json;;
     kssd_packed)
-      run_section kssd_packed --mode kssd --steps 3 --warmup 1 -- --mode kssd --steps 3 --warmup 1 --no-cpu-baseline -- --mode kssd --steps 1 --warmup 0 --no-cpu-baseline
+      run_section kssd_packed --full --mode kssd --steps 3 --warmup 1 -- --mode kssd --steps 3 --warmup 1 --no-cpu-baseline -- --mode kssd --steps 1 --warmup 0 --no-cpu-baseline
       python $R/tools/make_pmc_json.py $OUT/kssd_packed ${TAG}_kssd_packed kssd 25000 2000000 packed > $OUT/${TAG}_kssd_packed_pmc_traffic.json;;
     greedy)
       # 50 000 prefix genomes of 0.4 .. 2 Mbp: 64 Gbp, mean length 1.28 Mbp (the "derived" per-step figures use genomes x this length)
