@@ -206,7 +206,7 @@ int rtc_pair_last_path(const rtc_ctx* ctx);
 /* Which paths this context has taken since it was created (tests and measurement): out[0] tiles the inverted join took,
  * out[1] tiles the tiled kernel took, out[2] tiles of the merge kernel, out[3] candidate lists contracted to their forest
  * between row chunks, out[4] greedy runs replayed from one global join, out[5] query blocks of greedy's block loop, out[6]
- * estimates rtc_pair_edges_dev handed back instead of a launch; out[7] reserved. */
+ * estimates rtc_pair_edges_dev handed back instead of a launch; out[7] query chunks rtc_rep_match measured. */
 int rtc_diag_counters(const rtc_ctx* ctx, uint64_t out[8]);
 /* Duration of this context's last tiled pair kernel launch (rtc_pair_last_path == 2), from HIP events recorded on the
  * stream it was launched on; waits for the launch to finish (measurement: bench.py's roofline_dist). */
@@ -423,6 +423,22 @@ int rtc_tree_medoids(rtc_ctx* ctx, uint32_t n, const rtc_edge* h_edges, uint64_t
 int rtc_dedup_last_path(const rtc_ctx* ctx);
 /* Host threads of the context's host-side work (rtc_tree_medoids' small groups); default 1. */
 int rtc_ctx_set_host_threads(rtc_ctx* ctx, int threads);
+
+/* ---- clust-mst --append against a --save-rep state ------------------------------------- */
+typedef struct { uint32_t query, slot, common, pad; double dist; } rtc_rep_pair;
+/* The measuring half of MinHashMstAppendCluster / KssdMstAppendCluster (src/mst_state.cpp:681-1106).  The set holds
+ * n_reps representatives (genomes [0, n_reps)) followed by n_queries new sketches (genome n_reps + q is query q).  Every
+ * pair (query q, slot s) with s < n_reps + q -- an old representative, or an earlier query that may have become one -- that
+ * shares a hash and passes the reference's filters is written: is_kssd: sizeQry / sizeRef within [1 / radio, radio],
+ * radio = exp(threshold k); common >= (int)(jmin min(sizeQry, sizeRef)) (is_containment) or
+ * (int)(jmin (sizeQry + sizeRef) / (1 + jmin)), jmin = e / (2 - e), e = exp(-threshold k); the distance -ln(2j / (1 + j)) / k
+ * from the full-set common (j = common / min(sizes) or common / (sizeQry + sizeRef - common), capped at 1) is <= threshold,
+ * neither NaN nor Inf.  dist is the host libm's value.  h_pairs[0 .. min(*n_pairs, cap)) sorted by (query, slot); *n_pairs
+ * beyond cap: call again with a buffer that large.  query_chunk > 0 measures that many queries at a time (0: all at once);
+ * a chunk whose scratch does not fit is halved and measured again.  Synchronous. */
+int rtc_rep_match(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len,
+                  uint32_t n_reps, uint32_t n_queries, int kmer_size, int is_kssd, int is_containment, double threshold,
+                  uint32_t query_chunk, rtc_rep_pair* h_pairs, uint64_t cap, uint64_t* n_pairs);
 
 #ifdef __cplusplus
 }

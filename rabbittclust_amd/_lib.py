@@ -119,6 +119,7 @@ SIGNATURES = {
     "rtc_tree_medoids": (_i, [_vp, _u32, _vp, _u64, C.c_double, _vp, _vp]),
     "rtc_dedup_last_path": (_i, [_vp]),
     "rtc_ctx_set_host_threads": (_i, [_vp, _i]),
+    "rtc_rep_match": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _u32, _i, _i, _i, C.c_double, _u32, _vp, _u64, C.POINTER(_u64)]),
 }
 
 _lib = None

@@ -17,6 +17,7 @@ from ._lib import RtcError, SynthDesc
 SYNTH_DT = np.dtype([("fam_seed", "<u8"), ("mut_seed", "<u8"), ("mut_thr", "<u4"), ("n_every", "<u4")])
 CEDGE_DT = np.dtype([("i", "<u4"), ("j", "<u4"), ("common", "<u4")])
 EDGE_DT = np.dtype([("preNode", "<i4"), ("sufNode", "<i4"), ("dist", "<f8")])  # edge.mst record
+REP_PAIR_DT = np.dtype([("query", "<u4"), ("slot", "<u4"), ("common", "<u4"), ("pad", "<u4"), ("dist", "<f8")])  # rtc_rep_pair
 
 
 def _np_ptr(a):
@@ -158,7 +159,8 @@ class Context:
         """rtc_diag_counters as a dict: which paths this context has taken since it was created"""
         a = (C.c_uint64 * 8)()
         self.check(self.lib.rtc_diag_counters(self.h, a))
-        names = ("join_tiles", "tiled_tiles", "merge_tiles", "contractions", "greedy_global", "greedy_blocks", "estimates")
+        names = ("join_tiles", "tiled_tiles", "merge_tiles", "contractions", "greedy_global", "greedy_blocks", "estimates",
+                 "repmatch_chunks")
         return {k: int(a[i]) for i, k in enumerate(names)}
 
     def pair_last_kernel_ms(self):
@@ -516,6 +518,24 @@ class Context:
     def dedup_last_path(self):
         """Where the last tree_medoids call computed its sums: 0 nowhere, 1 host, 2 GPU, 3 both."""
         return int(self.lib.rtc_dedup_last_path(self.h))
+
+    def rep_match(self, sk, n_reps, threshold, is_kssd=False, is_containment=False, query_chunk=0):
+        """clust-mst --append against a stored state: sk holds the n_reps representatives, then the queries.  Returns the
+        REP_PAIR_DT pairs (query, slot < n_reps + query, common, dist) that pass the reference's filters, sorted by (query,
+        slot).  query_chunk > 0: that many queries per join (diag()["repmatch_chunks"] counts them)."""
+        nq = sk.n - int(n_reps)
+        if nq < 0:
+            raise ValueError("n_reps exceeds the sketch set")
+        cap = max(1024, 16 * max(nq, 1))
+        while True:
+            out = np.zeros(cap, dtype=REP_PAIR_DT)
+            n = C.c_uint64()
+            self.check(self.lib.rtc_rep_match(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len),
+                                              int(n_reps), nq, sk.k, int(bool(is_kssd)), int(bool(is_containment)),
+                                              float(threshold), int(query_chunk), _np_ptr(out), cap, C.byref(n)))
+            if n.value <= cap:
+                return out[:n.value].copy()
+            cap = int(n.value)
 
 
 class Comm:

@@ -149,4 +149,34 @@ int rtch_dedup_reps(int n, const rtc_edge* forest, long m, const uint64_t* seq_l
   flat(rp, reps, reps_off);
   return (int)cl.size();
 }
+
+// mst_cluster_state.bin: load, then save again (byte-level format check); 1 if it does not load
+int rtch_mst_state_resave(const char* in_path, const char* out_path, int kssd) {
+  MstState st;
+  if (!load_mst_state(in_path, kssd != 0, st)) return 1;
+  return save_mst_state(out_path, st) ? 0 : 2;
+}
+
+// --append against a state file without a GPU: the replay of rtc_rep_match's pairs (n_pairs records, sorted by (query, slot)).
+// Query q: names[q], lens[q], hashes qhash[qoff[q] .. qoff[q + 1]) (u64, or u32 for a KSSD state without use64).  Writes the
+// cluster file (out_cluster) and the compacted state (out_state, may be NULL); returns the live cluster count, -1 if the state
+// does not load.
+int rtch_mst_state_append(const char* in_state, int kssd, int n_queries, const char* const* names, const uint64_t* lens,
+                          const void* qhash, const uint64_t* qoff, const rtc_rep_pair* pairs, long n_pairs,
+                          const char* out_cluster, const char* out_state) {
+  MstState st;
+  if (!load_mst_state(in_state, kssd != 0, st)) return -1;
+  std::vector<std::string> nm; std::vector<uint64_t> ln;
+  std::vector<std::vector<uint64_t>> q64; std::vector<std::vector<uint32_t>> q32;
+  for (int q = 0; q < n_queries; q++) {
+    nm.push_back(names[q]); ln.push_back(lens[q]);
+    if (st.use64) q64.emplace_back((const uint64_t*)qhash + qoff[q], (const uint64_t*)qhash + qoff[q + 1]);
+    else q32.emplace_back((const uint32_t*)qhash + qoff[q], (const uint32_t*)qhash + qoff[q + 1]);
+  }
+  const std::vector<rtc_rep_pair> pv(pairs, pairs + n_pairs);
+  const std::vector<std::vector<int>> live = append_mst_state(st, nm, ln, st.use64 ? &q64 : nullptr, st.use64 ? nullptr : &q32, pv);
+  print_mst_state_clusters(live, st.member_names, st.member_lens, st.sketch_by_file, out_cluster, st.threshold);
+  if (out_state && out_state[0] && !save_mst_state(out_state, st)) return -1;
+  return (int)live.size();
+}
 }

@@ -911,6 +911,7 @@ static Options parse(int argc, char** argv) {
       o.useIndex = !(v == "false" || v == "0" || v == "off" || v == "no");
     }
 #ifndef GREEDY_CLUST
+    else if (a == "--save-rep") o.saveRep = true;
     else if (a == "--premsted") { o.folder_path = need(i); o.has_premsted = true; }
     else if (a == "--auto-threshold") o.autoThreshold = true;
     else if (a == "--stability") o.stability = true;
@@ -929,7 +930,8 @@ static Options parse(int argc, char** argv) {
            "  --inverted-index=false (MinHash: the dense loops modifyMST / greedyCluster with MinHash::distance())"
 #ifndef GREEDY_CLUST
            "  --premsted DIR  --append LIST (with --presketched/--premsted DIR)\n"
-           "  --auto-threshold  --stability  --dedup-dist D  --reps-per-cluster K (with --fast: <output>.dedup / .reps)"
+           "  --auto-threshold  --stability  --dedup-dist D  --reps-per-cluster K (with --fast: <output>.dedup / .reps)\n"
+           "  --save-rep (mst_cluster_state.bin beside the sketches; a later --append measures against its representatives)"
 #else
            "  --append LIST (with --presketched DIR)  --save-rep (cluster_state.bin beside the sketches)\n"
            "  [--fast] --db FILE --build|--query|--assign|--append LIST|--stats [--top-k N] (representative database)"
@@ -939,7 +941,7 @@ static Options parse(int argc, char** argv) {
     }
     else if (
 #ifndef GREEDY_CLUST
-             a == "--db" || a == "--build" || a == "--query" || a == "--assign" || a == "--stats" || a == "--top-k" || a == "--save-rep" ||
+             a == "--db" || a == "--build" || a == "--query" || a == "--assign" || a == "--stats" || a == "--top-k" ||
 #else
              a == "--dense" || a == "--auto-threshold" || a == "--stability" || a == "--dedup-dist" || a == "--reps-per-cluster" ||
 #endif
@@ -1037,8 +1039,19 @@ static void write_trees(const Options& o, const vector<GenomeInfo>& genomes, con
 // stored folder's parameters, evaluate only the pairs that involve a new genome (rows >= start_index,
 // src/MST.cpp:1375-1383 -- rtc_mst_append), merge that forest with the stored MST (sort + Kruskal,
 // :1693-1700), cut, print, and write the combined folder.
+static int append_mst_from_state(const Options& o, vector<Gpu>& gpus, MstState& st, const string& state_path);
 static int append_clust_mst(const Options& o, vector<Gpu>& gpus) {
   rtc_ctx* ctx = gpus[0].ctx;
+  {  // a --save-rep state beside the sketches: the new genomes are measured against its representatives (src/sub_command.cpp:1289-1316, :1533-1560)
+    const string state_path = o.folder_path + "/mst_cluster_state.bin";
+    struct stat sb;
+    if (stat(state_path.c_str(), &sb) == 0) {
+      cerr << "===== clust-mst " << (o.is_fast ? "--fast " : "") << "append (inverted-index state) =====" << endl;
+      MstState st;
+      if (!load_mst_state(state_path, o.is_fast, st)) cerr << "ERROR: failed to load " << state_path << ", falling back to classic append" << endl;
+      else return append_mst_from_state(o, gpus, st, state_path);
+    }
+  }
   vector<GenomeInfo> genomes; MinHashSketchFile mh; KssdSketchFile ks; bool byFile = true;
   double t0 = get_sec();
   if (o.is_fast) { if (!load_kssd_sketches(o.folder_path, genomes, ks, byFile)) return 1; }
@@ -1109,6 +1122,111 @@ static int append_clust_mst(const Options& o, vector<Gpu>& gpus) {
   cluster_from_mst(final_mst, genomes, byFile, o.outputFile, o.threshold);
   if (!o.noSave) { save_genome_info(genomes, new_folder, "mst", true, o.is_fast); save_mst(final_mst, new_folder); }
   return 0;
+}
+
+// The state path of append_clust_mst[_fast]: sketch the new genomes with the state's parameters, measure them against the
+// representatives and against each other on the GPU (rtc_rep_match), replay the decisions in list order on the host
+// (append_mst_state), print the live clusters (printMstStateClusterResult), and write the state back with --save-rep and no -e.
+static int append_mst_from_state(const Options& o, vector<Gpu>& gpus, MstState& st, const string& state_path) {
+  rtc_ctx* ctx = gpus[0].ctx;
+  if (!o.sketchByFile) unsupported("single-FASTA input (run with -l and a genome list)");
+  SketchJob job;
+  job.kssd = st.kssd; job.minLen = o.minLen; job.threads = o.threads;
+  if (st.kssd) { job.kmerSize = st.half_k * 2; job.drlevel = st.drlevel; }
+  else {
+    // the reference stores contain_compress = 0 (src/sub_command.cpp:2821, :3065) and sketches the new genomes with it
+    if (st.is_containment && st.contain_compress <= 0) {
+      cerr << "ERROR: is_containment is true but contain_compress is " << st.contain_compress << endl;
+      return 1;
+    }
+    job.kmerSize = st.kmer_size; job.sketchSize = st.sketch_size; job.isContainment = st.is_containment; job.containCompress = st.contain_compress;
+  }
+  const double t0 = get_sec();
+  vector<GenomeInfo> add; MinHashSketchFile mh2; KssdSketchFile ks2; Resident rs2;
+  sketch_files(gpus, o.inputFile, job, add, &mh2, &ks2, rs2, true);
+  const bool q64 = st.kssd ? ks2.use64 : true;
+  if (!add.empty() && q64 != st.use64) {
+    cerr << "ERROR: the new sketches have use64=" << q64 << " but the state has use64=" << st.use64 << endl;
+    return 1;
+  }
+  const vector<vector<uint64_t>>& qh64 = st.kssd ? ks2.h64 : mh2.hashes;
+  const vector<vector<uint32_t>>& qh32 = ks2.h32;
+  cerr << "========time of computing sketch is: " << get_sec() - t0 << "========" << endl;
+  cerr << "\n[clust-mst" << (st.kssd ? " --fast" : "") << " append] using inverted-index state" << endl;
+  cerr << "  existing members: " << st.N << ", existing reps: " << st.reps() << ", new sketches: " << add.size() << endl;
+  const double t1 = get_sec();
+  const uint32_t R = (uint32_t)st.reps(), Q = (uint32_t)add.size();
+  vector<rtc_rep_pair> pairs;
+  if (Q) {
+    DeviceSketches ds;
+    if (st.use64) { vector<vector<uint64_t>> all(st.h64); all.insert(all.end(), qh64.begin(), qh64.end()); upload_sketches(ctx, &all, nullptr, ds); }
+    else { vector<vector<uint32_t>> all(st.h32); all.insert(all.end(), qh32.begin(), qh32.end()); upload_sketches(ctx, nullptr, &all, ds); }
+    const int kmer_size = st.kssd ? st.half_k * 2 : st.kmer_size;
+    uint64_t np = 0;
+    pairs.resize((size_t)Q * 8);
+    CHECK(ctx, rtc_rep_match(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, R, Q, kmer_size, (int)st.kssd, (int)st.is_containment, st.threshold, 0,
+                             pairs.data(), pairs.size(), &np));
+    if (np > pairs.size()) {
+      pairs.resize(np);
+      CHECK(ctx, rtc_rep_match(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, R, Q, kmer_size, (int)st.kssd, (int)st.is_containment, st.threshold, 0,
+                               pairs.data(), pairs.size(), &np));
+    }
+    pairs.resize(np);
+    (void)rtc_dev_free(ctx, ds.d_hashes); (void)rtc_dev_free(ctx, ds.d_start); (void)rtc_dev_free(ctx, ds.d_len);
+  }
+  const double t2 = get_sec();
+  vector<string> names; vector<uint64_t> lens;
+  for (const GenomeInfo& g : add) { names.push_back(g.fileName); lens.push_back(st.sketch_by_file ? g.totalSeqLength : (uint64_t)g.seq0.length); }
+  const vector<vector<int>> live = append_mst_state(st, names, lens, st.use64 ? &qh64 : nullptr, st.use64 ? nullptr : &qh32, pairs);
+  const double t3 = get_sec();
+  cerr << "========time of rep match (GPU) is: " << t2 - t1 << "========" << endl;
+  cerr << "========time of append replay (host) is: " << t3 - t2 << "========" << endl;
+  g_metrics.num("rep_match_s", t2 - t1);
+  g_metrics.num("append_replay_s", t3 - t2);
+  print_mst_state_clusters(live, st.member_names, st.member_lens, st.sketch_by_file, o.outputFile, st.threshold);
+  cerr << "-----write the cluster result into: " << o.outputFile << endl;
+  cerr << "-----the cluster number of: " << o.outputFile << " is: " << live.size() << endl;
+  if (!o.noSave && o.saveRep && !save_mst_state(state_path, st)) return 1;
+  return 0;
+}
+
+// MinHashInitialMstState / KssdInitialMstState + save (src/sub_command.cpp:2083-2087, :2577-2581, :2814-2823, :3058-3068): every
+// cluster of the forest collapsed to its tree medoid (rtc_tree_medoids with dedup_dist = +inf), written to
+// <folder>/mst_cluster_state.bin
+static int save_initial_mst_state(rtc_ctx* ctx, const Options& o, const string& folder, const vector<GenomeInfo>& genomes, bool sketchByFile,
+                                  const vector<rtc_edge>& forest, const vector<vector<int>>& clusters, const MinHashSketchFile& mh,
+                                  const KssdSketchFile& ks, bool from_sketches) {
+  const int n = (int)genomes.size();
+  const size_t nh = o.is_fast ? (ks.use64 ? ks.h64.size() : ks.h32.size()) : mh.hashes.size();
+  if ((int)nh != n) { cerr << "ERROR: --save-rep needs the sketches on the host (" << nh << " of " << n << ")" << endl; return 1; }
+  const double inf = std::numeric_limits<double>::max();
+  vector<uint64_t> lens(n);
+  for (int i = 0; i < n; i++) lens[i] = sketchByFile ? genomes[i].totalSeqLength : (uint64_t)genomes[i].seq0.length;
+  vector<int32_t> rep(n);
+  CHECK(ctx, rtc_ctx_set_host_threads(ctx, o.threads));
+  CHECK(ctx, rtc_tree_medoids(ctx, (uint32_t)n, forest.data(), forest.size(), inf, lens.data(), rep.data()));
+  const vector<vector<int>> cands = dedup_candidates(clusters, vector<int>(rep.begin(), rep.end()), inf);
+  vector<int> rep_of_cluster(clusters.size());
+  for (size_t c = 0; c < clusters.size(); c++) rep_of_cluster[c] = cands[c].empty() ? (clusters[c].empty() ? -1 : clusters[c][0]) : cands[c][0];
+  MstState st;
+  st.kssd = o.is_fast;
+  st.threshold = o.threshold;
+  if (o.is_fast) {
+    st.half_k = ks.info.half_k; st.half_subk = ks.info.half_subk; st.drlevel = ks.info.drlevel; st.kmer_size = ks.info.half_k * 2;
+    init_mst_state(st, genomes, sketchByFile, clusters, rep_of_cluster, ks.use64 ? &ks.h64 : nullptr, ks.use64 ? nullptr : &ks.h32);
+  } else {
+    // sketches[0].minHash->getSketchSize(): the fixed size, or in containment mode genome 0's own size when it was sketched
+    // here (src/SketchInfo.cpp) and containCompress when it was loaded (src/Sketch_IO.cpp:334)
+    st.kmer_size = mh.kmerSize;
+    st.is_containment = mh.isContainment;
+    st.contain_compress = 0;
+    st.sketch_size = !mh.isContainment ? mh.sketchSize
+                     : from_sketches ? mh.containCompress
+                     : sketchByFile ? std::max(file_length_for_containment(genomes[0].fileName) / mh.containCompress, 100)
+                                    : std::max(genomes[0].seq0.length / mh.containCompress, 100);
+    init_mst_state(st, genomes, sketchByFile, clusters, rep_of_cluster, &mh.hashes, nullptr);
+  }
+  return save_mst_state(folder + "/mst_cluster_state.bin", st) ? 0 : 1;
 }
 #endif
 
@@ -2132,6 +2250,10 @@ int main(int argc, char** argv) {
   vector<rtc_edge> forest;
   vector<vector<int>> clusters;
   cluster_from_mst(mst, genomes, sketchByFile, o.outputFile, o.threshold, &forest, &clusters);
+  // --save-rep: the presketched flows always, the flows from genomes when they keep a sketch folder (-e: none)
+  if (o.saveRep && (from_sketches || !o.noSave) &&
+      save_initial_mst_state(ctx, o, folder_path, genomes, sketchByFile, forest, clusters, mh, ks, from_sketches) != 0)
+    return 1;
   // --dedup-dist / --reps-per-cluster: the KSSD flows only (compute_kssd_clusters, clust_from_sketch_fast)
   if (o.is_fast) dedup_and_reps(ctx, o.dedupDist, o.repsPerCluster, o.threads, forest, clusters, genomes, sketchByFile, o.outputFile);
   if (o.dense) {

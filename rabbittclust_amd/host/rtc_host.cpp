@@ -2238,6 +2238,291 @@ std::vector<std::vector<int>> select_k_reps(const std::vector<std::vector<int>>&
   return reps;
 }
 
+// ---- clust-mst --save-rep / --append state (src/mst_state.cpp) ----
+namespace {
+template <typename T> void mw_pod(std::ofstream& o, const T& v) { o.write(reinterpret_cast<const char*>(&v), sizeof(T)); }
+template <typename T> void mr_pod(std::ifstream& i, T& v) { i.read(reinterpret_cast<char*>(&v), sizeof(T)); }
+void mw_str(std::ofstream& o, const std::string& s) {
+  const uint32_t n = (uint32_t)s.size();
+  mw_pod(o, n);
+  if (n) o.write(s.data(), n);
+}
+bool mr_str(std::ifstream& i, std::string& s) {
+  uint32_t n = 0;
+  mr_pod(i, n);
+  if (!i) return false;
+  s.resize(n);
+  if (n) i.read(&s[0], n);
+  return (bool)i;
+}
+template <typename T> void mw_vec(std::ofstream& o, const std::vector<T>& v) {
+  const uint64_t n = v.size();
+  mw_pod(o, n);
+  if (n) o.write(reinterpret_cast<const char*>(v.data()), sizeof(T) * n);
+}
+template <typename T> bool mr_vec(std::ifstream& i, std::vector<T>& v) {
+  uint64_t n = 0;
+  mr_pod(i, n);
+  if (!i) return false;
+  // a length past what is left of the file is a damaged file, not a request for memory
+  const std::streampos here = i.tellg();
+  i.seekg(0, std::ios::end);
+  const std::streampos end = i.tellg();
+  i.seekg(here);
+  if (n > (uint64_t)(end - here) / sizeof(T)) { i.setstate(std::ios::failbit); return false; }
+  v.resize(n);
+  if (n) i.read(reinterpret_cast<char*>(v.data()), sizeof(T) * n);
+  return (bool)i;
+}
+// build_inverted_index_from_reps: hash -> the representatives that hold it, ascending
+template <typename T> std::vector<std::pair<T, std::vector<int>>> mst_index(const std::vector<std::vector<T>>& reps) {
+  std::vector<std::pair<T, int>> all;
+  for (size_t r = 0; r < reps.size(); r++) for (T h : reps[r]) all.push_back({h, (int)r});
+  std::sort(all.begin(), all.end());
+  std::vector<std::pair<T, std::vector<int>>> idx;
+  for (size_t a = 0; a < all.size(); a++) {
+    if (idx.empty() || idx.back().first != all[a].first) idx.push_back({all[a].first, {}});
+    idx.back().second.push_back(all[a].second);
+  }
+  return idx;
+}
+template <typename T> void mw_index(std::ofstream& o, const std::vector<std::vector<T>>& reps, uint64_t& H) {
+  const auto idx = mst_index(reps);
+  H = idx.size();
+  mw_pod(o, H);
+  for (const auto& kv : idx) { mw_pod(o, kv.first); mw_vec(o, kv.second); }
+}
+template <typename T> bool mr_index(std::ifstream& i, uint64_t& H) {
+  mr_pod(i, H);
+  for (uint64_t a = 0; a < H && i; a++) { T h; std::vector<int> lst; mr_pod(i, h); if (!mr_vec(i, lst)) return false; }
+  return (bool)i;
+}
+// UnionFind.h: path compression, union by rank (equal ranks: the second argument's root wins)
+struct MstUF {
+  std::vector<int> parent, rank;
+  explicit MstUF(int n) : parent(n), rank(n, 0) { for (int i = 0; i < n; i++) parent[i] = i; }
+  void extend() { parent.push_back((int)parent.size()); rank.push_back(0); }
+  int find(int x) { while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; } return x; }
+  void merge(int x, int y) {
+    x = find(x); y = find(y);
+    if (x == y) return;
+    if (rank[x] > rank[y]) parent[y] = x;
+    else if (rank[x] < rank[y]) parent[x] = y;
+    else { parent[x] = y; rank[y]++; }
+  }
+};
+}  // namespace
+
+bool save_mst_state(const std::string& path, const MstState& st) {
+  std::ofstream o(path, std::ios::binary);
+  if (!o) { std::cerr << "ERROR: " << (st.kssd ? "KssdMstState" : "MinHashMstState") << "::save cannot open " << path << std::endl; return false; }
+  o.write(st.kssd ? "KSMSTST01" : "MHMSTST01", 9);
+  mw_pod(o, st.threshold);
+  mw_pod(o, st.kmer_size);
+  if (st.kssd) { mw_pod(o, st.half_k); mw_pod(o, st.half_subk); mw_pod(o, st.drlevel); mw_pod(o, st.use64); }
+  else { mw_pod(o, st.sketch_size); mw_pod(o, st.contain_compress); mw_pod(o, st.is_containment); }
+  mw_pod(o, st.sketch_by_file);
+  mw_pod(o, st.N);
+  const uint64_t R = st.reps();
+  mw_pod(o, R);
+  for (uint64_t r = 0; r < R; r++) {
+    const int rid = r < st.rep_ids.size() ? st.rep_ids[r] : -1;
+    mw_pod(o, rid);
+    const uint64_t tlen = r < st.rep_lens.size() ? st.rep_lens[r] : 0;
+    mw_pod(o, tlen);
+    mw_str(o, r < st.rep_names.size() ? st.rep_names[r] : std::string());
+    if (st.use64) mw_vec(o, st.h64[r]);
+    else mw_vec(o, st.h32[r]);
+  }
+  const uint64_t C = st.clusters.size();
+  mw_pod(o, C);
+  for (const auto& cl : st.clusters) mw_vec(o, cl);
+  const uint64_t M = st.member_names.size();
+  mw_pod(o, M);
+  for (const auto& nm : st.member_names) mw_str(o, nm);
+  mw_vec(o, st.member_lens);
+  uint64_t H = 0;
+  if (st.use64) mw_index(o, st.h64, H);
+  else mw_index(o, st.h32, H);
+  o.close();
+  if (st.kssd)
+    std::cerr << "Saved KSSD MST state to " << path << " (reps=" << R << ", clusters=" << C << ", members=" << M << ")" << std::endl;
+  else
+    std::cerr << "Saved MinHash MST state to " << path << " (reps=" << R << ", clusters=" << C << ", members=" << M
+              << ", unique_hashes=" << H << ")" << std::endl;
+  return (bool)o;
+}
+
+bool load_mst_state(const std::string& path, bool kssd, MstState& st) {
+  const char* who = kssd ? "KssdMstState" : "MinHashMstState";
+  std::ifstream i(path, std::ios::binary);
+  if (!i) { std::cerr << "ERROR: " << who << "::load cannot open " << path << std::endl; return false; }
+  char magic[10] = {0};
+  i.read(magic, 9);
+  if (memcmp(magic, kssd ? "KSMSTST01" : "MHMSTST01", 9) != 0) {
+    std::cerr << "ERROR: " << path << " is not a " << (kssd ? "KSSD" : "MinHash") << " MST state (bad magic)" << std::endl;
+    return false;
+  }
+  st = MstState();
+  st.kssd = kssd;
+  mr_pod(i, st.threshold);
+  mr_pod(i, st.kmer_size);
+  if (kssd) { mr_pod(i, st.half_k); mr_pod(i, st.half_subk); mr_pod(i, st.drlevel); mr_pod(i, st.use64); }
+  else { mr_pod(i, st.sketch_size); mr_pod(i, st.contain_compress); mr_pod(i, st.is_containment); st.use64 = true; }
+  mr_pod(i, st.sketch_by_file);
+  mr_pod(i, st.N);
+  uint64_t R = 0, C = 0, M = 0, H = 0;
+  mr_pod(i, R);
+  bool ok = (bool)i && R <= (uint64_t)INT32_MAX;
+  for (uint64_t r = 0; ok && r < R; r++) {
+    int rid = 0; uint64_t tlen = 0; std::string nm;
+    mr_pod(i, rid); mr_pod(i, tlen);
+    ok = mr_str(i, nm);
+    st.rep_ids.push_back(rid); st.rep_lens.push_back(tlen); st.rep_names.push_back(nm);
+    if (st.use64) { st.h64.emplace_back(); ok = ok && mr_vec(i, st.h64.back()); }
+    else { st.h32.emplace_back(); ok = ok && mr_vec(i, st.h32.back()); }
+  }
+  if (ok) { mr_pod(i, C); ok = (bool)i && C <= (uint64_t)INT32_MAX; }
+  for (uint64_t c = 0; ok && c < C; c++) { st.clusters.emplace_back(); ok = mr_vec(i, st.clusters.back()); }
+  if (ok) { mr_pod(i, M); ok = (bool)i && M <= (uint64_t)INT32_MAX; }
+  for (uint64_t m = 0; ok && m < M; m++) { st.member_names.emplace_back(); ok = mr_str(i, st.member_names.back()); }
+  ok = ok && mr_vec(i, st.member_lens);
+  ok = ok && (st.use64 ? mr_index<uint64_t>(i, H) : mr_index<uint32_t>(i, H));
+  if (!ok || st.clusters.size() != R) {
+    std::cerr << "ERROR: " << path << " ends early or does not hold one cluster per representative" << std::endl;
+    return false;
+  }
+  if (kssd)
+    std::cerr << "Loaded KSSD MST state from " << path << " (reps=" << R << ", clusters=" << C << ", members=" << M << ")" << std::endl;
+  else
+    std::cerr << "Loaded MinHash MST state from " << path << " (reps=" << R << ", clusters=" << C << ", members=" << M
+              << ", unique_hashes=" << H << ")" << std::endl;
+  return true;
+}
+
+void init_mst_state(MstState& st, const std::vector<GenomeInfo>& g, bool sketchByFile, const std::vector<std::vector<int>>& clusters,
+                    const std::vector<int>& rep_of_cluster, const std::vector<std::vector<uint64_t>>* h64,
+                    const std::vector<std::vector<uint32_t>>* h32) {
+  st.N = (int)g.size();
+  st.sketch_by_file = sketchByFile;
+  st.use64 = h64 != nullptr;
+  auto len_of = [&](int id) { return sketchByFile ? g[id].totalSeqLength : (uint64_t)g[id].seq0.length; };
+  for (int i = 0; i < st.N; i++) { st.member_names.push_back(g[i].fileName); st.member_lens.push_back(len_of(i)); }
+  for (size_t c = 0; c < clusters.size(); c++) {
+    if (clusters[c].empty()) continue;
+    int rep = rep_of_cluster[c];
+    if (rep < 0 || rep >= st.N) rep = clusters[c][0];
+    st.rep_ids.push_back(rep);
+    st.rep_names.push_back(g[rep].fileName);
+    st.rep_lens.push_back(len_of(rep));
+    if (h64) st.h64.push_back((*h64)[rep]);
+    else st.h32.push_back((*h32)[rep]);
+    st.clusters.push_back(clusters[c]);
+  }
+}
+
+std::vector<std::vector<int>> append_mst_state(MstState& st, const std::vector<std::string>& names, const std::vector<uint64_t>& lens,
+                                               const std::vector<std::vector<uint64_t>>* qh64, const std::vector<std::vector<uint32_t>>* qh32,
+                                               const std::vector<rtc_rep_pair>& pairs) {
+  const int R0 = (int)st.reps();
+  const int Q = (int)names.size();
+  MstUF uf(R0);
+  std::vector<int> became(Q, -1);  // query -> its representative index, if it opened a cluster
+  int assigned = 0, merges = 0, opened = 0;
+  size_t p = 0;
+  std::vector<std::pair<int, double>> matches;
+  for (int q = 0; q < Q; q++) {
+    matches.clear();
+    for (; p < pairs.size() && (int)pairs[p].query == q; p++) {
+      const int s = (int)pairs[p].slot;
+      const int r = s < R0 ? s : became[s - R0];
+      if (r < 0 || uf.find(r) != r) continue;  // not a representative, or merged away: its root's own count decides
+      matches.push_back({r, pairs[p].dist});
+    }
+    const int id = st.N++;
+    st.member_names.push_back(names[q]);
+    st.member_lens.push_back(lens[q]);
+    if (matches.empty()) {
+      became[q] = (int)st.reps();
+      st.rep_ids.push_back(id);
+      st.rep_names.push_back(names[q]);
+      st.rep_lens.push_back(lens[q]);
+      if (st.use64) st.h64.push_back((*qh64)[q]);
+      else st.h32.push_back((*qh32)[q]);
+      st.clusters.push_back({id});
+      uf.extend();
+      opened++;
+      continue;
+    }
+    size_t best = 0;  // decide_assignment: the closest; equal distances to the lowest slot (matches ascend by slot)
+    for (size_t m = 1; m < matches.size(); m++) if (matches[m].second < matches[best].second) best = m;
+    const int survivor = matches[best].first;
+    for (size_t m = 0; m < matches.size(); m++) {
+      if (m == best) continue;
+      const int other_root = uf.find(matches[m].first), surv_root = uf.find(survivor);
+      if (other_root == surv_root) continue;
+      uf.merge(surv_root, other_root);
+      const int new_root = uf.find(surv_root);
+      const int loser = new_root == surv_root ? other_root : surv_root;
+      auto& src = st.clusters[loser];
+      auto& dst = st.clusters[new_root];
+      dst.insert(dst.end(), src.begin(), src.end());
+      src.clear();
+      merges++;
+    }
+    st.clusters[uf.find(survivor)].push_back(id);
+    assigned++;
+  }
+  std::cerr << "\n[clust-mst" << (st.kssd ? " --fast" : "") << " append summary]" << std::endl
+            << "  assigned to existing : " << assigned << std::endl
+            << "  new clusters         : " << opened << std::endl
+            << "  cluster merges       : " << merges << std::endl;
+  // collect_live_clusters + compact_*_state: the non-empty roots, in representative order
+  std::vector<std::vector<int>> live;
+  MstState out = st;
+  out.rep_ids.clear(); out.rep_names.clear(); out.rep_lens.clear(); out.h64.clear(); out.h32.clear(); out.clusters.clear();
+  for (int r = 0; r < (int)st.reps(); r++) {
+    if (st.clusters[r].empty() || uf.find(r) != r) continue;
+    live.push_back(st.clusters[r]);
+    out.rep_ids.push_back(st.rep_ids[r]);
+    out.rep_names.push_back(st.rep_names[r]);
+    out.rep_lens.push_back(st.rep_lens[r]);
+    if (st.use64) out.h64.push_back(std::move(st.h64[r]));
+    else out.h32.push_back(std::move(st.h32[r]));
+    out.clusters.push_back(std::move(st.clusters[r]));
+  }
+  st = std::move(out);
+  return live;
+}
+
+void print_mst_state_clusters(const std::vector<std::vector<int>>& clusters, const std::vector<std::string>& member_names,
+                              const std::vector<uint64_t>& member_lens, bool sketch_by_file, const std::string& output_file,
+                              double threshold) {
+  FILE* fp = fopen(output_file.c_str(), "w");
+  if (!fp) { std::cerr << "ERROR: printMstStateClusterResult cannot open " << output_file << std::endl; return; }
+  if (threshold >= 0.0) {
+    fprintf(fp, "# Clustering threshold: %.6f\n", threshold);
+    fprintf(fp, "# Total clusters: %zu\n", clusters.size());
+    fprintf(fp, "#\n");
+  }
+  for (size_t c = 0; c < clusters.size(); c++) {
+    fprintf(fp, "the cluster %zu is: \n", c);
+    for (size_t j = 0; j < clusters[c].size(); j++) {
+      const int id = clusters[c][j];
+      const char* name = "N/A";
+      uint64_t len = 0;
+      if (id >= 0 && (size_t)id < member_names.size()) {
+        name = member_names[id].c_str();
+        len = (size_t)id < member_lens.size() ? member_lens[id] : 0;
+      }
+      if (sketch_by_file) fprintf(fp, "\t%5zu\t%6d\t%12lunt\t%20s\n", j, id, (unsigned long)len, name);
+      else fprintf(fp, "\t%6zu\t%6d\t%12lunt\t%20s\n", j, id, (unsigned long)len, name);
+    }
+    fprintf(fp, "\n");
+  }
+  fclose(fp);
+}
+
 std::string current_date_time() {
   time_t now = time(0);
   struct tm tstruct = *localtime(&now);

@@ -210,6 +210,52 @@ std::vector<std::vector<int>> dedup_candidates(const std::vector<std::vector<int
 std::vector<std::vector<int>> select_k_reps(const std::vector<std::vector<int>>& clusters, const std::vector<std::vector<int>>& candidates,
                                             const std::vector<rtc_edge>& forest, int n, const std::vector<int>& node_to_rep, int k);
 
+// ---- clust-mst --save-rep / --append state (src/mst_state.h, src/mst_state.cpp) ----
+// mst_cluster_state.bin: one tree-medoid representative per cluster, the clusters, every member's name and length, and
+// the representatives' inverted index.  "MHMSTST01" (MinHashMstState::save, :129-255) or "KSMSTST01" (KssdMstState::save,
+// :293-435): both share one struct here.  The index is written from the representatives' hashes, keys ascending (the
+// reference writes phmap's iteration order), and skipped when read: the append measures on the GPU (rtc_rep_match).
+struct MstState {
+  bool kssd = false;
+  double threshold = 0.0;
+  int kmer_size = 0;
+  int sketch_size = 0, contain_compress = 0;  // MinHash
+  bool is_containment = false;                // MinHash
+  int half_k = 0, half_subk = 0, drlevel = 0;  // KSSD
+  bool use64 = true;                           // KSSD: h64 or h32; MinHash: always h64
+  int N = 0;
+  bool sketch_by_file = true;
+  std::vector<int> rep_ids;
+  std::vector<uint64_t> rep_lens;
+  std::vector<std::string> rep_names;
+  std::vector<std::vector<uint64_t>> h64;
+  std::vector<std::vector<uint32_t>> h32;
+  std::vector<std::vector<int>> clusters;  // clusters[r] belongs to representative r
+  std::vector<std::string> member_names;
+  std::vector<uint64_t> member_lens;
+  size_t reps() const { return use64 ? h64.size() : h32.size(); }
+};
+bool save_mst_state(const std::string& path, const MstState& st);
+// false (and a message) when the file is missing, has the other magic, or ends early: the caller falls back
+bool load_mst_state(const std::string& path, bool kssd, MstState& st);
+// MinHashInitialMstState / KssdInitialMstState (:436-560): clusters[i]'s representative is rep_of_cluster[i]
+// (build_dedup_candidates_per_cluster with dedup_dist = +inf: the cluster's tree medoid); the hashes are the sketch file's.
+void init_mst_state(MstState& st, const std::vector<GenomeInfo>& g, bool sketchByFile, const std::vector<std::vector<int>>& clusters,
+                    const std::vector<int>& rep_of_cluster, const std::vector<std::vector<uint64_t>>* h64,
+                    const std::vector<std::vector<uint32_t>>* h32);
+// MinHashMstAppendCluster / KssdMstAppendCluster (:681-1106) from the pairs rtc_rep_match emitted, sorted by (query, slot):
+// the queries in order, a union-find over the representatives.  A query's matches are its pairs whose slot is live (an old
+// representative, or query i that became one) and still a root; the closest is the survivor (equal distances: the lowest
+// slot -- DESIGN 5), the others are merged into it in ascending slot order; no match opens a cluster.  Appends the members,
+// returns the live clusters and compacts the state (compact_*_state, :601-680).  Query q's hashes: qh64[q] or qh32[q].
+std::vector<std::vector<int>> append_mst_state(MstState& st, const std::vector<std::string>& names, const std::vector<uint64_t>& lens,
+                                               const std::vector<std::vector<uint64_t>>* qh64, const std::vector<std::vector<uint32_t>>* qh32,
+                                               const std::vector<rtc_rep_pair>& pairs);
+// printMstStateClusterResult (:1108-1168)
+void print_mst_state_clusters(const std::vector<std::vector<int>>& clusters, const std::vector<std::string>& member_names,
+                              const std::vector<uint64_t>& member_lens, bool sketch_by_file, const std::string& output_file,
+                              double threshold);
+
 std::string current_date_time();  // src/common.hpp:36-44
 
 // Time the parser threads spent inside gzip decompression (libdeflate or zlib), summed over threads, and the bytes it produced
