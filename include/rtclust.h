@@ -440,6 +440,30 @@ int rtc_rep_match(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t*
                   uint32_t n_reps, uint32_t n_queries, int kmer_size, int is_kssd, int is_containment, double threshold,
                   uint32_t query_chunk, rtc_rep_pair* h_pairs, uint64_t cap, uint64_t* n_pairs);
 
+/* ---- clust-mst --db --query / --assign: the best representatives of every query ---------------- */
+typedef struct { uint32_t query, slot, common, denom; } rtc_rep_hit;
+/* The search of MinHashMstQueryTopK / KssdMstQueryTopK (src/mst_state.cpp:1211-1340).  The set holds n_reps representatives
+ * (genomes [0, n_reps)) followed by n_queries queries (genome n_reps + q is query q).  A candidate of query q is every live
+ * slot s < n_reps (h_live == NULL, or h_live[s] != 0) that shares a hash with it; queries never see each other.  (common,
+ * denom) by wmode: 0 set Jaccard (denom = |A| + |B| - common), 1 containment (denom = min(|A|, |B|)), 2 | s << 2 Mash's
+ * union-truncated estimator with sketch size s > 0 (common and denom recounted over the first s union elements, as
+ * rtc_pair_mash_dev).  Every query keeps its best topk candidates (topk == 0: all of them): larger common / denom first,
+ * compared exactly; equal keys by the lower slot.  h_hits[0 .. min(*n_hits, cap)) sorted by (query, rank); h_per_query
+ * (n_queries entries, may be NULL) receives the number kept for each query; *n_hits beyond cap: call again with a buffer that
+ * large.  query_chunk > 0 measures that many queries at a time (0: all at once); a chunk whose scratch does not fit is halved
+ * and measured again.  The device forms no distance.  topk in [1, 256] selects on the device; topk == 0 and topk > 256 sort
+ * every segment on the host.  Synchronous. */
+int rtc_rep_topk(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len,
+                 uint32_t n_reps, uint32_t n_queries, const uint8_t* h_live, int wmode, uint32_t topk,
+                 uint32_t query_chunk, rtc_rep_hit* h_hits, uint64_t cap, uint64_t* n_hits, uint32_t* h_per_query);
+/* Which selection paths the last rtc_rep_topk call took: bit 0 the one-wave workgroup (segments of up to 4 096 candidates),
+ * bit 1 the 256-lane workgroup (longer segments), bit 2 the full-segment host sort (topk == 0 or topk > 256). */
+int rtc_rep_topk_last_path(const rtc_ctx* ctx);
+/* What the last rtc_rep_topk call did: out[0] query chunks measured, out[1] / out[2] / out[3] queries selected by the wave /
+ * workgroup / full-sort path, out[4] candidates, out[5] bytes read back, out[6] join ns, out[7] bucketing ns (count, scan,
+ * scatter), out[8] selection ns (with the read-back), out[9] reserved. */
+int rtc_rep_topk_counters(const rtc_ctx* ctx, uint64_t out[10]);
+
 #ifdef __cplusplus
 }
 #endif

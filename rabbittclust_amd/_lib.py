@@ -120,6 +120,9 @@ SIGNATURES = {
     "rtc_dedup_last_path": (_i, [_vp]),
     "rtc_ctx_set_host_threads": (_i, [_vp, _i]),
     "rtc_rep_match": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _u32, _i, _i, _i, C.c_double, _u32, _vp, _u64, C.POINTER(_u64)]),
+    "rtc_rep_topk": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _u32, _vp, _i, _u32, _u32, _vp, _u64, C.POINTER(_u64), _vp]),
+    "rtc_rep_topk_last_path": (_i, [_vp]),
+    "rtc_rep_topk_counters": (_i, [_vp, C.POINTER(_u64)]),
 }
 
 _lib = None

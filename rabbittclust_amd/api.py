@@ -18,6 +18,7 @@ SYNTH_DT = np.dtype([("fam_seed", "<u8"), ("mut_seed", "<u8"), ("mut_thr", "<u4"
 CEDGE_DT = np.dtype([("i", "<u4"), ("j", "<u4"), ("common", "<u4")])
 EDGE_DT = np.dtype([("preNode", "<i4"), ("sufNode", "<i4"), ("dist", "<f8")])  # edge.mst record
 REP_PAIR_DT = np.dtype([("query", "<u4"), ("slot", "<u4"), ("common", "<u4"), ("pad", "<u4"), ("dist", "<f8")])  # rtc_rep_pair
+REP_HIT_DT = np.dtype([("query", "<u4"), ("slot", "<u4"), ("common", "<u4"), ("denom", "<u4")])  # rtc_rep_hit
 
 
 def _np_ptr(a):
@@ -536,6 +537,42 @@ class Context:
             if n.value <= cap:
                 return out[:n.value].copy()
             cap = int(n.value)
+
+    def rep_topk(self, sk, n_reps, wmode, topk, live=None, query_chunk=0):
+        """clust-mst --db --query: sk holds the n_reps representatives, then the queries.  wmode: 0 set Jaccard, 1
+        containment, 2 | s << 2 Mash's union-truncated estimator; topk 0 keeps every candidate.  live: n_reps flags (None:
+        all live).  Returns (REP_HIT_DT records sorted by (query, rank), kept count per query as uint32)."""
+        nq = sk.n - int(n_reps)
+        if nq < 0:
+            raise ValueError("n_reps exceeds the sketch set")
+        lv = None
+        if live is not None:
+            lv = np.ascontiguousarray(np.asarray(live, dtype=np.uint8))
+            if lv.shape != (int(n_reps),):
+                raise ValueError("live needs one flag per representative")
+        per = np.zeros(max(nq, 1), dtype=np.uint32)
+        cap = max(1024, (int(topk) if topk else 16) * max(nq, 1))
+        while True:
+            out = np.zeros(cap, dtype=REP_HIT_DT)
+            n = C.c_uint64()
+            self.check(self.lib.rtc_rep_topk(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), int(n_reps), nq,
+                                             _np_ptr(lv) if lv is not None else None, int(wmode), int(topk), int(query_chunk),
+                                             _np_ptr(out), cap, C.byref(n), _np_ptr(per)))
+            if n.value <= cap:
+                return out[:n.value].copy(), per[:nq].copy()
+            cap = int(n.value)
+
+    def rep_topk_last_path(self):
+        """Selection paths of the last rep_topk call: bit 0 one wave, bit 1 a 256-lane workgroup, bit 2 the host sort."""
+        return int(self.lib.rtc_rep_topk_last_path(self.h))
+
+    def rep_topk_counters(self):
+        """rtc_rep_topk_counters as a dict (the last rep_topk call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_rep_topk_counters(self.h, a))
+        names = ("chunks", "wave_queries", "workgroup_queries", "sort_queries", "candidates", "bytes_read", "join_ns",
+                 "bucket_ns", "select_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
 
 
 class Comm:

@@ -75,6 +75,8 @@ struct rtc_ctx {
   int quiet = 0;           // rtc_warmup's context: no RTC_VERBOSE lines
   int pair_last_path = 0;  // rtc_pair_last_path
   int dedup_last_path = 0;  // rtc_dedup_last_path
+  int rep_topk_path = 0;    // rtc_rep_topk_last_path
+  uint64_t rep_topk[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_rep_topk_counters
   int host_threads = 1;     // rtc_ctx_set_host_threads: the host side of rtc_tree_medoids
   // rtc_diag_counters: [0] pair tiles the join took, [1] tiled-kernel tiles, [2] merge-kernel tiles, [3] candidate lists contracted
   // to their forest, [4] greedy runs replayed from ONE global join, [5] greedy query blocks of the block loop, [6] estimates handed

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "rtc_internal.h"
+#include "rtc_mash_merge.h"
 
 int rtc_pair_common_tiled(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start,
                           const uint32_t* d_len, uint32_t n, uint32_t row0, uint32_t row1,
@@ -65,19 +66,8 @@ __global__ __launch_bounds__(256) void pair_mash_kernel(const T* __restrict__ ha
   if (row >= row1 || col >= col1) return;
   const T* a = hashes + start[row];
   const T* b = hashes + start[col];
-  const uint32_t na = len[row], nb = len[col];
-  uint32_t i = 0, j = 0, c = 0, d = 0;
-  while (d < sketch_size && i < na && j < nb) {
-    const T va = a[i], vb = b[j];
-    if (va < vb) i++;
-    else if (vb < va) j++;
-    else { c++; i++; j++; }
-    d++;
-  }
-  if (d < sketch_size) {  // one list exhausted: the rest of the other one still belongs to the union
-    const uint32_t rest = (i < na ? na - i : 0) + (j < nb ? nb - j : 0);
-    d += rest < sketch_size - d ? rest : sketch_size - d;
-  }
+  uint32_t c, d;
+  rtc_mash_merge(a, len[row], b, len[col], sketch_size, &c, &d);
   const uint64_t o = (uint64_t)(row - row0) * ld + (col - col0);
   common_out[o] = c;
   denom_out[o] = d;

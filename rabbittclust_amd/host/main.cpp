@@ -13,9 +13,9 @@
 // row-sharded with one all-reduce per Boruvka round (rtc_mst_sharded).  Also here: --append (clust-mst, and
 // clust-greedy --fast with or without a stored state), --dense, the tree / linkage writers, clust-greedy's
 // --save-rep cluster state (KSSD and MinHash) and representative database (--db ..., KSSD and MinHash), clust-greedy
-// --append on MinHash sketches, and the dense estimator loops (--inverted-index=false: modifyMST / greedyCluster).
-// clust-mst's --db / --save-rep, --auto-threshold and its companions and single-FASTA input to --append / --db are
-// outside this path and exit with a message.
+// --append on MinHash sketches, the dense estimator loops (--inverted-index=false: modifyMST / greedyCluster), and
+// clust-mst's --save-rep state and its MST representative database (--db ..., the search on the GPU: rtc_rep_topk).
+// Single-FASTA input to --append and to --db --build / --append is outside this path and exits with a message.
 #include <math.h>
 #include <iomanip>
 #include <limits>
@@ -849,6 +849,7 @@ struct Options {
   string repdb_path;        // clust-greedy --fast --db FILE with one of --build / --query / --assign / --append / --stats
   bool db_build = false, db_query = false, db_assign = false, db_stats = false;
   int topk = 5;             // --top-k of --query
+  bool has_topk = false;
   int threads = default_threads();
   bool sketchByFile = false, noSave = false, is_fast = false, isContainment = false, isJaccard = false, isSetKmer = false;
   bool has_threshold = false, has_input = false, has_presketched = false, has_premsted = false, has_output = false;
@@ -889,13 +890,13 @@ static Options parse(int argc, char** argv) {
     else if (a == "--fast") o.is_fast = true;
 #ifdef GREEDY_CLUST
     else if (a == "--save-rep") o.saveRep = true;
+#endif
     else if (a == "--db") o.repdb_path = need(i);
     else if (a == "--build") o.db_build = true;
     else if (a == "--query") o.db_query = true;
     else if (a == "--assign") o.db_assign = true;
     else if (a == "--stats") o.db_stats = true;
-    else if (a == "--top-k") o.topk = atoi(need(i));
-#endif
+    else if (a == "--top-k") { o.topk = atoi(need(i)); o.has_topk = true; }
     else if (a == "--drlevel") o.drlevel = atoi(need(i));
     else if (a == "--gpus") o.gpus = need(i);
 #ifndef GREEDY_CLUST
@@ -931,7 +932,8 @@ static Options parse(int argc, char** argv) {
 #ifndef GREEDY_CLUST
            "  --premsted DIR  --append LIST (with --presketched/--premsted DIR)\n"
            "  --auto-threshold  --stability  --dedup-dist D  --reps-per-cluster K (with --fast: <output>.dedup / .reps)\n"
-           "  --save-rep (mst_cluster_state.bin beside the sketches; a later --append measures against its representatives)"
+           "  --save-rep (mst_cluster_state.bin beside the sketches; a later --append measures against its representatives)\n"
+           "  [--fast] --db FILE --build|--query|--assign|--append LIST|--stats [--top-k N] (MST representative database)"
 #else
            "  --append LIST (with --presketched DIR)  --save-rep (cluster_state.bin beside the sketches)\n"
            "  [--fast] --db FILE --build|--query|--assign|--append LIST|--stats [--top-k N] (representative database)"
@@ -940,9 +942,7 @@ static Options parse(int argc, char** argv) {
       exit(0);
     }
     else if (
-#ifndef GREEDY_CLUST
-             a == "--db" || a == "--build" || a == "--query" || a == "--assign" || a == "--stats" || a == "--top-k" ||
-#else
+#ifdef GREEDY_CLUST
              a == "--dense" || a == "--auto-threshold" || a == "--stability" || a == "--dedup-dist" || a == "--reps-per-cluster" ||
 #endif
               a == "--newick-tree" || a == "--phylip-tree" ||
@@ -1039,7 +1039,7 @@ static void write_trees(const Options& o, const vector<GenomeInfo>& genomes, con
 // stored folder's parameters, evaluate only the pairs that involve a new genome (rows >= start_index,
 // src/MST.cpp:1375-1383 -- rtc_mst_append), merge that forest with the stored MST (sort + Kruskal,
 // :1693-1700), cut, print, and write the combined folder.
-static int append_mst_from_state(const Options& o, vector<Gpu>& gpus, MstState& st, const string& state_path);
+static int append_mst_from_state(const Options& o, vector<Gpu>& gpus, MstState& st, const string& state_path, bool db = false);
 static int append_clust_mst(const Options& o, vector<Gpu>& gpus) {
   rtc_ctx* ctx = gpus[0].ctx;
   {  // a --save-rep state beside the sketches: the new genomes are measured against its representatives (src/sub_command.cpp:1289-1316, :1533-1560)
@@ -1127,13 +1127,16 @@ static int append_clust_mst(const Options& o, vector<Gpu>& gpus) {
 // The state path of append_clust_mst[_fast]: sketch the new genomes with the state's parameters, measure them against the
 // representatives and against each other on the GPU (rtc_rep_match), replay the decisions in list order on the host
 // (append_mst_state), print the live clusters (printMstStateClusterResult), and write the state back with --save-rep and no -e.
-static int append_mst_from_state(const Options& o, vector<Gpu>& gpus, MstState& st, const string& state_path) {
+static int append_mst_from_state(const Options& o, vector<Gpu>& gpus, MstState& st, const string& state_path, bool db) {
   rtc_ctx* ctx = gpus[0].ctx;
   if (!o.sketchByFile) unsupported("single-FASTA input (run with -l and a genome list)");
   SketchJob job;
   job.kssd = st.kssd; job.minLen = o.minLen; job.threads = o.threads;
   if (st.kssd) { job.kmerSize = st.half_k * 2; job.drlevel = st.drlevel; }
-  else {
+  else if (db) {  // mst_repdb_append: contain_compress > 0 ? contain_compress : 1000 (src/sub_command.cpp:1238-1242)
+    job.kmerSize = st.kmer_size; job.sketchSize = st.sketch_size; job.isContainment = st.is_containment;
+    job.containCompress = st.contain_compress > 0 ? st.contain_compress : 1000;
+  } else {
     // the reference stores contain_compress = 0 (src/sub_command.cpp:2821, :3065) and sketches the new genomes with it
     if (st.is_containment && st.contain_compress <= 0) {
       cerr << "ERROR: is_containment is true but contain_compress is " << st.contain_compress << endl;
@@ -1186,16 +1189,113 @@ static int append_mst_from_state(const Options& o, vector<Gpu>& gpus, MstState& 
   print_mst_state_clusters(live, st.member_names, st.member_lens, st.sketch_by_file, o.outputFile, st.threshold);
   cerr << "-----write the cluster result into: " << o.outputFile << endl;
   cerr << "-----the cluster number of: " << o.outputFile << " is: " << live.size() << endl;
+  if (db) {  // mst_repdb_append[_fast]: the database is always saved back
+    if (!save_mst_state(state_path, st)) { cerr << "ERROR: failed to save updated MST RepDB state to: " << state_path << endl; return 1; }
+    cerr << "  Live clusters:       " << live.size() << endl << "  Total genomes:       " << st.N << endl << "  RepDB updated:       " << state_path << endl;
+    return 0;
+  }
   if (!o.noSave && o.saveRep && !save_mst_state(state_path, st)) return 1;
   return 0;
+}
+
+// mst_repdb_query[_fast] / mst_repdb_assign[_fast] (src/sub_command.cpp:942-1050, :1152-1236): the queries (-l LIST, or the
+// records of one FASTA file, named query_<i>) sketched with the database's parameters, every query's best representatives
+// from rtc_rep_topk on the GPU (assign: the best one, kept within the database's threshold), the TSV.
+static int mst_db_search(const Options& o, vector<Gpu>& gpus) {
+  rtc_ctx* ctx = gpus[0].ctx;
+  MstState st;
+  if (!load_mst_state(o.repdb_path, o.is_fast, st)) { cerr << "ERROR: failed to load MST RepDB from: " << o.repdb_path << endl; return 1; }
+  SketchJob job;
+  job.kssd = st.kssd; job.minLen = o.minLen; job.threads = o.threads;
+  if (st.kssd) { job.kmerSize = st.kmer_size > 0 ? st.kmer_size : st.half_k * 2; job.drlevel = st.drlevel; }
+  else {
+    job.kmerSize = st.kmer_size; job.sketchSize = st.sketch_size; job.isContainment = st.is_containment;
+    job.containCompress = st.contain_compress > 0 ? st.contain_compress : 1000;
+  }
+  const double t0 = get_sec();
+  vector<GenomeInfo> q; MinHashSketchFile mh; KssdSketchFile ks; Resident rs;
+  if (o.sketchByFile) sketch_files(gpus, o.inputFile, job, q, &mh, &ks, rs, true);
+  else {
+    vector<FastaRecord> recs; SeqModeSizes sz;
+    if (!read_sequences(o.inputFile, o.minLen, recs, sz)) return 1;
+    sketch_sequences(gpus, recs, job, q, &mh, &ks);
+  }
+  const double t1 = get_sec();
+  g_metrics.num("sketch_queries_s", t1 - t0);
+  const bool q64 = st.kssd ? ks.use64 : true;
+  if (!q.empty() && q64 != st.use64) {
+    cerr << "ERROR: the query sketches have use64=" << q64 << " but the MST RepDB has use64=" << st.use64 << " (different hash width)" << endl;
+    return 1;
+  }
+  vector<string> names;
+  for (size_t i = 0; i < q.size(); i++) names.push_back(o.sketchByFile ? q[i].fileName : string());  // single FASTA: fileName is empty
+  const uint32_t R = (uint32_t)st.reps(), Q = (uint32_t)q.size();
+  const uint32_t topk = o.db_assign ? 1u : (uint32_t)std::max(o.topk, 0);
+  cerr << "===== MST RepDB " << (o.db_assign ? "Assignment" : "Query") << " (" << (st.kssd ? "KSSD" : "MinHash") << ") =====" << endl
+       << "  Query genomes:  " << Q << endl;
+  if (!o.db_assign) cerr << "  Top-k:          " << o.topk << endl;
+  cerr << "  DB reps:        " << R << endl;
+  if (o.db_assign) cerr << "  Threshold:      " << st.threshold << endl;
+  vector<rtc_rep_hit> hits;
+  vector<uint32_t> per(Q, 0);
+  if (Q && R) {
+    vector<uint8_t> live(R);
+    for (uint32_t r = 0; r < R; r++) live[r] = st.clusters[r].empty() ? 0 : 1;
+    DeviceSketches ds;
+    if (st.use64) {
+      vector<vector<uint64_t>> all(st.h64);
+      const vector<vector<uint64_t>>& qh = st.kssd ? ks.h64 : mh.hashes;
+      all.insert(all.end(), qh.begin(), qh.end());
+      upload_sketches(ctx, &all, nullptr, ds);
+    } else {
+      vector<vector<uint32_t>> all(st.h32);
+      all.insert(all.end(), ks.h32.begin(), ks.h32.end());
+      upload_sketches(ctx, nullptr, &all, ds);
+    }
+    uint64_t nh = 0;
+    hits.resize((size_t)Q * (topk ? std::min<uint32_t>(topk, 64) : 16));
+    CHECK(ctx, rtc_rep_topk(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, R, Q, live.data(), mst_query_wmode(st), topk, 0, hits.data(),
+                            hits.size(), &nh, per.data()));
+    if (nh > hits.size()) {
+      hits.resize(nh);
+      CHECK(ctx, rtc_rep_topk(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, R, Q, live.data(), mst_query_wmode(st), topk, 0, hits.data(),
+                              hits.size(), &nh, per.data()));
+    }
+    hits.resize(nh);
+    (void)rtc_dev_free(ctx, ds.d_hashes); (void)rtc_dev_free(ctx, ds.d_start); (void)rtc_dev_free(ctx, ds.d_len);
+  }
+  const double t2 = get_sec();
+  g_metrics.num("rep_topk_s", t2 - t1);
+  cerr << "========time of rep top-k (GPU) is: " << t2 - t1 << "========" << endl;
+  if (o.db_assign) {
+    int assigned = 0;
+    if (!write_mst_assign_tsv(o.outputFile, st, names, hits, per, &assigned)) return 1;
+    cerr << "===== Assignment Results =====" << endl;
+    if (Q) cerr << "  Assigned:    " << assigned << " (" << std::fixed << std::setprecision(1) << (100.0 * assigned / Q) << "%)" << endl
+                << "  Novel:       " << Q - assigned << " (" << std::fixed << std::setprecision(1) << (100.0 * (Q - assigned) / Q) << "%)" << endl;
+    cerr << "  Output:      " << o.outputFile << endl << "==============================" << endl;
+  } else {
+    if (!write_mst_query_tsv(o.outputFile, st, names, hits, per)) return 1;
+    cerr << "===== Query Results =====" << endl << "  Output: " << o.outputFile << endl << "=========================" << endl;
+  }
+  return 0;
+}
+
+// mst_repdb_append[_fast] (src/sub_command.cpp:1051-1100, :1237-1280): the --append machinery against the database, saved in place
+static int mst_db_append(const Options& o, vector<Gpu>& gpus) {
+  MstState st;
+  if (!load_mst_state(o.repdb_path, o.is_fast, st)) { cerr << "ERROR: failed to load MST RepDB from: " << o.repdb_path << endl; return 1; }
+  cerr << "===== MST RepDB Append (" << (o.is_fast ? "KSSD" : "MinHash") << ") =====" << endl << "  Existing reps:    " << st.reps() << endl
+       << "  Existing genomes: " << st.N << endl;
+  return append_mst_from_state(o, gpus, st, o.repdb_path, true);
 }
 
 // MinHashInitialMstState / KssdInitialMstState + save (src/sub_command.cpp:2083-2087, :2577-2581, :2814-2823, :3058-3068): every
 // cluster of the forest collapsed to its tree medoid (rtc_tree_medoids with dedup_dist = +inf), written to
 // <folder>/mst_cluster_state.bin
-static int save_initial_mst_state(rtc_ctx* ctx, const Options& o, const string& folder, const vector<GenomeInfo>& genomes, bool sketchByFile,
+static int save_initial_mst_state(rtc_ctx* ctx, const Options& o, const string& state_path, const vector<GenomeInfo>& genomes, bool sketchByFile,
                                   const vector<rtc_edge>& forest, const vector<vector<int>>& clusters, const MinHashSketchFile& mh,
-                                  const KssdSketchFile& ks, bool from_sketches) {
+                                  const KssdSketchFile& ks, bool from_sketches, int contain_compress = 0) {
   const int n = (int)genomes.size();
   const size_t nh = o.is_fast ? (ks.use64 ? ks.h64.size() : ks.h32.size()) : mh.hashes.size();
   if ((int)nh != n) { cerr << "ERROR: --save-rep needs the sketches on the host (" << nh << " of " << n << ")" << endl; return 1; }
@@ -1219,14 +1319,21 @@ static int save_initial_mst_state(rtc_ctx* ctx, const Options& o, const string& 
     // here (src/SketchInfo.cpp) and containCompress when it was loaded (src/Sketch_IO.cpp:334)
     st.kmer_size = mh.kmerSize;
     st.is_containment = mh.isContainment;
-    st.contain_compress = 0;
+    st.contain_compress = contain_compress;
     st.sketch_size = !mh.isContainment ? mh.sketchSize
                      : from_sketches ? mh.containCompress
                      : sketchByFile ? std::max(file_length_for_containment(genomes[0].fileName) / mh.containCompress, 100)
                                     : std::max(genomes[0].seq0.length / mh.containCompress, 100);
     init_mst_state(st, genomes, sketchByFile, clusters, rep_of_cluster, &mh.hashes, nullptr);
   }
-  return save_mst_state(folder + "/mst_cluster_state.bin", st) ? 0 : 1;
+  if (!save_mst_state(state_path, st)) return 1;
+  if (!o.repdb_path.empty()) {  // build_and_save_{kssd,minhash}_mst_db's summary
+    cerr << "\n===== MST RepDB Build Summary (" << (o.is_fast ? "KSSD" : "MinHash") << ") =====" << endl << "  Total genomes:    " << n << endl
+         << "  Representatives:  " << st.reps() << endl;
+    if (n) cerr << "  Compression:      " << std::fixed << std::setprecision(2) << (1.0 - (double)st.reps() / n) * 100.0 << "%" << endl;
+    cerr << "  RepDB saved to:   " << state_path << endl;
+  }
+  return 0;
 }
 #endif
 
@@ -1896,9 +2003,37 @@ int main(int argc, char** argv) {
   if (o.has_append && !o.has_presketched && o.repdb_path.empty()) { cerr << "ERROR option --append, option --presketched needed" << endl; return 1; }  // src/main.cpp:378-381
 #endif
 #ifndef GREEDY_CLUST
+  // ---- MST RepDB mode: --db FILE (src/main.cpp:213-254, :525-600) ----
+  if (o.has_topk && !o.db_query) { cerr << "ERROR: --top-k requires --query" << endl; return 1; }
+  const bool db_action = o.db_build || o.db_query || o.db_assign || o.db_stats;
+  if (db_action && o.repdb_path.empty()) { cerr << "ERROR: --build / --query / --assign / --stats require --db" << endl; return 1; }
+  if ((int)o.db_build + (int)o.db_query + (int)o.db_assign + (int)o.db_stats > 1) { cerr << "ERROR: --build, --query, --assign and --stats exclude each other" << endl; return 1; }
+  if (!o.repdb_path.empty()) {
+    if (o.db_stats) {  // mst_repdb_stats[_fast]: before any GPU context
+      MstState st;
+      if (!load_mst_state(o.repdb_path, o.is_fast, st)) { cerr << "ERROR: failed to load MST RepDB from: " << o.repdb_path << endl; return 1; }
+      print_mst_state_stats(st, std::cout);
+      std::cout.flush();
+      return 0;
+    }
+    if (o.db_build && !o.has_presketched && !o.has_input) { cerr << "ERROR: --build requires --presketched <folder> or -i <genome_list> -l" << endl; return 1; }
+    if (o.db_query && !o.has_input) { cerr << "ERROR: --query requires -i <input_file>" << endl; return 1; }
+    if (o.db_assign && !o.has_input) { cerr << "ERROR: --assign requires -i <input_file>" << endl; return 1; }
+    if (!db_action && !o.has_append) { cerr << "ERROR: --db requires one of: --build, --query, --assign, --append, --stats" << endl; return 1; }
+    if (o.db_build && !o.has_presketched && !o.sketchByFile) unsupported("single-FASTA input (run with -l and a genome list)");
+    // the tree writers, --dense and the post-processing flags have no effect here; the build keeps no sketch folder
+    // (isSave = false) and takes -k or 21, -s or 1000, without the tuner
+    o.newick = o.phylip = o.nexus = o.linkage = o.dense = o.autoThreshold = o.stability = o.saveRep = false;
+    o.dedupDist = -1.0; o.repsPerCluster = 0; o.useIndex = true;
+    if (o.db_build && !o.has_presketched) {
+      o.noSave = true;
+      if (!o.isSetKmer) { o.kmerSize = 21; cerr << "-----use default kmerSize: " << o.kmerSize << endl; }
+      if (!o.is_fast && !o.isJaccard) o.sketchSize = 1000;
+    }
+  }
   // ---- --premsted: no sketching, no GPU (clust_from_mst[_fast], src/sub_command.cpp:1760-1934) ----
   if (o.has_append && o.has_input) { cerr << "ERROR: --append and -i/--input exclude each other" << endl; return 1; }
-  if (o.has_append && !o.has_presketched && !o.has_premsted) { cerr << "ERROR option --append, option --presketched or --premsted needed" << endl; return 1; }
+  if (o.has_append && !o.has_presketched && !o.has_premsted && o.repdb_path.empty()) { cerr << "ERROR option --append, option --presketched or --premsted needed" << endl; return 1; }
   if (o.has_premsted && !o.has_append) {
     vector<GenomeInfo> genomes; vector<rtc_edge> mst; bool byFile = true;
     if (!load_genome_info(o.folder_path, "mst", genomes, o.is_fast, byFile)) return 1;
@@ -1936,7 +2071,7 @@ int main(int argc, char** argv) {
 #ifdef GREEDY_CLUST
         o.has_append || !o.repdb_path.empty() || o.has_presketched;
 #else
-        o.has_append || ((o.dense || !o.useIndex) && o.has_presketched);
+        o.has_append || ((o.dense || !o.useIndex) && o.has_presketched) || !o.repdb_path.empty();
 #endif
     if (spec == "all") { gpus_by_default = true; for (int d = 0; d < ndev; d++) devs.push_back(d); }
     else if (spec.find(',') == string::npos && atoi(spec.c_str()) > 0 && spec.find_first_not_of("0123456789") == string::npos) {
@@ -2012,12 +2147,23 @@ int main(int argc, char** argv) {
   const bool list_run = !o.has_presketched && !o.has_append && o.has_input && o.sketchByFile
 #ifdef GREEDY_CLUST
                         && o.repdb_path.empty()
+#else
+                        && (o.repdb_path.empty() || o.db_build)
 #endif
       ;
   const GpusReady gpus_ready{wait_gpus, &gpus_done};
   if (!list_run) wait_gpus();
   Resident rs;
 #ifndef GREEDY_CLUST
+  if (!o.repdb_path.empty() && !o.db_build) {  // --build goes on through the MST flow below
+    const int rc = (o.db_query || o.db_assign) ? mst_db_search(o, gpus) : mst_db_append(o, gpus);
+    g_metrics.str("command", "clust-mst");
+    g_metrics.str("sketch", o.is_fast ? "kssd" : "minhash");
+    g_metrics.write();
+    for (Gpu& g : gpus) { if (g.comm) rtc_comm_destroy(g.comm); }
+    for (Gpu& g : gpus) rtc_ctx_destroy(g.ctx);
+    return rc;
+  }
   if (o.has_append) return append_clust_mst(o, gpus);
 #else
   if (!o.repdb_path.empty()) {
@@ -2064,13 +2210,14 @@ int main(int argc, char** argv) {
       maxSize = sz.maxSize; minSize = sz.minSize; averageSize = sz.totalSize / sz.number;
     }
     // main.cpp:632 (clust-mst --fast uses the kssd tuner) / :659 (everything else)
-    if (o.is_fast && !greedy) { if (!tune_kssd_parameters(o.isSetKmer, maxSize, minSize, averageSize, o.isContainment, o.kmerSize, o.threshold, o.drlevel)) return 1; }
+    if (o.db_build) { /* mst_repdb_build_from_genome[_fast]: the parameters as given, no tuner */ }
+    else if (o.is_fast && !greedy) { if (!tune_kssd_parameters(o.isSetKmer, maxSize, minSize, averageSize, o.isContainment, o.kmerSize, o.threshold, o.drlevel)) return 1; }
     else if (!tune_parameters(greedy, o.isSetKmer, maxSize, minSize, averageSize, o.isContainment, o.isJaccard, o.kmerSize, o.threshold, o.containCompress, o.sketchSize)) return 1;
     SketchJob job;
     job.kssd = o.is_fast; job.kmerSize = o.kmerSize; job.sketchSize = o.sketchSize; job.isContainment = o.isContainment;
     job.containCompress = o.containCompress; job.drlevel = o.drlevel; job.minLen = o.minLen; job.threads = o.threads;
     if (getenv("RTC_VERBOSE")) fprintf(stderr, "[tune]  cal_size + tune_parameters in %.3fs\n", get_sec() - t0);
-    if (o.sketchByFile) sketch_files(gpus, o.inputFile, job, genomes, &mh, &ks, rs, !o.noSave, &gpus_ready);
+    if (o.sketchByFile) sketch_files(gpus, o.inputFile, job, genomes, &mh, &ks, rs, !o.noSave || o.db_build, &gpus_ready);
     else { wait_gpus(); sketch_sequences(gpus, seq_recs, job, genomes, &mh, &ks); }
     wait_gpus();
     mh.kmerSize = o.kmerSize; mh.isContainment = o.isContainment; mh.containCompress = o.containCompress; mh.sketchSize = o.sketchSize;
@@ -2252,7 +2399,13 @@ int main(int argc, char** argv) {
   cluster_from_mst(mst, genomes, sketchByFile, o.outputFile, o.threshold, &forest, &clusters);
   // --save-rep: the presketched flows always, the flows from genomes when they keep a sketch folder (-e: none)
   if (o.saveRep && (from_sketches || !o.noSave) &&
-      save_initial_mst_state(ctx, o, folder_path, genomes, sketchByFile, forest, clusters, mh, ks, from_sketches) != 0)
+      save_initial_mst_state(ctx, o, folder_path + "/mst_cluster_state.bin", genomes, sketchByFile, forest, clusters, mh, ks, from_sketches) != 0)
+    return 1;
+  // --db --build: the state is the database (build_and_save_{kssd,minhash}_mst_db); a MinHash containment build from genomes
+  // stores -c, a --presketched build 0
+  if (o.db_build &&
+      save_initial_mst_state(ctx, o, o.repdb_path, genomes, sketchByFile, forest, clusters, mh, ks, from_sketches,
+                             (!o.is_fast && !from_sketches && mh.isContainment) ? o.containCompress : 0) != 0)
     return 1;
   // --dedup-dist / --reps-per-cluster: the KSSD flows only (compute_kssd_clusters, clust_from_sketch_fast)
   if (o.is_fast) dedup_and_reps(ctx, o.dedupDist, o.repsPerCluster, o.threads, forest, clusters, genomes, sketchByFile, o.outputFile);

@@ -14,6 +14,7 @@
 #include <sys/stat.h>
 #include <time.h>
 #include <atomic>
+#include <cmath>
 #include <zlib.h>
 #if defined(__x86_64__)
 #include <immintrin.h>  // the AVX2 / AVX-512 tiers of the FASTA intake; other hosts build the portable tier only
@@ -2493,6 +2494,151 @@ std::vector<std::vector<int>> append_mst_state(MstState& st, const std::vector<s
   }
   st = std::move(out);
   return live;
+}
+
+// print_cluster_size_histogram + MinHashMstPrintStats / KssdMstPrintStats (src/mst_state.cpp:1342-1415)
+void print_mst_state_stats(const MstState& st, std::ostream& os) {
+  size_t uniq = 0;
+  if (st.use64) {
+    std::vector<uint64_t> all;
+    for (const auto& h : st.h64) all.insert(all.end(), h.begin(), h.end());
+    std::sort(all.begin(), all.end());
+    uniq = (size_t)(std::unique(all.begin(), all.end()) - all.begin());
+  } else {
+    std::vector<uint32_t> all;
+    for (const auto& h : st.h32) all.insert(all.end(), h.begin(), h.end());
+    std::sort(all.begin(), all.end());
+    uniq = (size_t)(std::unique(all.begin(), all.end()) - all.begin());
+  }
+  if (st.kssd) {
+    os << "========== KSSD MST RepDB stats ==========\n";
+    os << "  Kmer size:        " << st.kmer_size << "\n";
+    os << "  half_k:           " << st.half_k << "\n";
+    os << "  half_subk:        " << st.half_subk << "\n";
+    os << "  drlevel:          " << st.drlevel << "\n";
+    os << "  use64:            " << (st.use64 ? "yes" : "no") << "\n";
+  } else {
+    os << "========== MinHash MST RepDB stats ==========\n";
+    os << "  Kmer size:        " << st.kmer_size << "\n";
+    os << "  Sketch size:      " << st.sketch_size << "\n";
+    os << "  Containment:      " << (st.is_containment ? "yes" : "no") << "\n";
+    if (st.is_containment) os << "  Contain compress: " << st.contain_compress << "\n";
+  }
+  os << "  Threshold:        " << std::fixed << std::setprecision(6) << st.threshold << "\n";
+  os << "  Total reps slots: " << st.reps() << "\n";
+  os << "  sketch_by_file:   " << (st.sketch_by_file ? "yes" : "no") << "\n";
+  os << "  Total members N:  " << st.N << "\n";
+  if (!st.kssd) os << "  Inverted index:   " << uniq << " unique hashes\n";
+  else os << "  Inverted index:   " << uniq << " unique hashes (" << (st.use64 ? "64" : "32") << "-bit)\n";
+  int b1 = 0, b2 = 0, b3_5 = 0, b6_10 = 0, b11_100 = 0, b101_1000 = 0, bgt = 0, live = 0, total = 0, mx = 0;
+  int mn = std::numeric_limits<int>::max();
+  for (const auto& c : st.clusters) {
+    const int sz = (int)c.size();
+    if (sz == 0) continue;
+    live++; total += sz;
+    mx = std::max(mx, sz); mn = std::min(mn, sz);
+    if (sz == 1) b1++;
+    else if (sz == 2) b2++;
+    else if (sz <= 5) b3_5++;
+    else if (sz <= 10) b6_10++;
+    else if (sz <= 100) b11_100++;
+    else if (sz <= 1000) b101_1000++;
+    else bgt++;
+  }
+  if (live == 0) mn = 0;
+  os << "  Live clusters:    " << live << "\n";
+  os << "  Total members:    " << total << "\n";
+  os << "  Cluster size:     min=" << mn << " max=" << mx << " avg=" << std::fixed << std::setprecision(2)
+     << (live ? (double)total / live : 0.0) << "\n";
+  os << "  Size histogram:\n";
+  os << "    size=1         : " << b1 << "\n";
+  os << "    size=2         : " << b2 << "\n";
+  os << "    size=3-5       : " << b3_5 << "\n";
+  os << "    size=6-10      : " << b6_10 << "\n";
+  os << "    size=11-100    : " << b11_100 << "\n";
+  os << "    size=101-1000  : " << b101_1000 << "\n";
+  os << "    size>1000      : " << bgt << "\n";
+  os << (st.kssd ? "==========================================\n" : "==============================================\n");
+}
+
+std::vector<int> mst_live_index(const MstState& st) {
+  std::vector<int> live(st.clusters.size(), -1);
+  int n = 0;
+  for (size_t i = 0; i < st.clusters.size(); i++) if (!st.clusters[i].empty()) live[i] = n++;
+  return live;
+}
+
+int mst_query_wmode(const MstState& st) {
+  if (st.kssd) return 0;
+  if (st.is_containment) return 1;
+  return 2 | (int)((uint32_t)std::max(st.sketch_size, 1) << 2);
+}
+
+double mst_query_distance(uint32_t common, uint32_t denom, int wmode, int kmer_size) {
+  const double j = denom == 0 ? 0.0 : (double)common / (double)denom;
+  double d;
+  if ((wmode & 3) == 1) {  // containDistance
+    if (j == 1.0) d = 0.0;
+    else if (j == 0.0) d = 1.0;
+    else d = -(1.0 / kmer_size) * log(j);
+  } else {  // mash_distance (set Jaccard) / MinHash::distance (union-truncated Jaccard)
+    if (j == 1.0) d = 0.0;
+    else if (j == 0.0) d = 1.0;
+    else { d = -log(2.0 * j / (1.0 + j)) / (double)kmer_size; if (d > 1.0) d = 1.0; }
+  }
+  return std::isnan(d) ? std::numeric_limits<double>::infinity() : d;
+}
+
+static std::string mst_query_name(const std::vector<std::string>& qnames, size_t q) {
+  return qnames[q].empty() ? "query_" + std::to_string(q) : qnames[q];
+}
+
+bool write_mst_query_tsv(const std::string& path, const MstState& st, const std::vector<std::string>& qnames,
+                         const std::vector<rtc_rep_hit>& hits, const std::vector<uint32_t>& per_query) {
+  FILE* fp = fopen(path.c_str(), "w");
+  if (!fp) { std::cerr << "ERROR: cannot open output file: " << path << std::endl; return false; }
+  const std::vector<int> live = mst_live_index(st);
+  const int wmode = mst_query_wmode(st);
+  fprintf(fp, "#query\trank\trep_name\tdistance\tcluster_id\tcluster_size\n");
+  size_t h = 0;
+  for (size_t q = 0; q < qnames.size(); q++) {
+    const std::string name = mst_query_name(qnames, q);
+    if (per_query[q] == 0) fprintf(fp, "%s\t0\tno_match\t-1\t-1\t0\n", name.c_str());
+    for (uint32_t r = 0; r < per_query[q]; r++, h++) {
+      const rtc_rep_hit& x = hits[h];
+      fprintf(fp, "%s\t%d\t%s\t%.6f\t%d\t%d\n", name.c_str(), (int)r + 1, st.rep_names[x.slot].c_str(),
+              mst_query_distance(x.common, x.denom, wmode, st.kmer_size), live[x.slot], (int)st.clusters[x.slot].size());
+    }
+  }
+  fclose(fp);
+  return true;
+}
+
+bool write_mst_assign_tsv(const std::string& path, const MstState& st, const std::vector<std::string>& qnames,
+                          const std::vector<rtc_rep_hit>& hits, const std::vector<uint32_t>& per_query, int* n_assigned) {
+  FILE* fp = fopen(path.c_str(), "w");
+  if (!fp) { std::cerr << "ERROR: cannot open output file: " << path << std::endl; return false; }
+  const std::vector<int> live = mst_live_index(st);
+  const int wmode = mst_query_wmode(st);
+  fprintf(fp, "#query\tassigned_cluster\trep_name\tdistance\tcluster_size\tstatus\n");
+  size_t h = 0;
+  int assigned = 0;
+  for (size_t q = 0; q < qnames.size(); q++) {
+    const std::string name = mst_query_name(qnames, q);
+    double d = 0.0;
+    if (per_query[q]) d = mst_query_distance(hits[h].common, hits[h].denom, wmode, st.kmer_size);
+    if (per_query[q] && d <= st.threshold) {  // MinHashMstAssign / KssdMstAssign: the top-1 hit within the state's threshold
+      const uint32_t s = hits[h].slot;
+      fprintf(fp, "%s\t%d\t%s\t%.6f\t%d\tassigned\n", name.c_str(), live[s], st.rep_names[s].c_str(), d, (int)st.clusters[s].size());
+      assigned++;
+    } else {
+      fprintf(fp, "%s\t-1\tunassigned\t-1\t0\tnovel\n", name.c_str());
+    }
+    h += per_query[q];
+  }
+  fclose(fp);
+  if (n_assigned) *n_assigned = assigned;
+  return true;
 }
 
 void print_mst_state_clusters(const std::vector<std::vector<int>>& clusters, const std::vector<std::string>& member_names,

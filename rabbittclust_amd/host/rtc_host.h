@@ -256,6 +256,23 @@ void print_mst_state_clusters(const std::vector<std::vector<int>>& clusters, con
                               const std::vector<uint64_t>& member_lens, bool sketch_by_file, const std::string& output_file,
                               double threshold);
 
+// ---- clust-mst --db: the MST RepDB is the state file (src/mst_state.cpp:1150-1415) ----
+// MinHashMstPrintStats / KssdMstPrintStats, byte for byte; the "unique hashes" are the distinct hashes over the representatives
+void print_mst_state_stats(const MstState& st, std::ostream& os);
+// build_live_index: slot -> its number among the slots with a non-empty cluster, -1 for a retired slot
+std::vector<int> mst_live_index(const MstState& st);
+// the search's weight mode for this state (rtc_rep_topk): 0 KSSD, 1 MinHash containment, 2 | sketch_size << 2 MinHash
+int mst_query_wmode(const MstState& st);
+// the reference's distance from a hit's (common, denom) with libm: mash_distance (mode 0), containDistance (1),
+// MinHash::distance (2); NaN becomes +inf
+double mst_query_distance(uint32_t common, uint32_t denom, int wmode, int kmer_size);
+// the --query TSV (mst_repdb_query[_fast]) and the --assign TSV (mst_repdb_assign[_fast]) from rtc_rep_topk's hits, sorted by
+// (query, rank), per_query[q] of them for query q; false if the file does not open
+bool write_mst_query_tsv(const std::string& path, const MstState& st, const std::vector<std::string>& qnames,
+                         const std::vector<rtc_rep_hit>& hits, const std::vector<uint32_t>& per_query);
+bool write_mst_assign_tsv(const std::string& path, const MstState& st, const std::vector<std::string>& qnames,
+                          const std::vector<rtc_rep_hit>& hits, const std::vector<uint32_t>& per_query, int* n_assigned);
+
 std::string current_date_time();  // src/common.hpp:36-44
 
 // Time the parser threads spent inside gzip decompression (libdeflate or zlib), summed over threads, and the bytes it produced
