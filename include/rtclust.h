@@ -464,6 +464,25 @@ int rtc_rep_topk_last_path(const rtc_ctx* ctx);
  * scatter), out[8] selection ns (with the read-back), out[9] reserved. */
 int rtc_rep_topk_counters(const rtc_ctx* ctx, uint64_t out[10]);
 
+/* ---- clust-dbscan --fast: KSSD DBSCAN on one GPU ----------------------------------------------------- */
+/* KssdDBSCAN (src/dbscan.cpp:725-985) without --knn.  Neighbours are findNeighborsKSSDWithIndex's (:366-612): p != q, both
+ * non-empty, floor(t |p|) <= |q| <= ceil(|p| / t) and !(common (1 + t) + 1e-12 < t |p| + t |q|) in double, t = x / (2 - x),
+ * x = exp(-eps kmer_size) on the host (:751-752).  width 4 (u32, the inverted index): common is the u16 count of MarkCnt,
+ * min(common, 65535), and max_posting > 0 drops every hash held by more than max_posting sketches before counting (:95-130)
+ * while |p| and |q| stay the unpruned sizes.  width 8 (u64, the brute force :383-445): no saturation, no pruning, and the
+ * empty sketches are neighbours of each other.  A core point has |N(p)| + 1 >= min_pts.  h_labels[n]: the cluster of every
+ * point, numbered in the order the reference's walk opens them (by smallest core index), -1 for noise; border points join the
+ * lowest-numbered cluster among their core neighbours'.  h_core[n] (may be NULL): 1 for the core points.  Returns RTC_ERR_UNSUPPORTED where the reference's relation is not
+ * symmetric or not defined: t <= 1e-12, ceil(max |p| / t) > INT_MAX for u32 sketches, or a candidate pair whose two
+ * orientations disagree (the message names it).  RTC_EDGE_BUDGET bounds the candidate edges of one row chunk.  Synchronous. */
+int rtc_dbscan(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+               double eps, int min_pts, int kmer_size, int max_posting, int32_t* h_labels, uint8_t* h_core,
+               uint32_t* h_n_clusters, uint32_t* h_n_noise);
+/* What the last rtc_dbscan call did: out[0] row chunks of the pair phase, out[1] candidate edges (pairs sharing a hash),
+ * out[2] eps edges, out[3] core points, out[4] pairs whose orientations disagreed, out[5] hook rounds, out[6] pair phase ns,
+ * out[7] eps filter ns, out[8] components and labels ns, out[9] whole call ns. */
+int rtc_dbscan_counters(const rtc_ctx* ctx, uint64_t out[10]);
+
 #ifdef __cplusplus
 }
 #endif

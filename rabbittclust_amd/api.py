@@ -574,6 +574,29 @@ class Context:
                  "bucket_ns", "select_ns")
         return {k: int(a[i]) for i, k in enumerate(names)}
 
+    def dbscan(self, sk, eps, min_pts, kmer_size, max_posting=0, return_core=False):
+        """clust-dbscan --fast (KssdDBSCAN, src/dbscan.cpp:725-985) on the sketch set: int32 label per point, clusters numbered
+        in the reference's order, -1 for noise.  kmer_size: the k of exp(-eps k) (from genomes the tuned k, from a sketch folder
+        half_k * 2).  return_core: (labels, bool core flags)."""
+        n = sk.n
+        labels = np.zeros(max(n, 1), dtype=np.int32)
+        core = np.zeros(max(n, 1), dtype=np.uint8)
+        ncl, nnoise = C.c_uint32(), C.c_uint32()
+        self.check(self.lib.rtc_dbscan(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n, float(eps),
+                                       int(min_pts), int(kmer_size), int(max_posting), _np_ptr(labels), _np_ptr(core),
+                                       C.byref(ncl), C.byref(nnoise)))
+        if return_core:
+            return labels[:n].copy(), core[:n].astype(bool)
+        return labels[:n].copy()
+
+    def dbscan_counters(self):
+        """rtc_dbscan_counters as a dict (the last dbscan call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_dbscan_counters(self.h, a))
+        names = ("chunks", "candidate_edges", "eps_edges", "core_points", "asymmetric_pairs", "hook_rounds", "pair_ns",
+                 "filter_ns", "components_ns", "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
 
 class Comm:
     """One rtc_comm (RCCL communicator of one GPU / context).  Ranks are processes (init_rank, the id

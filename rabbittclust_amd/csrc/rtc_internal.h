@@ -77,6 +77,9 @@ struct rtc_ctx {
   int dedup_last_path = 0;  // rtc_dedup_last_path
   int rep_topk_path = 0;    // rtc_rep_topk_last_path
   uint64_t rep_topk[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_rep_topk_counters
+  // rtc_dbscan_counters: [0] row chunks, [1] candidate edges, [2] eps edges, [3] core points, [4] asymmetric pairs, [5] hook rounds,
+  // [6] pair phase ns, [7] eps filter ns, [8] components + labels ns, [9] whole call ns
+  uint64_t dbscan[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   int host_threads = 1;     // rtc_ctx_set_host_threads: the host side of rtc_tree_medoids
   // rtc_diag_counters: [0] pair tiles the join took, [1] tiled-kernel tiles, [2] merge-kernel tiles, [3] candidate lists contracted
   // to their forest, [4] greedy runs replayed from ONE global join, [5] greedy query blocks of the block loop, [6] estimates handed
@@ -171,6 +174,7 @@ int rtc_msf_device(rtc_ctx* ctx, const rtc_cedge* d_edges, uint64_t m, const uin
                    int is_containment, uint32_t s_fixed, const rtc_reduce_hook* hook, rtc_cedge* d_sel,
                    uint64_t* n_sel_out, int* rounds_out, bool sorted = true, uint32_t max_len = 0);
 int rtc_sort_forest_device(rtc_ctx* ctx, rtc_cedge* d_sel, uint64_t ns, const uint32_t* d_len, int wmode);
+int rtc_sort_u32_pairs(rtc_ctx* ctx, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t n);
 uint32_t rtc_fixed_size_of(const uint32_t* h_len, uint32_t n);
 size_t rtc_msf_scratch_bytes(uint32_t n);
 struct rtc_mst_bufs_t { uint32_t* h_len; rtc_cedge* h_sel; rtc_cedge* d_sel; };  // page-locked sizes + forest, device forest list

@@ -79,3 +79,15 @@ int rtc_sort_forest_device(rtc_ctx* ctx, rtc_cedge* d_sel, uint64_t ns64, const 
   RTC_HIP(ctx, hipMemcpyAsync(d_sel, out, (size_t)ns * sizeof(rtc_cedge), hipMemcpyDeviceToDevice, s));
   return RTC_OK;
 }
+
+// n u32 keys sorted ascending with their u32 values (stable LSD radix sort), keys_in / vals_in left as they are.  Scratch: slot 5
+// of the context.  Context stream, asynchronous.  (clust-dbscan --max-posting: the hashes with their positions.)
+int rtc_sort_u32_pairs(rtc_ctx* ctx, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t n) {
+  if (!n) return RTC_OK;
+  size_t tb = 0;
+  RTC_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tb, keys_in, keys_out, vals_in, vals_out, n, 0u, 32u, ctx->stream));
+  void* tmp = nullptr;
+  RTC_TRY(rtc_ws(ctx, 5, tb + 256, &tmp));
+  RTC_HIP(ctx, rocprim::radix_sort_pairs(tmp, tb, keys_in, keys_out, vals_in, vals_out, n, 0u, 32u, ctx->stream));
+  return RTC_OK;
+}

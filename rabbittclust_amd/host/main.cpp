@@ -5,8 +5,8 @@
 // records are the genomes (no -l), MinHash
 // and KSSD (--fast) sketching, --presketched / --premsted resume, -e/--no-save, and the same
 // intermediate folder (info.sketch, hash.sketch, minhash.sketch.index, kssd.*, info.mst,
-// edge.mst).  Built twice: -DGREEDY_CLUST gives clust-greedy, otherwise clust-mst
-// (CMakeLists.txt:40-58 of the reference does the same).
+// edge.mst).  Built three times: -DGREEDY_CLUST gives clust-greedy, -DDBSCAN_CLUST clust-dbscan (KSSD only, src/main.cpp:478-522;
+// rtc_dbscan), otherwise clust-mst (CMakeLists.txt:40-58 of the reference does the same).
 // GPUs: every visible MI355X is used (--gpus LIST / RTC_GPUS to choose): one context + one host thread
 // per GPU, file batches go round-robin to the GPUs, the sketches stay in HBM (copied to the host only
 // to write hash.sketch), are shared among the GPUs with RCCL broadcasts, and the MST runs
@@ -863,6 +863,8 @@ struct Options {
   double dedupDist = -1.0;
   int repsPerCluster = 0;
   string gpus;  // --gpus / RTC_GPUS: "all" (default), a count, or a comma list of device ordinals
+  double dbscanEps = 0.05;  // clust-dbscan --eps / --minpts / --max-posting (src/main.cpp:173-182)
+  int dbscanMinPts = 5, maxPosting = 0;
 };
 
 static void unsupported(const char* what) {
@@ -875,6 +877,20 @@ static Options parse(int argc, char** argv) {
   auto need = [&](int& i) -> const char* { if (i + 1 >= argc) { fprintf(stderr, "ERROR: option %s requires a value\n", argv[i]); exit(1); } return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     const string a = argv[i];
+#ifdef DBSCAN_CLUST
+    // the options of the DBSCAN build (src/main.cpp:173-182); the MST / greedy ones are not defined there.  The common options
+    // -c (given to the KSSD tuner, as src/main.cpp:516 does), -s and --save-rep (no effect on DBSCAN) are parsed below.
+    if (a == "--eps") { o.dbscanEps = atof(need(i)); continue; }
+    if (a == "--minpts") { o.dbscanMinPts = atoi(need(i)); continue; }
+    if (a == "--max-posting") { o.maxPosting = atoi(need(i)); continue; }
+    if (a == "--knn") unsupported("--knn (approximate k-NN DBSCAN)");
+    if (a == "--db" || a == "--build" || a == "--query" || a == "--assign" || a == "--stats" || a == "--top-k" || a == "--dense" ||
+        a == "--premsted" || a == "--auto-threshold" || a == "--stability" || a == "--dedup-dist" || a == "--reps-per-cluster" ||
+        a == "--newick-tree" || a == "--phylip-tree" || a == "--nexus-tree" || a == "--linkage-matrix" || a == "--buildDB") {
+      fprintf(stderr, "ERROR: unknown option %s\n", a.c_str());
+      exit(1);
+    }
+#endif
     if (a == "-t" || a == "--threads") { o.threads = atoi(need(i)); }
     else if (a == "-m" || a == "--min-length") { o.minLen = strtoull(need(i), nullptr, 10); fprintf(stderr, "-----set the filter minimum length: %ld\n", (long)o.minLen); }
     else if (a == "-c" || a == "--containment") { o.containCompress = atoi(need(i)); o.isContainment = true; fprintf(stderr, "-----use AAF distance with containment coefficient, the sketch size is in porportion with 1/%d\n", o.containCompress); }
@@ -922,6 +938,13 @@ static Options parse(int argc, char** argv) {
     else if (a == "-h" || a == "--help") {
 #ifdef GREEDY_CLUST
       puts("clust-greedy (MI355X build): greedy incremental clustering module");
+#elif defined(DBSCAN_CLUST)
+      puts("clust-dbscan (MI355X build): DBSCAN density-based clustering module (KSSD, --fast)");
+      puts("  -t,--threads N  -m,--min-length N  -k,--kmer-size N  -l,--list  -e,--no-save  -d,--threshold X (KSSD tuner)\n"
+           "  -o,--output FILE  -i,--input FILE  --presketched DIR  --fast  --drlevel N  --gpus all|N|i,j,..\n"
+           "  --eps X (default 0.05)  --minpts N (default 5)  --max-posting M (0: off)\n"
+           "  -c,--containment N (KSSD tuner)  -s,--sketch-size N  --save-rep (accepted, no effect on DBSCAN)  --knn: not in this build");
+      exit(0);
 #else
       puts("clust-mst (MI355X build): minimum-spanning-tree-based module");
 #endif
@@ -1034,7 +1057,7 @@ static void write_trees(const Options& o, const vector<GenomeInfo>& genomes, con
   if (o.linkage) { const string f = o.outputFile + ".linkage.txt"; print_linkage_matrix((int)genomes.size(), mst, f); cerr << "-----write the linkage matrix into: " << f << endl; }
 }
 
-#ifndef GREEDY_CLUST
+#if !defined(GREEDY_CLUST) && !defined(DBSCAN_CLUST)
 // append_clust_mst / append_clust_mst_fast (src/sub_command.cpp:1532-1759): sketch the new genomes with the
 // stored folder's parameters, evaluate only the pairs that involve a new genome (rows >= start_index,
 // src/MST.cpp:1375-1383 -- rtc_mst_append), merge that forest with the stored MST (sort + Kruskal,
@@ -1940,6 +1963,89 @@ static int append_clust_greedy(const Options& o, vector<Gpu>& gpus) {
 }
 #endif
 
+#ifdef DBSCAN_CLUST
+// KssdDBSCAN's closing lines (src/dbscan.cpp:951-980).  Its progress lines (:918-930) leave std::fixed and precision 1 on cerr
+// once one has been printed, and the core-point percentage comes out in that format then: the walk is replayed from the labels
+// to learn whether it printed one.  After cluster c (opened at its smallest core index s_c) the walk has visited
+// {0 .. s_c} and the members of clusters 0 .. c; it reports when that count has grown by max(1000, n / 100) since its last
+// report or equals n.
+static void dbscan_report(const vector<int32_t>& labels, const vector<uint8_t>& core, uint32_t ncl, uint32_t nnoise) {
+  const int n = (int)labels.size();
+  vector<int> seed(ncl, -1);
+  vector<vector<int>> members(ncl);
+  uint64_t n_core = 0;
+  for (int v = 0; v < n; v++) {
+    if (core[v]) { n_core++; if (seed[labels[v]] < 0) seed[labels[v]] = v; }
+    if (labels[v] >= 0) members[labels[v]].push_back(v);
+  }
+  vector<int> bit(n + 1, 0);  // Fenwick tree over the indices of the members placed so far
+  auto add = [&](int i) { for (i++; i <= n; i += i & -i) bit[i]++; };
+  auto prefix = [&](int i) { int r = 0; for (i++; i > 0; i -= i & -i) r += bit[i]; return r; };
+  const int interval = std::max(1000, n / 100);
+  int last = 0, placed = 0;
+  bool fixed_fmt = false;
+  for (uint32_t c = 0; c < ncl; c++) {
+    for (int v : members[c]) add(v);
+    placed += (int)members[c].size();
+    const int processed = seed[c] + 1 + (placed - prefix(seed[c]));
+    if (processed - last >= interval || processed == n) { fixed_fmt = true; last = processed; }
+  }
+  cerr << "-----DBSCAN clustering complete!" << endl;
+  cerr << "-----Found " << ncl << " clusters" << endl;
+  cerr << "-----Found " << nnoise << " noise points (outliers)" << endl;
+  if (n_core > 0) {
+    if (fixed_fmt) cerr << std::fixed << std::setprecision(1);
+    cerr << "-----Core points: " << n_core << " (" << (100.0 * n_core / n) << "%)" << endl;
+    cerr.unsetf(std::ios_base::floatfield);
+    cerr << std::setprecision(6);
+  }
+}
+
+// printKssdDBSCANResult (src/dbscan.cpp:1212-1310): the clusters with their members in ascending index order, then every noise
+// point as a cluster of its own.  mismatch: the sketches were stored in the other layout than -l asks for (the warning of
+// :3237-3240).  The reference then prints fields it never loaded: with -l an empty fileSeqs gives the names "N/A" (:1246-1250)
+// beside an empty file name, without -l an empty seqInfo gives empty names.  The lengths it prints there are whatever the
+// unloaded field holds; this prints 0.
+static void print_dbscan_result(const vector<int32_t>& labels, uint32_t ncl, const vector<GenomeInfo>& g, bool sketchByFile, bool mismatch,
+                                const string& outputFile, double eps, int minPts) {
+  FILE* fp = fopen(outputFile.c_str(), "w");
+  if (!fp) { cerr << "Error in printKssdDBSCANResult(), cannot open file: " << outputFile << endl; exit(1); }
+  vector<vector<int>> clusters(ncl);
+  vector<int> noise;
+  for (size_t i = 0; i < labels.size(); i++) {
+    if (labels[i] < 0) noise.push_back((int)i);
+    else clusters[labels[i]].push_back((int)i);
+  }
+  fprintf(fp, "# DBSCAN clustering parameters: eps=%.6f, minPts=%d\n", eps, minPts);
+  fprintf(fp, "# Total clusters: %d\n", (int)ncl);
+  if (!noise.empty()) fprintf(fp, "# Total noise points (outliers): %d\n", (int)noise.size());
+  fprintf(fp, "#\n");
+  auto line = [&](int j, int curId) {
+    const GenomeInfo& s = g[curId];
+    if (sketchByFile && mismatch)
+      fprintf(fp, "\t%5d\t%6d\t%12dnt\t%20s\t%20s\t%s\n", j, curId, 0, "", "N/A", "N/A");
+    else if (sketchByFile)
+      fprintf(fp, "\t%5d\t%6d\t%12dnt\t%20s\t%20s\t%s\n", j, curId, (int)s.totalSeqLength, s.fileName.c_str(), s.seq0.name.c_str(),
+              s.seq0.comment.c_str());
+    else if (mismatch)
+      fprintf(fp, "\t%6d\t%6d\t%12dnt\t%20s\t%s\n", j, curId, 0, "", "");
+    else
+      fprintf(fp, "\t%6d\t%6d\t%12dnt\t%20s\t%s\n", j, curId, s.seq0.length, s.seq0.name.c_str(), s.seq0.comment.c_str());
+  };
+  for (size_t i = 0; i < clusters.size(); i++) {
+    fprintf(fp, "the cluster %d is: \n", (int)i);
+    for (size_t j = 0; j < clusters[i].size(); j++) line((int)j, clusters[i][j]);
+    fprintf(fp, "\n");
+  }
+  for (size_t i = 0; i < noise.size(); i++) {
+    fprintf(fp, "the cluster %d is: \n", (int)(clusters.size() + i));
+    line(0, noise[i]);
+    fprintf(fp, "\n");
+  }
+  fclose(fp);
+}
+#endif
+
 // Will this run use exactly one GPU?  Answered without the HIP runtime (its environment must be final before it starts): a
 // --gpus / RTC_GPUS choice that names one device, or "all" on a host whose driver topology lists one GPU node.
 static bool single_gpu_run(const string& spec) {
@@ -2002,7 +2108,18 @@ int main(int argc, char** argv) {
   if (o.has_append && o.has_input) { cerr << "ERROR: --append and -i/--input exclude each other" << endl; return 1; }
   if (o.has_append && !o.has_presketched && o.repdb_path.empty()) { cerr << "ERROR option --append, option --presketched needed" << endl; return 1; }  // src/main.cpp:378-381
 #endif
-#ifndef GREEDY_CLUST
+#ifdef DBSCAN_CLUST
+  // ---- clust-dbscan: the checks of src/main.cpp:478-517, in that order ----
+  if (!o.is_fast) { cerr << "ERROR: clust-dbscan requires --fast option" << endl; return 1; }
+  cerr << "-----Using DBSCAN clustering" << endl;
+  cerr << "-----DBSCAN parameters: eps=" << o.dbscanEps << ", minPts=" << o.dbscanMinPts;
+  if (o.maxPosting > 0) cerr << ", max-posting=" << o.maxPosting;
+  cerr << endl;
+  if (!o.isSetKmer) { o.kmerSize = 19; cerr << "-----use default kmerSize: " << o.kmerSize << endl; }
+  if (o.drlevel < 0 || o.drlevel > 8) { cerr << "ERROR: invalid drlevel " << o.drlevel << ", should be in [0, 8]" << endl; return 1; }
+  if (o.has_append) { cerr << "ERROR: --append not supported for DBSCAN clustering" << endl; return 1; }
+#endif
+#if !defined(GREEDY_CLUST) && !defined(DBSCAN_CLUST)
   // ---- MST RepDB mode: --db FILE (src/main.cpp:213-254, :525-600) ----
   if (o.has_topk && !o.db_query) { cerr << "ERROR: --top-k requires --query" << endl; return 1; }
   const bool db_action = o.db_build || o.db_query || o.db_assign || o.db_stats;
@@ -2070,6 +2187,8 @@ int main(int argc, char** argv) {
     single_gpu_flow =
 #ifdef GREEDY_CLUST
         o.has_append || !o.repdb_path.empty() || o.has_presketched;
+#elif defined(DBSCAN_CLUST)
+        o.has_presketched;
 #else
         o.has_append || ((o.dense || !o.useIndex) && o.has_presketched) || !o.repdb_path.empty();
 #endif
@@ -2145,7 +2264,7 @@ int main(int argc, char** argv) {
     }
   };
   const bool list_run = !o.has_presketched && !o.has_append && o.has_input && o.sketchByFile
-#ifdef GREEDY_CLUST
+#if defined(GREEDY_CLUST) || defined(DBSCAN_CLUST)
                         && o.repdb_path.empty()
 #else
                         && (o.repdb_path.empty() || o.db_build)
@@ -2154,7 +2273,7 @@ int main(int argc, char** argv) {
   const GpusReady gpus_ready{wait_gpus, &gpus_done};
   if (!list_run) wait_gpus();
   Resident rs;
-#ifndef GREEDY_CLUST
+#if !defined(GREEDY_CLUST) && !defined(DBSCAN_CLUST)
   if (!o.repdb_path.empty() && !o.db_build) {  // --build goes on through the MST flow below
     const int rc = (o.db_query || o.db_assign) ? mst_db_search(o, gpus) : mst_db_append(o, gpus);
     g_metrics.str("command", "clust-mst");
@@ -2165,7 +2284,7 @@ int main(int argc, char** argv) {
     return rc;
   }
   if (o.has_append) return append_clust_mst(o, gpus);
-#else
+#elif defined(GREEDY_CLUST)
   if (!o.repdb_path.empty()) {
     const int rc = o.db_build ? (o.is_fast ? repdb_build(o, gpus) : mh_repdb_build(o, gpus)) : o.db_query ? repdb_query(o, gpus) : o.db_assign ? repdb_assign(o, gpus) : repdb_append(o, gpus);
     for (Gpu& g : gpus) { if (g.comm) rtc_comm_destroy(g.comm); }
@@ -2191,11 +2310,23 @@ int main(int argc, char** argv) {
 #else
       false;
 #endif
+  const bool dbscan =
+#ifdef DBSCAN_CLUST
+      true;
+#else
+      false;
+#endif
+  [[maybe_unused]] bool dbscan_format_mismatch = false;
 
   double t0 = get_sec();
   if (from_sketches) {
     if (o.is_fast) { if (!load_kssd_sketches(folder_path, genomes, ks, sketchByFile)) return 1; }
     else { if (!load_minhash_sketches(folder_path, genomes, mh, sketchByFile)) return 1; }
+#ifdef DBSCAN_CLUST
+    // clust_from_sketch_dbscan prints with the -l of the command line, not the one stored with the sketches (:3237-3240)
+    if (sketchByFile != o.sketchByFile) { cerr << "Warning: sketch format mismatch" << endl; dbscan_format_mismatch = true; }
+    sketchByFile = o.sketchByFile;
+#endif
     cerr << "-----the size of sketches is: " << genomes.size() << endl;
     cerr << "========time of load genome Infos and sketch Infos is: " << get_sec() - t0 << endl;
   } else {
@@ -2235,14 +2366,16 @@ int main(int argc, char** argv) {
     if (!o.noSave) {
       string command = "mkdir -p " + folder_path;
       if (system(command.c_str()) != 0) { cerr << "ERROR: cannot create " << folder_path << endl; return 1; }
-      if (o.is_fast) { save_kssd_sketches(genomes, ks, folder_path, sketchByFile); if (!greedy) save_kssd_index(ks, folder_path); }
+      // compute_kssd_sketches (clust-dbscan, src/sub_command.cpp:2154-2188) keeps the sketches alone
+      if (o.is_fast) { save_kssd_sketches(genomes, ks, folder_path, sketchByFile); if (!greedy && !dbscan) save_kssd_index(ks, folder_path); }
       else { save_minhash_sketches(genomes, mh, folder_path, sketchByFile); save_minhash_index(mh, folder_path); }
       cerr << "========time of saveSketches is: " << get_sec() - t1 << "========" << endl;
       g_metrics.num("saveSketches_s", get_sec() - t1);
     }
   }
   if (genomes.empty()) { cerr << "ERROR: no genome to cluster" << endl; return 1; }
-  const int kmer_size = o.is_fast ? ks.info.half_k * 2 : mh.kmerSize;
+  // clust-dbscan from genomes takes the tuned / given k, from a sketch folder half_k * 2 (src/sub_command.cpp:3247, :3278)
+  const int kmer_size = (dbscan && !from_sketches) ? o.kmerSize : o.is_fast ? ks.info.half_k * 2 : mh.kmerSize;
 
   double t2 = get_sec();
 #ifdef GREEDY_CLUST
@@ -2331,6 +2464,26 @@ int main(int argc, char** argv) {
   cerr << "========time of greedyCluster is: " << get_sec() - t2 << "========" << endl;
   g_metrics.num("greedyCluster_s", get_sec() - t2);
   g_metrics.num("clusters", (double)cluster.size());
+#elif defined(DBSCAN_CLUST)
+  // ---- clust-dbscan: KssdDBSCAN (src/dbscan.cpp:725-985) on the first GPU, printKssdDBSCANResult (:1212-1310) ----
+  DeviceSketches ds;
+  if (rs.ok) resident_sketches(ctx, gpus[0], rs, nullptr, ds);
+  else upload_sketches(ctx, ks.use64 ? &ks.h64 : nullptr, ks.use64 ? nullptr : &ks.h32, ds);
+  cerr << "-----Running DBSCAN clustering (KSSD)..." << endl;
+  cerr << "-----Parameters: eps=" << o.dbscanEps << ", minPts=" << o.dbscanMinPts << endl;
+  vector<int32_t> labels(genomes.size());
+  vector<uint8_t> core(genomes.size());
+  uint32_t ncl = 0, nnoise = 0;
+  CHECK(ctx, rtc_dbscan(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, o.dbscanEps, o.dbscanMinPts, kmer_size, o.maxPosting,
+                        labels.data(), core.data(), &ncl, &nnoise));
+  dbscan_report(labels, core, ncl, nnoise);
+  print_dbscan_result(labels, ncl, genomes, sketchByFile, dbscan_format_mismatch, o.outputFile, o.dbscanEps, o.dbscanMinPts);
+  cerr << "-----write the cluster result into: " << o.outputFile << endl;
+  cerr << "-----the cluster number of " << o.outputFile << " is: " << ncl << endl;
+  cerr << "-----the noise point number is: " << nnoise << endl;
+  g_metrics.num("dbscan_s", get_sec() - t2);
+  g_metrics.num("clusters", (double)ncl);
+  g_metrics.num("noise", (double)nnoise);
 #else
   // ---- clust-mst: compute_clusters MST branch (src/sub_command.cpp:2924-3053, :1988-2152) ----
   const int is_containment = o.is_fast ? (int)o.isContainment : (int)mh.isContainment;
@@ -2419,6 +2572,8 @@ int main(int argc, char** argv) {
   const double t_end = get_sec();
 #ifdef GREEDY_CLUST
   g_metrics.str("command", "clust-greedy");
+#elif defined(DBSCAN_CLUST)
+  g_metrics.str("command", "clust-dbscan");
 #else
   g_metrics.str("command", "clust-mst");
 #endif

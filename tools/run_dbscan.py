@@ -1,0 +1,112 @@
+"""clust-dbscan --fast on one GPU: Context.dbscan timed warm next to Context.mst on the same resident sketches, with the split
+of the DBSCAN call into the pair phase, the eps filter and the components from rtc_dbscan_counters.
+
+    python tools/run_dbscan.py [--sets dense25k,cfg4_200k] [--eps 0.05] [--minpts 5] [--repeat 3]
+
+Sets (KSSD u32 sketches from synthetic genomes, k 21, drlevel 3, sketched on the GPU as bench.py does):
+  dense25k   25 000 x 2 Mbp genomes in 25 families of 1 000 (substitution rate <= 0.01): bench.py's dense u32_25000 set, the
+             dense regime (~12.5 M pairs within the families);
+  cfg4_200k  200 000 x 2 Mbp genomes in families of ten: BASELINE config[4]'s shape on one GPU, sketched in batches of 25 000;
+  sparse25k / sparse200k  host-drawn random u32 sets of ~1 100 / ~330 hashes in families of ten (~2 % of a member's hashes
+             replaced): a sparse eps graph.
+Prints one JSON line per set.  The kernel split under rocprofv3 --kernel-trace --stats comes from a run of its own."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SPARSE = {"sparse25k": (25_000, 1100, 10), "sparse200k": (200_000, 330, 10)}
+SYNTH = {"dense25k": (25_000, 1000, 0.01, 44), "cfg4_200k": (200_000, 10, None, 42)}  # n, family size, max_rate, seed
+
+
+def _sparse(rng, n, size, per):
+    n_fam = (n + per - 1) // per
+    bases = rng.integers(1, (1 << 31) - 1, size=(n_fam, size), dtype=np.int64)
+    out = []
+    for g in range(n):
+        s = bases[g // per].copy()
+        flip = rng.random(size) < 0.02
+        s[flip] = rng.integers(1, (1 << 31) - 1, size=int(flip.sum()), dtype=np.int64)
+        out.append(np.unique(s).astype(np.uint32))
+    return out
+
+
+def _synth(ctx, api, n, per, max_rate, seed, L=2_000_000, batch=25_000):
+    """KSSD sketches of n synthetic genomes, batch by batch (a batch of 25 000 x 2 Mbp is 50 GB of bases), joined into one set"""
+    import torch
+    from rabbittclust_amd import host
+    kw = {} if max_rate is None else {"max_rate": max_rate}
+    desc = api.synth_family_descs(n // per, per, global_seed=seed, **kw)
+    sd = host.generate_shuffle_dim(6)
+    parts = []
+    for b0 in range(0, n, batch):
+        d = desc[b0:b0 + batch]
+        off = np.arange(len(d) + 1, dtype=np.uint64) * np.uint64(L)
+        seq = ctx.synth_genomes(d, off)
+        parts.append(ctx.sketch_kssd(seq, off, sd, kmer_size=21, drlevel=3))
+        ctx.sync()
+        del seq
+        torch.cuda.empty_cache()
+    base, hs, st = 0, [], []
+    for p in parts:
+        hs.append(p.hashes)
+        st.append(p.start + base)
+        base += p.hashes.numel()
+    return api.SketchSet(torch.cat(hs), torch.cat(st), torch.cat([p.len for p in parts]), 4, parts[0].k, "kssd")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sets", default="dense25k,cfg4_200k")
+    ap.add_argument("--eps", type=float, default=0.05)
+    ap.add_argument("--minpts", type=int, default=5)
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--no-mst", action="store_true")
+    a = ap.parse_args()
+    import torch
+    from rabbittclust_amd import api
+    ctx = api.Context(0)
+    for name in a.sets.split(","):
+        if name in SPARSE:
+            n, size, per = SPARSE[name]
+            sk = api.SketchSet.from_host(_sparse(np.random.default_rng(7), n, size, per), ctx.device, k=22, kind="kssd", width=4)
+        else:
+            n, per, rate, seed = SYNTH[name]
+            sk = _synth(ctx, api, n, per, rate, seed)
+        kmer = sk.k  # half_k * 2, as clust-dbscan --presketched takes it
+        torch.cuda.synchronize()
+        ctx.dbscan(sk, a.eps, a.minpts, kmer)  # warm-up: code objects, scratch
+        ts, cs = [], []
+        for _ in range(a.repeat):
+            t0 = time.perf_counter()
+            lab = ctx.dbscan(sk, a.eps, a.minpts, kmer)
+            ts.append(time.perf_counter() - t0)
+            cs.append(ctx.dbscan_counters())
+        best = int(np.argmin(ts))
+        c = cs[best]
+        row = {"set": name, "n": n, "mean_hashes": round(float(sk.len.float().mean().item()), 1), "kmer": kmer, "eps": a.eps, "minpts": a.minpts, "dbscan_ms": round(ts[best] * 1e3, 3),
+               "pair_ms": round(c["pair_ns"] / 1e6, 3), "filter_ms": round(c["filter_ns"] / 1e6, 3),
+               "components_ms": round(c["components_ns"] / 1e6, 3), "chunks": c["chunks"],
+               "candidate_edges": c["candidate_edges"], "eps_edges": c["eps_edges"], "core_points": c["core_points"],
+               "hook_rounds": c["hook_rounds"], "clusters": int(lab.max()) + 1, "noise": int((lab < 0).sum())}
+        if not a.no_mst:
+            ctx.mst(sk, a.eps)
+            tm = []
+            for _ in range(a.repeat):
+                t0 = time.perf_counter()
+                ctx.mst(sk, a.eps)
+                tm.append(time.perf_counter() - t0)
+            row["mst_ms"] = round(min(tm) * 1e3, 3)
+        print(json.dumps(row), flush=True)
+        del sk
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
