@@ -483,6 +483,30 @@ int rtc_dbscan(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_
  * out[7] eps filter ns, out[8] components and labels ns, out[9] whole call ns. */
 int rtc_dbscan_counters(const rtc_ctx* ctx, uint64_t out[10]);
 
+/* ---- clust-dbscan --eps-sweep / --kdist: many eps values and the k-distance curve from one pair phase ---------- */
+/* A point's k-th nearest candidate, k = min_pts - 1: j = common / (size_p + size_q - common).  neighbour = UINT32_MAX: the
+ * point has fewer than k candidates (the other fields are 0 but size_p). */
+typedef struct { uint32_t common, size_p, size_q, neighbour; } rtc_kdist;
+/* rtc_dbscan for n_eps values of eps (1 .. 32, any order, duplicates allowed) with ONE pair phase.  Row e of h_labels
+ * [n_eps x n] and h_core [n_eps x n, may be NULL] and entry e of h_n_clusters / h_n_noise [n_eps, may be NULL] are exactly what
+ * rtc_dbscan returns for h_eps[e] with the same other arguments.  Whatever makes rtc_dbscan return RTC_ERR_UNSUPPORTED for one
+ * of the values fails the whole call; the message names that eps.
+ * h_kdist [n, may be NULL]: among the points sharing at least one (kept) hash with p, ranked by j compared exactly as integers
+ * (larger first; common is the count the predicate sees, min(common, 65535) over the pruned sketches at width 4; the sizes
+ * are the unpruned ones; equal j: the lower index first), the k-th.  k <= 0: {|p|, |p|, |p|, p} (j = 1).  At width 8 the
+ * empty sketches see each other at j = 1, as rtc_dbscan's predicate accepts them at every eps; at width 4 an empty sketch has no
+ * candidates.  The device forms no distance: the caller computes -ln(2 j / (1 + j)) / kmer_size with its libm.  The integer order
+ * is exact for sketches of up to 2^31 - 1 hashes; a longer one returns RTC_ERR_UNSUPPORTED when the curve is asked for.
+ * k <= 256 selects on the device chunk by chunk; a larger k reads every candidate chunk back and selects on the host.
+ * n_eps == 0 with h_kdist computes the curve alone.  Synchronous. */
+int rtc_dbscan_sweep(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                     const double* h_eps, uint32_t n_eps, int min_pts, int kmer_size, int max_posting, int32_t* h_labels,
+                     uint8_t* h_core, uint32_t* h_n_clusters, uint32_t* h_n_noise, rtc_kdist* h_kdist);
+/* What the last rtc_dbscan_sweep call did: out[0] row chunks and out[1] candidate edges of its one pair phase, out[2] pairs
+ * kept (passing at some level), out[3] levels, out[4] hook rounds (the level that took longest), out[5] pair phase ns, out[6]
+ * predicate ns, out[7] components and labels ns, out[8] k-distance ns, out[9] whole call ns. */
+int rtc_dbscan_sweep_counters(const rtc_ctx* ctx, uint64_t out[10]);
+
 #ifdef __cplusplus
 }
 #endif

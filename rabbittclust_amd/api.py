@@ -19,6 +19,10 @@ CEDGE_DT = np.dtype([("i", "<u4"), ("j", "<u4"), ("common", "<u4")])
 EDGE_DT = np.dtype([("preNode", "<i4"), ("sufNode", "<i4"), ("dist", "<f8")])  # edge.mst record
 REP_PAIR_DT = np.dtype([("query", "<u4"), ("slot", "<u4"), ("common", "<u4"), ("pad", "<u4"), ("dist", "<f8")])  # rtc_rep_pair
 REP_HIT_DT = np.dtype([("query", "<u4"), ("slot", "<u4"), ("common", "<u4"), ("denom", "<u4")])  # rtc_rep_hit
+KDIST_DT = np.dtype([("common", "<u4"), ("size_p", "<u4"), ("size_q", "<u4"), ("neighbour", "<u4")])  # rtc_kdist
+# Context.dbscan_sweep's curve: rtc_kdist plus the distance the host forms from it
+KDIST_CURVE_DT = np.dtype(KDIST_DT.descr + [("distance", "<f8")])
+KDIST_NONE = 0xFFFFFFFF  # neighbour of a point with fewer than minPts - 1 candidates (distance inf)
 
 
 def _np_ptr(a):
@@ -589,6 +593,45 @@ class Context:
             return labels[:n].copy(), core[:n].astype(bool)
         return labels[:n].copy()
 
+    def dbscan_sweep(self, sk, eps_list, min_pts, kmer_size, max_posting=0, return_core=False, kdist=False):
+        """clust-dbscan --eps-sweep / --kdist (rtc_dbscan_sweep): Context.dbscan for every eps of eps_list (at most 32, any order)
+        from one pair phase.  Returns int32 labels[n_eps, n]; with return_core also bool core[n_eps, n]; with kdist also the
+        k-distance curve, KDIST_CURVE_DT per point (k = min_pts - 1; neighbour KDIST_NONE and distance inf where a point has
+        fewer than k candidates).  An empty eps_list with kdist=True computes the curve alone.  The call's cluster and noise
+        counts per eps stay in self.dbscan_sweep_counts."""
+        n = sk.n
+        eps = np.ascontiguousarray(np.asarray(list(eps_list), dtype=np.float64))
+        L = int(eps.size)
+        labels = np.zeros((L, n), dtype=np.int32)
+        core = np.zeros((L, n), dtype=np.uint8)
+        ncl, nnoise = np.zeros(max(L, 1), dtype=np.uint32), np.zeros(max(L, 1), dtype=np.uint32)
+        kd = np.zeros(max(n, 1), dtype=KDIST_DT) if kdist else None
+        buf_l = labels if labels.size else np.zeros(1, dtype=np.int32)
+        buf_c = core if core.size else np.zeros(1, dtype=np.uint8)
+        self.check(self.lib.rtc_dbscan_sweep(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n, _np_ptr(eps) if L else None,
+                                             L, int(min_pts), int(kmer_size), int(max_posting), _np_ptr(buf_l), _np_ptr(buf_c),
+                                             _np_ptr(ncl), _np_ptr(nnoise), _np_ptr(kd) if kdist else None))
+        self.dbscan_sweep_counts = {"clusters": ncl[:L].copy(), "noise": nnoise[:L].copy()}
+        out = [labels]
+        if return_core:
+            out.append(core.astype(bool))
+        if kdist:
+            curve = np.zeros(n, dtype=KDIST_CURVE_DT)
+            for f in KDIST_DT.names:
+                curve[f] = kd[f][:n]
+            cols = [kd[f][:n].tolist() for f in KDIST_DT.names]  # plain ints: a record at a time is slow at 200 000 points
+            curve["distance"] = [math.inf if q == KDIST_NONE else kdist_distance(c, a, b, kmer_size) for c, a, b, q in zip(*cols)]
+            out.append(curve)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def dbscan_sweep_counters(self):
+        """rtc_dbscan_sweep_counters as a dict (the last dbscan_sweep call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_dbscan_sweep_counters(self.h, a))
+        names = ("chunks", "candidate_edges", "kept_edges", "levels", "hook_rounds", "pair_ns", "predicate_ns", "components_ns",
+                 "kdist_ns", "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
     def dbscan_counters(self):
         """rtc_dbscan_counters as a dict (the last dbscan call)."""
         a = (C.c_uint64 * 10)()
@@ -596,6 +639,16 @@ class Context:
         names = ("chunks", "candidate_edges", "eps_edges", "core_points", "asymmetric_pairs", "hook_rounds", "pair_ns",
                  "filter_ns", "components_ns", "total_ns")
         return {k: int(a[i]) for i, k in enumerate(names)}
+
+
+def kdist_distance(common, size_p, size_q, kmer_size):
+    """The distance of one rtc_kdist record: -ln(2 j / (1 + j)) / kmer_size with j = common / (size_p + size_q - common), in
+    double with the C library's log; 0 where j = 1 (two empty u64 sketches included)."""
+    denom = int(size_p) + int(size_q) - int(common)
+    if denom == int(common):
+        return 0.0
+    j = float(common) / float(denom)
+    return -math.log(2.0 * j / (1.0 + j)) / kmer_size
 
 
 class Comm:

@@ -1,0 +1,104 @@
+// rtc_topk_select.h -- segmented top-k by an exact rational key, shared by rtc_rep_topk.hip (the best representatives of a
+// query) and rtc_dbscan_sweep.hip (the k-th nearest candidate of a point): the record, its total order, the one-workgroup
+// scan of the segment offsets and the running top-k selection in LDS (one wave for segments of up to TK_LONG records, 256
+// lanes for the longer ones).  DESIGN 3.4b describes the selection.
+#pragma once
+#include "rtc_internal.h"
+
+namespace {
+
+constexpr uint32_t TK_KMAX = 256;        // largest topk of the select path
+constexpr uint32_t TK_LONG = 4096;       // segments longer than this take the 256-lane workgroup
+constexpr uint32_t TK_SCAN_THREADS = 1024;
+
+struct TkRec { uint32_t slot, common, denom, pad; };
+
+// a ranks before b
+__device__ __forceinline__ bool tk_beats(const TkRec& a, const TkRec& b) {
+  const uint64_t l = (uint64_t)a.common * b.denom, r = (uint64_t)b.common * a.denom;
+  return l != r ? l > r : a.slot < b.slot;
+}
+static bool tk_beats_host(const TkRec& a, const TkRec& b) {
+  const uint64_t l = (uint64_t)a.common * b.denom, r = (uint64_t)b.common * a.denom;
+  return l != r ? l > r : a.slot < b.slot;
+}
+
+// one workgroup of TK_SCAN_THREADS: off[q] = sum of cnt[0 .. q), koff[q] = sum of min(cnt, k) (k == 0: cnt); off[nq], koff[nq]: totals
+__global__ __launch_bounds__(TK_SCAN_THREADS) void tk_scan_kernel(const uint32_t* __restrict__ cnt, uint32_t nq, uint32_t k,
+                                                                  uint64_t* __restrict__ off, uint64_t* __restrict__ koff) {
+  __shared__ uint64_t sa[TK_SCAN_THREADS], sb[TK_SCAN_THREADS];
+  const uint32_t t = threadIdx.x;
+  const uint32_t per = (nq + TK_SCAN_THREADS - 1) / TK_SCAN_THREADS;
+  const uint32_t b0 = (uint32_t)min((uint64_t)nq, (uint64_t)t * per), b1 = (uint32_t)min((uint64_t)nq, (uint64_t)b0 + per);
+  uint64_t a = 0, b = 0;
+  for (uint32_t i = b0; i < b1; i++) { const uint32_t c = cnt[i]; a += c; b += (k && c > k) ? k : c; }
+  sa[t] = a; sb[t] = b;
+  __syncthreads();
+  for (uint32_t d = 1; d < TK_SCAN_THREADS; d <<= 1) {
+    const uint64_t va = t >= d ? sa[t - d] : 0, vb = t >= d ? sb[t - d] : 0;
+    __syncthreads();
+    sa[t] += va; sb[t] += vb;
+    __syncthreads();
+  }
+  uint64_t xa = sa[t] - a, xb = sb[t] - b;
+  for (uint32_t i = b0; i < b1; i++) {
+    const uint32_t c = cnt[i];
+    off[i] = xa; koff[i] = xb;
+    xa += c; xb += (k && c > k) ? k : c;
+  }
+  if (t == TK_SCAN_THREADS - 1) { off[nq] = sa[t]; koff[nq] = sb[t]; }
+}
+
+// a workgroup of B lanes per query whose segment length lies in [lo, hi]; k in [1, TK_KMAX]
+template <int B>
+__global__ __launch_bounds__(B) void tk_select_kernel(const TkRec* __restrict__ seg, const uint64_t* __restrict__ off,
+                                                      const uint64_t* __restrict__ koff, uint32_t nq, uint32_t q0, uint32_t k,
+                                                      uint32_t lo, uint32_t hi, rtc_rep_hit* __restrict__ out) {
+  __shared__ TkRec top[2][TK_KMAX];
+  __shared__ TkRec cand[B];
+  __shared__ uint32_t ncand;
+  const uint32_t q = blockIdx.x;
+  if (q >= nq) return;
+  const uint64_t s0 = off[q], s1 = off[q + 1];
+  if (s1 - s0 < lo || s1 - s0 > hi) return;  // uniform across the workgroup
+  uint32_t cnt = 0, cur = 0;
+  for (uint64_t base = s0; base < s1; base += B) {
+    const uint64_t idx = base + threadIdx.x;
+    TkRec x = {0, 0, 1, 0};
+    bool keep = false;
+    if (idx < s1) { x = seg[idx]; keep = cnt < k || tk_beats(x, top[cur][cnt - 1]); }
+    if (threadIdx.x == 0) ncand = 0;
+    __syncthreads();
+    if (keep) cand[atomicAdd(&ncand, 1u)] = x;
+    __syncthreads();
+    const uint32_t mm = ncand;
+    if (mm == 0) continue;  // uniform; ncand stays 0 until every lane has read it
+    const uint32_t nxt = cur ^ 1u;
+    for (uint32_t t = threadIdx.x; t < cnt; t += B) {  // a record of the top-k: its rank there plus the survivors before it
+      const TkRec y = top[cur][t];
+      uint32_t r = t;
+      for (uint32_t j = 0; j < mm; j++) r += tk_beats(cand[j], y) ? 1u : 0u;
+      if (r < k) top[nxt][r] = y;
+    }
+    for (uint32_t t = threadIdx.x; t < mm; t += B) {  // a survivor: the top-k records before it (a prefix) plus the survivors
+      const TkRec y = cand[t];
+      uint32_t a = 0, b = cnt;
+      while (a < b) { const uint32_t mid = (a + b) >> 1; if (tk_beats(top[cur][mid], y)) a = mid + 1; else b = mid; }
+      uint32_t r = a;
+      for (uint32_t j = 0; j < mm; j++) r += tk_beats(cand[j], y) ? 1u : 0u;
+      if (r < k) top[nxt][r] = y;
+    }
+    __syncthreads();
+    cnt = cnt + mm < k ? cnt + mm : k;
+    cur = nxt;
+  }
+  const uint64_t o = koff[q];
+  for (uint32_t t = threadIdx.x; t < cnt; t += B) {
+    const TkRec y = top[cur][t];
+    rtc_rep_hit h;
+    h.query = q0 + q; h.slot = y.slot; h.common = y.common; h.denom = y.denom;
+    out[o + t] = h;
+  }
+}
+
+}  // namespace

@@ -865,6 +865,8 @@ struct Options {
   string gpus;  // --gpus / RTC_GPUS: "all" (default), a count, or a comma list of device ordinals
   double dbscanEps = 0.05;  // clust-dbscan --eps / --minpts / --max-posting (src/main.cpp:173-182)
   int dbscanMinPts = 5, maxPosting = 0;
+  vector<double> epsSweep;  // clust-dbscan --eps-sweep: further eps values served by the pair phase of --eps (rtc_dbscan_sweep)
+  bool kdist = false;       // clust-dbscan --kdist: the k-distance curve, k = minPts - 1
 };
 
 static void unsupported(const char* what) {
@@ -883,6 +885,22 @@ static Options parse(int argc, char** argv) {
     if (a == "--eps") { o.dbscanEps = atof(need(i)); continue; }
     if (a == "--minpts") { o.dbscanMinPts = atoi(need(i)); continue; }
     if (a == "--max-posting") { o.maxPosting = atoi(need(i)); continue; }
+    if (a == "--eps-sweep") {
+      // e1,e2,...: at most 32 values, each > 0 as atof reads it
+      const string v = need(i);
+      for (size_t p0 = 0; p0 <= v.size();) {
+        size_t p1 = v.find(',', p0);
+        if (p1 == string::npos) p1 = v.size();
+        if (p1 == p0) { fprintf(stderr, "ERROR: --eps-sweep %s: empty element\n", v.c_str()); exit(1); }
+        const double e = atof(v.substr(p0, p1 - p0).c_str());
+        if (!(e > 0.0)) { fprintf(stderr, "ERROR: --eps-sweep %s: every value must be > 0\n", v.c_str()); exit(1); }
+        o.epsSweep.push_back(e);
+        p0 = p1 + 1;
+      }
+      if (o.epsSweep.size() > 32) { fprintf(stderr, "ERROR: --eps-sweep takes at most 32 values, got %zu\n", o.epsSweep.size()); exit(1); }
+      continue;
+    }
+    if (a == "--kdist") { o.kdist = true; continue; }
     if (a == "--knn") unsupported("--knn (approximate k-NN DBSCAN)");
     if (a == "--db" || a == "--build" || a == "--query" || a == "--assign" || a == "--stats" || a == "--top-k" || a == "--dense" ||
         a == "--premsted" || a == "--auto-threshold" || a == "--stability" || a == "--dedup-dist" || a == "--reps-per-cluster" ||
@@ -943,6 +961,8 @@ static Options parse(int argc, char** argv) {
       puts("  -t,--threads N  -m,--min-length N  -k,--kmer-size N  -l,--list  -e,--no-save  -d,--threshold X (KSSD tuner)\n"
            "  -o,--output FILE  -i,--input FILE  --presketched DIR  --fast  --drlevel N  --gpus all|N|i,j,..\n"
            "  --eps X (default 0.05)  --minpts N (default 5)  --max-posting M (0: off)\n"
+           "  --eps-sweep e1,e2,.. (at most 32 further eps values from the same pair phase: FILE.eps_<value>, FILE.eps_sweep.tsv)\n"
+           "  --kdist (FILE.kdist.tsv: every genome's distance to its (minpts - 1)-th nearest candidate, largest first)\n"
            "  -c,--containment N (KSSD tuner)  -s,--sketch-size N  --save-rep (accepted, no effect on DBSCAN)  --knn: not in this build");
       exit(0);
 #else
@@ -2474,8 +2494,92 @@ int main(int argc, char** argv) {
   vector<int32_t> labels(genomes.size());
   vector<uint8_t> core(genomes.size());
   uint32_t ncl = 0, nnoise = 0;
-  CHECK(ctx, rtc_dbscan(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, o.dbscanEps, o.dbscanMinPts, kmer_size, o.maxPosting,
-                        labels.data(), core.data(), &ncl, &nnoise));
+  if (o.epsSweep.empty() && !o.kdist) {
+    CHECK(ctx, rtc_dbscan(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, o.dbscanEps, o.dbscanMinPts, kmer_size, o.maxPosting,
+                          labels.data(), core.data(), &ncl, &nnoise));
+  } else {
+    // --eps is one more level of the sweep: one pair phase for the whole run.  An --eps that repeats a sweep value shares its
+    // level; 32 sweep values and a 33rd --eps are past rtc_dbscan_sweep's 32 levels, and --eps then takes a call of its own.
+    const size_t n = genomes.size(), S = o.epsSweep.size();
+    vector<double> levels = o.epsSweep;
+    size_t eps_level = std::find(levels.begin(), levels.end(), o.dbscanEps) - levels.begin();
+    const bool own_call = eps_level == S && S == 32;
+    if (eps_level == S && !own_call) levels.push_back(o.dbscanEps);
+    const size_t L = levels.size();
+    vector<int32_t> all_labels(L * n);
+    vector<uint8_t> all_core(L * n);
+    vector<uint32_t> all_ncl(L), all_nnoise(L);
+    vector<rtc_kdist> kd(o.kdist ? n : 0);
+    CHECK(ctx, rtc_dbscan_sweep(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, levels.data(), (uint32_t)L, o.dbscanMinPts, kmer_size,
+                                o.maxPosting, all_labels.data(), all_core.data(), all_ncl.data(), all_nnoise.data(), o.kdist ? kd.data() : nullptr));
+    uint64_t sc[10] = {0};
+    rtc_dbscan_sweep_counters(ctx, sc);
+    if (getenv("RTC_VERBOSE"))
+      fprintf(stderr, "[sweep] %zu levels: %llu candidate edges in %llu chunk(s), %llu kept; pair %.3f ms, predicate %.3f ms, components %.3f ms, "
+              "k-distance %.3f ms\n", L, (unsigned long long)sc[1], (unsigned long long)sc[0], (unsigned long long)sc[2], sc[5] / 1e6, sc[6] / 1e6,
+              sc[7] / 1e6, sc[8] / 1e6);
+    g_metrics.num("dbscan_sweep_levels", (double)L);
+    g_metrics.num("dbscan_sweep_pair_s", sc[5] / 1e9);
+    g_metrics.num("dbscan_sweep_predicate_s", sc[6] / 1e9);
+    g_metrics.num("dbscan_sweep_components_s", sc[7] / 1e9);
+    g_metrics.num("dbscan_sweep_kdist_s", sc[8] / 1e9);
+    if (own_call) {
+      CHECK(ctx, rtc_dbscan(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, o.dbscanEps, o.dbscanMinPts, kmer_size, o.maxPosting,
+                            labels.data(), core.data(), &ncl, &nnoise));
+    } else {
+      std::copy(all_labels.begin() + eps_level * n, all_labels.begin() + (eps_level + 1) * n, labels.begin());
+      std::copy(all_core.begin() + eps_level * n, all_core.begin() + (eps_level + 1) * n, core.begin());
+      ncl = all_ncl[eps_level]; nnoise = all_nnoise[eps_level];
+    }
+    if (S) {
+      const string tsv = o.outputFile + ".eps_sweep.tsv";
+      FILE* fp = fopen(tsv.c_str(), "w");
+      if (!fp) { cerr << "ERROR: cannot open file: " << tsv << endl; return 1; }
+      fprintf(fp, "eps\tclusters\tnoise\tcore_points\tlargest_cluster\tborder_points\n");
+      for (size_t e = 0; e < S; e++) {
+        const vector<int32_t> lab(all_labels.begin() + e * n, all_labels.begin() + (e + 1) * n);
+        char name[64];
+        snprintf(name, sizeof name, ".eps_%.6f", levels[e]);
+        print_dbscan_result(lab, all_ncl[e], genomes, sketchByFile, dbscan_format_mismatch, o.outputFile + name, levels[e], o.dbscanMinPts);
+        vector<uint32_t> size(all_ncl[e], 0);
+        uint64_t n_core = 0, n_border = 0;
+        for (size_t v = 0; v < n; v++) {
+          if (lab[v] >= 0) size[lab[v]]++;
+          if (all_core[e * n + v]) n_core++;
+          else if (lab[v] >= 0) n_border++;
+        }
+        fprintf(fp, "%.6f\t%u\t%u\t%llu\t%u\t%llu\n", levels[e], all_ncl[e], all_nnoise[e], (unsigned long long)n_core,
+                size.empty() ? 0u : *std::max_element(size.begin(), size.end()), (unsigned long long)n_border);
+      }
+      fclose(fp);
+      cerr << "-----write the eps sweep (" << S << " values) into: " << tsv << endl;
+    }
+    if (o.kdist) {
+      // the curve as one plots it: the distances in descending order (no k-th candidate: inf, first), ties by index
+      const string tsv = o.outputFile + ".kdist.tsv";
+      FILE* fp = fopen(tsv.c_str(), "w");
+      if (!fp) { cerr << "ERROR: cannot open file: " << tsv << endl; return 1; }
+      vector<double> dist(n);
+      for (size_t v = 0; v < n; v++) {
+        const rtc_kdist& r = kd[v];
+        const uint64_t denom = (uint64_t)r.size_p + r.size_q - r.common;
+        if (r.neighbour == UINT32_MAX) dist[v] = INFINITY;
+        else if (denom == r.common) dist[v] = 0.0;  // j = 1, two empty u64 sketches included
+        else { const double j = (double)r.common / (double)denom; dist[v] = -log(2.0 * j / (1.0 + j)) / kmer_size; }
+      }
+      vector<uint32_t> order(n);
+      for (size_t v = 0; v < n; v++) order[v] = (uint32_t)v;
+      std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return dist[a] != dist[b] ? dist[a] > dist[b] : a < b; });
+      fprintf(fp, "index\tkth_neighbour\tcommon\tsize\tsize_neighbour\tdistance\n");
+      for (uint32_t v : order) {
+        const rtc_kdist& r = kd[v];
+        if (r.neighbour == UINT32_MAX) fprintf(fp, "%u\t-1\t0\t%u\t0\tinf\n", v, r.size_p);
+        else fprintf(fp, "%u\t%u\t%u\t%u\t%u\t%.10g\n", v, r.neighbour, r.common, r.size_p, r.size_q, dist[v]);
+      }
+      fclose(fp);
+      cerr << "-----write the k-distance curve (k=" << o.dbscanMinPts - 1 << ") into: " << tsv << endl;
+    }
+  }
   dbscan_report(labels, core, ncl, nnoise);
   print_dbscan_result(labels, ncl, genomes, sketchByFile, dbscan_format_mismatch, o.outputFile, o.dbscanEps, o.dbscanMinPts);
   cerr << "-----write the cluster result into: " << o.outputFile << endl;

@@ -1,7 +1,11 @@
 """clust-dbscan --fast on one GPU: Context.dbscan timed warm next to Context.mst on the same resident sketches, with the split
 of the DBSCAN call into the pair phase, the eps filter and the components from rtc_dbscan_counters.
 
-    python tools/run_dbscan.py [--sets dense25k,cfg4_200k] [--eps 0.05] [--minpts 5] [--repeat 3]
+    python tools/run_dbscan.py [--sets dense25k,cfg4_200k] [--eps 0.05] [--minpts 5] [--repeat 3] [--sweep e1,e2,...] [--kdist]
+
+--sweep times one Context.dbscan_sweep over the listed eps values (best of --repeat warm calls) against the same values run as
+separate Context.dbscan calls (the sum of each value's best warm call), with the sweep's phases from rtc_dbscan_sweep_counters;
+--kdist adds the k-distance curve to the sweep.  --separate-only times the separate calls alone (a library without the sweep).
 
 Sets (KSSD u32 sketches from synthetic genomes, k 21, drlevel 3, sketched on the GPU as bench.py does):
   dense25k   25 000 x 2 Mbp genomes in 25 families of 1 000 (substitution rate <= 0.01): bench.py's dense u32_25000 set, the
@@ -61,6 +65,41 @@ def _synth(ctx, api, n, per, max_rate, seed, L=2_000_000, batch=25_000):
     return api.SketchSet(torch.cat(hs), torch.cat(st), torch.cat([p.len for p in parts]), 4, parts[0].k, "kssd")
 
 
+def _sweep_row(ctx, sk, name, n, kmer, eps_list, a):
+    """one sweep against the same eps values as separate calls, each warm, best of a.repeat"""
+    sep_ms, sep_labels = [], []
+    for eps in eps_list:
+        ctx.dbscan(sk, eps, a.minpts, kmer)
+        ts = []
+        for _ in range(a.repeat):
+            t0 = time.perf_counter()
+            lab = ctx.dbscan(sk, eps, a.minpts, kmer)
+            ts.append(time.perf_counter() - t0)
+        sep_ms.append(min(ts) * 1e3)
+        sep_labels.append(lab)
+    row = {"set": name, "n": n, "kmer": kmer, "minpts": a.minpts, "eps": eps_list, "separate_ms": [round(x, 3) for x in sep_ms],
+           "separate_sum_ms": round(sum(sep_ms), 3)}
+    if a.separate_only:
+        return row
+    ctx.dbscan_sweep(sk, eps_list, a.minpts, kmer, kdist=a.kdist)
+    ts, cs = [], []
+    for _ in range(a.repeat):
+        t0 = time.perf_counter()
+        out = ctx.dbscan_sweep(sk, eps_list, a.minpts, kmer, kdist=a.kdist)
+        ts.append(time.perf_counter() - t0)
+        cs.append(ctx.dbscan_sweep_counters())
+    labels = out[0] if a.kdist else out
+    c = cs[int(np.argmin(ts))]
+    row.update({"sweep_ms": round(min(ts) * 1e3, 3), "sweep_all_ms": [round(x * 1e3, 3) for x in ts], "kdist": bool(a.kdist),
+                "identical": all(np.array_equal(labels[e], sep_labels[e]) for e in range(len(eps_list))),
+                "pair_ms": round(c["pair_ns"] / 1e6, 3), "predicate_ms": round(c["predicate_ns"] / 1e6, 3),
+                "components_ms": round(c["components_ns"] / 1e6, 3), "kdist_ms": round(c["kdist_ns"] / 1e6, 3),
+                "library_ms": round(c["total_ns"] / 1e6, 3), "chunks": c["chunks"], "candidate_edges": c["candidate_edges"],
+                "kept_edges": c["kept_edges"], "hook_rounds": c["hook_rounds"],
+                "clusters": [int(x.max(initial=-1)) + 1 for x in labels]})
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="dense25k,cfg4_200k")
@@ -68,6 +107,9 @@ def main():
     ap.add_argument("--minpts", type=int, default=5)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--no-mst", action="store_true")
+    ap.add_argument("--sweep", default="")
+    ap.add_argument("--kdist", action="store_true")
+    ap.add_argument("--separate-only", action="store_true")
     a = ap.parse_args()
     import torch
     from rabbittclust_amd import api
@@ -81,6 +123,10 @@ def main():
             sk = _synth(ctx, api, n, per, rate, seed)
         kmer = sk.k  # half_k * 2, as clust-dbscan --presketched takes it
         torch.cuda.synchronize()
+        if a.sweep:
+            print(json.dumps(_sweep_row(ctx, sk, name, n, kmer, [float(x) for x in a.sweep.split(",")], a)), flush=True)
+            del sk
+            continue
         ctx.dbscan(sk, a.eps, a.minpts, kmer)  # warm-up: code objects, scratch
         ts, cs = [], []
         for _ in range(a.repeat):
