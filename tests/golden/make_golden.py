@@ -1,12 +1,15 @@
 """Generates the committed fixtures under tests/golden/.  Run in the build container:
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py                              # every fixture
+    python tests/golden/make_golden.py ref_dbscan ref_postprocess   # only the named reference pins
 
 Two kinds of fixtures, labelled in MANIFEST.json:
   * "reference": outputs of the reference's own code run here -- oracle/_ref/libref_harness.so is
     compiled from the reference's src/{kseq.h,UnionFind.h} where they lie, oracle/_ref/libref_fns.so from its
     self-contained distance-half functions (oracle/Makefile, REF_FNS).  They pin the host FASTA reader, the
     union-find, the size-ratio bound, the KSSD greedy distance, Kruskal + the forest cut and the KSSD shuffle table.
+    oracle/_ref/libref_dbscan.so and libref_post.so are the reference's src/dbscan.cpp and src/cluster_postprocess.cpp
+    compiled whole; they pin the DBSCAN labels and printed file and the --dedup-dist / --reps-per-cluster lists.
   * "oracle": outputs of oracle/ (the CPU restatement).  They let the GPU box check the HIP path
     without regenerating expectations, and freeze the oracle against accidental edits.  The MinHash
     ones are NOT pinned against upstream RabbitSketch (see oracle/rtc_oracle.h).
@@ -25,7 +28,9 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.join(ROOT, "tests"))
 from oracle import pyoracle as O  # noqa: E402
+from tests import reflib, refpin_cases  # noqa: E402
 
 REF = os.path.join(ROOT, "oracle", "_ref", "libref_harness.so")
 REF_FNS = os.path.join(ROOT, "oracle", "_ref", "libref_fns.so")
@@ -160,6 +165,108 @@ def write_ref_distance_half(L):
             "at INT32_MAX; the reference's int conversion and int product overflow past 2^31 (DESIGN 5)"}
 
 
+def write_ref_dbscan(L):
+    """ref_dbscan.npz: the reference's KssdDBSCAN + printKssdDBSCANResult on refpin_cases.dbscan_cases(): labels, cluster /
+    noise / core counts and the SHA-256 of the printed file per case, and a SHA-256 per input set.  Inputs are not stored:
+    refpin_cases rebuilds them.  Every case runs with 1 and with 4 threads; the two must agree."""
+    import re
+    cases = refpin_cases.dbscan_cases()
+    labels, ncl, nnoise, ncore, shas, inputs = [], [], [], [], [], {}
+    for i, case in enumerate(cases):
+        gen, args, eps, min_pts, k, mp = case
+        sk = refpin_cases.sketches_of(gen, args)
+        use64 = refpin_cases.use64_of(sk)
+        inputs[json.dumps([gen, args], sort_keys=True)] = refpin_cases.input_sha(sk)
+        by_file = refpin_cases.print_layout(i)
+        lab, text, log = reflib.kssd_dbscan_print(L, sk, use64, eps, min_pts, k, refpin_cases.genomes_of(len(sk), by_file), by_file,
+                                                  threads=1, max_posting=mp)
+        lab4, c4, n4 = reflib.kssd_dbscan(L, sk, use64, eps, min_pts, k, threads=4, max_posting=mp)
+        assert np.array_equal(lab, lab4), case
+        m = re.search(r"-----Core points: (\d+) ", log)
+        labels.append(lab)
+        ncl.append(c4)
+        nnoise.append(n4)
+        ncore.append(int(m.group(1)) if m else 0)
+        shas.append(hashlib.sha256(text).hexdigest())
+    cli = []  # the printed file under the names clust-dbscan's own run gives the genomes (tests/test_gpu_refpin.py)
+    sk = refpin_cases.sketches_of("kssd_family", refpin_cases.KSSD_FAMILY_CLI)
+    for eps, min_pts, by_file in refpin_cases.CLI_RUNS:
+        _, text, _ = reflib.kssd_dbscan_print(L, sk, False, eps, min_pts, 17, refpin_cases.cli_genomes(by_file), by_file, threads=4)
+        cli.append(hashlib.sha256(text).hexdigest())
+    off = np.zeros(len(cases) + 1, dtype=np.int64)
+    np.cumsum([len(x) for x in labels], out=off[1:])
+    np.savez_compressed(os.path.join(HERE, "ref_dbscan.npz"), cli_sha256=np.array(cli), cases=np.array(json.dumps([list(c) for c in cases], sort_keys=True)),
+                        inputs=np.array(json.dumps(inputs, sort_keys=True)), labels_flat=np.concatenate(labels).astype(np.int32),
+                        labels_off=off, n_clusters=np.array(ncl, dtype=np.int32), n_noise=np.array(nnoise, dtype=np.int32),
+                        n_core=np.array(ncore, dtype=np.int64), print_sha256=np.array(shas))
+    return {"kind": "reference", "source": "KssdDBSCAN + printKssdDBSCANResult (src/dbscan.cpp compiled whole) via "
+            "oracle/ref_dbscan_shims.cpp on tests/refpin_cases.py's %d cases: labels, cluster / noise / core counts, SHA-256 of the "
+            "printed file; inputs by generator and seed with a SHA-256 each; threads 1 and 4 agreed on every case" % len(cases),
+            "pins": "reference-pinned: tests/refdbscan.py (labels_of, print_result), rtc_dbscan, rtc_dbscan_sweep, clust-dbscan's "
+            "output file; still restated only: tests/refkdist.py (the k-distance curve has no counterpart in the reference)",
+            "refusal": "u32 sets with ceil(max size / jaccard_min) past INT_MAX: the reference's int conversion overflows and its "
+            "labels differ from the restatement (recorded here); the kernels refuse them"}
+
+
+def big_forests():
+    """the 10 000-member groups of tests/test_gpu_postprocess.py"""
+    from tests import test_gpu_postprocess as T
+    return [(shape, weights) + T._forest(11, [10_000, 3000, 40, 2], shape, weights)
+            for shape, weights in [("chain", "rand"), ("star", "tie"), ("random", "tie"), ("random", "rand")]]
+
+
+def write_ref_postprocess(L):
+    """ref_postprocess.npz: the reference's build_dedup_candidates_per_cluster (KSSD overload) and
+    select_k_reps_per_cluster_tree on refpin_cases.forest_case(seed): node_to_rep and the candidate lists per dedup distance,
+    the representative lists per k; node_to_rep of the forests of tests/test_gpu_postprocess.py (CASES and the 10 000-member
+    groups) at dedup distance 0.01."""
+    rep_flat, lists, shape = [], [], []
+    for seed in refpin_cases.FOREST_SEEDS:
+        n, edges, lens, dedups, ks = refpin_cases.forest_case(seed)
+        clusters = refpin_cases.components(n, edges)
+        shape.append((n, len(edges), len(clusters)))
+        for di, dd in enumerate(dedups):
+            rep, cand = reflib.dedup_candidates(L, n, clusters, edges, lens, dd, by_file=(seed + di) % 2 == 0)
+            rep_flat += rep
+            lists += cand
+            for k in ks:
+                lists += reflib.select_k_reps(L, n, clusters, cand, edges, rep, k)
+    off = np.zeros(len(lists) + 1, dtype=np.int64)
+    np.cumsum([len(x) for x in lists], out=off[1:])
+    out = dict(shape=np.array(shape, dtype=np.int32), rep_flat=np.array(rep_flat, dtype=np.int32),
+               lists_flat=np.array([v for x in lists for v in x], dtype=np.int32), lists_off=off)
+    for i, (_, _, n, edges, lens) in enumerate(big_forests()):
+        rep, _ = reflib.dedup_candidates(L, n, [list(range(n))], edges, [int(x) for x in lens], 0.01)
+        out["big%d_rep" % i] = np.array(rep, dtype=np.int32)
+    from tests import test_gpu_postprocess as T
+    for i, (seed, sizes, shp, weights) in enumerate(T.CASES):
+        n, edges, lens = T._forest(seed, sizes, shp, weights)
+        rep, _ = reflib.dedup_candidates(L, n, [list(range(n))], edges, [int(x) for x in lens], 0.01)
+        out["small%d_rep" % i] = np.array(rep, dtype=np.int32)
+    np.savez_compressed(os.path.join(HERE, "ref_postprocess.npz"), **out)
+    return {"kind": "reference", "source": "build_dedup_candidates_per_cluster (KSSD overload) + select_k_reps_per_cluster_tree "
+            "(src/cluster_postprocess.cpp compiled whole) via oracle/ref_post_shims.cpp on tests/refpin_cases.py's %d seeded forests "
+            "(chains, stars, caterpillars, random trees; tied and distinct weights and lengths; dedup 0, 0.005, 0.01, 0.015, 1.0, "
+            "on an edge weight and one ulp either side; k 0, 1, 2, 3, 1000) and node_to_rep of tests/test_gpu_postprocess.py's "
+            "forests, four with 10 000-member groups" % len(refpin_cases.FOREST_SEEDS),
+            "pins": "reference-pinned: tests/refpost.py (tree_medoids, dedup_candidates, select_k_reps), rtc_tree_medoids on the GPU "
+            "and host paths; still restated only: tests/refmststate.py, tests/refmstdb.py and refpost.py's --auto-threshold / "
+            "--stability analysis (src/MST.cpp needs the whole sketch library to compile)"}
+
+
+REF_PINS = {"ref_dbscan": (reflib.ref_dbscan, write_ref_dbscan), "ref_postprocess": (reflib.ref_post, write_ref_postprocess)}
+
+
+def write_ref_pins(manifest, names):
+    for name in names:
+        load, write = REF_PINS[name]
+        L = load()
+        if L is None:
+            raise SystemExit("oracle/_ref/lib%s.so missing: run `make -C oracle` where the reference tree exists"
+                             % name.replace("postprocess", "post"))
+        manifest[name + ".npz"] = write(L)
+
+
 def write_fasta_inputs():
     rng = np.random.default_rng(2024)
 
@@ -242,6 +349,14 @@ def write_kseq_random(ref):
 
 
 def main():
+    if len(sys.argv) > 1:  # only the named reference pins; the other entries of the manifest stay
+        with open(os.path.join(HERE, "MANIFEST.json")) as f:
+            manifest = json.load(f)
+        write_ref_pins(manifest, sys.argv[1:])
+        with open(os.path.join(HERE, "MANIFEST.json"), "w") as f:
+            json.dump(manifest, f, indent=1, sort_keys=True)
+        print("wrote", sys.argv[1:])
+        return
     manifest = {}
     names = write_fasta_inputs()
     if not os.path.exists(REF):
@@ -280,6 +395,8 @@ def main():
                         head=sd[:64].astype(np.int32))
     manifest["kssd_shuffle_hs6.npz"] = {"kind": "reference", "source": "generate_shuffle_dim(6) via oracle/ref_fns_shims.inc "
                                         "(glibc srand/rand); 4096 surviving (dim_id, rank) pairs + first 64 table entries"}
+
+    write_ref_pins(manifest, sorted(REF_PINS))
 
     # ---- oracle fixtures ----
     L = 60_000

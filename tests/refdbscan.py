@@ -179,7 +179,8 @@ def labels_of(sketches, eps, min_pts, kmer_size, use64, max_posting=0):
 
 def print_result(labels, genomes, by_file, eps, min_pts):
     """printKssdDBSCANResult (:1212-1310) as text.  genomes: per point (fileName, totalSeqLength, name, comment) with -l, or
-    (name, length, comment) without.  Members in ascending index order, noise after the clusters, one point each."""
+    (name, length, comment) without.  Members in ascending index order, noise after the clusters, one point each.  The -l
+    layout prints the 64-bit totalSeqLength with %12d (:1250-1251): its low 32 bits as a signed int, negative from 2^31 on."""
     ncl = max([x for x in labels] + [-1]) + 1
     clusters = [[] for _ in range(ncl)]
     noise = []
@@ -193,7 +194,7 @@ def print_result(labels, genomes, by_file, eps, min_pts):
     def line(j, cur):
         g = genomes[cur]
         if by_file:
-            return "\t%5d\t%6d\t%12dnt\t%20s\t%20s\t%s\n" % (j, cur, g[1], g[0], g[2], g[3])
+            return "\t%5d\t%6d\t%12dnt\t%20s\t%20s\t%s\n" % (j, cur, (g[1] + 2 ** 31) % 2 ** 32 - 2 ** 31, g[0], g[2], g[3])
         return "\t%6d\t%6d\t%12dnt\t%20s\t%s\n" % (j, cur, g[1], g[0], g[2])
     for i, c in enumerate(clusters):
         out.append("the cluster %d is: \n" % i)
