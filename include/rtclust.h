@@ -507,6 +507,62 @@ int rtc_dbscan_sweep(rtc_ctx* ctx, const void* d_hashes, int width, const uint64
  * predicate ns, out[7] components and labels ns, out[8] k-distance ns, out[9] whole call ns. */
 int rtc_dbscan_sweep_counters(const rtc_ctx* ctx, uint64_t out[10]);
 
+/* ---- clust-dbscan --hierarchy: the density hierarchy (HDBSCAN*) of the neighbour graph at eps_max ------------- */
+/* One edge of the hierarchy: its mutual-reachability similarity is m = common / (size_p + size_q - common), p < q
+ * (size_p = size_q = common = 0: m = 1, two empty u64 sketches). */
+typedef struct { uint32_t p, q, common, size_p, size_q; } rtc_hedge;
+/* The maximum spanning forest of the mutual-reachability relation over the pairs rtc_dbscan keeps at eps_max (both
+ * orientations of its predicate; the same common, sizes, max_posting and empty u64 sketches), from ONE pair phase.
+ *   j(p, q) = common / (|p| + |q| - common), compared exactly by 64-bit cross-multiplication (sketches of up to 2^31 - 1 hashes;
+ *             a longer one returns RTC_ERR_UNSUPPORTED);
+ *   jcore(p) = the j of h_core[p], which is exactly rtc_dbscan_sweep's h_kdist[p] (k = min_pts - 1, ranked over all candidates);
+ *             neighbour = UINT32_MAX: p has no core level, is never a core point, and its edges are not part of the forest;
+ *   m(p, q) = min(j(p, q), jcore(p), jcore(q)); the edge carries the triple of the term that limits it: the pair's own
+ *             (common, |p|, |q|) unless jcore(p) is strictly smaller, then h_core[p]'s, unless jcore(q) is strictly smaller
+ *             than that, then h_core[q]'s (p < q).
+ * The forest is the one Kruskal's algorithm builds under the total order (larger m first, then smaller p, then smaller q), and
+ * h_forest [n - 1 slots] holds its *h_n_forest edges in that order.  The device forms no distance: an edge's distance is
+ * -ln(2 m / (1 + m)) / kmer_size with the caller's libm (kmer_size only enters t(eps_max)).  Fails as rtc_dbscan_sweep fails
+ * for the single level eps_max (RTC_ERR_UNSUPPORTED, RTC_ERR_NOMEM: no fallback).  Synchronous. */
+int rtc_dbscan_hierarchy(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                         double eps_max, int min_pts, int kmer_size, int max_posting, rtc_hedge* h_forest, uint64_t* h_n_forest,
+                         rtc_kdist* h_core);
+/* rtc_dbscan_sweep and rtc_dbscan_hierarchy from ONE pair phase (what clust-dbscan --hierarchy --eps-sweep --kdist runs):
+ * the arguments and results of both, each exactly as from its own call; both counter sets are filled.  n_eps may be 0. */
+int rtc_dbscan_sweep_hierarchy(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                               const double* h_eps, uint32_t n_eps, int min_pts, int kmer_size, int max_posting, int32_t* h_labels,
+                               uint8_t* h_core_flags, uint32_t* h_n_clusters, uint32_t* h_n_noise, rtc_kdist* h_kdist, double eps_max,
+                               rtc_hedge* h_forest, uint64_t* h_n_forest, rtc_kdist* h_core);
+/* What the last hierarchy call did: out[0] row chunks and out[1] candidate edges of its pair phase, out[2] pairs kept at
+ * eps_max, out[3] forest edges, out[4] Boruvka rounds, out[5] pair phase ns, out[6] k-distance ns, out[7] filter, weights and
+ * ranking ns, out[8] forest ns, out[9] whole call ns. */
+int rtc_dbscan_hierarchy_counters(const rtc_ctx* ctx, uint64_t out[10]);
+/* DBSCAN*'s clusters at eps <= eps_max from a hierarchy (host only, O(n alpha)).  t = t(eps) as rtc_dbscan forms it.  p is a
+ * core point iff h_core[p] has a neighbour and its triple passes rtc_dbscan's predicate at t in both orientations (in double,
+ * with the 1e-12 term; the triple 0, 0, 0 passes, as two empty u64 sketches do).  A forest edge joins its ends iff both are core
+ * points and its triple passes the same test.  h_labels[n]: clusters numbered by their smallest core index; every non-core
+ * point is -1 -- there is NO border attachment (DBSCAN*), unlike rtc_dbscan, whose labels agree with these on the core points.
+ * h_is_core[n] may be NULL.  eps > eps_max (the value the hierarchy was built with) or eps <= 0: RTC_ERR_ARG; t <= 1e-12:
+ * RTC_ERR_UNSUPPORTED. */
+int rtc_hierarchy_cut(uint32_t n, const rtc_hedge* h_forest, uint64_t n_forest, const rtc_kdist* h_core, double eps_max, double eps,
+                      int kmer_size, int32_t* h_labels, uint8_t* h_is_core, uint32_t* n_clusters);
+/* A flat clustering without eps (host only, O(n log n)): the condensed tree of the forest, selected by excess of mass.
+ *   - distance(e) = -ln(2 m / (1 + m)) / kmer_size (0 at m = 1), lambda(e) = 1 / max(distance(e), 1e-12).
+ *   - The forest's edges, taken in forest order, merge components into a binary dendrogram (left child: p's side, right: q's).
+ *     Points without a core level are outside it.  Each tree with at least min_cluster_size (>= 2) points is a top-level cluster
+ *     born at lambda 0; the points of a smaller tree are -1.
+ *   - Walking down, a merge at lambda whose two sides both hold >= min_cluster_size points ends its cluster and starts two
+ *     children born at lambda; a side with fewer points falls out of the cluster at lambda and its points stay attached to it.
+ *     Each such event adds  points leaving x (lambda - lambda of the cluster's birth)  to the cluster's stability, one term per
+ *     merge, the terms added in forest order.
+ *   - Selection from the leaves up: a cluster is selected iff its stability is strictly greater than the sum (left + right) of
+ *     its children's best -- on a tie the children win -- and its best is the larger of the two.  A top-level cluster that is
+ *     the only one and has children is the root and is not selected.
+ *   - h_labels[n]: a point takes the selected cluster it fell out of or the nearest selected ancestor of that, else -1; clusters are
+ *     numbered by their smallest member.  h_stability [as many as clusters, at most n / min_cluster_size; may be NULL]. */
+int rtc_hierarchy_flat(uint32_t n, const rtc_hedge* h_forest, uint64_t n_forest, const rtc_kdist* h_core, int kmer_size,
+                       int min_cluster_size, int32_t* h_labels, double* h_stability, uint32_t* n_clusters);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ KDIST_DT = np.dtype([("common", "<u4"), ("size_p", "<u4"), ("size_q", "<u4"), ("
 # Context.dbscan_sweep's curve: rtc_kdist plus the distance the host forms from it
 KDIST_CURVE_DT = np.dtype(KDIST_DT.descr + [("distance", "<f8")])
 KDIST_NONE = 0xFFFFFFFF  # neighbour of a point with fewer than minPts - 1 candidates (distance inf)
+HEDGE_DT = np.dtype([("p", "<u4"), ("q", "<u4"), ("common", "<u4"), ("size_p", "<u4"), ("size_q", "<u4")])  # rtc_hedge
 
 
 def _np_ptr(a):
@@ -632,6 +633,49 @@ class Context:
                  "kdist_ns", "total_ns")
         return {k: int(a[i]) for i, k in enumerate(names)}
 
+    def dbscan_hierarchy(self, sk, eps_max, min_pts, kmer_size, max_posting=0):
+        """clust-dbscan --hierarchy (rtc_dbscan_hierarchy): the maximum spanning forest of the mutual-reachability relation over
+        the pairs Context.dbscan keeps at eps_max, and every point's core triple.  Returns (forest, core): HEDGE_DT edges in the
+        total order (larger m first, then smaller p, then smaller q) and KDIST_DT per point, which is dbscan_sweep's k-distance
+        curve.  hierarchy_cut / hierarchy_flat read both."""
+        n = sk.n
+        forest = np.zeros(max(n, 1), dtype=HEDGE_DT)
+        core = np.zeros(max(n, 1), dtype=KDIST_DT)
+        nf = C.c_uint64(0)
+        self.check(self.lib.rtc_dbscan_hierarchy(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n, float(eps_max),
+                                                 int(min_pts), int(kmer_size), int(max_posting), _np_ptr(forest), C.byref(nf), _np_ptr(core)))
+        return forest[:nf.value].copy(), core[:n].copy()
+
+    def dbscan_sweep_hierarchy(self, sk, eps_list, eps_max, min_pts, kmer_size, max_posting=0):
+        """rtc_dbscan_sweep_hierarchy: dbscan_sweep(eps_list, return_core=True) and dbscan_hierarchy(eps_max) from ONE pair phase
+        (what clust-dbscan --hierarchy --eps-sweep runs).  Returns (labels[n_eps, n], bool core flags[n_eps, n], forest, core
+        triples), each exactly as from its own call; both counter sets are filled."""
+        n = sk.n
+        eps = np.ascontiguousarray(np.asarray(list(eps_list), dtype=np.float64))
+        L = int(eps.size)
+        labels = np.zeros((L, n), dtype=np.int32)
+        flags = np.zeros((L, n), dtype=np.uint8)
+        ncl, nnoise = np.zeros(max(L, 1), dtype=np.uint32), np.zeros(max(L, 1), dtype=np.uint32)
+        buf_l = labels if labels.size else np.zeros(1, dtype=np.int32)
+        buf_c = flags if flags.size else np.zeros(1, dtype=np.uint8)
+        forest = np.zeros(max(n, 1), dtype=HEDGE_DT)
+        core = np.zeros(max(n, 1), dtype=KDIST_DT)
+        nf = C.c_uint64(0)
+        self.check(self.lib.rtc_dbscan_sweep_hierarchy(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n,
+                                                       _np_ptr(eps) if L else None, L, int(min_pts), int(kmer_size), int(max_posting),
+                                                       _np_ptr(buf_l), _np_ptr(buf_c), _np_ptr(ncl), _np_ptr(nnoise), None, float(eps_max),
+                                                       _np_ptr(forest), C.byref(nf), _np_ptr(core)))
+        self.dbscan_sweep_counts = {"clusters": ncl[:L].copy(), "noise": nnoise[:L].copy()}
+        return labels, flags.astype(bool), forest[:nf.value].copy(), core[:n].copy()
+
+    def dbscan_hierarchy_counters(self):
+        """rtc_dbscan_hierarchy_counters as a dict (the last hierarchy call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_dbscan_hierarchy_counters(self.h, a))
+        names = ("chunks", "candidate_edges", "kept_edges", "forest_edges", "boruvka_rounds", "pair_ns", "kdist_ns", "rank_ns",
+                 "forest_ns", "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
     def dbscan_counters(self):
         """rtc_dbscan_counters as a dict (the last dbscan call)."""
         a = (C.c_uint64 * 10)()
@@ -639,6 +683,41 @@ class Context:
         names = ("chunks", "candidate_edges", "eps_edges", "core_points", "asymmetric_pairs", "hook_rounds", "pair_ns",
                  "filter_ns", "components_ns", "total_ns")
         return {k: int(a[i]) for i, k in enumerate(names)}
+
+
+def _hier_args(forest, core):
+    forest = np.ascontiguousarray(forest, dtype=HEDGE_DT)
+    core = np.ascontiguousarray(core, dtype=KDIST_DT)
+    return forest, core, (forest if forest.size else np.zeros(1, dtype=HEDGE_DT)), (core if core.size else np.zeros(1, dtype=KDIST_DT))
+
+
+def _hier_check(st, what):
+    if st != _lib.RTC_OK:
+        raise RtcError(st, what)
+
+
+def hierarchy_cut(forest, core, eps_max, eps, kmer_size):
+    """rtc_hierarchy_cut (host only): DBSCAN*'s clusters at eps <= eps_max from Context.dbscan_hierarchy's result.  Returns
+    (int32 labels, bool core flags): clusters numbered by smallest core index, every non-core point -1 (no border attachment)."""
+    forest, core, fb, cb = _hier_args(forest, core)
+    n = int(core.size)
+    labels, flags, ncl = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.uint8), C.c_uint32(0)
+    _hier_check(_lib.load().rtc_hierarchy_cut(n, _np_ptr(fb), int(forest.size), _np_ptr(cb), float(eps_max), float(eps), int(kmer_size),
+                                              _np_ptr(labels), _np_ptr(flags), C.byref(ncl)),
+                "hierarchy_cut: eps %g (eps_max %g, k %d)" % (eps, eps_max, kmer_size))
+    return labels[:n].copy(), flags[:n].astype(bool)
+
+
+def hierarchy_flat(forest, core, kmer_size, min_cluster_size, return_stability=False):
+    """rtc_hierarchy_flat (host only): the flat clustering of the condensed tree by excess of mass; int32 labels numbered by
+    smallest member, -1 elsewhere.  return_stability: (labels, float64 stability per cluster)."""
+    forest, core, fb, cb = _hier_args(forest, core)
+    n = int(core.size)
+    labels, stab, ncl = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.float64), C.c_uint32(0)
+    _hier_check(_lib.load().rtc_hierarchy_flat(n, _np_ptr(fb), int(forest.size), _np_ptr(cb), int(kmer_size), int(min_cluster_size),
+                                               _np_ptr(labels), _np_ptr(stab), C.byref(ncl)),
+                "hierarchy_flat: min_cluster_size %d, k %d" % (min_cluster_size, kmer_size))
+    return (labels[:n].copy(), stab[:ncl.value].copy()) if return_stability else labels[:n].copy()
 
 
 def kdist_distance(common, size_p, size_q, kmer_size):

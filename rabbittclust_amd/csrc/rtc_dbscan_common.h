@@ -24,7 +24,7 @@ inline uint32_t blocks_for(uint64_t work, int num_cu) {
 // The neighbour test of findNeighborsKSSDWithIndex for reference point p (size a) and candidate q (size b): the size
 // filter floor(t a) <= b <= ceil(a / t), then  !(common (1 + t) + 1e-12 < t a + t b)  in double, in that form
 // (:531-533, :573-585; the u64 brute force :393-397, :426-431).  The unit is built with -ffp-contract=off: no FMA.
-__device__ __forceinline__ bool eps_pred(uint32_t a, uint32_t b, uint32_t common, double t, double one_plus_t) {
+__host__ __device__ __forceinline__ bool eps_pred(uint32_t a, uint32_t b, uint32_t common, double t, double one_plus_t) {
   if (a == 0 || b == 0) return false;
   const double da = (double)a, db = (double)b;
   const double t_times_a = t * da;

@@ -17,6 +17,7 @@
 // point and level, and for the curve 32 B per candidate of one chunk plus 16 B x k per point.  Past that: RTC_ERR_NOMEM.
 #include "rtc_dbscan_common.h"
 #include "rtc_topk_select.h"
+#include "rtc_dbscan_hier.h"
 
 namespace {
 
@@ -286,16 +287,25 @@ int kdist_chunk_host(rtc_ctx* ctx, KdState& K, const rtc_cedge* d_cand, uint64_t
 
 }  // namespace
 
-extern "C" int rtc_dbscan_sweep(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
-                                const double* h_eps, uint32_t n_eps, int min_pts, int kmer_size, int max_posting, int32_t* h_labels,
-                                uint8_t* h_core, uint32_t* h_n_clusters, uint32_t* h_n_noise, rtc_kdist* h_kdist) {
+// What a hierarchy call adds to the sweep's pair phase (rtc_dbscan_hier.h): the level it keeps pairs at, and where its results go.
+struct HierReq { double eps_max; rtc_hedge* h_forest; uint64_t* h_n_forest; rtc_kdist* h_core; };
+
+// rtc_dbscan_sweep, and with hq the hierarchy from the same pair phase.  who: the entry point, for the messages.
+static int sweep_impl(rtc_ctx* ctx, const char* who, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+               const double* h_eps, uint32_t n_eps, int min_pts, int kmer_size, int max_posting, int32_t* h_labels,
+               uint8_t* h_core, uint32_t* h_n_clusters, uint32_t* h_n_noise, rtc_kdist* h_kdist, const HierReq* hq) {
   if (!ctx || (n && (!d_hashes || !d_start || !d_len)) || (width != 4 && width != 8)) return RTC_ERR_ARG;
-  if (n_eps > SW_MAX_LEVELS) return rtc_fail(ctx, RTC_ERR_ARG, "rtc_dbscan_sweep: %u eps values, at most %u", n_eps, SW_MAX_LEVELS);
-  if (n_eps == 0 && !h_kdist) return rtc_fail(ctx, RTC_ERR_ARG, "rtc_dbscan_sweep: no eps value and no k-distance curve asked for");
+  if (n_eps > SW_MAX_LEVELS) return rtc_fail(ctx, RTC_ERR_ARG, "%s: %u eps values, at most %u", who, n_eps, SW_MAX_LEVELS);
+  if (n_eps == 0 && !h_kdist && !hq) return rtc_fail(ctx, RTC_ERR_ARG, "%s: no eps value and no k-distance curve asked for", who);
+  if (hq && (!hq->h_n_forest || (n && !hq->h_core) || (n > 1 && !hq->h_forest))) return RTC_ERR_ARG;
   if (n_eps && (!h_eps || (n && !h_labels))) return RTC_ERR_ARG;
-  if (n >= 0x7fffffffu) return rtc_fail(ctx, RTC_ERR_ARG, "rtc_dbscan_sweep: %u points", n);
+  if (n >= 0x7fffffffu) return rtc_fail(ctx, RTC_ERR_ARG, "%s: %u points", who, n);
   for (int i = 0; i < 10; i++) ctx->dbscan_sweep[i] = 0;
   ctx->dbscan_sweep[3] = n_eps;
+  if (hq) {
+    for (int i = 0; i < 10; i++) ctx->dbscan_hier[i] = 0;
+    *hq->h_n_forest = 0;
+  }
   for (uint32_t e = 0; e < n_eps; e++) {
     if (h_n_clusters) h_n_clusters[e] = 0;
     if (h_n_noise) h_n_noise[e] = 0;
@@ -312,8 +322,16 @@ extern "C" int rtc_dbscan_sweep(rtc_ctx* ctx, const void* d_hashes, int width, c
     lv.t[e] = x / (2.0 - x);
     lv.one_plus_t[e] = 1.0 + lv.t[e];
     if (!(lv.t[e] > 1e-12))
-      return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "rtc_dbscan_sweep: eps %g (value %u of the list) with k %d gives jaccard_min %g <= 1e-12", h_eps[e], e,
+      return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "%s: eps %g (value %u of the list) with k %d gives jaccard_min %g <= 1e-12", who, h_eps[e], e,
                       kmer_size, lv.t[e]);
+  }
+  // the hierarchy's level: the same x, t and refusals
+  double ht = 0.0;
+  if (hq) {
+    const double x = exp(-hq->eps_max * kmer_size);
+    ht = x / (2.0 - x);
+    if (!(ht > 1e-12))
+      return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "%s: eps %g with k %d gives jaccard_min %g <= 1e-12", who, hq->eps_max, kmer_size, ht);
   }
   std::vector<uint32_t> h_len(n);
   RTC_HIP(ctx, hipMemcpyAsync(h_len.data(), d_len, (size_t)n * 4, hipMemcpyDeviceToHost, s));
@@ -327,21 +345,24 @@ extern "C" int rtc_dbscan_sweep(rtc_ctx* ctx, const void* d_hashes, int width, c
   if (width == 4)
     for (uint32_t e = 0; e < n_eps; e++)
       if (ceil((double)max_len / lv.t[e]) > 2147483647.0)
-        return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "rtc_dbscan_sweep: eps %g (value %u of the list): size bound ceil(%u / %g) past INT_MAX", h_eps[e], e,
+        return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "%s: eps %g (value %u of the list): size bound ceil(%u / %g) past INT_MAX", who, h_eps[e], e,
                         max_len, lv.t[e]);
-  if (h_kdist && max_len > SW_KDIST_MAX_LEN)
-    return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "rtc_dbscan_sweep: a sketch of %u hashes, the k-distance order is exact up to %u", max_len, SW_KDIST_MAX_LEN);
+  if (hq && width == 4 && ceil((double)max_len / ht) > 2147483647.0)
+    return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "%s: eps %g: size bound ceil(%u / %g) past INT_MAX", who, hq->eps_max, max_len, ht);
+  rtc_kdist* const kd_out = hq ? hq->h_core : h_kdist;  // the hierarchy's core triples ARE the curve
+  if (kd_out && max_len > SW_KDIST_MAX_LEN)
+    return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "%s: a sketch of %u hashes, the k-distance order is exact up to %u", who, max_len, SW_KDIST_MAX_LEN);
   const uint32_t n_empty = (uint32_t)empties.size();
   const uint32_t empty_deg = (width == 8 && n_empty) ? n_empty - 1 : 0;  // the u64 brute force's clique of empty sketches (rtc_dbscan.hip)
   const uint32_t empty_root = (width == 8 && n_empty) ? empties[0] : 0xffffffffu;
   const long long kth = (long long)min_pts - 1;
-  const bool curve = h_kdist && kth >= 1;  // k <= 0: every point is its own k-th neighbour, no candidates needed
+  const bool curve = kd_out && kth >= 1;  // k <= 0: every point is its own k-th neighbour, no candidates needed
 
   DevBuf db;
   const void* ph = d_hashes;
   const uint64_t* pstart = d_start;
   const uint32_t* plen = d_len;
-  if (width == 4 && max_posting > 0 && (n_eps || curve)) {
+  if (width == 4 && max_posting > 0 && (n_eps || curve || hq)) {
     uint32_t *d_ph = nullptr, *d_plen = nullptr;
     uint64_t* d_pstart = nullptr;
     RTC_TRY(prune_postings(ctx, db, (const uint32_t*)d_hashes, d_start, d_len, n, h_len, (uint64_t)max_posting, &d_ph, &d_pstart, &d_plen));
@@ -352,7 +373,7 @@ extern "C" int rtc_dbscan_sweep(rtc_ctx* ctx, const void* d_hashes, int width, c
   // ---- one pair phase: every chunk gives its level masks and its share of the curve ----
   rtc_cedge* d_kept = nullptr;
   uint64_t kept_cap = std::max<uint64_t>((uint64_t)1 << 16, (uint64_t)n * 16);
-  unsigned long long* d_cnt = nullptr;  // [0] pair count, [1..4] mask counters
+  unsigned long long* d_cnt = nullptr;  // [0] pair count, [1..4] mask counters, [5..7] the hierarchy filter's
   RTC_TRY(db.get(ctx, 8, &d_cnt));
   if (n_eps) RTC_TRY(db.get(ctx, kept_cap, &d_kept));
   KdState K;
@@ -366,20 +387,27 @@ extern "C" int rtc_dbscan_sweep(rtc_ctx* ctx, const void* d_hashes, int width, c
     }
   }
   uint64_t m_kept = 0, asym = 0, first_asym = ~0ull, asym_levels = 0, mask_ns = 0, kdist_ns = 0;
+  rtc_cedge* d_hkept = nullptr;  // the hierarchy's own list: the pairs kept at eps_max, p < q
+  uint64_t hkept_cap = std::max<uint64_t>((uint64_t)1 << 16, (uint64_t)n * 16);
+  uint64_t m_hkept = 0, h_asym = 0, h_first_asym = ~0ull, hfilter_ns = 0;
+  if (hq) RTC_TRY(db.get(ctx, hkept_cap, &d_hkept));
   PairPhase pp;
+  // a kept list moved into `want` records (the filter kernels never write past a list that holds used + the chunk's candidates)
+  auto regrow = [&](rtc_cedge*& d_list, uint64_t& cap, uint64_t used, uint64_t want) -> int {
+      rtc_cedge* nd = nullptr;
+      RTC_TRY(db.get(ctx, want, &nd));
+      if (used) RTC_HIP(ctx, hipMemcpyAsync(nd, d_list, used * sizeof(rtc_cedge), hipMemcpyDeviceToDevice, s));
+      RTC_HIP(ctx, hipStreamSynchronize(s));
+      db.release(d_list);
+      d_list = nd; cap = want;
+      return RTC_OK;
+  };
   auto on_chunk = [&](const rtc_cedge* d_cand, uint64_t cnt) -> int {
       if (!cnt) return RTC_OK;
       if (n_eps) {
         const uint64_t tf = now_ns();
-        if (m_kept + cnt > kept_cap) {  // at most every candidate is kept: the mask kernel never runs past the list
-          rtc_cedge* nd = nullptr;
-          const uint64_t want = m_kept + cnt;
-          RTC_TRY(db.get(ctx, want, &nd));
-          if (m_kept) RTC_HIP(ctx, hipMemcpyAsync(nd, d_kept, m_kept * sizeof(rtc_cedge), hipMemcpyDeviceToDevice, s));
-          RTC_HIP(ctx, hipStreamSynchronize(s));
-          db.release(d_kept);
-          d_kept = nd; kept_cap = want;
-        }
+        // at most every candidate is kept: the mask kernel never runs past the list
+        if (m_kept + cnt > kept_cap) RTC_TRY(regrow(d_kept, kept_cap, m_kept, m_kept + cnt));
         unsigned long long fc[4] = {(unsigned long long)m_kept, 0ull, ~0ull, 0ull};
         RTC_HIP(ctx, hipMemcpyAsync(d_cnt + 1, fc, sizeof fc, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(eps_mask_kernel, dim3(blocks_for(cnt, ctx->num_cu)), dim3(256), 0, s, d_cand, cnt, d_len, lv, n_eps, sat, d_kept,
@@ -387,12 +415,35 @@ extern "C" int rtc_dbscan_sweep(rtc_ctx* ctx, const void* d_hashes, int width, c
         RTC_CHECK_LAUNCH(ctx);
         RTC_HIP(ctx, hipMemcpyAsync(fc, d_cnt + 1, sizeof fc, hipMemcpyDeviceToHost, s));
         RTC_HIP(ctx, hipStreamSynchronize(s));
-        if (fc[0] > kept_cap) return rtc_fail(ctx, RTC_ERR_OVERFLOW, "rtc_dbscan_sweep: %llu pairs kept, room for %llu", fc[0], (unsigned long long)kept_cap);
+        if (fc[0] > kept_cap) return rtc_fail(ctx, RTC_ERR_OVERFLOW, "%s: %llu pairs kept, room for %llu", who, fc[0], (unsigned long long)kept_cap);
         m_kept = fc[0];
         asym += fc[1];
         first_asym = std::min<uint64_t>(first_asym, fc[2]);
         asym_levels |= fc[3];
         mask_ns += now_ns() - tf;
+      }
+      if (hq) {
+        const uint64_t tf = now_ns();
+        // room for the kept pairs and every candidate of the chunk; doubled when short, so many row chunks move the list a few times
+        if (m_hkept + cnt > hkept_cap) {
+          const uint64_t need = m_hkept + cnt;
+          if (2 * hkept_cap <= need || regrow(d_hkept, hkept_cap, m_hkept, 2 * hkept_cap) != RTC_OK) {
+            (void)hipGetLastError();  // a doubled list that did not fit is no failure yet: the exact size may
+            RTC_TRY(regrow(d_hkept, hkept_cap, m_hkept, need));
+          }
+        }
+        unsigned long long fc[3] = {(unsigned long long)m_hkept, 0ull, ~0ull};
+        RTC_HIP(ctx, hipMemcpyAsync(d_cnt + 5, fc, sizeof fc, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(hier_filter_kernel, dim3(blocks_for(cnt, ctx->num_cu)), dim3(256), 0, s, d_cand, cnt, d_len, ht, 1.0 + ht, sat, d_hkept,
+                           hkept_cap, d_cnt + 5);
+        RTC_CHECK_LAUNCH(ctx);
+        RTC_HIP(ctx, hipMemcpyAsync(fc, d_cnt + 5, sizeof fc, hipMemcpyDeviceToHost, s));
+        RTC_HIP(ctx, hipStreamSynchronize(s));
+        if (fc[0] > hkept_cap) return rtc_fail(ctx, RTC_ERR_OVERFLOW, "%s: %llu pairs kept, room for %llu", who, fc[0], (unsigned long long)hkept_cap);
+        m_hkept = fc[0];
+        h_asym += fc[1];
+        h_first_asym = std::min<uint64_t>(h_first_asym, fc[2]);
+        hfilter_ns += now_ns() - tf;
       }
       if (curve) {
         const uint64_t tk = now_ns();
@@ -402,50 +453,80 @@ extern "C" int rtc_dbscan_sweep(rtc_ctx* ctx, const void* d_hashes, int width, c
       }
       return RTC_OK;
   };
-  if (n_eps || curve) RTC_TRY(dbscan_pair_chunks(ctx, db, ph, width, pstart, plen, n, d_cnt, &pp, on_chunk));
+  if (n_eps || curve || hq) RTC_TRY(dbscan_pair_chunks(ctx, db, ph, width, pstart, plen, n, d_cnt, &pp, on_chunk));
   ctx->dbscan_sweep[0] = pp.chunks;
   ctx->dbscan_sweep[1] = pp.cand_total;
   ctx->dbscan_sweep[2] = m_kept;
   ctx->dbscan_sweep[5] = pp.pair_ns;
   ctx->dbscan_sweep[6] = mask_ns;
+  if (hq) {
+    ctx->dbscan_hier[0] = pp.chunks;
+    ctx->dbscan_hier[1] = pp.cand_total;
+    ctx->dbscan_hier[2] = m_hkept;
+    ctx->dbscan_hier[5] = pp.pair_ns;
+    if (h_asym)
+      return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "%s: eps %g: %llu pairs whose eps test depends on the orientation, e.g. (%u, %u)", who, hq->eps_max,
+                      (unsigned long long)h_asym, (uint32_t)(h_first_asym >> 32), (uint32_t)h_first_asym);
+  }
   if (asym) {
     const uint32_t e = (uint32_t)__builtin_ctzll(asym_levels);
-    return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "rtc_dbscan_sweep: eps %g (value %u of the list): %llu pairs whose eps test depends on the orientation, e.g. (%u, %u)",
+    return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "%s: eps %g (value %u of the list): %llu pairs whose eps test depends on the orientation, e.g. (%u, %u)", who,
                     h_eps[e], e, (unsigned long long)asym, (uint32_t)(first_asym >> 32), (uint32_t)first_asym);
   }
 
   // ---- the curve: the k-th record of every point, the empty sketches of the u64 path, k <= 0 ----
-  if (h_kdist) {
+  if (kd_out) {
     const uint64_t tk = now_ns();
     if (!curve) {
-      for (uint32_t p = 0; p < n; p++) h_kdist[p] = rtc_kdist{h_len[p], h_len[p], h_len[p], p};
+      for (uint32_t p = 0; p < n; p++) kd_out[p] = rtc_kdist{h_len[p], h_len[p], h_len[p], p};
     } else if (K.k <= TK_KMAX) {
       rtc_kdist* d_out = nullptr;
       RTC_TRY(db.get(ctx, n, &d_out));
       hipLaunchKernelGGL(kd_pick_kernel, dim3(blocks_for(n, ctx->num_cu)), dim3(256), 0, s, (const rtc_rep_hit*)K.d_hits, (const uint64_t*)K.d_koff,
                          d_len, n, K.k, d_out);
       RTC_CHECK_LAUNCH(ctx);
-      RTC_HIP(ctx, hipMemcpyAsync(h_kdist, d_out, (size_t)n * sizeof(rtc_kdist), hipMemcpyDeviceToHost, s));
+      RTC_HIP(ctx, hipMemcpyAsync(kd_out, d_out, (size_t)n * sizeof(rtc_kdist), hipMemcpyDeviceToHost, s));
       RTC_HIP(ctx, hipStreamSynchronize(s));
       db.release(d_out); db.release(K.d_hits); db.release(K.d_koff);
     } else {
       for (uint32_t p = 0; p < n; p++) {
         std::vector<TkRec>& v = K.host[p];
-        h_kdist[p] = rtc_kdist{0, h_len[p], 0, 0xffffffffu};
+        kd_out[p] = rtc_kdist{0, h_len[p], 0, 0xffffffffu};
         if (v.size() < K.k) continue;
         std::nth_element(v.begin(), v.begin() + (K.k - 1), v.end(), tk_beats_host);
         const TkRec& r = v[K.k - 1];
-        h_kdist[p] = rtc_kdist{r.common, h_len[p], h_len[r.slot], r.slot};
+        kd_out[p] = rtc_kdist{r.common, h_len[p], h_len[r.slot], r.slot};
       }
     }
     if (curve && width == 8)  // the brute force accepts two empty sketches at every eps: j = 1 among them, the lower index first
       for (uint32_t r = 0; r < n_empty; r++) {
         const uint64_t at = (uint64_t)K.k - 1 < r ? (uint64_t)K.k - 1 : K.k;  // the k-th of the empties without r
-        h_kdist[empties[r]] = rtc_kdist{0, 0, 0, at < n_empty ? empties[at] : 0xffffffffu};
+        kd_out[empties[r]] = rtc_kdist{0, 0, 0, at < n_empty ? empties[at] : 0xffffffffu};
       }
     kdist_ns += now_ns() - tk;
   }
   ctx->dbscan_sweep[8] = kdist_ns;
+  if (hq && h_kdist) memcpy(h_kdist, kd_out, (size_t)n * sizeof(rtc_kdist));
+
+  // ---- the hierarchy: weights, ranking and the forest on the device; the clique of empty u64 sketches is a star on the host ----
+  if (hq) {
+    HierStats hs;
+    RTC_TRY(hier_forest(ctx, db, who, (const rtc_cedge*)d_hkept, m_hkept, d_len, n, (const rtc_kdist*)kd_out, hq->h_forest, &hs));
+    db.release(d_hkept);
+    uint64_t nf = hs.n_forest;
+    if (width == 8 && n_empty >= 2 && kd_out[empties[0]].neighbour != 0xffffffffu) {
+      // every pair of empty sketches has m = 1: the order takes (e0, e1), (e0, e2), ... first, and those already span them
+      for (uint32_t r = 1; r < n_empty; r++) hq->h_forest[nf++] = rtc_hedge{empties[0], empties[r], 0, 0, 0};
+      std::sort(hq->h_forest, hq->h_forest + nf, HedgeBefore());
+    }
+    *hq->h_n_forest = nf;
+    ctx->dbscan_hier[3] = nf;
+    ctx->dbscan_hier[4] = hs.rounds;
+    ctx->dbscan_hier[6] = kdist_ns;
+    ctx->dbscan_hier[7] = hfilter_ns + hs.rank_ns;
+    ctx->dbscan_hier[8] = hs.forest_ns;
+    ctx->dbscan_hier[9] = now_ns() - t_begin;
+  }
   if (!n_eps) { ctx->dbscan_sweep[9] = now_ns() - t_begin; return RTC_OK; }
 
   // ---- core points, components, cluster numbers, border points: every level in one pass per step ----
@@ -480,7 +561,7 @@ extern "C" int rtc_dbscan_sweep(rtc_ctx* ctx, const void* d_hashes, int width, c
     RTC_HIP(ctx, hipStreamSynchronize(s));
     rounds++;
     active = *h_changed;
-    if (active && rounds > 256) return rtc_fail(ctx, RTC_ERR_HIP, "rtc_dbscan_sweep: components not settled after %llu rounds", (unsigned long long)rounds);
+    if (active && rounds > 256) return rtc_fail(ctx, RTC_ERR_HIP, "%s: components not settled after %llu rounds", who, (unsigned long long)rounds);
   }
   hipLaunchKernelGGL(sw_root_flags_kernel, gl, b, 0, s, (const uint32_t*)d_coremask, (const uint32_t*)d_parent, n, L, d_deg);
   RTC_CHECK_LAUNCH(ctx);
@@ -513,6 +594,41 @@ extern "C" int rtc_dbscan_sweep(rtc_ctx* ctx, const void* d_hashes, int width, c
   ctx->dbscan_sweep[4] = rounds;
   ctx->dbscan_sweep[7] = now_ns() - tc;
   ctx->dbscan_sweep[9] = now_ns() - t_begin;
+  return RTC_OK;
+}
+
+extern "C" int rtc_dbscan_sweep(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                                const double* h_eps, uint32_t n_eps, int min_pts, int kmer_size, int max_posting, int32_t* h_labels,
+                                uint8_t* h_core, uint32_t* h_n_clusters, uint32_t* h_n_noise, rtc_kdist* h_kdist) {
+  return sweep_impl(ctx, "rtc_dbscan_sweep", d_hashes, width, d_start, d_len, n, h_eps, n_eps, min_pts, kmer_size, max_posting, h_labels, h_core,
+                    h_n_clusters, h_n_noise, h_kdist, nullptr);
+}
+
+extern "C" int rtc_dbscan_sweep_hierarchy(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len,
+                                          uint32_t n, const double* h_eps, uint32_t n_eps, int min_pts, int kmer_size, int max_posting,
+                                          int32_t* h_labels, uint8_t* h_core_flags, uint32_t* h_n_clusters, uint32_t* h_n_noise,
+                                          rtc_kdist* h_kdist, double eps_max, rtc_hedge* h_forest, uint64_t* h_n_forest, rtc_kdist* h_core) {
+  const HierReq hq{eps_max, h_forest, h_n_forest, h_core};
+  return sweep_impl(ctx, "rtc_dbscan_sweep_hierarchy", d_hashes, width, d_start, d_len, n, h_eps, n_eps, min_pts, kmer_size, max_posting, h_labels,
+                    h_core_flags, h_n_clusters, h_n_noise, h_kdist, &hq);
+}
+
+extern "C" int rtc_dbscan_hierarchy(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                                    double eps_max, int min_pts, int kmer_size, int max_posting, rtc_hedge* h_forest, uint64_t* h_n_forest,
+                                    rtc_kdist* h_core) {
+  if (!ctx) return RTC_ERR_ARG;
+  uint64_t sweep[10];  // the last sweep's counters stay the last sweep's
+  memcpy(sweep, ctx->dbscan_sweep, sizeof sweep);
+  const HierReq hq{eps_max, h_forest, h_n_forest, h_core};
+  const int st = sweep_impl(ctx, "rtc_dbscan_hierarchy", d_hashes, width, d_start, d_len, n, nullptr, 0, min_pts, kmer_size, max_posting, nullptr,
+                            nullptr, nullptr, nullptr, nullptr, &hq);
+  memcpy(ctx->dbscan_sweep, sweep, sizeof sweep);
+  return st;
+}
+
+extern "C" int rtc_dbscan_hierarchy_counters(const rtc_ctx* ctx, uint64_t out[10]) {
+  if (!ctx || !out) return RTC_ERR_ARG;
+  for (int i = 0; i < 10; i++) out[i] = ctx->dbscan_hier[i];
   return RTC_OK;
 }
 

@@ -81,6 +81,7 @@ struct rtc_ctx {
   // [6] pair phase ns, [7] eps filter ns, [8] components + labels ns, [9] whole call ns
   uint64_t dbscan[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t dbscan_sweep[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_dbscan_sweep_counters (include/rtclust.h lists them)
+  uint64_t dbscan_hier[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // rtc_dbscan_hierarchy_counters (include/rtclust.h lists them)
   int host_threads = 1;     // rtc_ctx_set_host_threads: the host side of rtc_tree_medoids
   // rtc_diag_counters: [0] pair tiles the join took, [1] tiled-kernel tiles, [2] merge-kernel tiles, [3] candidate lists contracted
   // to their forest, [4] greedy runs replayed from ONE global join, [5] greedy query blocks of the block loop, [6] estimates handed

@@ -867,6 +867,9 @@ struct Options {
   int dbscanMinPts = 5, maxPosting = 0;
   vector<double> epsSweep;  // clust-dbscan --eps-sweep: further eps values served by the pair phase of --eps (rtc_dbscan_sweep)
   bool kdist = false;       // clust-dbscan --kdist: the k-distance curve, k = minPts - 1
+  bool hierarchy = false;   // clust-dbscan --hierarchy: the density hierarchy below --eps (rtc_dbscan_hierarchy) and its flat clustering
+  bool hasMinClusterSize = false;
+  int minClusterSize = 0;   // --min-cluster-size (default: --minpts)
 };
 
 static void unsupported(const char* what) {
@@ -901,6 +904,8 @@ static Options parse(int argc, char** argv) {
       continue;
     }
     if (a == "--kdist") { o.kdist = true; continue; }
+    if (a == "--hierarchy") { o.hierarchy = true; continue; }
+    if (a == "--min-cluster-size") { o.minClusterSize = atoi(need(i)); o.hasMinClusterSize = true; continue; }
     if (a == "--knn") unsupported("--knn (approximate k-NN DBSCAN)");
     if (a == "--db" || a == "--build" || a == "--query" || a == "--assign" || a == "--stats" || a == "--top-k" || a == "--dense" ||
         a == "--premsted" || a == "--auto-threshold" || a == "--stability" || a == "--dedup-dist" || a == "--reps-per-cluster" ||
@@ -963,6 +968,8 @@ static Options parse(int argc, char** argv) {
            "  --eps X (default 0.05)  --minpts N (default 5)  --max-posting M (0: off)\n"
            "  --eps-sweep e1,e2,.. (at most 32 further eps values from the same pair phase: FILE.eps_<value>, FILE.eps_sweep.tsv)\n"
            "  --kdist (FILE.kdist.tsv: every genome's distance to its (minpts - 1)-th nearest candidate, largest first)\n"
+           "  --hierarchy (the density hierarchy of every eps up to --eps from the same pair phase: FILE.hierarchy.tsv, FILE.core.tsv,\n"
+           "               and FILE.hdbscan, a flat clustering that needs no eps)  --min-cluster-size M (default: --minpts, >= 2)\n"
            "  -c,--containment N (KSSD tuner)  -s,--sketch-size N  --save-rep (accepted, no effect on DBSCAN)  --knn: not in this build");
       exit(0);
 #else
@@ -2027,7 +2034,7 @@ static void dbscan_report(const vector<int32_t>& labels, const vector<uint8_t>& 
 // beside an empty file name, without -l an empty seqInfo gives empty names.  The lengths it prints there are whatever the
 // unloaded field holds; this prints 0.
 static void print_dbscan_result(const vector<int32_t>& labels, uint32_t ncl, const vector<GenomeInfo>& g, bool sketchByFile, bool mismatch,
-                                const string& outputFile, double eps, int minPts) {
+                                const string& outputFile, double eps, int minPts, int minClusterSize = 0) {
   FILE* fp = fopen(outputFile.c_str(), "w");
   if (!fp) { cerr << "Error in printKssdDBSCANResult(), cannot open file: " << outputFile << endl; exit(1); }
   vector<vector<int>> clusters(ncl);
@@ -2036,7 +2043,9 @@ static void print_dbscan_result(const vector<int32_t>& labels, uint32_t ncl, con
     if (labels[i] < 0) noise.push_back((int)i);
     else clusters[labels[i]].push_back((int)i);
   }
-  fprintf(fp, "# DBSCAN clustering parameters: eps=%.6f, minPts=%d\n", eps, minPts);
+  // minClusterSize > 0: the flat clustering of --hierarchy (rtc_hierarchy_flat), eps the ceiling the hierarchy was built under
+  if (minClusterSize > 0) fprintf(fp, "# HDBSCAN* flat clustering parameters: min_cluster_size=%d, minPts=%d, eps_max=%.6f\n", minClusterSize, minPts, eps);
+  else fprintf(fp, "# DBSCAN clustering parameters: eps=%.6f, minPts=%d\n", eps, minPts);
   fprintf(fp, "# Total clusters: %d\n", (int)ncl);
   if (!noise.empty()) fprintf(fp, "# Total noise points (outliers): %d\n", (int)noise.size());
   fprintf(fp, "#\n");
@@ -2129,6 +2138,13 @@ int main(int argc, char** argv) {
   if (o.has_append && !o.has_presketched && o.repdb_path.empty()) { cerr << "ERROR option --append, option --presketched needed" << endl; return 1; }  // src/main.cpp:378-381
 #endif
 #ifdef DBSCAN_CLUST
+  // ---- clust-dbscan --hierarchy: this build's own flags, checked before anything of the reference's ----
+  if (o.hasMinClusterSize && !o.hierarchy) { cerr << "ERROR: --min-cluster-size needs --hierarchy" << endl; return 1; }
+  if (o.hierarchy && !o.hasMinClusterSize) o.minClusterSize = o.dbscanMinPts;
+  if (o.hierarchy && o.minClusterSize < 2) {
+    cerr << "ERROR: --min-cluster-size must be >= 2, got " << o.minClusterSize << (o.hasMinClusterSize ? "" : " (from --minpts)") << endl;
+    return 1;
+  }
   // ---- clust-dbscan: the checks of src/main.cpp:478-517, in that order ----
   if (!o.is_fast) { cerr << "ERROR: clust-dbscan requires --fast option" << endl; return 1; }
   cerr << "-----Using DBSCAN clustering" << endl;
@@ -2494,7 +2510,10 @@ int main(int argc, char** argv) {
   vector<int32_t> labels(genomes.size());
   vector<uint8_t> core(genomes.size());
   uint32_t ncl = 0, nnoise = 0;
-  if (o.epsSweep.empty() && !o.kdist) {
+  vector<rtc_hedge> forest(o.hierarchy ? genomes.size() : 0);  // --hierarchy: n - 1 slots, the core triples beside them
+  vector<rtc_kdist> hcore(o.hierarchy ? genomes.size() : 0);
+  uint64_t n_forest = 0;
+  if (o.epsSweep.empty() && !o.kdist && !o.hierarchy) {
     CHECK(ctx, rtc_dbscan(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, o.dbscanEps, o.dbscanMinPts, kmer_size, o.maxPosting,
                           labels.data(), core.data(), &ncl, &nnoise));
   } else {
@@ -2510,8 +2529,25 @@ int main(int argc, char** argv) {
     vector<uint8_t> all_core(L * n);
     vector<uint32_t> all_ncl(L), all_nnoise(L);
     vector<rtc_kdist> kd(o.kdist ? n : 0);
-    CHECK(ctx, rtc_dbscan_sweep(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, levels.data(), (uint32_t)L, o.dbscanMinPts, kmer_size,
-                                o.maxPosting, all_labels.data(), all_core.data(), all_ncl.data(), all_nnoise.data(), o.kdist ? kd.data() : nullptr));
+    if (o.hierarchy) {  // the hierarchy below --eps from the sweep's pair phase
+      CHECK(ctx, rtc_dbscan_sweep_hierarchy(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, levels.data(), (uint32_t)L, o.dbscanMinPts,
+                                            kmer_size, o.maxPosting, all_labels.data(), all_core.data(), all_ncl.data(), all_nnoise.data(),
+                                            o.kdist ? kd.data() : nullptr, o.dbscanEps, forest.data(), &n_forest, hcore.data()));
+      uint64_t hc[10] = {0};
+      rtc_dbscan_hierarchy_counters(ctx, hc);
+      if (getenv("RTC_VERBOSE"))
+        fprintf(stderr, "[hierarchy] %llu candidate edges in %llu chunk(s), %llu kept at eps %g, %llu forest edges in %llu round(s); pair %.3f ms, "
+                "k-distance %.3f ms, weights and ranking %.3f ms, forest %.3f ms\n", (unsigned long long)hc[1], (unsigned long long)hc[0],
+                (unsigned long long)hc[2], o.dbscanEps, (unsigned long long)hc[3], (unsigned long long)hc[4], hc[5] / 1e6, hc[6] / 1e6, hc[7] / 1e6,
+                hc[8] / 1e6);
+      g_metrics.num("dbscan_hierarchy_pair_s", hc[5] / 1e9);
+      g_metrics.num("dbscan_hierarchy_kdist_s", hc[6] / 1e9);
+      g_metrics.num("dbscan_hierarchy_forest_s", (hc[7] + hc[8]) / 1e9);
+      g_metrics.num("dbscan_hierarchy_edges", (double)hc[3]);
+    } else {
+      CHECK(ctx, rtc_dbscan_sweep(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, levels.data(), (uint32_t)L, o.dbscanMinPts, kmer_size,
+                                  o.maxPosting, all_labels.data(), all_core.data(), all_ncl.data(), all_nnoise.data(), o.kdist ? kd.data() : nullptr));
+    }
     uint64_t sc[10] = {0};
     rtc_dbscan_sweep_counters(ctx, sc);
     if (getenv("RTC_VERBOSE"))
@@ -2579,6 +2615,41 @@ int main(int argc, char** argv) {
       fclose(fp);
       cerr << "-----write the k-distance curve (k=" << o.dbscanMinPts - 1 << ") into: " << tsv << endl;
     }
+  }
+  if (o.hierarchy) {
+    const size_t n = genomes.size();
+    auto dist_of = [&](uint32_t common, uint32_t a, uint32_t b) {
+      const uint64_t denom = (uint64_t)a + b - common;
+      if (denom == common) return 0.0;  // m = 1, two empty u64 sketches included
+      const double j = (double)common / (double)denom;
+      return -log(2.0 * j / (1.0 + j)) / kmer_size;
+    };
+    const string htsv = o.outputFile + ".hierarchy.tsv", ctsv = o.outputFile + ".core.tsv", flat = o.outputFile + ".hdbscan";
+    FILE* fp = fopen(htsv.c_str(), "w");
+    if (!fp) { cerr << "ERROR: cannot open file: " << htsv << endl; return 1; }
+    fprintf(fp, "p\tq\tdistance\tcommon\tsize_p\tsize_q\n");
+    for (uint64_t e = 0; e < n_forest; e++) {  // the forest's order: the smallest distance first
+      const rtc_hedge& h = forest[e];
+      fprintf(fp, "%u\t%u\t%.6f\t%u\t%u\t%u\n", h.p, h.q, dist_of(h.common, h.size_p, h.size_q), h.common, h.size_p, h.size_q);
+    }
+    fclose(fp);
+    fp = fopen(ctsv.c_str(), "w");
+    if (!fp) { cerr << "ERROR: cannot open file: " << ctsv << endl; return 1; }
+    fprintf(fp, "index\tcore_distance\n");
+    for (size_t v = 0; v < n; v++) {
+      if (hcore[v].neighbour == UINT32_MAX) fprintf(fp, "%zu\tinf\n", v);
+      else fprintf(fp, "%zu\t%.6f\n", v, dist_of(hcore[v].common, hcore[v].size_p, hcore[v].size_q));
+    }
+    fclose(fp);
+    vector<int32_t> flat_labels(n);
+    uint32_t flat_ncl = 0;
+    const int st = rtc_hierarchy_flat((uint32_t)n, forest.data(), n_forest, hcore.data(), kmer_size, o.minClusterSize, flat_labels.data(), nullptr,
+                                      &flat_ncl);
+    if (st != RTC_OK) { cerr << "ERROR: rtc_hierarchy_flat failed with status " << st << endl; return 1; }
+    print_dbscan_result(flat_labels, flat_ncl, genomes, sketchByFile, dbscan_format_mismatch, flat, o.dbscanEps, o.dbscanMinPts, o.minClusterSize);
+    cerr << "-----write the hierarchy (" << n_forest << " edges) into: " << htsv << endl;
+    cerr << "-----write the core distances into: " << ctsv << endl;
+    cerr << "-----write the flat clustering (min_cluster_size=" << o.minClusterSize << ", " << flat_ncl << " clusters) into: " << flat << endl;
   }
   dbscan_report(labels, core, ncl, nnoise);
   print_dbscan_result(labels, ncl, genomes, sketchByFile, dbscan_format_mismatch, o.outputFile, o.dbscanEps, o.dbscanMinPts);

@@ -2,10 +2,12 @@
 of the DBSCAN call into the pair phase, the eps filter and the components from rtc_dbscan_counters.
 
     python tools/run_dbscan.py [--sets dense25k,cfg4_200k] [--eps 0.05] [--minpts 5] [--repeat 3] [--sweep e1,e2,...] [--kdist]
+                               [--hierarchy]
 
 --sweep times one Context.dbscan_sweep over the listed eps values (best of --repeat warm calls) against the same values run as
 separate Context.dbscan calls (the sum of each value's best warm call), with the sweep's phases from rtc_dbscan_sweep_counters;
---kdist adds the k-distance curve to the sweep.  --separate-only times the separate calls alone (a library without the sweep).
+--kdist adds the k-distance curve to the sweep.  --hierarchy (with --sweep) times Context.dbscan_hierarchy at the largest listed
+eps, its calls alternating with the sweep's, with its phases from rtc_dbscan_hierarchy_counters.  --separate-only times the separate calls alone (a library without the sweep).
 
 Sets (KSSD u32 sketches from synthetic genomes, k 21, drlevel 3, sketched on the GPU as bench.py does):
   dense25k   25 000 x 2 Mbp genomes in 25 families of 1 000 (substitution rate <= 0.01): bench.py's dense u32_25000 set, the
@@ -82,12 +84,19 @@ def _sweep_row(ctx, sk, name, n, kmer, eps_list, a):
     if a.separate_only:
         return row
     ctx.dbscan_sweep(sk, eps_list, a.minpts, kmer, kdist=a.kdist)
-    ts, cs = [], []
-    for _ in range(a.repeat):
+    if a.hierarchy:
+        ctx.dbscan_hierarchy(sk, max(eps_list), a.minpts, kmer)
+    ts, cs, hts, hcs = [], [], [], []
+    for _ in range(a.repeat):  # the two calls alternate, so drift of the machine falls on both
         t0 = time.perf_counter()
         out = ctx.dbscan_sweep(sk, eps_list, a.minpts, kmer, kdist=a.kdist)
         ts.append(time.perf_counter() - t0)
         cs.append(ctx.dbscan_sweep_counters())
+        if a.hierarchy:
+            t0 = time.perf_counter()
+            forest, _ = ctx.dbscan_hierarchy(sk, max(eps_list), a.minpts, kmer)
+            hts.append(time.perf_counter() - t0)
+            hcs.append(ctx.dbscan_hierarchy_counters())
     labels = out[0] if a.kdist else out
     c = cs[int(np.argmin(ts))]
     row.update({"sweep_ms": round(min(ts) * 1e3, 3), "sweep_all_ms": [round(x * 1e3, 3) for x in ts], "kdist": bool(a.kdist),
@@ -97,6 +106,13 @@ def _sweep_row(ctx, sk, name, n, kmer, eps_list, a):
                 "library_ms": round(c["total_ns"] / 1e6, 3), "chunks": c["chunks"], "candidate_edges": c["candidate_edges"],
                 "kept_edges": c["kept_edges"], "hook_rounds": c["hook_rounds"],
                 "clusters": [int(x.max(initial=-1)) + 1 for x in labels]})
+    if a.hierarchy:
+        h = hcs[int(np.argmin(hts))]
+        row["hierarchy"] = {"eps_max": max(eps_list), "ms": round(min(hts) * 1e3, 3), "all_ms": [round(x * 1e3, 3) for x in hts],
+                            "pair_ms": round(h["pair_ns"] / 1e6, 3), "kdist_ms": round(h["kdist_ns"] / 1e6, 3),
+                            "rank_ms": round(h["rank_ns"] / 1e6, 3), "forest_ms": round(h["forest_ns"] / 1e6, 3),
+                            "library_ms": round(h["total_ns"] / 1e6, 3), "kept_edges": h["kept_edges"], "forest_edges": len(forest),
+                            "boruvka_rounds": h["boruvka_rounds"]}
     return row
 
 
@@ -110,6 +126,7 @@ def main():
     ap.add_argument("--sweep", default="")
     ap.add_argument("--kdist", action="store_true")
     ap.add_argument("--separate-only", action="store_true")
+    ap.add_argument("--hierarchy", action="store_true")
     a = ap.parse_args()
     import torch
     from rabbittclust_amd import api
