@@ -1,6 +1,7 @@
-// rtc_dbscan_common.h -- what rtc_dbscan.hip and rtc_dbscan_sweep.hip share: the neighbour predicate, the --max-posting
-// pruning, the scratch holder and the row-chunk loop of the pair phase.  Both units are built with -ffp-contract=off, so the
-// predicate gives the same bits in both.
+// rtc_dbscan_common.h -- the parts of the one DBSCAN implementation (rtc_dbscan_sweep.hip, with rtc_dbscan_hier.h) that do not
+// depend on what a call asks for: the neighbour predicate and its refusals, the filter kernels' predicate block and wave
+// append, the growing device list a filter appends to, the --max-posting pruning, the scratch holder and the row-chunk loop of
+// the pair phase.  Every unit that evaluates eps_pred is built with -ffp-contract=off.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -32,6 +33,56 @@ __host__ __device__ __forceinline__ bool eps_pred(uint32_t a, uint32_t b, uint32
   const double lhs = (double)common * one_plus_t;
   const double rhs = t_times_a + t * db;
   return !(lhs + 1e-12 < rhs);
+}
+
+// x and t of an eps on the host with libm (:751-752).  Outside t > 1e-12 (false) the reference's relation is not the one the
+// closed form needs: pairs without a common hash pass the test (the u64 brute force lists them, the u32 index never sees them).
+inline bool eps_to_t(double eps, int kmer_size, double* t, double* one_plus_t) {
+  const double x = exp(-eps * kmer_size);
+  *t = x / (2.0 - x);
+  *one_plus_t = 1.0 + *t;
+  return *t > 1e-12;
+}
+// u32 sketches: a size bound ceil(a / t) past INT_MAX is an undefined int conversion in the reference (:514)
+inline bool u32_size_bound_fits(uint32_t max_len, double t) { return !(ceil((double)max_len / t) > 2147483647.0); }
+
+// ---- what the filter kernels share ----
+constexpr uint32_t DB_MAX_LEVELS = 32;
+struct EpsLevels { double t[DB_MAX_LEVELS], one_plus_t[DB_MAX_LEVELS]; };
+
+// The predicate block: the levels (one bit each) at which candidate c passes in both orientations, the levels not assumed to
+// be nested; *common is the count the predicate sees, MarkCnt's u16 count for u32 sketches (:75-80, :496-506; sat = ~0u for u64).
+// cnt[1]: pairs whose orientations disagree at some level, cnt[2]: the smallest such pair (i << 32 | j), cnt[3]: those levels.
+__device__ __forceinline__ uint32_t eps_level_mask(const rtc_cedge& c, const uint32_t* __restrict__ len, const EpsLevels& lv, uint32_t n_lv,
+                                                   uint32_t sat, uint32_t* common, unsigned long long* __restrict__ cnt) {
+  *common = c.common < sat ? c.common : sat;
+  const uint32_t a = len[c.i], b = len[c.j];
+  uint32_t mask = 0, asym = 0;
+  for (uint32_t l = 0; l < n_lv; l++) {
+    const bool fwd = eps_pred(a, b, *common, lv.t[l], lv.one_plus_t[l]), bwd = eps_pred(b, a, *common, lv.t[l], lv.one_plus_t[l]);
+    if (fwd != bwd) asym |= 1u << l;
+    if (fwd && bwd) mask |= 1u << l;
+  }
+  if (asym) {
+    atomicAdd(&cnt[1], 1ull);
+    atomicMin(&cnt[2], ((unsigned long long)c.i << 32) | c.j);
+    atomicOr(&cnt[3], (unsigned long long)asym);
+  }
+  return mask;
+}
+// The wave append: the lanes with `keep` take consecutive slots of a list behind *counter (one ballot, one atomic per wave, a
+// prefix popcount per lane) and store their record where the slot lies below cap; the counter runs on past it, which the
+// host sees.  Every lane of the wave calls it.
+template <class T>
+__device__ __forceinline__ void wave_append(bool keep, const T& rec, T* __restrict__ list, uint64_t cap, unsigned long long* __restrict__ counter) {
+  const uint64_t bal = __ballot(keep);
+  if (!bal) return;
+  const uint32_t lane = threadIdx.x & 63;
+  unsigned long long at = 0;
+  if (lane == 0) at = atomicAdd(counter, (unsigned long long)__popcll(bal));
+  at = __shfl(at, 0);
+  const uint64_t idx = at + (uint64_t)__popcll(bal & ((1ULL << lane) - 1ULL));
+  if (keep && idx < cap) list[idx] = rec;
 }
 
 // ---- --max-posting ----
@@ -92,6 +143,52 @@ struct DevBuf {  // hipMalloc'd scratch released on every way out
     for (auto& x : p) if (x == q) { (void)hipFree(x); x = nullptr; }
   }
 };
+
+// A device list of pairs that a filter kernel appends to chunk by chunk, and what the filter has found so far
+struct KeptList {
+  rtc_cedge* d = nullptr;
+  uint64_t cap = 0, used = 0, asym = 0, first_asym = ~0ull, asym_levels = 0, ns = 0;
+};
+using FilterKernel = void (*)(const rtc_cedge*, uint64_t, const uint32_t*, EpsLevels, uint32_t, uint32_t, rtc_cedge*, uint64_t, unsigned long long*);
+
+// One chunk of candidates through `filter` into the list.  The list is grown first to hold used + the whole chunk (at most
+// every candidate is kept), so the kernel never runs past it and runs once: doubled while that covers the need, so many row
+// chunks move the list a few times, and the exact size where the doubled list is too small or does not fit.  d_fc: the four
+// device counters of eps_level_mask and wave_append.
+int filter_chunk(rtc_ctx* ctx, DevBuf& db, const char* who, FilterKernel filter, const rtc_cedge* d_cand, uint64_t m,
+                 const uint32_t* d_len, const EpsLevels& lv, uint32_t n_lv, uint32_t sat, unsigned long long* d_fc, KeptList* L) {
+  hipStream_t s = ctx->stream;
+  const uint64_t t0 = now_ns();
+  const uint64_t need = L->used + m;
+  if (need > L->cap) {
+    auto regrow = [&](uint64_t want) -> int {
+      rtc_cedge* nd = nullptr;
+      RTC_TRY(db.get(ctx, want, &nd));
+      if (L->used) RTC_HIP(ctx, hipMemcpyAsync(nd, L->d, L->used * sizeof(rtc_cedge), hipMemcpyDeviceToDevice, s));
+      RTC_HIP(ctx, hipStreamSynchronize(s));
+      db.release(L->d);
+      L->d = nd; L->cap = want;
+      return RTC_OK;
+    };
+    if (2 * L->cap <= need || regrow(2 * L->cap) != RTC_OK) {
+      (void)hipGetLastError();  // a doubled list that did not fit is no failure yet: the exact size may
+      RTC_TRY(regrow(need));
+    }
+  }
+  unsigned long long fc[4] = {(unsigned long long)L->used, 0ull, ~0ull, 0ull};
+  RTC_HIP(ctx, hipMemcpyAsync(d_fc, fc, sizeof fc, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(filter, dim3(blocks_for(m, ctx->num_cu)), dim3(256), 0, s, d_cand, m, d_len, lv, n_lv, sat, L->d, L->cap, d_fc);
+  RTC_CHECK_LAUNCH(ctx);
+  RTC_HIP(ctx, hipMemcpyAsync(fc, d_fc, sizeof fc, hipMemcpyDeviceToHost, s));
+  RTC_HIP(ctx, hipStreamSynchronize(s));
+  if (fc[0] > L->cap) return rtc_fail(ctx, RTC_ERR_OVERFLOW, "%s: %llu pairs kept, room for %llu", who, fc[0], (unsigned long long)L->cap);
+  L->used = fc[0];
+  L->asym += fc[1];
+  L->first_asym = std::min<uint64_t>(L->first_asym, fc[2]);
+  L->asym_levels |= fc[3];
+  L->ns += now_ns() - t0;
+  return RTC_OK;
+}
 
 // The pruned copy of a u32 sketch set (buildInvertedIndexCSR32 with max_posting > 0): all hashes gathered with their positions,
 // sorted (rtc_sort_u32_pairs), every run of one hash measured against M, the kept hashes compacted in their original order.

@@ -35,11 +35,11 @@ struct HedgeBefore {
   }
 };
 
-// cnt[0]: pairs kept (u64), cnt[1]: pairs whose orientations disagree, cnt[2]: the smallest such pair (i << 32 | j)
+// The filter of the hierarchy's one level (lv level 0, n_lv = 1): eps_mask_kernel's predicate block and append, but the record
+// is (p < q, the count the predicate saw), which the forest's weights need.  cnt: as eps_mask_kernel's.
 __global__ __launch_bounds__(256) void hier_filter_kernel(const rtc_cedge* __restrict__ cand, uint64_t m, const uint32_t* __restrict__ len,
-                                                          double t, double one_plus_t, uint32_t sat, rtc_cedge* __restrict__ kept,
+                                                          EpsLevels lv, uint32_t n_lv, uint32_t sat, rtc_cedge* __restrict__ kept,
                                                           uint64_t cap, unsigned long long* __restrict__ cnt) {
-  const uint32_t lane = threadIdx.x & 63;
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < m; base += stride) {  // uniform per wave
     const uint64_t e = base + threadIdx.x;
@@ -47,24 +47,11 @@ __global__ __launch_bounds__(256) void hier_filter_kernel(const rtc_cedge* __res
     rtc_cedge c{0, 0, 0};
     if (e < m) {
       c = cand[e];
-      const uint32_t common = c.common < sat ? c.common : sat;
-      const uint32_t a = len[c.i], b = len[c.j];
-      const bool fwd = eps_pred(a, b, common, t, one_plus_t), bwd = eps_pred(b, a, common, t, one_plus_t);
-      if (fwd != bwd) {
-        atomicAdd(&cnt[1], 1ull);
-        atomicMin(&cnt[2], ((unsigned long long)c.i << 32) | c.j);
-      }
-      keep = fwd && bwd;
+      uint32_t common;
+      keep = eps_level_mask(c, len, lv, n_lv, sat, &common, cnt) != 0;
       c = rtc_cedge{c.i < c.j ? c.i : c.j, c.i < c.j ? c.j : c.i, common};
     }
-    const uint64_t bal = __ballot(keep);
-    if (bal) {
-      unsigned long long at = 0;
-      if (lane == 0) at = atomicAdd(&cnt[0], (unsigned long long)__popcll(bal));
-      at = __shfl(at, 0);
-      const uint64_t idx = at + (uint64_t)__popcll(bal & ((1ULL << lane) - 1ULL));
-      if (keep && idx < cap) kept[idx] = c;
-    }
+    wave_append(keep, c, kept, cap, &cnt[0]);
   }
 }
 
@@ -72,7 +59,6 @@ __global__ __launch_bounds__(256) void hier_filter_kernel(const rtc_cedge* __res
 __global__ __launch_bounds__(256) void hier_weight_kernel(const rtc_cedge* __restrict__ kept, uint64_t m, const uint32_t* __restrict__ len,
                                                           const rtc_kdist* __restrict__ core, rtc_hedge* __restrict__ out,
                                                           unsigned long long* __restrict__ cnt) {
-  const uint32_t lane = threadIdx.x & 63;
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < m; base += stride) {  // uniform per wave
     const uint64_t e = base + threadIdx.x;
@@ -88,14 +74,7 @@ __global__ __launch_bounds__(256) void hier_weight_kernel(const rtc_cedge* __res
       if (keep && hj_less(cp.common, dp, h.common, d)) { h.common = cp.common; h.size_p = cp.size_p; h.size_q = cp.size_q; d = dp; }
       if (keep && hj_less(cq.common, dq, h.common, d)) { h.common = cq.common; h.size_p = cq.size_p; h.size_q = cq.size_q; }
     }
-    const uint64_t bal = __ballot(keep);
-    if (bal) {
-      unsigned long long at = 0;
-      if (lane == 0) at = atomicAdd(&cnt[0], (unsigned long long)__popcll(bal));
-      at = __shfl(at, 0);
-      const uint64_t idx = at + (uint64_t)__popcll(bal & ((1ULL << lane) - 1ULL));
-      if (keep && idx < m) out[idx] = h;
-    }
+    wave_append(keep, h, out, m, &cnt[0]);
   }
 }
 

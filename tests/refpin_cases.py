@@ -254,7 +254,7 @@ def case_key(case):
 
 
 def u32_bound_exceeded(sketches, eps, k):
-    """the kernels' refusal (rtc_dbscan.hip): a u32 set whose largest ceil(size / t) is past INT_MAX"""
+    """the kernels' refusal (rtc_dbscan_common.h): a u32 set whose largest ceil(size / t) is past INT_MAX"""
     t = jaccard_min(eps, k)
     return (not use64_of(sketches)) and math.ceil(max(len(s) for s in sketches) / t) > INT_MAX
 

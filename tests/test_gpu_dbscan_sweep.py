@@ -112,6 +112,36 @@ def test_sets_with_empty_sketches(ctx, width):
         assert all((lab3[e][empty] == -1).all() for e in range(len(S.EPS)))
 
 
+@pytest.mark.parametrize("width", [4, 8])
+def test_each_call_fills_its_own_counters_and_no_others(ctx, width):
+    """dbscan, dbscan_sweep and dbscan_hierarchy run one implementation and keep three counter sets: a call fills its own and
+    leaves the other two exactly as they were, times included (width 8: with the clique of empty sketches in play)"""
+    host = S.family_sets(3, width == 8, n_empty=3)
+    sk = _set(ctx, host, width)
+    eps, min_pts = 0.04, 3
+    sets = {"dbscan": ctx.dbscan_counters, "sweep": ctx.dbscan_sweep_counters, "hierarchy": ctx.dbscan_hierarchy_counters}
+
+    def others_untouched(own, call):
+        before = {k: f() for k, f in sets.items() if k != own}
+        out = call()
+        assert {k: f() for k, f in sets.items() if k != own} == before, own
+        return out, sets[own]()
+
+    (lab, core), first = others_untouched("dbscan", lambda: ctx.dbscan(sk, eps, min_pts, S.KMER, return_core=True))
+    _, sweep = others_untouched("sweep", lambda: ctx.dbscan_sweep(sk, S.EPS, min_pts, S.KMER))
+    (forest, _), hier = others_untouched("hierarchy", lambda: ctx.dbscan_hierarchy(sk, max(S.EPS), min_pts, S.KMER))
+    (lab2, core2), second = others_untouched("dbscan", lambda: ctx.dbscan(sk, eps, min_pts, S.KMER, return_core=True))
+    assert np.array_equal(lab, lab2) and np.array_equal(core, core2)
+    assert {k: v for k, v in first.items() if not k.endswith("_ns")} == {k: v for k, v in second.items() if not k.endswith("_ns")}
+    assert sweep["levels"] == len(S.EPS) and sweep["chunks"] == first["chunks"] == hier["chunks"] >= 1
+    assert sweep["candidate_edges"] == first["candidate_edges"] == hier["candidate_edges"] > 0
+    assert hier["forest_edges"] == len(forest) > 0
+    ctx.dbscan_sweep(sk, [eps], min_pts, S.KMER)
+    assert first["eps_edges"] == ctx.dbscan_sweep_counters()["kept_edges"] > 0
+    assert first["core_points"] == int(core.sum()) > 0 and first["asymmetric_pairs"] == 0 and first["hook_rounds"] >= 1
+    assert all(first[k] > 0 for k in first if k.endswith("_ns"))
+
+
 def test_one_unsupported_level_fails_the_sweep_and_names_its_eps(ctx):
     from rabbittclust_amd import api
     host = S.family_sets(2, False)
@@ -121,6 +151,8 @@ def test_one_unsupported_level_fails_the_sweep_and_names_its_eps(ctx):
     with pytest.raises(api.RtcError) as single:
         ctx.dbscan(sk, bad, 5, S.KMER)
     assert single.value.status == api._lib.RTC_ERR_UNSUPPORTED
+    msg = str(single.value).split(": ", 1)[1]  # the single call names itself and no place in a list
+    assert msg.startswith("rtc_dbscan: eps 1.5 with k %d gives jaccard_min " % S.KMER) and "of the list" not in msg
     for width in (4, 8):
         s = _set(ctx, S.family_sets(2, width == 8), width)
         with pytest.raises(api.RtcError) as ei:

@@ -178,6 +178,8 @@ def test_refusals_past_the_u32_size_bound(ctx):
     with pytest.raises(api.RtcError) as ei:
         ctx.dbscan(sk32, 0.9, 2, P.KMER)
     assert ei.value.status == api._lib.RTC_ERR_UNSUPPORTED and "past INT_MAX" in str(ei.value)
+    msg = str(ei.value).split(": ", 1)[1]  # the single call names itself and no place in a list
+    assert msg.startswith("rtc_dbscan: size bound ceil(") and "of the list" not in msg
     with pytest.raises(api.RtcError) as ei:
         ctx.dbscan_sweep(sk32, [0.05, 0.9], 2, P.KMER)
     assert ei.value.status == api._lib.RTC_ERR_UNSUPPORTED and "past INT_MAX" in str(ei.value)
