@@ -1,7 +1,8 @@
 // rtc_minhash_core.h -- what the two MinHash sketch translation units share (rtc_sketch_minhash.hip: ASCII input,
 // rtc_sketch_minhash_packed.hip: the 2-bit staging format): the MurmurHash3 evaluation from LDS product tables, the
-// in-LDS bottom-s merge, the partial-sketch merge kernel and the host-side segment plan.  Everything lives in an
-// anonymous namespace: each unit gets its own copy.
+// in-LDS bottom-s merge, the candidate path of the sketch kernels (workgroup state, pass gate, queue, express hand-off,
+// window cut, the four-k-mer step, tile and kernel end), the partial-sketch merge kernel, kernel selection and the
+// host-side segment plan.  A unit adds what its input format needs: loads, decode, the express loop, validity.  Everything lives in an anonymous namespace: each unit compiles its own copy of this one text.
 #pragma once
 #include <algorithm>
 
@@ -542,6 +543,338 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t v) {
   return ((uint64_t)uniform32((uint32_t)(v >> 32)) << 32) | uniform32((uint32_t)v);
 }
 
+// ---- the candidate path of the two sketch kernels ------------------------------------------------
+// What a workgroup does with its k-mers once an input format has produced them: test, queue, append, merge, write
+// out.  Loading, decoding, the express loop's shape and rolls and the validity bookkeeping are each unit's.
+
+// LDS of one workgroup: [hash tables | candidate buffer (cap x u64) | Ctrl | NWAVE candidate queues]
+struct WgState {
+  lds_byte_ptr lut;    // at LDS offset 0: table offsets become ds_read immediates
+  lds_u64_ptr buf;
+  lds_ctrl_ptr ctrl;
+  lds_u64_ptr wq;      // this wave's candidate queue: QCAP x {f1, f2}
+  int cap;
+  uint32_t s;          // hashes to select
+  uint32_t room;       // cap - s, >= MIN_ROOM by construction
+  uint32_t lane;
+  int t;
+};
+__device__ __forceinline__ WgState carve_lds(unsigned char* smem, int k, bool pk, int cap, uint32_t s) {
+  const lds_byte_ptr lds0 = (lds_byte_ptr)smem;
+  // kmer_loads addresses the tables by absolute LDS address; the kernels have no static LDS, so the
+  // dynamic allocation starts at 0 -- trap rather than hash with wrong tables if that ever changes
+  if ((uint32_t)(uintptr_t)lds0 != 0u) __builtin_trap();
+  WgState W;
+  W.lut = lds0;
+  W.buf = (lds_u64_ptr)(lds0 + lut_bytes(k, pk));
+  W.ctrl = (lds_ctrl_ptr)(lds0 + lut_bytes(k, pk) + (size_t)cap * 8);
+  W.wq = (lds_u64_ptr)(lds0 + lut_bytes(k, pk) + (size_t)cap * 8 + ((sizeof(Ctrl) + 15) & ~(size_t)15)) +
+         (size_t)(threadIdx.x >> 6) * QCAP * 2;
+  W.cap = cap;
+  W.s = s;
+  W.room = (uint32_t)cap - s;
+  W.t = threadIdx.x;
+  W.lane = threadIdx.x & 63;
+  return W;
+}
+
+// Has this workgroup anything to do in this launch?  (workgroup-uniform)  Sets lo1.
+// The second launch over the partial segments walks only the genomes whose merged partial sketches came out short of
+// s under the starting threshold (flagged by merge_partials_kernel), from "everything passes".
+// Sketch sizes beyond one LDS buffer are selected in passes of ascending hash ranges: pass p only
+// admits hashes above the largest one kept so far (lo1 = that hash + 1; 0 in the first pass).
+__device__ __forceinline__ bool pass_gate(const Segment& sg, int pass_no, const uint32_t* __restrict__ redo, const uint32_t* cnt,
+                                          const uint64_t* out, uint32_t* pcnt, uint64_t& lo1) {
+  lo1 = 0;
+  if (redo && redo[sg.final_slot] == 0) return false;
+  if (pass_no > 0) {
+    const bool live = cnt[sg.final_slot] == sg.expect;  // genome not exhausted by earlier passes
+    const uint64_t lo = live ? out[sg.lo_off] : SENT;
+    if (!live || lo == SENT) {
+      if (threadIdx.x == 0 && sg.partial) pcnt[sg.cnt_slot] = 0;  // nothing from this segment
+      return false;
+    }
+    lo1 = lo + 1;
+  }
+  return true;
+}
+
+// (re)start of a walk from the threshold Tstart; the caller builds the tables and meets a barrier behind it
+__device__ __forceinline__ void reset_ctrl(const WgState& W, uint64_t Tstart) {
+  if (W.t == 0) { W.ctrl->T = Tstart; W.ctrl->T0 = Tstart; W.ctrl->sorted = 0; W.ctrl->count = 0; W.ctrl->overflow = 0; W.ctrl->saw_max = 0; W.ctrl->scan_base = 0; }
+}
+
+// finishes the queued halves (one lane each), keeps those still below T and appends them with ONE LDS
+// atomic for the whole batch; called where cap - count >= NWAVE * QCAP is guaranteed
+__device__ __forceinline__ void drain_queue(const WgState& W, uint32_t& qn, uint64_t T) {
+  if (qn == 0) return;
+  HashParts qp{0, 0};
+  uint64_t h = 0;
+  bool okq = false;
+  if (W.lane < qn) {
+    qp = HashParts{W.wq[2 * W.lane], W.wq[2 * W.lane + 1]};
+    h = mm_finish(qp);
+    okq = h < T || T == SENT;
+  }
+  const uint64_t bal = __ballot(okq);
+  uint32_t left = 0;
+  if (bal) {
+    uint32_t base = 0;
+    if (W.lane == 0) base = __hip_atomic_fetch_add(&W.ctrl->count, (uint32_t)__popcll(bal), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    base = __shfl(base, 0);
+    const uint32_t idx = base + (uint32_t)__popcll(bal & ((1ULL << W.lane) - 1ULL));
+    const bool fits = idx < (uint32_t)W.cap;
+    if (okq && fits) W.buf[idx] = h;
+    // No room (other waves filled the buffer meanwhile; cannot happen while the tile-end guarantee holds):
+    // the entry stays queued and the overflow flag forces a merge -- nothing is ever dropped here.
+    const uint64_t fbal = __ballot(okq && !fits);
+    if (fbal) {
+      if (okq && !fits) {
+        const uint32_t slot = (uint32_t)__popcll(fbal & ((1ULL << W.lane) - 1ULL));
+        W.wq[2 * slot] = qp.f1;
+        W.wq[2 * slot + 1] = qp.f2;
+        W.ctrl->overflow = 1;
+      }
+      left = (uint32_t)__popcll(fbal);
+    }
+  }
+  qn = left;
+}
+
+// Express walks: finishes the pending k-mer -- hash halves, high-word test against Thi1 = hi(T) + TEST_SLACK, a possible
+// candidate to the wave's queue (per k-mer, so that no halves stay live across a dword: the registers go to the reads in
+// flight).  lost: the queue could not take it (wave-uniform).
+__device__ __forceinline__ void express_handoff(const KmerLoads& pend, const KParams& P, uint32_t Thi1, lds_u64_ptr wq, uint32_t& qn, bool& lost) {
+  const HashParts hp = kmer_hash_finish(pend, P);
+  const uint64_t mq = __ballot(hash_test_word(hp) <= Thi1);
+  if (__builtin_expect(mq != 0, 0)) {  // wave-uniform, rare: kept out of line, the common path falls through
+    const uint32_t add = (uint32_t)__popcll(mq);
+    if (qn + add <= (uint32_t)QCAP) {
+      if (__builtin_amdgcn_inverse_ballot_w64(mq)) {
+        const uint32_t slot = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
+        wq[2 * slot] = hp.f1;
+        wq[2 * slot + 1] = hp.f2;
+      }
+      qn += add;
+    } else {
+      lost = true;
+    }
+  }
+}
+
+// General walks, one step of four bases: the four canonical k-mers (top-aligned, first base in bit 63) that end in the four bases `pack`
+// (c0<<6|c1<<4|c2<<2|c3) brings, cut out of the extended windows F = fwd << 8 | pack and R = rc | rp << 2k
+// (rp: the complemented codes in reverse significance) where `cut` says so (wave-uniform: warm-up bases only roll).
+// fwd carries bits above its window: they shift out in the cut.  The windows then take the extended ones' low 64 bits
+// and top 2k bits -- in here so that a runtime k meets ONE branch on the k range (a unit's own roll behind the cut cost
+// the runtime-k kernels 1 - 3.5 %).
+__device__ __forceinline__ void cut_kmers(uint64_t& fwd, uint64_t& rc, uint32_t pack, uint32_t rp, const KParams& P, bool cut, uint64_t canon[4]) {
+  if (P.k > 28) {
+    // 2k + 8 bits do not fit 64: the same cuts on 128-bit extended windows (k = 29..32)
+    typedef unsigned __int128 u128;
+    const u128 F = ((u128)fwd << 8) | pack;
+    const u128 R = (u128)rc | ((u128)rp << (2 * P.k));
+    if (cut) {
+#pragma unroll
+      for (int b = 0; b < 4; b++) {
+        const uint64_t f = (uint64_t)(F >> (6 - 2 * b)) & P.kmask;
+        const uint64_t r = (uint64_t)(R >> (2 * b + 2)) & P.kmask;
+        canon[b] = (f < r ? f : r) << P.lshift;
+      }
+    }
+    fwd = (uint64_t)F;
+    rc = (uint64_t)(R >> 8);
+  } else {
+    const uint64_t F = (fwd << 8) | pack;
+    const uint64_t R = rc | ((uint64_t)rp << (2 * P.k));
+    // the four windows are cut out of F / R already top-aligned (one shift + one mask each):
+    // the order of two k-mers does not depend on the alignment, and the hash wants them there
+    // Bits below the window are NOT cleared: they cannot change which of two different k-mers
+    // is smaller (of two equal ones either will do), and the hash never sees them -- table
+    // offsets are taken from whole bytes and the tables of a partially filled byte are built
+    // from the k-mer's bases only (build_kmer_lut masks by byte count).
+    if (cut) {
+#pragma unroll
+      for (int b = 0; b < 4; b++) {
+        const uint64_t f = F << (P.lshift - 6 + 2 * b);   // lshift >= 8 in this path
+        const uint64_t r = R << (P.lshift - 2 - 2 * b);
+        canon[b] = f < r ? f : r;
+      }
+    }
+    fwd = F;        // masked by whoever needs exactly 2k bits (the ASCII unit's per-base path)
+    rc = R >> 8;    // R < 2^(2k+8) by construction, so this is already < 2^(2k)
+  }
+}
+
+// appends the k-mers of the wave mask `bal` (their hashes in hv) with one LDS atomic
+__device__ __forceinline__ void append1(const WgState& W, uint64_t bal, uint64_t hv) {
+  if (bal) {  // wave-uniform
+    uint32_t base = 0;
+    if (W.lane == 0) base = __hip_atomic_fetch_add(&W.ctrl->count, (uint32_t)__popcll(bal), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    base = __shfl(base, 0);
+    const uint32_t idx = base + (uint32_t)__popcll(bal & ((1ULL << W.lane) - 1ULL));
+    if ((bal >> W.lane) & 1ULL) {
+      if (idx < (uint32_t)W.cap) W.buf[idx] = hv;
+      else W.ctrl->overflow = 1;
+    }
+  }
+}
+
+// General walks: one step of four k-mers per lane -- hash, test against T (scalar: the compares write wave masks
+// directly), candidates to the queue or the buffer.  allok (wave-uniform): all four k-mers of every lane are valid
+// and owned; otherwise valid(b) says so for this lane's k-mer b, and is asked on that branch only.
+template <class Valid>
+__device__ __forceinline__ void kmer_step4(const WgState& W, const KParams& P, const uint64_t canon[4], bool allok, uint64_t& T,
+                                           uint64_t lo1, uint32_t& qn, bool safe_mode, Valid&& valid) {
+  // what this wave appends directly (not through its queue): filled by the branches below, appended behind them --
+  // in safe mode one k-mer per lane at a time, every wave meeting the same barriers whether it appends or not
+  uint64_t am[4] = {0, 0, 0, 0}, ah[4] = {0, 0, 0, 0};
+  const uint32_t Thi = (uint32_t)(T >> 32);
+  if (allok && P.use64 && !lo1 && Thi < 0xffffffffu - TEST_SLACK) {
+    // The steady state: hash = fin(f1) + fin(f2) where fin() touches the low word only, so
+    // hi(hash) = hi(f1) + hi(f2) + carry.  The test word w (hash_test_word) is hi(hash) + {0, 1, 2}: with
+    // w > hi(T) + TEST_SLACK the hash cannot be below T -- one 32-bit compare per k-mer and the halves'
+    // last multiply is never formed (T != SENT here since hi(T) < 2^32 - 1 - TEST_SLACK).  The few
+    // waves holding a possible candidate (~64 s / N of them) finish exactly.
+    // four independent hash chains: their LDS table reads and multiplies overlap
+    HashParts hp[4];
+#pragma unroll
+    for (int b = 0; b < 4; b++) hp[b] = kmer_hash_parts(canon[b], P);
+    const uint32_t Thi1 = Thi + TEST_SLACK;
+    uint64_t cm = 0, mq[4];
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      const uint32_t u = hash_test_word(hp[b]);
+      mq[b] = __ballot(u <= Thi1);
+      cm |= mq[b];
+    }
+    if (cm) {  // wave-uniform, rare
+      // Possible candidates are not finished here (a wave would spend ~35 instructions on what is
+      // usually ONE lane's k-mer, ~5 % of the kernel at s = 1000): their two hash halves go to this
+      // wave's LDS queue -- slots from the wave masks, no atomics -- and are finished, tested exactly
+      // and appended a queue-full at a time (drain_queue, at tile ends where room is guaranteed).
+      const uint32_t add = (uint32_t)(__popcll(mq[0]) + __popcll(mq[1]) + __popcll(mq[2]) + __popcll(mq[3]));
+      if (qn + add <= (uint32_t)QCAP) {
+        uint32_t qb = qn;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+          if (mq[b]) {  // wave-uniform
+            if ((mq[b] >> W.lane) & 1ULL) {
+              const uint32_t slot = qb + (uint32_t)__popcll(mq[b] & ((1ULL << W.lane) - 1ULL));
+              W.wq[2 * slot] = hp[b].f1;
+              W.wq[2 * slot + 1] = hp[b].f2;
+            }
+            qb += (uint32_t)__popcll(mq[b]);
+          }
+        }
+        qn = qb;
+      } else {  // queue full (early in a genome, T still high): finish and append on the spot
+        uint64_t h[4], m[4];
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+          // (volatile: keeps the finishing arithmetic inside this branch -- left to itself the
+          // compiler computes it speculatively for every k-mer, which is the cost being avoided)
+          HashParts q = hp[b];
+          asm volatile("" : "+v"(q.f1), "+v"(q.f2));
+          h[b] = mm_finish(q);
+          m[b] = __ballot(h[b] < T);
+          am[b] = m[b]; ah[b] = h[b];
+        }
+      }
+    }
+  } else {
+    uint64_t h[4], m[4];
+#pragma unroll
+    for (int b = 0; b < 4; b++) h[b] = kmer_hash(canon[b], P);
+    if (allok && T != SENT) {  // one 64-bit compare per k-mer
+#pragma unroll
+      for (int b = 0; b < 4; b++) m[b] = __ballot(h[b] < T);
+    } else {
+#pragma unroll
+      for (int b = 0; b < 4; b++) {
+        // T == SENT means "sketch not full yet": everything passes (also a hash == SENT)
+        m[b] = __ballot(valid(b) && (h[b] < T || T == SENT));
+      }
+    }
+    if (lo1) {  // workgroup-uniform: later passes of a large sketch
+#pragma unroll
+      for (int b = 0; b < 4; b++) m[b] &= __ballot(h[b] >= lo1);
+    }
+#pragma unroll
+    for (int b = 0; b < 4; b++) { am[b] = m[b]; ah[b] = h[b]; }
+  }
+  if (safe_mode) {
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      // bound the next appends (at most one per lane) so the buffer cannot overflow
+      __syncthreads();
+      const uint32_t cn = uniform32(W.ctrl->count);
+      if ((uint32_t)W.cap - cn < (uint32_t)STEP_APPENDS) T = uniform64(merge_block(W.buf, W.ctrl, W.cap, W.s).T);
+      __syncthreads();
+      append1(W, am[b], ah[b]);
+    }
+  } else if (am[0] | am[1] | am[2] | am[3]) {
+#pragma unroll
+    for (int b = 0; b < 4; b++) append1(W, am[b], ah[b]);
+  }
+}
+
+// Behind a tile's walk (all threads arrive).  True: the optimistic walk lost candidates -- what the buffer holds
+// is folded (count may exceed cap: the clamp happens inside merge_block) and the caller walks the tile again, in safe mode.
+__device__ __forceinline__ bool tile_overflowed(const WgState& W, uint64_t& T, uint32_t& count_at_tile_start, bool& safe_mode) {
+  __syncthreads();
+  if (!uniform32(W.ctrl->overflow)) return false;
+  safe_mode = true;
+  const MergeResult mr = merge_block(W.buf, W.ctrl, W.cap, W.s);
+  count_at_tile_start = uniform32(mr.count);
+  T = uniform64(mr.T);
+  return true;
+}
+
+// End of a tile: decides about merging and the next tile's mode, drains a queue that is filling up.
+// count_at_tile_start is carried in registers: identical in every thread.
+__device__ __forceinline__ void end_tile(const WgState& W, uint64_t& T, uint32_t& qn, uint32_t& count_at_tile_start, bool& safe_mode) {
+  const uint32_t cn = uniform32(W.ctrl->count);
+  const uint32_t appended = cn - (count_at_tile_start < cn ? count_at_tile_start : cn);
+  // merge early enough that the rank merge's output still fits behind the candidates (2n <= cap)
+  const uint32_t half = (uint32_t)W.cap / 2;
+  const bool need_merge = cn > ((half > W.s + 512 && half < W.s + W.room / 2) ? half : W.s + W.room / 2);
+  safe_mode = appended > W.room / 4;
+  __syncthreads();  // all reads of ctrl->count done before merge or the next tile's appends
+  if (need_merge) {
+    const MergeResult mr = merge_block(W.buf, W.ctrl, W.cap, W.s);
+    count_at_tile_start = uniform32(mr.count);
+    T = uniform64(mr.T);
+  }
+  else count_at_tile_start = cn;
+  // room is guaranteed here (count <= s + room/2, so cap - count >= MIN_ROOM/2 >= NWAVE * QCAP)
+  if (qn >= (uint32_t)QDRAIN) drain_queue(W, qn, T);
+}
+
+// Final fold and write-out.  True (workgroup-uniform): fewer than s hashes under a starting threshold that was too
+// optimistic for this genome -- Tstart is lifted and the caller walks the segment again.
+__device__ __forceinline__ bool finish_sketch(const WgState& W, const Segment& sg, uint64_t T, uint32_t& qn, uint64_t& Tstart, int pass_no,
+                                              uint64_t* out, uint32_t* cnt, uint64_t* parts, uint32_t* pcnt) {
+  drain_queue(W, qn, T);
+  T = uniform64(merge_block(W.buf, W.ctrl, W.cap, W.s).T);   // frees room should a queue still hold entries
+  drain_queue(W, qn, T);
+  uint32_t n = merge_block(W.buf, W.ctrl, W.cap, W.s).count;
+  if (n < W.s && Tstart != SENT && !sg.partial) {
+    Tstart = SENT;
+    __syncthreads();
+    return true;
+  }
+  uint64_t* o = (sg.partial ? parts : out) + sg.out_off;
+  for (uint32_t i = W.t; i < n; i += WG) o[i] = W.buf[i];
+  if (W.t == 0) {
+    if (W.ctrl->saw_max && n < W.s) { o[n] = SENT; n++; }
+    // direct segments accumulate over passes; partial slots hold this pass's count only
+    if (sg.partial) pcnt[sg.cnt_slot] = n;
+    else cnt[sg.cnt_slot] = pass_no > 0 ? sg.expect + n : n;
+  }
+  return false;
+}
+
 // ---- merge of per-segment partial sketches (one workgroup per multi-segment genome) ---------------
 struct MergeJob {
   uint64_t part_off;   // element offset of first partial in partial buffer
@@ -617,6 +950,23 @@ struct MinhashLaunch {     // one launch of the sketch kernel
   uint32_t* d_pcnt;
   const uint32_t* d_redo;
 };
+
+// Defines NAME(k, seed, runtime_k, packed): the instantiation of the sketch kernel template KERN<KT, PK> to launch.
+// Compile-time k for 16..32: the values the reference's tune_parameters lands on for Mbp..Gbp
+// genomes (recommended k = ceil(log4(maxSize * 9999)) = 17..23, accepted up to +3), its default 21
+// and the customary 31/32; anything else, and any seed but the reference's, takes the runtime-k kernel.
+#define RTC_MINHASH_PICK(NAME, KERN)                                                                      \
+  inline decltype(&KERN<0, false>) NAME(int k, uint32_t seed, bool runtime_k, bool packed) {              \
+    switch (!runtime_k && seed == MASH_SEED ? k : 0) {                                                    \
+      RTC_PICK_K(KERN, 16) RTC_PICK_K(KERN, 17) RTC_PICK_K(KERN, 18) RTC_PICK_K(KERN, 19)                 \
+      RTC_PICK_K(KERN, 20) RTC_PICK_K(KERN, 21) RTC_PICK_K(KERN, 22) RTC_PICK_K(KERN, 23)                 \
+      RTC_PICK_K(KERN, 24) RTC_PICK_K(KERN, 25) RTC_PICK_K(KERN, 26) RTC_PICK_K(KERN, 27)                 \
+      RTC_PICK_K(KERN, 28) RTC_PICK_K(KERN, 29) RTC_PICK_K(KERN, 30) RTC_PICK_K(KERN, 31)                 \
+      RTC_PICK_K(KERN, 32)                                                                                \
+      default: return packed ? KERN<0, true> : KERN<0, false>;                                            \
+    }                                                                                                     \
+  }
+#define RTC_PICK_K(KERN, K) case K: return packed ? KERN<K, true> : KERN<K, false>;
 
 // tile_bases: bases a workgroup takes per tile (the unit the segment lengths are planned in); min_room: candidate slots the
 // kernel's buffer must offer beyond the sketch size.  prepare(MinhashPlanInfo)

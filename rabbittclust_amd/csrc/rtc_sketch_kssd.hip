@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "rtc_internal.h"
+#include "rtc_runs.h"
 
 namespace {
 
@@ -683,28 +684,12 @@ struct PackedBatch {
   const uint8_t* bytes;      // packed bases
   uint64_t n_bases;          // bases the buffer holds (a multiple of 64)
   const uint64_t* runs;      // (start, length) pairs
-  const uint2* seg_runs;     // per segment: the runs [x, y) that can touch a k-mer the segment owns (packed_seg_runs_kernel)
+  const uint2* seg_runs;     // per segment: the runs [x, y) that can touch a k-mer the segment owns (seg_runs_kernel)
 };
-
-// per segment, the first run that ends behind s_begin - (K - 1) and the first that starts at or behind s_end: the exact
-// drain looks a window up among these only (none for most segments of a finished genome)
-__global__ __launch_bounds__(256) void packed_seg_runs_kernel(const KSegment* __restrict__ segs, uint32_t nseg, const uint64_t* __restrict__ runs,
-                                                              uint32_t n_runs, int K, uint2* __restrict__ seg_runs) {
-  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= nseg) return;
-  const int64_t first = (int64_t)segs[s].s_begin - (K - 1), end = (int64_t)segs[s].s_end;
-  uint32_t lo = 0, hi = n_runs;  // runs that end at or before `first` (ends ascend with the starts: the runs are disjoint)
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)(runs[2 * (uint64_t)mid] + runs[2 * (uint64_t)mid + 1]) <= first) lo = mid + 1; else hi = mid; }
-  const uint32_t x = lo;
-  hi = n_runs;                   // runs that start before `end`
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)runs[2 * (uint64_t)mid] < end) lo = mid + 1; else hi = mid; }
-  seg_runs[s] = make_uint2(x, lo);
-}
 
 // is [first, last] free of the runs [rlo, rhi)?  (ascending by start, disjoint; the runs in front of rlo end at or before first)
 __device__ __forceinline__ bool window_valid(const uint64_t* __restrict__ runs, uint32_t rlo, uint32_t rhi, int64_t first, int64_t last) {
-  uint32_t lo = rlo, hi = rhi;  // -> the number of runs that start at or before `last`
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)runs[2 * (uint64_t)mid] <= last) lo = mid + 1; else hi = mid; }
+  const uint32_t lo = first_run_starting_from(runs, rlo, rhi, last + 1);  // behind the runs that start at or before `last`
   if (lo == rlo) return true;
   return (int64_t)(runs[2 * (uint64_t)(lo - 1)] + runs[2 * (uint64_t)(lo - 1) + 1]) <= first;
 }
@@ -1484,7 +1469,7 @@ static int sketch_kssd_impl(rtc_ctx* ctx, const uint8_t* d_seq, const PackedArgs
     if (ctx->opt.verbose) fprintf(stderr, "[kssd] forward-strand prefilter over packed bases, K=%d, %zu segments, %llu runs\n", K, segs.size(), (unsigned long long)pk->n_runs);
     void* ws4 = nullptr;
     RTC_TRY(rtc_ws(ctx, 4, segs.size() * sizeof(uint2) + 64, &ws4));
-    hipLaunchKernelGGL(packed_seg_runs_kernel, dim3((uint32_t)((segs.size() + 255) / 256)), dim3(256), 0, ctx->stream, (const KSegment*)ws0,
+    hipLaunchKernelGGL(seg_runs_kernel<KSegment>, dim3((uint32_t)((segs.size() + 255) / 256)), dim3(256), 0, ctx->stream, (const KSegment*)ws0,
                        (uint32_t)segs.size(), pk->d_runs, (uint32_t)pk->n_runs, K, (uint2*)ws4);
     RTC_CHECK_LAUNCH(ctx);
     const PackedBatch B{d_seq, pk->n_bases, pk->d_runs, (const uint2*)ws4};

@@ -14,12 +14,16 @@
 //     no re-encoding votes, no v_dot4;
 //   * what the characters were is the run list's business: a k-mer counts exactly when none of its k bases lies in
 //     a run or outside its genome.  A wave asks once per load whether any run can touch its 4 096 bases (a scalar
-//     cursor into the segment's run range, minhash_seg_runs_kernel); only a wave that meets one builds per-lane
+//     cursor into the segment's run range, seg_runs_kernel of rtc_runs.h); only a wave that meets one builds per-lane
 //     validity masks and takes the general walk.
-// The hash (MurmurHash3 from LDS product tables), the threshold test, the candidate queue, the in-LDS merges, the
-// segment plan and the partial-sketch merge are rtc_minhash_core.h's, shared with the ASCII unit; results are
-// identical to it and to the oracle bit for bit (tests/test_gpu_sketch_minhash_packed.py).
+// Everything behind the k-mers is rtc_minhash_core.h's, one copy for this unit and the ASCII one: the hash (MurmurHash3
+// from LDS product tables), the workgroup state in LDS, the cut and roll of the general walk's windows, the threshold tests, the
+// candidate queue, appends, the tile protocol, the in-LDS merges, the final fold and write-out, kernel selection, the
+// segment plan and the partial-sketch merge.  Written here: loads, window seeds, the express loop with its rolls, the masks and
+// the run cursor.  Results are identical to the ASCII unit's and to the oracle bit for bit
+// (tests/test_gpu_sketch_minhash_packed.py).
 #include "rtc_minhash_core.h"
+#include "rtc_runs.h"
 
 namespace {
 
@@ -32,20 +36,6 @@ struct PackedIn {
   uint64_t n_bases;         // a multiple of 64
   const uint64_t* runs;     // (start, length) pairs, ascending and disjoint
 };
-
-// per segment, the first run that ends behind s_begin - (k - 1) and the first that starts at or behind s_end
-__global__ __launch_bounds__(256) void minhash_seg_runs_kernel(const Segment* __restrict__ segs, uint32_t nseg, const uint64_t* __restrict__ runs,
-                                                               uint32_t n_runs, int k, uint2* __restrict__ seg_runs) {
-  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= nseg) return;
-  const int64_t first = (int64_t)segs[s].s_begin - (k - 1), end = (int64_t)segs[s].s_end;
-  uint32_t lo = 0, hi = n_runs;  // runs that end at or before `first` (ends ascend with the starts: the runs are disjoint)
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)(runs[2 * (uint64_t)mid] + runs[2 * (uint64_t)mid + 1]) <= first) lo = mid + 1; else hi = mid; }
-  const uint32_t x = lo;
-  hi = n_runs;                   // runs that start before `end`
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)runs[2 * (uint64_t)mid] < end) lo = mid + 1; else hi = mid; }
-  seg_runs[s] = make_uint2(x, lo);
-}
 
 // 16 packed bases (first base in the low bits) -> first base on top, every base's two bits in order
 __device__ __forceinline__ uint32_t pair_rev(uint32_t x) {
@@ -61,7 +51,7 @@ __host__ __device__ constexpr uint32_t fwd_roll_sel(int fsb, int q) {
   return sel;
 }
 
-template <int KT, bool PK>  // as sketch_minhash_kernel (rtc_sketch_minhash.hip)
+template <int KT, bool PK>  // KT > 0: k known at compile time; 0: runtime k.  PK: packed hash tables (lut_bytes)
 __global__ __launch_bounds__(WG, 6) void sketch_minhash_packed_kernel(PackedIn B, const Segment* __restrict__ segs,
                                                                    const uint2* __restrict__ seg_runs,
                                                                    int k_arg, uint32_t seed, int cap,
@@ -71,81 +61,29 @@ __global__ __launch_bounds__(WG, 6) void sketch_minhash_packed_kernel(PackedIn B
                                                                    const uint32_t* __restrict__ redo) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int k = KT > 0 ? KT : k_arg;
-  const lds_byte_ptr lds0 = (lds_byte_ptr)smem;
-  const lds_byte_ptr lut = lds0;  // at LDS offset 0: table offsets become ds_read immediates
-  if ((uint32_t)(uintptr_t)lds0 != 0u) __builtin_trap();
-  const lds_u64_ptr buf = (lds_u64_ptr)(lds0 + lut_bytes(k, PK));
-  const lds_ctrl_ptr ctrl = (lds_ctrl_ptr)(lds0 + lut_bytes(k, PK) + (size_t)cap * 8);
-  const lds_u64_ptr wq = (lds_u64_ptr)(lds0 + lut_bytes(k, PK) + (size_t)cap * 8 + ((sizeof(Ctrl) + 15) & ~(size_t)15)) +
-                         (size_t)(threadIdx.x >> 6) * QCAP * 2;
-  uint32_t qn = 0;  // entries waiting in this wave's candidate queue (wave-uniform)
-
   const Segment sg = segs[blockIdx.x];
-  if (redo && redo[sg.final_slot] == 0) return;  // workgroup-uniform (second launch: flagged genomes only)
-  const KParams P = make_kparams(k, KT > 0 ? MASH_SEED : seed, PK);
-  const int t = threadIdx.x;
-  const uint32_t lane = t & 63;
-  const int wv = (int)uniform32((uint32_t)(t >> 6));
-  const uint32_t s = sg.sketch_size;
+  const WgState W = carve_lds(smem, k, PK, cap, sg.sketch_size);
+  uint64_t lo1;  // later passes of a large sketch: only hashes from lo1 up (0: the first pass)
+  if (!pass_gate(sg, pass_no, redo, cnt, out, pcnt, lo1)) return;  // workgroup-uniform
+  const KParams P = make_kparams(k, KT > 0 ? MASH_SEED : seed, PK);  // compile-time k serves the reference's seed only
+  const uint32_t lane = W.lane;
+  const int wv = (int)uniform32((uint32_t)(W.t >> 6));
+  const uint32_t s = W.s;
+  uint32_t qn = 0;  // entries waiting in this wave's candidate queue (wave-uniform)
   const uint2 sr = seg_runs[blockIdx.x];
   const bool has_runs = sr.x != sr.y;  // workgroup-uniform: most segments of a finished genome meet no run at all
   const int64_t nbytes = (int64_t)(B.n_bases >> 2);
 
-  uint64_t lo1 = 0;  // later passes of a large sketch: only hashes above everything kept so far
-  if (pass_no > 0) {  // workgroup-uniform
-    const bool live = cnt[sg.final_slot] == sg.expect;
-    const uint64_t lo = live ? out[sg.lo_off] : SENT;
-    if (!live || lo == SENT) {
-      if (t == 0 && sg.partial) pcnt[sg.cnt_slot] = 0;
-      return;
-    }
-    lo1 = lo + 1;
-  }
-
-  uint64_t Tstart = (pass_no == 0 && !redo) ? sg.t0 : SENT;  // starting threshold, see sketch_minhash_kernel
+  uint64_t Tstart = (pass_no == 0 && !redo) ? sg.t0 : SENT;  // starting threshold (segment plan); lifted if it proves too optimistic
 restart:
-  if (t == 0) { ctrl->T = Tstart; ctrl->T0 = Tstart; ctrl->sorted = 0; ctrl->count = 0; ctrl->overflow = 0; ctrl->saw_max = 0; ctrl->scan_base = 0; }
-  build_kmer_lut(lut, k, PK);
+  reset_ctrl(W, Tstart);
+  build_kmer_lut(W.lut, k, PK);
   __syncthreads();
 
   uint64_t T = uniform64(Tstart);
   qn = 0;
   bool safe_mode = true;
-  const uint32_t room = (uint32_t)cap - s;  // >= MIN_ROOM by construction
   uint32_t rcur = sr.x;  // wave-uniform cursor into the run list: every run in front of it ends before anything this wave still looks at
-
-  auto drain_queue = [&]() {  // as in sketch_minhash_kernel
-    if (qn == 0) return;
-    HashParts qp{0, 0};
-    uint64_t h = 0;
-    bool okq = false;
-    if (lane < qn) {
-      qp = HashParts{wq[2 * lane], wq[2 * lane + 1]};
-      h = mm_finish(qp);
-      okq = h < T || T == SENT;
-    }
-    const uint64_t bal = __ballot(okq);
-    uint32_t left = 0;
-    if (bal) {
-      uint32_t base = 0;
-      if (lane == 0) base = __hip_atomic_fetch_add(&ctrl->count, (uint32_t)__popcll(bal), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      base = __shfl(base, 0);
-      const uint32_t idx = base + (uint32_t)__popcll(bal & ((1ULL << lane) - 1ULL));
-      const bool fits = idx < (uint32_t)cap;
-      if (okq && fits) buf[idx] = h;
-      const uint64_t fbal = __ballot(okq && !fits);
-      if (fbal) {
-        if (okq && !fits) {
-          const uint32_t slot = (uint32_t)__popcll(fbal & ((1ULL << lane) - 1ULL));
-          wq[2 * slot] = qp.f1;
-          wq[2 * slot + 1] = qp.f2;
-          ctrl->overflow = 1;
-        }
-        left = (uint32_t)__popcll(fbal);
-      }
-    }
-    qn = left;
-  };
 
   uint32_t count_at_tile_start = 0;
   for (uint64_t TB = sg.s_begin & ~63ULL; TB < sg.s_end && s > 0; TB += P_TILE_BASES) {
@@ -160,9 +98,7 @@ restart:
     const int64_t tile_byte = (int64_t)(TB >> 2);                 // wave-uniform
     const uint32_t rcur_tile = rcur;                              // a tile walked again starts from here again
 
-    bool redo_tile;
     do {
-      redo_tile = false;
       rcur = rcur_tile;
 #pragma unroll 1
       for (int j = 0; j < P_NL; j++) {
@@ -190,12 +126,7 @@ restart:
             const uint64_t en = B.runs[2 * (uint64_t)rc] + B.runs[2 * (uint64_t)rc + 1];
             if ((int64_t)en > first) break;
             rc++;
-            if (rc - rcur == 8) {  // many runs behind: the rest by bisection
-              uint32_t lo = rc, hi = sr.y;
-              while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)(B.runs[2 * (uint64_t)mid] + B.runs[2 * (uint64_t)mid + 1]) <= first) lo = mid + 1; else hi = mid; }
-              rc = lo;
-              break;
-            }
+            if (rc - rcur == 8) { rc = first_run_ending_after(B.runs, rc, sr.y, first); break; }  // many runs behind: the rest by bisection
           }
           rcur = uniform32(rc);
           wave_dirty = rcur < sr.y && (int64_t)B.runs[2 * (uint64_t)rcur] < (int64_t)TB + crel + P_CHUNK;
@@ -223,23 +154,7 @@ restart:
             uint32_t w0 = cw[0], w1 = cw[1], w2 = cw[2], w3 = cw[3];
             bool lost = false;  // wave-uniform: the queue could not take a candidate
             KmerLoads pend = {};
-            auto finish_pending = [&]() __attribute__((always_inline)) {
-              const HashParts hp = kmer_hash_finish(pend, P);
-              const uint64_t mq = __ballot(hash_test_word(hp) <= Thi1);
-              if (__builtin_expect(mq != 0, 0)) {  // wave-uniform, rare
-                const uint32_t add = (uint32_t)__popcll(mq);
-                if (qn + add <= (uint32_t)QCAP) {
-                  if (__builtin_amdgcn_inverse_ballot_w64(mq)) {
-                    const uint32_t slot = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
-                    wq[2 * slot] = hp.f1;
-                    wq[2 * slot + 1] = hp.f2;
-                  }
-                  qn += add;
-                } else {
-                  lost = true;
-                }
-              }
-            };
+            auto finish_pending = [&]() __attribute__((always_inline)) { express_handoff(pend, P, Thi1, W.wq, qn, lost); };
 #pragma unroll 1
             for (int d = 0; d < 4; d++) {
               const uint32_t PRd = pair_rev(w0), NCd = ~w0;
@@ -291,9 +206,7 @@ restart:
           if (ge < wstart + 96) mark(ge - wstart, 96);
           if (wave_dirty) {
             const int64_t wabs = (int64_t)TB + wstart;
-            uint32_t lo = rcur, hi = sr.y;  // the first run that ends behind the window's first base
-            while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)(B.runs[2 * (uint64_t)mid] + B.runs[2 * (uint64_t)mid + 1]) <= wabs) lo = mid + 1; else hi = mid; }
-            for (uint32_t r = lo; r < sr.y; r++) {
+            for (uint32_t r = first_run_ending_after(B.runs, rcur, sr.y, wabs); r < sr.y; r++) {  // from the first run that ends behind the window's first base
               const int64_t st = (int64_t)B.runs[2 * (uint64_t)r] - wabs;
               if (st >= 96) break;
               const int64_t en = st + (int64_t)B.runs[2 * (uint64_t)r + 1];
@@ -301,7 +214,7 @@ restart:
             }
           }
           const bool clean = !__any((M[0] | M[1] | M[2]) != 0u);  // wave-uniform
-          // windows in the general form (sketch_minhash_kernel's fwd / rc) from the 32 bases in front
+          // windows in the general form (cut_kmers' fwd / rc) from the 32 bases in front
           uint64_t fwd = ((uint64_t)pair_rev(p2) << 32) | pair_rev(p3);
           uint64_t rc;
           {
@@ -322,30 +235,7 @@ restart:
               const uint32_t pack = ((y & 3u) << 6) | ((y & 0xcu) << 2) | ((y >> 2) & 0xcu) | (y >> 6);
               const uint32_t rp = y ^ 0xffu;
               uint64_t canon[4];
-              if (k > 28) {
-                typedef unsigned __int128 u128;
-                const u128 F = ((u128)fwd << 8) | pack;
-                const u128 R = (u128)rc | ((u128)rp << (2 * P.k));
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                  const uint64_t f = (uint64_t)(F >> (6 - 2 * b)) & P.kmask;
-                  const uint64_t r = (uint64_t)(R >> (2 * b + 2)) & P.kmask;
-                  canon[b] = (f < r ? f : r) << P.lshift;
-                }
-                fwd = (uint64_t)F;
-                rc = (uint64_t)(R >> 8);
-              } else {
-                const uint64_t F = (fwd << 8) | pack;
-                const uint64_t R = rc | ((uint64_t)rp << (2 * P.k));
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                  const uint64_t f = F << (P.lshift - 6 + 2 * b);   // lshift >= 8 here; bits below the window stay (see sketch_minhash_kernel)
-                  const uint64_t r = R << (P.lshift - 2 - 2 * b);
-                  canon[b] = f < r ? f : r;
-                }
-                fwd = F;
-                rc = R >> 8;
-              }
+              cut_kmers(fwd, rc, pack, rp, P, true, canon);  // ... and rolls the windows on
               const bool allok = interior && clean;  // wave-uniform: every k-mer of every lane is valid and owned
               // a k-mer that ends at position i of the lane's 64 is valid when the k bits up to bit 32 + i of the mask are clear
               bool ok[4];
@@ -356,146 +246,19 @@ restart:
                 const int rel = rel0 + b;
                 ok[b] = win == 0 && rel >= rel_lo && rel < rel_hi;
               }
-              // what this wave appends directly (not through its queue): filled by the branches below, appended behind them --
-              // in safe mode one k-mer per lane at a time, every wave meeting the same barriers whether it appends or not
-              uint64_t am[4] = {0, 0, 0, 0}, ah[4] = {0, 0, 0, 0};
-              auto append1 = [&](uint64_t bal, uint64_t hv) __attribute__((always_inline)) {
-                if (bal) {  // wave-uniform
-                  uint32_t base = 0;
-                  if (lane == 0) base = __hip_atomic_fetch_add(&ctrl->count, (uint32_t)__popcll(bal), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                  base = __shfl(base, 0);
-                  const uint32_t idx = base + (uint32_t)__popcll(bal & ((1ULL << lane) - 1ULL));
-                  if ((bal >> lane) & 1ULL) {
-                    if (idx < (uint32_t)cap) buf[idx] = hv;
-                    else ctrl->overflow = 1;
-                  }
-                }
-              };
-              const uint32_t Thi = (uint32_t)(T >> 32);
-              if (allok && P.use64 && !lo1 && Thi < 0xffffffffu - TEST_SLACK) {
-                // the high-word test of the steady state (sketch_minhash_kernel), without the pipeline
-                HashParts hp[4];
-#pragma unroll
-                for (int b = 0; b < 4; b++) hp[b] = kmer_hash_parts(canon[b], P);
-                const uint32_t Thi1 = Thi + TEST_SLACK;
-                uint64_t cm = 0, mq[4];
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                  mq[b] = __ballot(hash_test_word(hp[b]) <= Thi1);
-                  cm |= mq[b];
-                }
-                if (cm) {  // wave-uniform, rare
-                  const uint32_t add = (uint32_t)(__popcll(mq[0]) + __popcll(mq[1]) + __popcll(mq[2]) + __popcll(mq[3]));
-                  if (qn + add <= (uint32_t)QCAP) {
-                    uint32_t qb = qn;
-#pragma unroll
-                    for (int b = 0; b < 4; b++) {
-                      if (mq[b]) {  // wave-uniform
-                        if ((mq[b] >> lane) & 1ULL) {
-                          const uint32_t slot = qb + (uint32_t)__popcll(mq[b] & ((1ULL << lane) - 1ULL));
-                          wq[2 * slot] = hp[b].f1;
-                          wq[2 * slot + 1] = hp[b].f2;
-                        }
-                        qb += (uint32_t)__popcll(mq[b]);
-                      }
-                    }
-                    qn = qb;
-                  } else {  // queue full: finish and append on the spot
-                    uint64_t h[4], m[4];
-#pragma unroll
-                    for (int b = 0; b < 4; b++) {
-                      HashParts qh = hp[b];
-                      asm volatile("" : "+v"(qh.f1), "+v"(qh.f2));  // keeps the finishing arithmetic inside this branch
-                      h[b] = mm_finish(qh);
-                      m[b] = __ballot(h[b] < T);
-                      am[b] = m[b]; ah[b] = h[b];
-                    }
-                  }
-                }
-              } else {
-                uint64_t h[4], m[4];
-#pragma unroll
-                for (int b = 0; b < 4; b++) h[b] = kmer_hash(canon[b], P);
-                if (allok && T != SENT) {
-#pragma unroll
-                  for (int b = 0; b < 4; b++) m[b] = __ballot(h[b] < T);
-                } else {
-#pragma unroll
-                  for (int b = 0; b < 4; b++) m[b] = __ballot(ok[b] && (h[b] < T || T == SENT));  // T == SENT: sketch not full yet, everything passes
-                }
-                if (lo1) {
-#pragma unroll
-                  for (int b = 0; b < 4; b++) m[b] &= __ballot(h[b] >= lo1);
-                }
-#pragma unroll
-                for (int b = 0; b < 4; b++) { am[b] = m[b]; ah[b] = h[b]; }
-              }
-              if (safe_mode) {
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                  // bound the next appends (at most one per lane) so the buffer cannot overflow
-                  __syncthreads();
-                  const uint32_t cn = uniform32(ctrl->count);
-                  if ((uint32_t)cap - cn < (uint32_t)STEP_APPENDS) T = uniform64(merge_block(buf, ctrl, cap, s).T);
-                  __syncthreads();
-                  append1(am[b], ah[b]);
-                }
-              } else if (am[0] | am[1] | am[2] | am[3]) {
-#pragma unroll
-                for (int b = 0; b < 4; b++) append1(am[b], ah[b]);
-              }
+              kmer_step4(W, P, canon, allok, T, lo1, qn, safe_mode, [&](int b) __attribute__((always_inline)) { return ok[b]; });
             }
           }
         }
-      }
-      __syncthreads();
-      if (uniform32(ctrl->overflow)) {
-        // the optimistic pass lost candidates: fold what we have, then walk this tile again in safe mode
-        const MergeResult mr = merge_block(buf, ctrl, cap, s);
-        count_at_tile_start = uniform32(mr.count);
-        T = uniform64(mr.T);
-        safe_mode = true;
-        redo_tile = true;
-      }
-    } while (redo_tile);
-
-    // ---- end of tile: decide about merging and the next tile's mode (sketch_minhash_kernel's protocol) ----
-    const uint32_t cn = uniform32(ctrl->count);
-    const uint32_t appended = cn - (count_at_tile_start < cn ? count_at_tile_start : cn);
-    const uint32_t half = (uint32_t)cap / 2;
-    const bool need_merge = cn > ((half > s + 512 && half < s + room / 2) ? half : s + room / 2);
-    safe_mode = appended > room / 4;
-    __syncthreads();
-    if (need_merge) {
-      const MergeResult mr = merge_block(buf, ctrl, cap, s);
-      count_at_tile_start = uniform32(mr.count);
-      T = uniform64(mr.T);
-    }
-    else count_at_tile_start = cn;
-    if (qn >= (uint32_t)QDRAIN) drain_queue();
+      }  // loads of the tile
+    } while (tile_overflowed(W, T, count_at_tile_start, safe_mode));
+    end_tile(W, T, qn, count_at_tile_start, safe_mode);
   }
 
-  // ---- final fold and write-out ----
-  drain_queue();
-  {
-    const MergeResult mr = merge_block(buf, ctrl, cap, s);
-    T = uniform64(mr.T);
-  }
-  drain_queue();
-  uint32_t nfin = merge_block(buf, ctrl, cap, s).count;
-  if (nfin < s && Tstart != SENT && !sg.partial) {  // the starting threshold was too optimistic for this genome
-    Tstart = SENT;
-    __syncthreads();
-    goto restart;
-  }
-  uint64_t* o = (sg.partial ? parts : out) + sg.out_off;
-  for (uint32_t i = t; i < nfin; i += WG) o[i] = buf[i];
-  if (t == 0) {
-    if (ctrl->saw_max && nfin < s) { o[nfin] = SENT; nfin++; }
-    if (sg.partial) pcnt[sg.cnt_slot] = nfin;
-    else cnt[sg.cnt_slot] = pass_no > 0 ? sg.expect + nfin : nfin;
-  }
+  if (finish_sketch(W, sg, T, qn, Tstart, pass_no, out, cnt, parts, pcnt)) goto restart;
 }
+
+RTC_MINHASH_PICK(pick_kernel, sketch_minhash_packed_kernel)
 
 }  // namespace
 
@@ -513,34 +276,22 @@ extern "C" int rtc_sketch_minhash_packed_dev(rtc_ctx* ctx, const uint8_t* d_pack
 
   RTC_TRY(rtc_sticky_error(ctx));
   RTC_TRY(rtc_check_runs_async(ctx, d_runs, n_runs, n_bases));  // asynchronous: a violation surfaces at the next packed call or rtc_ctx_sync
-  typedef void (*kern_t)(PackedIn, const Segment*, const uint2*, int, uint32_t, int, uint64_t*, uint32_t*, int, uint64_t*, uint32_t*, const uint32_t*);
-  auto pick = [&](bool runtime_k, bool packed) -> kern_t {
-    kern_t kern = packed ? sketch_minhash_packed_kernel<0, true> : sketch_minhash_packed_kernel<0, false>;
-    switch (!runtime_k && seed == MASH_SEED ? k : 0) {
-#define RTC_K(K) case K: kern = packed ? sketch_minhash_packed_kernel<K, true> : sketch_minhash_packed_kernel<K, false>; break;
-      RTC_K(16) RTC_K(17) RTC_K(18) RTC_K(19) RTC_K(20) RTC_K(21) RTC_K(22) RTC_K(23) RTC_K(24)
-      RTC_K(25) RTC_K(26) RTC_K(27) RTC_K(28) RTC_K(29) RTC_K(30) RTC_K(31) RTC_K(32)
-#undef RTC_K
-      default: break;
-    }
-    return kern;
-  };
   PackedIn B{d_packed, n_bases, d_runs};
   uint2* d_seg_runs = nullptr;
   auto prepare = [&](const MinhashPlanInfo& pi) -> int {
-    RTC_HIP(ctx, hipFuncSetAttribute((const void*)pick(false, pi.packed_tables), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pi.lds));
-    RTC_HIP(ctx, hipFuncSetAttribute((const void*)pick(true, pi.packed_tables), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pi.lds));
+    RTC_HIP(ctx, hipFuncSetAttribute((const void*)pick_kernel(k, seed, false, pi.packed_tables), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pi.lds));
+    RTC_HIP(ctx, hipFuncSetAttribute((const void*)pick_kernel(k, seed, true, pi.packed_tables), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pi.lds));
     void* ws = nullptr;
     RTC_TRY(rtc_ws(ctx, 3, pi.nsegs * sizeof(uint2) + 64, &ws));
     d_seg_runs = (uint2*)ws;
     if (ctx->opt.verbose && !ctx->quiet) fprintf(stderr, "[minhash] sketching over packed bases, k=%d, %zu segments, %llu runs\n", k, pi.nsegs, (unsigned long long)n_runs);
-    hipLaunchKernelGGL(minhash_seg_runs_kernel, dim3((uint32_t)((pi.nsegs + 255) / 256)), dim3(256), 0, ctx->stream, pi.d_segs, (uint32_t)pi.nsegs,
+    hipLaunchKernelGGL(seg_runs_kernel<Segment>, dim3((uint32_t)((pi.nsegs + 255) / 256)), dim3(256), 0, ctx->stream, pi.d_segs, (uint32_t)pi.nsegs,
                        d_runs, (uint32_t)n_runs, k, d_seg_runs);
     RTC_CHECK_LAUNCH(ctx);
     return RTC_OK;
   };
   auto launch = [&](const MinhashLaunch& L) -> int {
-    hipLaunchKernelGGL(pick(L.runtime_k, L.packed_tables), dim3(L.nseg), dim3(WG), L.lds, ctx->stream, B, L.d_segs,
+    hipLaunchKernelGGL(pick_kernel(k, seed, L.runtime_k, L.packed_tables), dim3(L.nseg), dim3(WG), L.lds, ctx->stream, B, L.d_segs,
                        (const uint2*)(d_seg_runs + L.seg_index), k, seed, L.cap, d_out, d_cnt, L.pass, L.d_parts, L.d_pcnt, L.d_redo);
     RTC_CHECK_LAUNCH(ctx);
     return RTC_OK;
