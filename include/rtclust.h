@@ -507,6 +507,41 @@ int rtc_dbscan_sweep(rtc_ctx* ctx, const void* d_hashes, int width, const uint64
  * predicate ns, out[7] components and labels ns, out[8] k-distance ns, out[9] whole call ns. */
 int rtc_dbscan_sweep_counters(const rtc_ctx* ctx, uint64_t out[10]);
 
+/* ---- clust-dbscan --minhash: DBSCAN over MinHash sketches -------------------------------------- */
+/* MinHashDBSCAN (src/dbscan.cpp:685-720, :987-1096; the reference's command line never reaches it) for the levels h_eps[0 ..
+ * n_eps), 1 <= n_eps <= 32, any order, duplicates allowed, from ONE pair phase.  The sketches are ascending lists of distinct
+ * hashes of at most sketch_size elements (shorter and empty ones allowed).  dist(p, q) is MinHash::distance() as
+ * rtc_pair_mash_dev restates it: (common, denom) of the merge truncated after sketch_size union elements, j = common / denom
+ * in double, 1 when j == 0, 0 when j == 1, otherwise min(1, -ln(2j / (1 + j)) / kmer_size) with the host's libm
+ * (rtc_mash_distance) -- parity-unpinned against RabbitSketch like rtc_mst_mash.  q is a neighbour of p iff q != p and
+ * dist(p, q) <= eps in double; the relation is symmetric.  p is a core point iff it has at least min_pts neighbours, ITSELF NOT
+ * COUNTED (:1017, :1050; rtc_dbscan's rule counts it).  min_pts <= 0 makes every point a core point; a negative min_pts is
+ * treated like 0 (the reference compares it against an unsigned size, which no caller can mean).  Labels, h_core, h_n_clusters
+ * and h_n_noise exactly as rtc_dbscan_sweep's: clusters are the components of the core points over core-core eps edges,
+ * numbered by their smallest core index; a non-core point with a core neighbour joins the lowest-numbered cluster among its
+ * core neighbours'; every other point is -1.  The device forms no distance: the host turns every eps into the least common
+ * that passes for every denom (rtc_dbscan_mash_table) and the device compares counts.
+ * 0 <= eps < 1: eps < 0 or NaN returns RTC_ERR_ARG; eps >= 1 returns RTC_ERR_UNSUPPORTED (pairs without a common hash have
+ * distance 1 and no candidate list holds them).  RTC_EDGE_BUDGET chunks the rows as in rtc_dbscan; RTC_ERR_NOMEM as there, no
+ * fallback.  RTC_DBSCAN_MASH_SERIAL=1: the per-thread merge instead of the wave-cooperative one; RTC_DBSCAN_MASH_NOPREFILTER=1:
+ * no candidate is dropped before the merge; results are identical either way.  Synchronous. */
+int rtc_dbscan_mash(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                    uint32_t sketch_size, const double* h_eps, uint32_t n_eps, int min_pts, int kmer_size, int32_t* h_labels,
+                    uint8_t* h_core, uint32_t* h_n_clusters, uint32_t* h_n_noise);
+/* What the last rtc_dbscan_mash call did: out[0] row chunks, out[1] candidate edges, out[2] candidates merged (past the
+ * prefilter), out[3] pairs kept (passing at some level), out[4] levels, out[5] hook rounds, out[6] pair phase ns, out[7]
+ * predicate ns, out[8] components and labels ns, out[9] whole call ns. */
+int rtc_dbscan_mash_counters(const rtc_ctx* ctx, uint64_t out[10]);
+/* The distance above for a given (common, denom <= sketch_size), and rtc_dbscan_mash's decision table for one eps in [0, 1):
+ * out[d], d = 0 .. sketch_size, is the least common with rtc_mash_distance(common, d) <= eps, d + 1 where none passes.  Host
+ * only, no context. */
+double rtc_mash_distance(uint32_t common, uint32_t denom, uint32_t sketch_size, int kmer_size);
+int rtc_dbscan_mash_table(uint32_t sketch_size, int kmer_size, double eps, uint32_t* out);
+/* The recount of rtc_dbscan_mash on its own: d_common[e], d_denom[e] = the union-truncated counts of rtc_pair_mash_dev for the
+ * pair (d_edges[e].i, d_edges[e].j), e < m, both below n (the edge's own count is ignored).  Context stream, asynchronous. */
+int rtc_pair_mash_edges_dev(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                            uint32_t sketch_size, const rtc_cedge* d_edges, uint64_t m, uint32_t* d_common, uint32_t* d_denom);
+
 /* ---- clust-dbscan --hierarchy: the density hierarchy (HDBSCAN*) of the neighbour graph at eps_max ------------- */
 /* One edge of the hierarchy: its mutual-reachability similarity is m = common / (size_p + size_q - common), p < q
  * (size_p = size_q = common = 0: m = 1, two empty u64 sketches). */

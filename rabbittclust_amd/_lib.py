@@ -128,6 +128,11 @@ SIGNATURES = {
     "rtc_dbscan_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_dbscan_sweep": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _u32, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "rtc_dbscan_sweep_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_dbscan_mash": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _u32, _vp, _u32, _i, _i, _vp, _vp, _vp, _vp]),
+    "rtc_dbscan_mash_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_mash_distance": (C.c_double, [_u32, _u32, _u32, _i]),
+    "rtc_dbscan_mash_table": (_i, [_u32, _i, C.c_double, _vp]),
+    "rtc_pair_mash_edges_dev": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp]),
     "rtc_dbscan_hierarchy": (_i, [_vp, _vp, _i, _vp, _vp, _u32, C.c_double, _i, _i, _i, _vp, C.POINTER(_u64), _vp]),
     "rtc_dbscan_sweep_hierarchy": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _u32, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp,
                                         C.POINTER(_u64), _vp]),

@@ -342,6 +342,23 @@ class Context:
                                               common.stride(0)))
         return common, denom
 
+    def pair_mash_edges(self, sk, sketch_size, pairs):
+        """rtc_pair_mash_edges_dev: pair_mash's (common, denom) for the given pairs alone, an (m, 2) array of indices below sk.n,
+        by the recount kernel of dbscan_mash.  Returns two uint32 arrays of m entries."""
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+        m = len(pairs)
+        if m and (pairs.min() < 0 or pairs.max() >= sk.n):
+            raise ValueError("pair_mash_edges: an index outside [0, n)")
+        edges = np.zeros(max(m, 1), dtype=CEDGE_DT)
+        edges["i"][:m], edges["j"][:m] = pairs[:, 0], pairs[:, 1]
+        d_edges = torch.from_numpy(edges.view(np.uint32).reshape(-1, 3).view(np.int32)).to(self.device)
+        common = torch.zeros(max(m, 1), dtype=torch.int32, device=self.device)
+        denom = torch.zeros(max(m, 1), dtype=torch.int32, device=self.device)
+        self.check(self.lib.rtc_pair_mash_edges_dev(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), sk.n,
+                                                    int(sketch_size), _t_ptr(d_edges), m, _t_ptr(common), _t_ptr(denom)))
+        self.sync()
+        return common[:m].cpu().numpy().view(np.uint32), denom[:m].cpu().numpy().view(np.uint32)
+
     def extract_edges(self, common, sk, row0, row1, col0, col1, radio, cap):
         edges = torch.empty((max(cap, 1), 3), dtype=torch.int32, device=self.device)
         count = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -631,6 +648,33 @@ class Context:
         self.check(self.lib.rtc_dbscan_sweep_counters(self.h, a))
         names = ("chunks", "candidate_edges", "kept_edges", "levels", "hook_rounds", "pair_ns", "predicate_ns", "components_ns",
                  "kdist_ns", "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
+    def dbscan_mash(self, sk, sketch_size, eps_list, min_pts, kmer_size, return_core=False):
+        """clust-dbscan --minhash (rtc_dbscan_mash): MinHashDBSCAN (src/dbscan.cpp:987-1096) over MinHash sketches of at most
+        sketch_size hashes for every eps of eps_list (1 to 32 values in [0, 1), any order) from one pair phase.  A point is a core
+        point with at least min_pts neighbours, itself not counted.  Returns int32 labels[n_eps, n] (-1 noise); with return_core
+        also bool core[n_eps, n].  The call's cluster and noise counts per eps stay in self.dbscan_mash_counts."""
+        n = sk.n
+        eps = np.ascontiguousarray(np.asarray(list(eps_list), dtype=np.float64))
+        L = int(eps.size)
+        labels = np.zeros((L, n), dtype=np.int32)
+        core = np.zeros((L, n), dtype=np.uint8)
+        ncl, nnoise = np.zeros(max(L, 1), dtype=np.uint32), np.zeros(max(L, 1), dtype=np.uint32)
+        buf_l = labels if labels.size else np.zeros(1, dtype=np.int32)
+        buf_c = core if core.size else np.zeros(1, dtype=np.uint8)
+        self.check(self.lib.rtc_dbscan_mash(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n, int(sketch_size),
+                                            _np_ptr(eps) if L else None, L, int(min_pts), int(kmer_size), _np_ptr(buf_l), _np_ptr(buf_c),
+                                            _np_ptr(ncl), _np_ptr(nnoise)))
+        self.dbscan_mash_counts = {"clusters": ncl[:L].copy(), "noise": nnoise[:L].copy()}
+        return (labels, core.astype(bool)) if return_core else labels
+
+    def dbscan_mash_counters(self):
+        """rtc_dbscan_mash_counters as a dict (the last dbscan_mash call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_dbscan_mash_counters(self.h, a))
+        names = ("chunks", "candidate_edges", "merged", "kept_edges", "levels", "hook_rounds", "pair_ns", "predicate_ns",
+                 "components_ns", "total_ns")
         return {k: int(a[i]) for i, k in enumerate(names)}
 
     def dbscan_hierarchy(self, sk, eps_max, min_pts, kmer_size, max_posting=0):

@@ -98,6 +98,8 @@ void rtc_options_from_env(rtc_options* o) {
   o->comm_force_rccl = flag("RTC_COMM_FORCE_RCCL");
   if (const char* e = getenv("RTC_COMM_TIMEOUT_S")) o->comm_timeout_s = atof(e);
   o->dedup_gpu = (int)num("RTC_DEDUP_GPU", 1);
+  o->dbscan_mash_serial = flag("RTC_DBSCAN_MASH_SERIAL");
+  o->dbscan_mash_noprefilter = flag("RTC_DBSCAN_MASH_NOPREFILTER");
 }
 
 extern "C" {

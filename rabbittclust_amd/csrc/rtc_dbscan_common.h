@@ -151,30 +151,34 @@ struct KeptList {
 };
 using FilterKernel = void (*)(const rtc_cedge*, uint64_t, const uint32_t*, EpsLevels, uint32_t, uint32_t, rtc_cedge*, uint64_t, unsigned long long*);
 
-// One chunk of candidates through `filter` into the list.  The list is grown first to hold used + the whole chunk (at most
-// every candidate is kept), so the kernel never runs past it and runs once: doubled while that covers the need, so many row
-// chunks move the list a few times, and the exact size where the doubled list is too small or does not fit.  d_fc: the four
-// device counters of eps_level_mask and wave_append.
+// Room for `need` pairs in the list before a filter runs, so the kernel never runs past it and runs once: doubled while that
+// covers the need, so many row chunks move the list a few times, and the exact size where the doubled list is too small or
+// does not fit.
+int kept_reserve(rtc_ctx* ctx, DevBuf& db, KeptList* L, uint64_t need) {
+  if (need <= L->cap) return RTC_OK;
+  auto regrow = [&](uint64_t want) -> int {
+    rtc_cedge* nd = nullptr;
+    RTC_TRY(db.get(ctx, want, &nd));
+    if (L->used) RTC_HIP(ctx, hipMemcpyAsync(nd, L->d, L->used * sizeof(rtc_cedge), hipMemcpyDeviceToDevice, ctx->stream));
+    RTC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    db.release(L->d);
+    L->d = nd; L->cap = want;
+    return RTC_OK;
+  };
+  if (2 * L->cap <= need || regrow(2 * L->cap) != RTC_OK) {
+    (void)hipGetLastError();  // a doubled list that did not fit is no failure yet: the exact size may
+    RTC_TRY(regrow(need));
+  }
+  return RTC_OK;
+}
+
+// One chunk of candidates through `filter` into the list, grown first to hold used + the whole chunk (at most every candidate
+// is kept: kept_reserve).  d_fc: the four device counters of eps_level_mask and wave_append.
 int filter_chunk(rtc_ctx* ctx, DevBuf& db, const char* who, FilterKernel filter, const rtc_cedge* d_cand, uint64_t m,
                  const uint32_t* d_len, const EpsLevels& lv, uint32_t n_lv, uint32_t sat, unsigned long long* d_fc, KeptList* L) {
   hipStream_t s = ctx->stream;
   const uint64_t t0 = now_ns();
-  const uint64_t need = L->used + m;
-  if (need > L->cap) {
-    auto regrow = [&](uint64_t want) -> int {
-      rtc_cedge* nd = nullptr;
-      RTC_TRY(db.get(ctx, want, &nd));
-      if (L->used) RTC_HIP(ctx, hipMemcpyAsync(nd, L->d, L->used * sizeof(rtc_cedge), hipMemcpyDeviceToDevice, s));
-      RTC_HIP(ctx, hipStreamSynchronize(s));
-      db.release(L->d);
-      L->d = nd; L->cap = want;
-      return RTC_OK;
-    };
-    if (2 * L->cap <= need || regrow(2 * L->cap) != RTC_OK) {
-      (void)hipGetLastError();  // a doubled list that did not fit is no failure yet: the exact size may
-      RTC_TRY(regrow(need));
-    }
-  }
+  RTC_TRY(kept_reserve(ctx, db, L, L->used + m));
   unsigned long long fc[4] = {(unsigned long long)L->used, 0ull, ~0ull, 0ull};
   RTC_HIP(ctx, hipMemcpyAsync(d_fc, fc, sizeof fc, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(filter, dim3(blocks_for(m, ctx->num_cu)), dim3(256), 0, s, d_cand, m, d_len, lv, n_lv, sat, L->d, L->cap, d_fc);

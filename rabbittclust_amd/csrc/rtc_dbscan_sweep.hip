@@ -30,9 +30,14 @@
 // Memory: the kept list (12 B per pair that passes at some level; doubled when short, so up to twice that), one candidate
 // chunk (RTC_EDGE_BUDGET), four words per point and level and one mask word per point, one byte per point and level where the
 // core flags are asked for, and for the curve 32 B per candidate of one chunk plus 16 B x k per point.  Past that: RTC_ERR_NOMEM.
+//
+// rtc_dbscan_mash (clust-dbscan --minhash) is MinHashDBSCAN (:685-720, :987-1096) through the same dbscan_run: the
+// pair phase and everything from the kept list onward are shared; its predicate (rtc_dbscan_mash.h) takes eps_mask_kernel's
+// place and its core rule counts the neighbours alone (|N(v)| >= minPts, :1017, :1050) where KssdDBSCAN's counts the point too.
 #include "rtc_dbscan_common.h"
 #include "rtc_topk_select.h"
 #include "rtc_dbscan_hier.h"
+#include "rtc_dbscan_mash.h"
 
 namespace {
 
@@ -75,10 +80,11 @@ __global__ __launch_bounds__(256) void degree_kernel(const rtc_cedge* __restrict
     }
   }
 }
-// coremask[v] bit l: v is a core point at level l, |N(v)| + 1 >= minPts (:845, :906); parent[l][v] = v, or the first empty
-// sketch for a core empty sketch of the u64 path; *n_core0: the core points of level 0 (one atomic per wave)
+// coremask[v] bit l: v is a core point at level l, |N(v)| + self >= minPts -- self = 1 for KssdDBSCAN, which counts the point
+// (:845, :906), 0 for MinHashDBSCAN (:1017, :1050); parent[l][v] = v, or the first empty sketch for a core empty sketch of the
+// u64 path; *n_core0: the core points of level 0 (one atomic per wave)
 __global__ __launch_bounds__(256) void core_init_kernel(const uint32_t* __restrict__ deg, const uint32_t* __restrict__ len, uint32_t n,
-                                                        uint32_t n_lv, long long min_pts, uint32_t empty_root,
+                                                        uint32_t n_lv, long long min_pts, long long self, uint32_t empty_root,
                                                         uint32_t* __restrict__ coremask, uint32_t* __restrict__ parent,
                                                         unsigned long long* __restrict__ n_core0) {
   const uint32_t lane = threadIdx.x & 63;
@@ -88,7 +94,7 @@ __global__ __launch_bounds__(256) void core_init_kernel(const uint32_t* __restri
     if (v < n) {
       const bool empty = len[v] == 0 && empty_root != 0xffffffffu;
       for (uint32_t l = 0; l < n_lv; l++) {
-        const bool c = (long long)deg[(uint64_t)l * n + v] + 1 >= min_pts;
+        const bool c = (long long)deg[(uint64_t)l * n + v] + self >= min_pts;
         if (c) cm |= 1u << l;
         parent[(uint64_t)l * n + v] = (c && empty) ? empty_root : v;
       }
@@ -296,11 +302,15 @@ int kdist_chunk_host(rtc_ctx* ctx, KdState& K, const rtc_cedge* d_cand, uint64_t
 
 // What a hierarchy call adds to the pair phase (rtc_dbscan_hier.h): the level it keeps pairs at, and where its results go.
 struct HierReq { double eps_max; rtc_hedge* h_forest; uint64_t* h_n_forest; rtc_kdist* h_core; };
+// What makes a call MinHashDBSCAN: the estimator's sketch size.  The levels' predicate is then rtc_dbscan_mash.h's, the core
+// rule |N(v)| >= minPts, and the empty sketches are plain points (distance 1 to everything).
+struct MashReq { uint32_t sketch_size; };
 
 // What one call did.  Every entry point maps it onto its own counter array and touches no other.
 struct DbscanStats {
   bool began = false;  // past the argument checks: from here on the entry point's counters are this call's
   uint64_t chunks = 0, candidates = 0, kept = 0, core0 = 0, asym = 0, rounds = 0;  // core0: the core points of level 0
+  uint64_t merged = 0;  // MinHash: the candidates past the prefilter
   uint64_t pair_ns = 0, filter_ns = 0, components_ns = 0, kdist_ns = 0, total_ns = 0;
   uint64_t h_kept = 0, h_forest = 0, h_rounds = 0, h_rank_ns = 0, h_forest_ns = 0, h_total_ns = 0;  // the hierarchy's
 };
@@ -309,13 +319,24 @@ struct DbscanStats {
 // who: the entry point, for the messages; single: rtc_dbscan, whose one level the messages do not name.
 static int dbscan_run(rtc_ctx* ctx, const char* who, bool single, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len,
                       uint32_t n, const double* h_eps, uint32_t n_eps, int min_pts, int kmer_size, int max_posting, int32_t* h_labels,
-                      uint8_t* h_core, uint32_t* h_n_clusters, uint32_t* h_n_noise, rtc_kdist* h_kdist, const HierReq* hq, DbscanStats* st) {
+                      uint8_t* h_core, uint32_t* h_n_clusters, uint32_t* h_n_noise, rtc_kdist* h_kdist, const HierReq* hq, DbscanStats* st,
+                      const MashReq* mq = nullptr) {
   if (!ctx || (n && (!d_hashes || !d_start || !d_len)) || (width != 4 && width != 8)) return RTC_ERR_ARG;
   if (n_eps > DB_MAX_LEVELS) return rtc_fail(ctx, RTC_ERR_ARG, "%s: %u eps values, at most %u", who, n_eps, DB_MAX_LEVELS);
   if (n_eps == 0 && !h_kdist && !hq) return rtc_fail(ctx, RTC_ERR_ARG, "%s: no eps value and no k-distance curve asked for", who);
   if (hq && (!hq->h_n_forest || (n && !hq->h_core) || (n > 1 && !hq->h_forest))) return RTC_ERR_ARG;
   if (n_eps && (!h_eps || (n && !h_labels))) return RTC_ERR_ARG;
   if (n >= 0x7fffffffu) return rtc_fail(ctx, RTC_ERR_ARG, "%s: %u points", who, n);
+  if (mq) {  // 0 <= eps < 1: from 1 on the pairs without a common hash (distance 1) are neighbours, and no candidate list holds them
+    if (mq->sketch_size == 0 || mq->sketch_size >= (1u << 28)) return rtc_fail(ctx, RTC_ERR_ARG, "%s: sketch size %u", who, mq->sketch_size);
+    if (kmer_size < 1) return rtc_fail(ctx, RTC_ERR_ARG, "%s: k-mer size %d", who, kmer_size);
+    for (uint32_t e = 0; e < n_eps; e++)
+      if (!(h_eps[e] >= 0.0)) return rtc_fail(ctx, RTC_ERR_ARG, "%s: eps %g (value %u of the list) is not in [0, 1)", who, h_eps[e], e);
+    for (uint32_t e = 0; e < n_eps; e++)
+      if (h_eps[e] >= 1.0)
+        return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "%s: eps %g (value %u of the list): from 1 on, pairs without a common hash are neighbours", who,
+                        h_eps[e], e);
+  }
   st->began = true;
   if (hq) *hq->h_n_forest = 0;
   for (uint32_t e = 0; e < n_eps; e++) {
@@ -341,7 +362,7 @@ static int dbscan_run(rtc_ctx* ctx, const char* who, bool single, const void* d_
   EpsLevels lv, hlv;
   memset(&lv, 0, sizeof lv);
   memset(&hlv, 0, sizeof hlv);
-  for (uint32_t e = 0; e < n_eps; e++)
+  for (uint32_t e = 0; e < n_eps && !mq; e++)
     if (!eps_to_t(h_eps[e], kmer_size, &lv.t[e], &lv.one_plus_t[e]))
       return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "%s: %s with k %d gives jaccard_min %g <= 1e-12", who, level((int)e).name, kmer_size, lv.t[e]);
   if (hq && !eps_to_t(hq->eps_max, kmer_size, &hlv.t[0], &hlv.one_plus_t[0]))
@@ -355,7 +376,7 @@ static int dbscan_run(rtc_ctx* ctx, const char* who, bool single, const void* d_
     max_len = std::max(max_len, h_len[g]);
     if (!h_len[g]) empties.push_back(g);
   }
-  if (width == 4) {
+  if (width == 4 && !mq) {
     for (uint32_t e = 0; e < n_eps; e++)
       if (!u32_size_bound_fits(max_len, lv.t[e]))
         return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "%s: %ssize bound ceil(%u / %g) past INT_MAX", who, level((int)e).about, max_len, lv.t[e]);
@@ -368,8 +389,8 @@ static int dbscan_run(rtc_ctx* ctx, const char* who, bool single, const void* d_
   // The u64 brute force (:383-445) has no emptiness test: two empty sketches pass its size filter (0 <= 0) and its inequality
   // (0 + 1e-12 < 0 fails), so the empty sketches are neighbours of each other.  The u32 path skips them (:470-473, :564).
   const uint32_t n_empty = (uint32_t)empties.size();
-  const uint32_t empty_deg = (width == 8 && n_empty) ? n_empty - 1 : 0;
-  const uint32_t empty_root = (width == 8 && n_empty) ? empties[0] : 0xffffffffu;
+  const uint32_t empty_deg = (width == 8 && n_empty && !mq) ? n_empty - 1 : 0;
+  const uint32_t empty_root = (width == 8 && n_empty && !mq) ? empties[0] : 0xffffffffu;
   const long long kth = (long long)min_pts - 1;
   const bool curve = kd_out && kth >= 1;  // k <= 0: every point is its own k-th neighbour, no candidates needed
 
@@ -403,10 +424,14 @@ static int dbscan_run(rtc_ctx* ctx, const char* who, bool single, const void* d_
       K.host.resize(n);
     }
   }
+  MashTables mt;
+  if (mq && n_eps) RTC_TRY(mash_tables(ctx, db, mq->sketch_size, max_len, kmer_size, h_eps, n_eps, &mt));
   PairPhase pp;
   auto on_chunk = [&](const rtc_cedge* d_cand, uint64_t cnt) -> int {
       if (!cnt) return RTC_OK;
-      if (n_eps) RTC_TRY(filter_chunk(ctx, db, who, eps_mask_kernel, d_cand, cnt, d_len, lv, n_eps, sat, d_cnt + 1, &kept));
+      if (n_eps && mq)
+        RTC_TRY(mash_filter_chunk(ctx, db, who, d_hashes, width, d_start, d_len, mq->sketch_size, d_cand, cnt, mt, n_eps, d_cnt + 1, &kept, &st->merged));
+      else if (n_eps) RTC_TRY(filter_chunk(ctx, db, who, eps_mask_kernel, d_cand, cnt, d_len, lv, n_eps, sat, d_cnt + 1, &kept));
       if (hq) RTC_TRY(filter_chunk(ctx, db, who, hier_filter_kernel, d_cand, cnt, d_len, hlv, 1, sat, d_cnt + 1, &hkept));
       if (curve) {
         const uint64_t tk = now_ns();
@@ -505,7 +530,7 @@ static int dbscan_run(rtc_ctx* ctx, const char* who, bool single, const void* d_
   if (m_kept) hipLaunchKernelGGL(degree_kernel, ge, b, 0, s, d_kept, m_kept, n, d_deg);
   RTC_CHECK_LAUNCH(ctx);
   RTC_HIP(ctx, hipMemsetAsync(d_changed, 0, 16, s));
-  hipLaunchKernelGGL(core_init_kernel, gv, b, 0, s, (const uint32_t*)d_deg, d_len, n, L, (long long)min_pts, empty_root, d_coremask, d_parent,
+  hipLaunchKernelGGL(core_init_kernel, gv, b, 0, s, (const uint32_t*)d_deg, d_len, n, L, (long long)min_pts, mq ? 0ll : 1ll, empty_root, d_coremask, d_parent,
                      (unsigned long long*)(d_changed + 2));
   RTC_CHECK_LAUNCH(ctx);
   uint32_t* h_changed = nullptr;
@@ -614,6 +639,57 @@ extern "C" int rtc_dbscan_hierarchy(rtc_ctx* ctx, const void* d_hashes, int widt
                             nullptr, nullptr, nullptr, nullptr, &hq, &st);
   put_hierarchy_counters(ctx, st);
   return rc;
+}
+
+// rtc_dbscan_mash: MinHashDBSCAN for the levels h_eps.  A negative minPts is 0: every point is a core point.
+extern "C" int rtc_dbscan_mash(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                               uint32_t sketch_size, const double* h_eps, uint32_t n_eps, int min_pts, int kmer_size, int32_t* h_labels,
+                               uint8_t* h_core, uint32_t* h_n_clusters, uint32_t* h_n_noise) {
+  if (ctx && n_eps == 0) return rtc_fail(ctx, RTC_ERR_ARG, "rtc_dbscan_mash: no eps value");
+  const MashReq mq{sketch_size};
+  DbscanStats st;
+  const int rc = dbscan_run(ctx, "rtc_dbscan_mash", false, d_hashes, width, d_start, d_len, n, h_eps, n_eps, std::max(min_pts, 0), kmer_size, 0,
+                            h_labels, h_core, h_n_clusters, h_n_noise, nullptr, nullptr, &st, &mq);
+  if (st.began) {
+    const uint64_t c[10] = {st.chunks, st.candidates, st.merged, st.kept, n_eps, st.rounds, st.pair_ns, st.filter_ns, st.components_ns, st.total_ns};
+    std::copy(c, c + 10, ctx->dbscan_mash);
+  }
+  return rc;
+}
+
+extern "C" int rtc_dbscan_mash_counters(const rtc_ctx* ctx, uint64_t out[10]) {
+  if (!ctx || !out) return RTC_ERR_ARG;
+  for (int i = 0; i < 10; i++) out[i] = ctx->dbscan_mash[i];
+  return RTC_OK;
+}
+
+// rtc_dbscan_mash's table for one eps, on the host alone: out[d] for d = 0 .. sketch_size
+extern "C" int rtc_dbscan_mash_table(uint32_t sketch_size, int kmer_size, double eps, uint32_t* out) {
+  if (!out || sketch_size == 0 || sketch_size >= (1u << 28) || kmer_size < 1 || !(eps >= 0.0) || eps >= 1.0) return RTC_ERR_ARG;
+  mash_cmin_row(sketch_size, sketch_size, kmer_size, eps, out);
+  return RTC_OK;
+}
+
+extern "C" double rtc_mash_distance(uint32_t common, uint32_t denom, uint32_t sketch_size, int kmer_size) {
+  return rtc_mash_distance_host(common, denom, sketch_size, kmer_size);
+}
+
+// The recount on its own: the truncated (common, denom) of m given pairs, by the kernel rtc_dbscan_mash runs (the cooperative
+// merge, or the per-thread one under RTC_DBSCAN_MASH_SERIAL).  Context stream, asynchronous.
+extern "C" int rtc_pair_mash_edges_dev(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                                       uint32_t sketch_size, const rtc_cedge* d_edges, uint64_t m, uint32_t* d_common, uint32_t* d_denom) {
+  if (!ctx || !d_start || !d_len || (m && (!d_edges || !d_common || !d_denom))) return RTC_ERR_ARG;
+  if (width != 4 && width != 8) return rtc_fail(ctx, RTC_ERR_ARG, "width must be 4 or 8");
+  if (m == 0 || n == 0) return m ? rtc_fail(ctx, RTC_ERR_ARG, "rtc_pair_mash_edges_dev: pairs of an empty set") : RTC_OK;
+  if (!d_hashes) return RTC_ERR_ARG;
+  RTC_HIP(ctx, hipSetDevice(ctx->device));
+  const MashParams P{nullptr, nullptr, 0, 0};
+  if (ctx->opt.dbscan_mash_serial)
+    mash_edges_launch<true>(ctx, d_hashes, width, d_start, d_len, sketch_size, d_edges, m, P, d_common, d_denom, nullptr, 0, nullptr);
+  else
+    mash_edges_launch<false>(ctx, d_hashes, width, d_start, d_len, sketch_size, d_edges, m, P, d_common, d_denom, nullptr, 0, nullptr);
+  RTC_CHECK_LAUNCH(ctx);
+  return RTC_OK;
 }
 
 extern "C" int rtc_dbscan_counters(const rtc_ctx* ctx, uint64_t out[10]) {

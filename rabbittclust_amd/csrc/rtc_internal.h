@@ -34,6 +34,8 @@ struct rtc_options {
   int comm_force_rccl = 0;         // RTC_COMM_FORCE_RCCL
   double comm_timeout_s = 120.0;   // RTC_COMM_TIMEOUT_S (<= 0: forever)
   int dedup_gpu = 1;               // RTC_DEDUP_GPU: 0 never, 1 groups from the measured cutoff up, 2 every group of two or more
+  int dbscan_mash_serial = 0;      // RTC_DBSCAN_MASH_SERIAL: the per-thread merge instead of the wave-cooperative one
+  int dbscan_mash_noprefilter = 0;  // RTC_DBSCAN_MASH_NOPREFILTER: every candidate is merged
 };
 void rtc_options_from_env(rtc_options* o);
 
@@ -82,6 +84,7 @@ struct rtc_ctx {
   uint64_t dbscan[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t dbscan_sweep[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_dbscan_sweep_counters (include/rtclust.h lists them)
   uint64_t dbscan_hier[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // rtc_dbscan_hierarchy_counters (include/rtclust.h lists them)
+  uint64_t dbscan_mash[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // rtc_dbscan_mash_counters (include/rtclust.h lists them)
   int host_threads = 1;     // rtc_ctx_set_host_threads: the host side of rtc_tree_medoids
   // rtc_diag_counters: [0] pair tiles the join took, [1] tiled-kernel tiles, [2] merge-kernel tiles, [3] candidate lists contracted
   // to their forest, [4] greedy runs replayed from ONE global join, [5] greedy query blocks of the block loop, [6] estimates handed

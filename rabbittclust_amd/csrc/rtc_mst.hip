@@ -384,6 +384,12 @@ static double host_mst_distance(int common, int size0, int size1, int kmer_size,
   return -inv_kmer_size * log(containment);
 }
 
+// the same distance for a given (common, denom) of the truncated merge, denom <= sketch_size (rtc_dbscan_mash.h's tables):
+// sizes (denom, common) give weight_denom the union denom + common - common
+double rtc_mash_distance_host(uint32_t common, uint32_t denom, uint32_t sketch_size, int kmer_size) {
+  return host_mst_distance((int)common, (int)denom, (int)common, kmer_size, 2 | (int)(sketch_size << 2));
+}
+
 // the union step of a round (hook + relabel + the counter read back): rtc_boruvka_union_dev and the multi-GPU rounds
 static int boruvka_union_round(rtc_ctx* ctx, uint32_t n, const RoundKeys& K, uint32_t* d_comp, uint32_t* d_succ, rtc_cedge* d_sel,
                                uint64_t* d_nsel, uint32_t* h_added) {

@@ -869,6 +869,8 @@ struct Options {
   bool kdist = false;       // clust-dbscan --kdist: the k-distance curve, k = minPts - 1
   bool hierarchy = false;   // clust-dbscan --hierarchy: the density hierarchy below --eps (rtc_dbscan_hierarchy) and its flat clustering
   bool hasMinClusterSize = false;
+  bool minhash = false;     // clust-dbscan --minhash: MinHashDBSCAN over MinHash sketches (rtc_dbscan_mash) instead of --fast
+  bool hasMaxPosting = false;
   int minClusterSize = 0;   // --min-cluster-size (default: --minpts)
 };
 
@@ -887,7 +889,8 @@ static Options parse(int argc, char** argv) {
     // -c (given to the KSSD tuner, as src/main.cpp:516 does), -s and --save-rep (no effect on DBSCAN) are parsed below.
     if (a == "--eps") { o.dbscanEps = atof(need(i)); continue; }
     if (a == "--minpts") { o.dbscanMinPts = atoi(need(i)); continue; }
-    if (a == "--max-posting") { o.maxPosting = atoi(need(i)); continue; }
+    if (a == "--max-posting") { o.maxPosting = atoi(need(i)); o.hasMaxPosting = true; continue; }
+    if (a == "--minhash") { o.minhash = true; continue; }
     if (a == "--eps-sweep") {
       // e1,e2,...: at most 32 values, each > 0 as atof reads it
       const string v = need(i);
@@ -962,7 +965,7 @@ static Options parse(int argc, char** argv) {
 #ifdef GREEDY_CLUST
       puts("clust-greedy (MI355X build): greedy incremental clustering module");
 #elif defined(DBSCAN_CLUST)
-      puts("clust-dbscan (MI355X build): DBSCAN density-based clustering module (KSSD, --fast)");
+      puts("clust-dbscan (MI355X build): DBSCAN density-based clustering module (KSSD with --fast, MinHash with --minhash)");
       puts("  -t,--threads N  -m,--min-length N  -k,--kmer-size N  -l,--list  -e,--no-save  -d,--threshold X (KSSD tuner)\n"
            "  -o,--output FILE  -i,--input FILE  --presketched DIR  --fast  --drlevel N  --gpus all|N|i,j,..\n"
            "  --eps X (default 0.05)  --minpts N (default 5)  --max-posting M (0: off)\n"
@@ -970,6 +973,9 @@ static Options parse(int argc, char** argv) {
            "  --kdist (FILE.kdist.tsv: every genome's distance to its (minpts - 1)-th nearest candidate, largest first)\n"
            "  --hierarchy (the density hierarchy of every eps up to --eps from the same pair phase: FILE.hierarchy.tsv, FILE.core.tsv,\n"
            "               and FILE.hdbscan, a flat clustering that needs no eps)  --min-cluster-size M (default: --minpts, >= 2)\n"
+           "  --minhash (instead of --fast: MinHash sketches as clust-mst makes and saves them, -k / -s / -m as there, or a MinHash\n"
+           "             --presketched DIR; neighbours by MinHash::distance() <= eps, 0 <= eps < 1, a core point has minpts neighbours\n"
+           "             besides itself; with --eps-sweep, not with --kdist, --hierarchy, --min-cluster-size, --max-posting or -c)\n"
            "  -c,--containment N (KSSD tuner)  -s,--sketch-size N  --save-rep (accepted, no effect on DBSCAN)  --knn: not in this build");
       exit(0);
 #else
@@ -2138,6 +2144,16 @@ int main(int argc, char** argv) {
   if (o.has_append && !o.has_presketched && o.repdb_path.empty()) { cerr << "ERROR option --append, option --presketched needed" << endl; return 1; }  // src/main.cpp:378-381
 #endif
 #ifdef DBSCAN_CLUST
+  // ---- clust-dbscan --minhash: this build's own flag, what it excludes named before any GPU context exists ----
+  if (o.minhash) {
+    const char* bad = o.is_fast ? "--fast (the two sketch kinds exclude each other)" : o.kdist ? "--kdist" : o.hierarchy ? "--hierarchy"
+                      : o.hasMinClusterSize ? "--min-cluster-size" : o.hasMaxPosting ? "--max-posting" : o.isContainment ? "-c/--containment" : nullptr;
+    if (bad) { cerr << "ERROR: --minhash does not go with " << bad << endl; return 1; }
+    vector<double> all = o.epsSweep;
+    all.push_back(o.dbscanEps);
+    for (double e : all)
+      if (!(e >= 0.0 && e < 1.0)) { cerr << "ERROR: --minhash needs 0 <= eps < 1, got " << e << endl; return 1; }
+  }
   // ---- clust-dbscan --hierarchy: this build's own flags, checked before anything of the reference's ----
   if (o.hasMinClusterSize && !o.hierarchy) { cerr << "ERROR: --min-cluster-size needs --hierarchy" << endl; return 1; }
   if (o.hierarchy && !o.hasMinClusterSize) o.minClusterSize = o.dbscanMinPts;
@@ -2146,7 +2162,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   // ---- clust-dbscan: the checks of src/main.cpp:478-517, in that order ----
-  if (!o.is_fast) { cerr << "ERROR: clust-dbscan requires --fast option" << endl; return 1; }
+  if (!o.is_fast && !o.minhash) { cerr << "ERROR: clust-dbscan requires --fast option" << endl; return 1; }
   cerr << "-----Using DBSCAN clustering" << endl;
   cerr << "-----DBSCAN parameters: eps=" << o.dbscanEps << ", minPts=" << o.dbscanMinPts;
   if (o.maxPosting > 0) cerr << ", max-posting=" << o.maxPosting;
@@ -2501,11 +2517,27 @@ int main(int argc, char** argv) {
   g_metrics.num("greedyCluster_s", get_sec() - t2);
   g_metrics.num("clusters", (double)cluster.size());
 #elif defined(DBSCAN_CLUST)
-  // ---- clust-dbscan: KssdDBSCAN (src/dbscan.cpp:725-985) on the first GPU, printKssdDBSCANResult (:1212-1310) ----
+  // ---- clust-dbscan: KssdDBSCAN (src/dbscan.cpp:725-985) on the first GPU, printKssdDBSCANResult (:1212-1310); with
+  // --minhash MinHashDBSCAN (:987-1096) and printDBSCANResult (:1102-1210), whose layout is the same ----
+  if (o.minhash && mh.isContainment) { cerr << "ERROR: --minhash: " << folder_path << " holds containment sketches (-c), which are out of scope" << endl; return 1; }
   DeviceSketches ds;
   if (rs.ok) resident_sketches(ctx, gpus[0], rs, nullptr, ds);
+  else if (o.minhash) upload_sketches(ctx, &mh.hashes, nullptr, ds);
   else upload_sketches(ctx, ks.use64 ? &ks.h64 : nullptr, ks.use64 ? nullptr : &ks.h32, ds);
-  cerr << "-----Running DBSCAN clustering (KSSD)..." << endl;
+  auto dbscan_mash = [&](const double* eps, size_t L, int32_t* lab, uint8_t* cr, uint32_t* nc, uint32_t* nn) {
+    CHECK(ctx, rtc_dbscan_mash(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, (uint32_t)mh.sketchSize, eps, (uint32_t)L, o.dbscanMinPts,
+                               kmer_size, lab, cr, nc, nn));
+    uint64_t mc[10] = {0};
+    rtc_dbscan_mash_counters(ctx, mc);
+    if (getenv("RTC_VERBOSE"))
+      fprintf(stderr, "[minhash] %zu levels: %llu candidate edges in %llu chunk(s), %llu merged, %llu kept; pair %.3f ms, predicate %.3f ms, "
+              "components %.3f ms\n", L, (unsigned long long)mc[1], (unsigned long long)mc[0], (unsigned long long)mc[2], (unsigned long long)mc[3],
+              mc[6] / 1e6, mc[7] / 1e6, mc[8] / 1e6);
+    g_metrics.num("dbscan_mash_pair_s", mc[6] / 1e9);
+    g_metrics.num("dbscan_mash_predicate_s", mc[7] / 1e9);
+    g_metrics.num("dbscan_mash_components_s", mc[8] / 1e9);
+  };
+  cerr << "-----Running DBSCAN clustering (" << (o.minhash ? "MinHash" : "KSSD") << ")..." << endl;
   cerr << "-----Parameters: eps=" << o.dbscanEps << ", minPts=" << o.dbscanMinPts << endl;
   vector<int32_t> labels(genomes.size());
   vector<uint8_t> core(genomes.size());
@@ -2513,7 +2545,9 @@ int main(int argc, char** argv) {
   vector<rtc_hedge> forest(o.hierarchy ? genomes.size() : 0);  // --hierarchy: n - 1 slots, the core triples beside them
   vector<rtc_kdist> hcore(o.hierarchy ? genomes.size() : 0);
   uint64_t n_forest = 0;
-  if (o.epsSweep.empty() && !o.kdist && !o.hierarchy) {
+  if (o.minhash && o.epsSweep.empty()) {
+    dbscan_mash(&o.dbscanEps, 1, labels.data(), core.data(), &ncl, &nnoise);
+  } else if (o.epsSweep.empty() && !o.kdist && !o.hierarchy) {
     CHECK(ctx, rtc_dbscan(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, o.dbscanEps, o.dbscanMinPts, kmer_size, o.maxPosting,
                           labels.data(), core.data(), &ncl, &nnoise));
   } else {
@@ -2529,7 +2563,9 @@ int main(int argc, char** argv) {
     vector<uint8_t> all_core(L * n);
     vector<uint32_t> all_ncl(L), all_nnoise(L);
     vector<rtc_kdist> kd(o.kdist ? n : 0);
-    if (o.hierarchy) {  // the hierarchy below --eps from the sweep's pair phase
+    if (o.minhash) {
+      dbscan_mash(levels.data(), L, all_labels.data(), all_core.data(), all_ncl.data(), all_nnoise.data());
+    } else if (o.hierarchy) {  // the hierarchy below --eps from the sweep's pair phase
       CHECK(ctx, rtc_dbscan_sweep_hierarchy(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, levels.data(), (uint32_t)L, o.dbscanMinPts,
                                             kmer_size, o.maxPosting, all_labels.data(), all_core.data(), all_ncl.data(), all_nnoise.data(),
                                             o.kdist ? kd.data() : nullptr, o.dbscanEps, forest.data(), &n_forest, hcore.data()));
@@ -2549,17 +2585,21 @@ int main(int argc, char** argv) {
                                   o.maxPosting, all_labels.data(), all_core.data(), all_ncl.data(), all_nnoise.data(), o.kdist ? kd.data() : nullptr));
     }
     uint64_t sc[10] = {0};
-    rtc_dbscan_sweep_counters(ctx, sc);
-    if (getenv("RTC_VERBOSE"))
+    if (!o.minhash) rtc_dbscan_sweep_counters(ctx, sc);
+    if (getenv("RTC_VERBOSE") && !o.minhash)
       fprintf(stderr, "[sweep] %zu levels: %llu candidate edges in %llu chunk(s), %llu kept; pair %.3f ms, predicate %.3f ms, components %.3f ms, "
               "k-distance %.3f ms\n", L, (unsigned long long)sc[1], (unsigned long long)sc[0], (unsigned long long)sc[2], sc[5] / 1e6, sc[6] / 1e6,
               sc[7] / 1e6, sc[8] / 1e6);
     g_metrics.num("dbscan_sweep_levels", (double)L);
-    g_metrics.num("dbscan_sweep_pair_s", sc[5] / 1e9);
-    g_metrics.num("dbscan_sweep_predicate_s", sc[6] / 1e9);
-    g_metrics.num("dbscan_sweep_components_s", sc[7] / 1e9);
-    g_metrics.num("dbscan_sweep_kdist_s", sc[8] / 1e9);
-    if (own_call) {
+    if (!o.minhash) {
+      g_metrics.num("dbscan_sweep_pair_s", sc[5] / 1e9);
+      g_metrics.num("dbscan_sweep_predicate_s", sc[6] / 1e9);
+      g_metrics.num("dbscan_sweep_components_s", sc[7] / 1e9);
+      g_metrics.num("dbscan_sweep_kdist_s", sc[8] / 1e9);
+    }
+    if (own_call && o.minhash) {
+      dbscan_mash(&o.dbscanEps, 1, labels.data(), core.data(), &ncl, &nnoise);
+    } else if (own_call) {
       CHECK(ctx, rtc_dbscan(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, o.dbscanEps, o.dbscanMinPts, kmer_size, o.maxPosting,
                             labels.data(), core.data(), &ncl, &nnoise));
     } else {
@@ -2651,7 +2691,13 @@ int main(int argc, char** argv) {
     cerr << "-----write the core distances into: " << ctsv << endl;
     cerr << "-----write the flat clustering (min_cluster_size=" << o.minClusterSize << ", " << flat_ncl << " clusters) into: " << flat << endl;
   }
-  dbscan_report(labels, core, ncl, nnoise);
+  if (o.minhash) {  // MinHashDBSCAN's closing lines (:1091-1093): it counts no core points
+    cerr << "-----DBSCAN clustering complete!" << endl;
+    cerr << "-----Found " << ncl << " clusters" << endl;
+    cerr << "-----Found " << nnoise << " noise points (outliers)" << endl;
+  } else {
+    dbscan_report(labels, core, ncl, nnoise);
+  }
   print_dbscan_result(labels, ncl, genomes, sketchByFile, dbscan_format_mismatch, o.outputFile, o.dbscanEps, o.dbscanMinPts);
   cerr << "-----write the cluster result into: " << o.outputFile << endl;
   cerr << "-----the cluster number of " << o.outputFile << " is: " << ncl << endl;

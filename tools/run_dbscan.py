@@ -15,6 +15,11 @@ Sets (KSSD u32 sketches from synthetic genomes, k 21, drlevel 3, sketched on the
   cfg4_200k  200 000 x 2 Mbp genomes in families of ten: BASELINE config[4]'s shape on one GPU, sketched in batches of 25 000;
   sparse25k / sparse200k  host-drawn random u32 sets of ~1 100 / ~330 hashes in families of ten (~2 % of a member's hashes
              replaced): a sparse eps graph.
+--minhash times Context.dbscan_mash (clust-dbscan --minhash) instead, on 10 000 MinHash sketches of s = 1000 in 10 families of
+1 000 (bench.py's extra.dense_pairs shape), --eps and --sweep as its levels: one JSON line with the counters of the best of
+--repeat warm calls for each of the four configurations -- the wave-cooperative merge and RTC_DBSCAN_MASH_SERIAL=1, each with
+the prefilter and with RTC_DBSCAN_MASH_NOPREFILTER=1 -- and whether the four label sets are identical.
+
 Prints one JSON line per set.  The kernel split under rocprofv3 --kernel-trace --stats comes from a run of its own."""
 import argparse
 import json
@@ -116,6 +121,39 @@ def _sweep_row(ctx, sk, name, n, kmer, eps_list, a):
     return row
 
 
+def _minhash_rows(ctx, api, a, n=10_000, fam=10, rate=0.01, L=500_000, s=1000, k=21):
+    desc = api.synth_family_descs(fam, n // fam, global_seed=42, max_rate=rate)
+    off = np.arange(n + 1, dtype=np.uint64) * np.uint64(L)
+    seq = ctx.synth_genomes(desc, off)
+    sk = ctx.sketch_minhash(seq, off, k=k, size=s)
+    ctx.sync()
+    del seq
+    eps_list = [float(x) for x in a.sweep.split(",")] if a.sweep else [a.eps]
+    row = {"set": "minhash10k", "n": n, "sketch_size": s, "kmer": k, "minpts": a.minpts, "eps": eps_list, "configs": {}}
+    labels = []
+    for name, env in (("cooperative", {}), ("cooperative_noprefilter", {"RTC_DBSCAN_MASH_NOPREFILTER": "1"}),
+                      ("serial", {"RTC_DBSCAN_MASH_SERIAL": "1"}),
+                      ("serial_noprefilter", {"RTC_DBSCAN_MASH_SERIAL": "1", "RTC_DBSCAN_MASH_NOPREFILTER": "1"})):
+        with ctx.env(RTC_DBSCAN_MASH_SERIAL=env.get("RTC_DBSCAN_MASH_SERIAL"), RTC_DBSCAN_MASH_NOPREFILTER=env.get("RTC_DBSCAN_MASH_NOPREFILTER")):
+            ctx.dbscan_mash(sk, s, eps_list, a.minpts, k)  # warm-up
+            ts, cs = [], []
+            for _ in range(a.repeat):
+                t0 = time.perf_counter()
+                lab = ctx.dbscan_mash(sk, s, eps_list, a.minpts, k)
+                ts.append(time.perf_counter() - t0)
+                cs.append(ctx.dbscan_mash_counters())
+        c = cs[int(np.argmin([x["predicate_ns"] for x in cs]))]
+        labels.append(lab)
+        row["configs"][name] = {"call_ms": round(min(ts) * 1e3, 3), "pair_ms": round(c["pair_ns"] / 1e6, 3),
+                                "predicate_ms": round(c["predicate_ns"] / 1e6, 3), "components_ms": round(c["components_ns"] / 1e6, 3),
+                                "chunks": c["chunks"], "candidate_edges": c["candidate_edges"], "merged": c["merged"],
+                                "kept_edges": c["kept_edges"], "hook_rounds": c["hook_rounds"]}
+    row["identical"] = all(np.array_equal(labels[0], x) for x in labels[1:])
+    row["clusters"] = [int(x.max(initial=-1)) + 1 for x in labels[0]]
+    row["noise"] = [int((x < 0).sum()) for x in labels[0]]
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="dense25k,cfg4_200k")
@@ -127,10 +165,15 @@ def main():
     ap.add_argument("--kdist", action="store_true")
     ap.add_argument("--separate-only", action="store_true")
     ap.add_argument("--hierarchy", action="store_true")
+    ap.add_argument("--minhash", action="store_true")
     a = ap.parse_args()
     import torch
     from rabbittclust_amd import api
     ctx = api.Context(0)
+    if a.minhash:
+        print(json.dumps(_minhash_rows(ctx, api, a)), flush=True)
+        ctx.close()
+        return
     for name in a.sets.split(","):
         if name in SPARSE:
             n, size, per = SPARSE[name]
