@@ -598,6 +598,46 @@ int rtc_hierarchy_cut(uint32_t n, const rtc_hedge* h_forest, uint64_t n_forest, 
 int rtc_hierarchy_flat(uint32_t n, const rtc_hedge* h_forest, uint64_t n_forest, const rtc_kdist* h_core, int kmer_size,
                        int min_cluster_size, int32_t* h_labels, double* h_stability, uint32_t* n_clusters);
 
+/* ---- clust-dbscan --db --assign: new points placed into a clustered set ------------------------------- */
+/* DBSCAN's border rule applied to a point that was not there.  The reference has nothing of the kind: this is the definition.
+ * A model is a clustered sketch set: the rows [0, n_db) of the set with rtc_dbscan's (is_minhash = 0) or rtc_dbscan_mash's
+ * (is_minhash = 1, sketch_size as there) labels h_labels[n_db] and core flags h_core[n_db] for ONE (eps, min_pts, kmer_size),
+ * clustered WITHOUT max_posting.  The rows [n_db, n_db + n_queries) are the queries, the layout of rtc_rep_topk.  For a query q:
+ *   - N(q): the model points p the model's own predicate accepts.  KSSD: rtc_dbscan's, both orientations in double with the
+ *     1e-12 term and the size bounds, on the count that predicate sees (saturated at 65 535 at width 4); at width 8 an empty
+ *     query is the neighbour of every empty model sketch and of nothing else, at width 4 of nothing.  A pair whose two
+ *     orientations disagree fails the call with RTC_ERR_UNSUPPORTED, the message naming the pair.  MinHash:
+ *     rtc_mash_distance(common, denom) <= eps, decided through rtc_dbscan_mash_table; the device forms no distance.
+ *   - label / label_max: the lowest / highest cluster number among the CORE points of N(q), both -1 where there is none (noise;
+ *     the command line prints "novel").  label != label_max: q would bridge clusters.
+ *   - n_neighbours = |N(q)|, n_core = the core points among them.
+ *   - flags bit 0: q would itself be a core point -- KSSD n_neighbours + 1 >= min_pts, MinHash n_neighbours >= max(min_pts, 0).
+ *   - nearest, common, denom: over ALL model points sharing a hash with q, in N(q) or not, the one with the largest
+ *     common / denom, compared exactly by 64-bit cross-multiplication (common_a * denom_b against common_b * denom_a) as
+ *     rtc_rep_topk compares; equal keys go to the lower index.  KSSD: common as above, denom = |p| + |q| - common; MinHash: the
+ *     union-truncated counts.  nearest = UINT32_MAX and zeros when q shares no hash with the model.  The caller forms the
+ *     distance with its libm.
+ *   - Queries never see each other, and the model is not changed.
+ * Anchor: if adding q last to a set S changes no core flag of S and q is not a core point of S + {q}, DBSCAN on S + {q}
+ * labels S as it labels S alone and gives q exactly `label`.
+ * query_chunk: queries per join (0: all); a chunk whose candidates exceed RTC_EDGE_BUDGET or whose join scratch does not fit
+ * is halved -- down to one join per query, each with its three host round trips -- and RTC_ERR_NOMEM past one query; no fallback.  Errors as rtc_dbscan / rtc_dbscan_mash for the kind: MinHash eps < 0
+ * or NaN RTC_ERR_ARG, eps >= 1 RTC_ERR_UNSUPPORTED; KSSD jaccard_min <= 1e-12 and, at width 4, a size bound past INT_MAX
+ * RTC_ERR_UNSUPPORTED; h_labels or h_core NULL with n_db > 0 RTC_ERR_ARG.  Containment sketches are out of scope.  Synchronous. */
+typedef struct { int32_t label, label_max; uint32_t n_neighbours, n_core, nearest, common, denom, flags; } rtc_dbscan_place;
+int rtc_dbscan_assign(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len,
+                      uint32_t n_db, uint32_t n_queries, const int32_t* h_labels, const uint8_t* h_core,
+                      int is_minhash, uint32_t sketch_size, double eps, int min_pts, int kmer_size,
+                      uint32_t query_chunk, rtc_dbscan_place* h_out);
+/* What the last rtc_dbscan_assign call did: out[0] query chunks, out[1] candidates (pairs sharing a hash; a MinHash model merges
+ * every one of them, a KSSD model none), out[2] neighbours found (the sum of n_neighbours), out[3] queries placed (label >= 0),
+ * out[4] novel, out[5] bridging (among the placed), out[6] join ns, out[7] predicate and bucketing ns, out[8] fold ns, out[9]
+ * whole call ns.  A call that fails after its argument checks leaves zeros. */
+int rtc_dbscan_assign_counters(const rtc_ctx* ctx, uint64_t out[10]);
+/* The fold paths of the last rtc_dbscan_assign call: bit 0 one wave per query (segments of up to 4 096 candidates), bit 1 a
+ * 256-lane workgroup (the longer ones). */
+int rtc_dbscan_assign_last_path(const rtc_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,9 @@ SIGNATURES = {
     "rtc_dbscan_sweep_hierarchy": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _u32, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp,
                                         C.POINTER(_u64), _vp]),
     "rtc_dbscan_hierarchy_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_dbscan_assign": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _u32, _vp, _vp, _i, _u32, C.c_double, _i, _i, _u32, _vp]),
+    "rtc_dbscan_assign_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_dbscan_assign_last_path": (_i, [_vp]),
     "rtc_hierarchy_cut": (_i, [_u32, _vp, _u64, _vp, C.c_double, C.c_double, _i, _vp, _vp, C.POINTER(_u32)]),
     "rtc_hierarchy_flat": (_i, [_u32, _vp, _u64, _vp, _i, _i, _vp, _vp, C.POINTER(_u32)]),
 }

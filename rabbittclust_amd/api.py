@@ -23,6 +23,10 @@ KDIST_DT = np.dtype([("common", "<u4"), ("size_p", "<u4"), ("size_q", "<u4"), ("
 # Context.dbscan_sweep's curve: rtc_kdist plus the distance the host forms from it
 KDIST_CURVE_DT = np.dtype(KDIST_DT.descr + [("distance", "<f8")])
 KDIST_NONE = 0xFFFFFFFF  # neighbour of a point with fewer than minPts - 1 candidates (distance inf)
+# rtc_dbscan_place
+PLACE_DT = np.dtype([("label", "<i4"), ("label_max", "<i4"), ("n_neighbours", "<u4"), ("n_core", "<u4"), ("nearest", "<u4"),
+                     ("common", "<u4"), ("denom", "<u4"), ("flags", "<u4")])
+PLACE_NONE = 0xFFFFFFFF  # nearest of a query that shares no hash with the model
 HEDGE_DT = np.dtype([("p", "<u4"), ("q", "<u4"), ("common", "<u4"), ("size_p", "<u4"), ("size_q", "<u4")])  # rtc_hedge
 
 
@@ -676,6 +680,35 @@ class Context:
         names = ("chunks", "candidate_edges", "merged", "kept_edges", "levels", "hook_rounds", "pair_ns", "predicate_ns",
                  "components_ns", "total_ns")
         return {k: int(a[i]) for i, k in enumerate(names)}
+
+    def dbscan_assign(self, sk, n_db, labels, core, eps, min_pts, kmer_size, sketch_size=None, query_chunk=0):
+        """clust-dbscan --db --assign (rtc_dbscan_assign): sk holds the n_db model points, then the queries; labels / core are the
+        model's, from Context.dbscan (sketch_size None) or Context.dbscan_mash (sketch_size: the estimator's) at this eps,
+        min_pts and kmer_size.  Returns PLACE_DT per query: label / label_max (-1: novel; different: a bridge), n_neighbours,
+        n_core, nearest (PLACE_NONE: no shared hash) with its common / denom, flags (bit 0: would be a core point)."""
+        nq = sk.n - int(n_db)
+        if nq < 0:
+            raise ValueError("n_db exceeds the sketch set")
+        lab = None if labels is None else np.ascontiguousarray(np.asarray(labels, dtype=np.int32))
+        cr = None if core is None else np.ascontiguousarray(np.asarray(core, dtype=np.uint8))
+        if (lab is not None and lab.shape != (int(n_db),)) or (cr is not None and cr.shape != (int(n_db),)):
+            raise ValueError("labels and core need one entry per model point")
+        out = np.zeros(max(nq, 1), dtype=PLACE_DT)
+        self.check(self.lib.rtc_dbscan_assign(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), int(n_db), nq,
+                                              _np_ptr(lab) if lab is not None else None, _np_ptr(cr) if cr is not None else None,
+                                              0 if sketch_size is None else 1, 0 if sketch_size is None else int(sketch_size),
+                                              float(eps), int(min_pts), int(kmer_size), int(query_chunk), _np_ptr(out)))
+        return out[:nq].copy()
+
+    def dbscan_assign_counters(self):
+        """rtc_dbscan_assign_counters as a dict (the last dbscan_assign call); fold_paths: bit 0 one wave per query, bit 1 a
+        256-lane workgroup (rtc_dbscan_assign_last_path)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_dbscan_assign_counters(self.h, a))
+        names = ("chunks", "candidates", "neighbours", "placed", "novel", "bridging", "join_ns", "predicate_ns", "fold_ns", "total_ns")
+        out = {k: int(a[i]) for i, k in enumerate(names)}
+        out["fold_paths"] = int(self.lib.rtc_dbscan_assign_last_path(self.h))
+        return out
 
     def dbscan_hierarchy(self, sk, eps_max, min_pts, kmer_size, max_posting=0):
         """clust-dbscan --hierarchy (rtc_dbscan_hierarchy): the maximum spanning forest of the mutual-reachability relation over

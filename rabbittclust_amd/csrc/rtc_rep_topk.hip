@@ -29,16 +29,6 @@
 
 namespace {
 
-__global__ __launch_bounds__(256) void tk_count_kernel(const rtc_cedge* __restrict__ e, uint64_t m, uint32_t row0, uint32_t nq,
-                                                       uint32_t n_reps, const uint8_t* __restrict__ live, uint32_t* __restrict__ cnt) {
-  const uint64_t a = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (a >= m) return;
-  const rtc_cedge c = e[a];
-  const uint32_t q = c.i - row0;
-  if (q >= nq || c.j >= n_reps || (live && !live[c.j])) return;
-  atomicAdd(&cnt[q], 1u);
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void tk_scatter_kernel(const rtc_cedge* __restrict__ e, uint64_t m, uint32_t row0, uint32_t nq,
                                                          uint32_t n_reps, const uint8_t* __restrict__ live,

@@ -1,5 +1,6 @@
 // rtc_topk_select.h -- segmented top-k by an exact rational key, shared by rtc_rep_topk.hip (the best representatives of a
-// query) and rtc_dbscan_sweep.hip (the k-th nearest candidate of a point): the record, its total order, the one-workgroup
+// query), rtc_dbscan_sweep.hip (the k-th nearest candidate of a point) and rtc_dbscan_assign.hip (a query's candidates, folded
+// instead of selected): the record, its total order, the per-query count of the join's candidates, the one-workgroup
 // scan of the segment offsets and the running top-k selection in LDS (one wave for segments of up to TK_LONG records, 256
 // lanes for the longer ones).  DESIGN 3.4b describes the selection.
 #pragma once
@@ -21,6 +22,17 @@ __device__ __forceinline__ bool tk_beats(const TkRec& a, const TkRec& b) {
 static bool tk_beats_host(const TkRec& a, const TkRec& b) {
   const uint64_t l = (uint64_t)a.common * b.denom, r = (uint64_t)b.common * a.denom;
   return l != r ? l > r : a.slot < b.slot;
+}
+
+// a lane per candidate (row0 + q, slot, common) of the join: cnt[q] += 1 for the live slots below n_reps (live == NULL: all)
+__global__ __launch_bounds__(256) void tk_count_kernel(const rtc_cedge* __restrict__ e, uint64_t m, uint32_t row0, uint32_t nq,
+                                                       uint32_t n_reps, const uint8_t* __restrict__ live, uint32_t* __restrict__ cnt) {
+  const uint64_t a = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= m) return;
+  const rtc_cedge c = e[a];
+  const uint32_t q = c.i - row0;
+  if (q >= nq || c.j >= n_reps || (live && !live[c.j])) return;
+  atomicAdd(&cnt[q], 1u);
 }
 
 // one workgroup of TK_SCAN_THREADS: off[q] = sum of cnt[0 .. q), koff[q] = sum of min(cnt, k) (k == 0: cnt); off[nq], koff[nq]: totals

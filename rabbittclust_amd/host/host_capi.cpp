@@ -179,4 +179,12 @@ int rtch_mst_state_append(const char* in_state, int kssd, int n_queries, const c
   if (out_state && out_state[0] && !save_mst_state(out_state, st)) return -1;
   return (int)live.size();
 }
+
+// a clust-dbscan --db model read and written back (tests: the loader and the writer against the documented layout)
+int rtch_dbscan_model_resave(const char* in_path, const char* out_path) {
+  DbscanModel m;
+  std::string why;
+  if (!load_dbscan_model(in_path, m, &why)) return -1;
+  return save_dbscan_model(out_path, m) ? 0 : -2;
+}
 }

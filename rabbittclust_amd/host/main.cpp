@@ -910,7 +910,7 @@ static Options parse(int argc, char** argv) {
     if (a == "--hierarchy") { o.hierarchy = true; continue; }
     if (a == "--min-cluster-size") { o.minClusterSize = atoi(need(i)); o.hasMinClusterSize = true; continue; }
     if (a == "--knn") unsupported("--knn (approximate k-NN DBSCAN)");
-    if (a == "--db" || a == "--build" || a == "--query" || a == "--assign" || a == "--stats" || a == "--top-k" || a == "--dense" ||
+    if (a == "--query" || a == "--top-k" || a == "--dense" ||
         a == "--premsted" || a == "--auto-threshold" || a == "--stability" || a == "--dedup-dist" || a == "--reps-per-cluster" ||
         a == "--newick-tree" || a == "--phylip-tree" || a == "--nexus-tree" || a == "--linkage-matrix" || a == "--buildDB") {
       fprintf(stderr, "ERROR: unknown option %s\n", a.c_str());
@@ -976,6 +976,12 @@ static Options parse(int argc, char** argv) {
            "  --minhash (instead of --fast: MinHash sketches as clust-mst makes and saves them, -k / -s / -m as there, or a MinHash\n"
            "             --presketched DIR; neighbours by MinHash::distance() <= eps, 0 <= eps < 1, a core point has minpts neighbours\n"
            "             besides itself; with --eps-sweep, not with --kdist, --hierarchy, --min-cluster-size, --max-posting or -c)\n"
+           "  --db FILE --build (with the flags above: the run as without --db, then the model of --eps -- labels, core flags, genome\n"
+           "                     records and all sketches -- into FILE; not with --max-posting)\n"
+           "  --db FILE --assign (-l -i LIST | -i FASTA) -o assign.tsv (new genomes placed into the model on the GPU: kind, k, sketch\n"
+           "                     parameters, eps and minpts come from FILE; per query its cluster or novel, bridges, neighbours, core\n"
+           "                     neighbours, would_be_core, the nearest genome and its distance)\n"
+           "  --db FILE --stats (kind, parameters, genomes, clusters, noise and core points of FILE; no GPU)\n"
            "  -c,--containment N (KSSD tuner)  -s,--sketch-size N  --save-rep (accepted, no effect on DBSCAN)  --knn: not in this build");
       exit(0);
 #else
@@ -2079,6 +2085,95 @@ static void print_dbscan_result(const vector<int32_t>& labels, uint32_t ncl, con
   }
   fclose(fp);
 }
+
+// clust-dbscan --db FILE --assign: the queries sketched as the model's genomes were, placed by rtc_dbscan_assign, one TSV line each
+static int dbscan_db_assign(const Options& o, vector<Gpu>& gpus, const DbscanModel& md) {
+  rtc_ctx* ctx = gpus[0].ctx;
+  SketchJob job;
+  job.kssd = !md.minhash; job.kmerSize = md.kmer_size; job.minLen = md.min_len; job.threads = o.threads;
+  if (md.minhash) job.sketchSize = md.sketch_size;
+  else job.drlevel = md.drlevel;
+  const double t0 = get_sec();
+  vector<GenomeInfo> q; MinHashSketchFile mh; KssdSketchFile ks; Resident rs;
+  if (o.sketchByFile) sketch_files(gpus, o.inputFile, job, q, &mh, &ks, rs, true);
+  else {
+    vector<FastaRecord> recs; SeqModeSizes sz;
+    if (!read_sequences(o.inputFile, md.min_len, recs, sz)) return 1;
+    sketch_sequences(gpus, recs, job, q, &mh, &ks);
+  }
+  const double t1 = get_sec();
+  g_metrics.num("sketch_queries_s", t1 - t0);
+  const int qwidth = md.minhash ? 8 : (ks.use64 ? 8 : 4);
+  if (!q.empty() && qwidth != md.width) {
+    cerr << "ERROR: the query sketches have hash width " << qwidth << " but the model has " << md.width << endl;
+    return 1;
+  }
+  if (!md.minhash && !q.empty() && (ks.info.half_k != md.half_k || ks.info.half_subk != md.half_subk)) {
+    cerr << "ERROR: the query sketches have half_k " << ks.info.half_k << ", half_subk " << ks.info.half_subk << " but the model has " << md.half_k
+         << ", " << md.half_subk << endl;
+    return 1;
+  }
+  const uint32_t N = (uint32_t)md.labels.size(), Q = (uint32_t)q.size();
+  cerr << "===== DBSCAN model assignment (" << (md.minhash ? "MinHash" : "KSSD") << ") =====" << endl
+       << "  Query genomes:  " << Q << endl << "  Model genomes:  " << N << endl << "  Eps, minPts:    " << md.eps << ", " << md.min_pts << endl;
+  vector<rtc_dbscan_place> place(Q);
+  uint64_t c[10] = {0};
+  if (Q) {
+    DeviceSketches ds;
+    if (md.width == 8) {
+      vector<vector<uint64_t>> all(md.h64);
+      const vector<vector<uint64_t>>& qh = md.minhash ? mh.hashes : ks.h64;
+      all.insert(all.end(), qh.begin(), qh.end());
+      upload_sketches(ctx, &all, nullptr, ds);
+    } else {
+      vector<vector<uint32_t>> all(md.h32);
+      all.insert(all.end(), ks.h32.begin(), ks.h32.end());
+      upload_sketches(ctx, nullptr, &all, ds);
+    }
+    if (ds.n != N + Q) { cerr << "ERROR: --assign needs the query sketches on the host (" << ds.n - N << " of " << Q << ")" << endl; return 1; }
+    CHECK(ctx, rtc_dbscan_assign(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, N, Q, md.labels.data(), md.core.data(), md.minhash ? 1 : 0,
+                                 (uint32_t)md.sketch_size, md.eps, md.min_pts, md.kmer_size, 0, place.data()));
+    rtc_dbscan_assign_counters(ctx, c);
+    (void)rtc_dev_free(ctx, ds.d_hashes); (void)rtc_dev_free(ctx, ds.d_start); (void)rtc_dev_free(ctx, ds.d_len);
+  }
+  const double t2 = get_sec();
+  if (getenv("RTC_VERBOSE"))
+    fprintf(stderr, "[assign] %llu candidates in %llu chunk(s), %llu neighbours; join %.3f ms, predicate %.3f ms, fold %.3f ms\n", (unsigned long long)c[1],
+            (unsigned long long)c[0], (unsigned long long)c[2], c[6] / 1e6, c[7] / 1e6, c[8] / 1e6);
+  g_metrics.num("dbscan_assign_s", t2 - t1);
+  g_metrics.num("dbscan_assign_join_s", c[6] / 1e9);
+  g_metrics.num("dbscan_assign_predicate_s", c[7] / 1e9);
+  g_metrics.num("dbscan_assign_fold_s", c[8] / 1e9);
+  g_metrics.num("dbscan_assign_placed", (double)c[3]);
+  g_metrics.num("dbscan_assign_novel", (double)c[4]);
+  g_metrics.num("dbscan_assign_bridging", (double)c[5]);
+  g_metrics.num("genomes", (double)Q);
+  FILE* fp = fopen(o.outputFile.c_str(), "w");
+  if (!fp) { cerr << "ERROR: cannot open file: " << o.outputFile << endl; return 1; }
+  fprintf(fp, "query\tcluster\tbridges\tneighbours\tcore_neighbours\twould_be_core\tnearest\tdistance\n");
+  for (uint32_t i = 0; i < Q; i++) {
+    const rtc_dbscan_place& r = place[i];
+    const string& name = o.sketchByFile ? q[i].fileName : q[i].seq0.name;
+    char cluster[16] = "novel", dist[32] = "inf";
+    if (r.label >= 0) snprintf(cluster, sizeof cluster, "%d", r.label);
+    string nearest = "-";
+    if (r.nearest != UINT32_MAX) {
+      const GenomeInfo& g = md.genomes[r.nearest];
+      nearest = md.sketch_by_file ? g.fileName : g.seq0.name;
+      double d;
+      if (md.minhash) d = rtc_mash_distance(r.common, r.denom, (uint32_t)md.sketch_size, md.kmer_size);
+      else if (r.common == r.denom) d = 0.0;
+      else { const double j = (double)r.common / (double)r.denom; d = -log(2.0 * j / (1.0 + j)) / md.kmer_size; }
+      snprintf(dist, sizeof dist, "%.6f", d);
+    }
+    fprintf(fp, "%s\t%s\t%d\t%u\t%u\t%u\t%s\t%s\n", name.c_str(), cluster, r.label != r.label_max ? 1 : 0, r.n_neighbours, r.n_core, r.flags & 1u,
+            nearest.c_str(), dist);
+  }
+  fclose(fp);
+  cerr << "===== Assignment Results =====" << endl << "  Placed:      " << c[3] << endl << "  Novel:       " << c[4] << endl << "  Bridging:    " << c[5] << endl
+       << "  Output:      " << o.outputFile << endl << "==============================" << endl;
+  return 0;
+}
 #endif
 
 // Will this run use exactly one GPU?  Answered without the HIP runtime (its environment must be final before it starts): a
@@ -2144,6 +2239,41 @@ int main(int argc, char** argv) {
   if (o.has_append && !o.has_presketched && o.repdb_path.empty()) { cerr << "ERROR option --append, option --presketched needed" << endl; return 1; }  // src/main.cpp:378-381
 #endif
 #ifdef DBSCAN_CLUST
+  // ---- clust-dbscan --db: the model file's flows, their flag errors before any GPU context exists ----
+  DbscanModel db_model;
+  {
+    const int actions = (int)o.db_build + (int)o.db_assign + (int)o.db_stats;
+    if (actions && o.repdb_path.empty()) { cerr << "ERROR: --build / --assign / --stats require --db" << endl; return 1; }
+    if (!o.repdb_path.empty() && o.has_append) { cerr << "ERROR: --append not supported for DBSCAN clustering" << endl; return 1; }
+    if (!o.repdb_path.empty() && actions != 1) { cerr << "ERROR: --db requires exactly one of --build, --assign, --stats" << endl; return 1; }
+    if (o.db_build && o.hasMaxPosting && o.maxPosting > 0) {
+      cerr << "ERROR: --build does not go with --max-posting (its pruning depends on posting counts that new genomes would change)" << endl;
+      return 1;
+    }
+    if (o.db_stats || o.db_assign) {
+      string why;
+      if (!load_dbscan_model(o.repdb_path, db_model, &why)) { cerr << "ERROR: --db " << o.repdb_path << ": " << why << endl; return 1; }
+    }
+    if (o.db_stats) {
+      print_dbscan_model_stats(db_model, std::cout);
+      std::cout.flush();
+      return 0;
+    }
+    if (o.db_assign) {
+      // -k, -s, --eps and --minpts beside --assign have no effect, as clust-mst --db --assign treats -k and -s: the model's hold
+      if (o.is_fast && db_model.minhash) { cerr << "ERROR: --assign: --fast given, but " << o.repdb_path << " is a MinHash model" << endl; return 1; }
+      if (o.minhash && !db_model.minhash) { cerr << "ERROR: --assign: --minhash given, but " << o.repdb_path << " is a KSSD model" << endl; return 1; }
+      if (db_model.max_posting > 0) {
+        cerr << "ERROR: --assign: " << o.repdb_path << " was built with --max-posting " << db_model.max_posting << ", which is out of scope" << endl;
+        return 1;
+      }
+      if (!o.has_input) { cerr << "ERROR: --assign requires -i <input_file>" << endl; return 1; }
+      o.is_fast = !db_model.minhash;
+      o.minhash = db_model.minhash;
+      o.epsSweep.clear(); o.kdist = o.hierarchy = o.hasMinClusterSize = o.isContainment = false;
+      o.dbscanEps = db_model.eps; o.dbscanMinPts = db_model.min_pts;
+    }
+  }
   // ---- clust-dbscan --minhash: this build's own flag, what it excludes named before any GPU context exists ----
   if (o.minhash) {
     const char* bad = o.is_fast ? "--fast (the two sketch kinds exclude each other)" : o.kdist ? "--kdist" : o.hierarchy ? "--hierarchy"
@@ -2240,7 +2370,7 @@ int main(int argc, char** argv) {
 #ifdef GREEDY_CLUST
         o.has_append || !o.repdb_path.empty() || o.has_presketched;
 #elif defined(DBSCAN_CLUST)
-        o.has_presketched;
+        o.has_presketched || o.db_assign;
 #else
         o.has_append || ((o.dense || !o.useIndex) && o.has_presketched) || !o.repdb_path.empty();
 #endif
@@ -2349,6 +2479,16 @@ int main(int argc, char** argv) {
     for (Gpu& g : gpus) rtc_ctx_destroy(g.ctx);
     return rc;
   }
+#else
+  if (o.db_assign) {
+    const int rc = dbscan_db_assign(o, gpus, db_model);
+    g_metrics.str("command", "clust-dbscan");
+    g_metrics.str("sketch", db_model.minhash ? "minhash" : "kssd");
+    g_metrics.write();
+    for (Gpu& g : gpus) { if (g.comm) rtc_comm_destroy(g.comm); }
+    for (Gpu& g : gpus) rtc_ctx_destroy(g.ctx);
+    return rc;
+  }
 #endif
 
   vector<GenomeInfo> genomes;
@@ -2393,7 +2533,7 @@ int main(int argc, char** argv) {
       maxSize = sz.maxSize; minSize = sz.minSize; averageSize = sz.totalSize / sz.number;
     }
     // main.cpp:632 (clust-mst --fast uses the kssd tuner) / :659 (everything else)
-    if (o.db_build) { /* mst_repdb_build_from_genome[_fast]: the parameters as given, no tuner */ }
+    if (o.db_build && !dbscan) { /* mst_repdb_build_from_genome[_fast]: the parameters as given, no tuner */ }
     else if (o.is_fast && !greedy) { if (!tune_kssd_parameters(o.isSetKmer, maxSize, minSize, averageSize, o.isContainment, o.kmerSize, o.threshold, o.drlevel)) return 1; }
     else if (!tune_parameters(greedy, o.isSetKmer, maxSize, minSize, averageSize, o.isContainment, o.isJaccard, o.kmerSize, o.threshold, o.containCompress, o.sketchSize)) return 1;
     SketchJob job;
@@ -2702,6 +2842,21 @@ int main(int argc, char** argv) {
   cerr << "-----write the cluster result into: " << o.outputFile << endl;
   cerr << "-----the cluster number of " << o.outputFile << " is: " << ncl << endl;
   cerr << "-----the noise point number is: " << nnoise << endl;
+  if (o.db_build) {  // the model of --eps: what --db --assign places new genomes into
+    DbscanModel md;
+    md.minhash = o.minhash; md.width = ds.width; md.sketch_by_file = sketchByFile; md.kmer_size = kmer_size;
+    if (!o.minhash) { md.half_k = ks.info.half_k; md.half_subk = ks.info.half_subk; md.drlevel = ks.info.drlevel; }
+    else md.sketch_size = mh.sketchSize;
+    md.min_pts = o.dbscanMinPts; md.max_posting = 0; md.n_clusters = (int)ncl; md.min_len = o.minLen; md.eps = o.dbscanEps;
+    md.labels = labels; md.core = core; md.genomes = genomes;
+    if (o.minhash) md.h64 = mh.hashes; else if (ks.use64) md.h64 = ks.h64; else md.h32 = ks.h32;
+    if ((md.width == 8 ? md.h64.size() : md.h32.size()) != genomes.size()) {
+      cerr << "ERROR: --build needs the sketches on the host (" << (md.width == 8 ? md.h64.size() : md.h32.size()) << " of " << genomes.size() << ")" << endl;
+      return 1;
+    }
+    if (!save_dbscan_model(o.repdb_path, md)) return 1;
+    cerr << "-----write the DBSCAN model (" << genomes.size() << " genomes, " << ncl << " clusters) into: " << o.repdb_path << endl;
+  }
   g_metrics.num("dbscan_s", get_sec() - t2);
   g_metrics.num("clusters", (double)ncl);
   g_metrics.num("noise", (double)nnoise);

@@ -2677,4 +2677,136 @@ std::string current_date_time() {
   return buf;
 }
 
+// ---- clust-dbscan --db: the model file ----
+namespace {
+const char DBSCAN_MODEL_MAGIC[9] = "RTCDBSM1";
+struct ModelReader {
+  const std::string& b;
+  size_t at = 0;
+  bool ok = true;
+  template <typename T> T pod() {
+    T v{};
+    if (!ok || b.size() - at < sizeof(T)) { ok = false; return v; }
+    memcpy(&v, b.data() + at, sizeof(T));
+    at += sizeof(T);
+    return v;
+  }
+  std::string str() {
+    const uint32_t n = pod<uint32_t>();
+    if (!ok || b.size() - at < n) { ok = false; return std::string(); }
+    std::string s = b.substr(at, n);
+    at += n;
+    return s;
+  }
+  template <typename T> void vec(std::vector<T>& v, uint64_t n) {
+    if (!ok || (b.size() - at) / sizeof(T) < n) { ok = false; return; }
+    v.resize(n);
+    if (n) memcpy(v.data(), b.data() + at, n * sizeof(T));
+    at += n * sizeof(T);
+  }
+};
+template <typename T> void model_put(std::string& o, const T& v) { o.append((const char*)&v, sizeof(T)); }
+void model_put_str(std::string& o, const std::string& s) { model_put(o, (uint32_t)s.size()); o += s; }
+}  // namespace
+
+bool save_dbscan_model(const std::string& path, const DbscanModel& m) {
+  const uint64_t n = m.labels.size();
+  std::string o(DBSCAN_MODEL_MAGIC, 8);
+  const int32_t head[12] = {1, m.minhash ? 1 : 0, m.width, m.sketch_by_file ? 1 : 0, m.kmer_size, m.half_k, m.half_subk, m.drlevel,
+                            m.sketch_size, m.min_pts, m.max_posting, m.n_clusters};
+  o.append((const char*)head, sizeof head);
+  model_put(o, m.min_len);
+  model_put(o, n);
+  model_put(o, m.eps);
+  o.append((const char*)m.labels.data(), n * 4);
+  o.append((const char*)m.core.data(), n);
+  for (uint64_t g = 0; g < n; g++) {
+    const GenomeInfo& gi = m.genomes[g];
+    model_put_str(o, gi.fileName); model_put_str(o, gi.seq0.name); model_put_str(o, gi.seq0.comment);
+    model_put(o, (uint64_t)gi.seq0.length);
+    model_put(o, gi.totalSeqLength);
+  }
+  for (uint64_t g = 0; g < n; g++) model_put(o, (uint32_t)(m.width == 8 ? m.h64[g].size() : m.h32[g].size()));
+  for (uint64_t g = 0; g < n; g++) {
+    if (m.width == 8) o.append((const char*)m.h64[g].data(), m.h64[g].size() * 8);
+    else o.append((const char*)m.h32[g].data(), m.h32[g].size() * 4);
+  }
+  const std::string tmp = path + ".tmp";
+  {
+    std::ofstream f(tmp, std::ios::binary | std::ios::trunc);
+    if (!f) { std::cerr << "ERROR: --db " << path << ": cannot write " << tmp << std::endl; return false; }
+    f.write(o.data(), (std::streamsize)o.size());
+    f.close();
+    if (!f) { std::cerr << "ERROR: --db " << path << ": writing " << tmp << " failed" << std::endl; remove(tmp.c_str()); return false; }
+  }
+  if (rename(tmp.c_str(), path.c_str()) != 0) { std::cerr << "ERROR: --db " << path << ": cannot rename " << tmp << std::endl; remove(tmp.c_str()); return false; }
+  return true;
+}
+
+bool load_dbscan_model(const std::string& path, DbscanModel& m, std::string* why) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f) { *why = "cannot open"; return false; }
+  std::string blob((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  if (blob.size() < 8 || memcmp(blob.data(), DBSCAN_MODEL_MAGIC, 8) != 0) { *why = "is not a clust-dbscan model (bad magic)"; return false; }
+  ModelReader r{blob};
+  r.at = 8;
+  int32_t head[12];
+  for (int i = 0; i < 12; i++) head[i] = r.pod<int32_t>();
+  if (!r.ok) { *why = "is truncated"; return false; }
+  if (head[0] != 1) { *why = "has version " + std::to_string(head[0]) + ", this build reads version 1"; return false; }
+  m = DbscanModel();
+  m.minhash = head[1] == 1; m.width = head[2]; m.sketch_by_file = head[3] != 0; m.kmer_size = head[4]; m.half_k = head[5];
+  m.half_subk = head[6]; m.drlevel = head[7]; m.sketch_size = head[8]; m.min_pts = head[9]; m.max_posting = head[10]; m.n_clusters = head[11];
+  if ((head[1] != 0 && head[1] != 1) || (m.width != 4 && m.width != 8) || (m.minhash && m.width != 8)) {
+    *why = "is not a clust-dbscan model (kind " + std::to_string(head[1]) + ", hash width " + std::to_string(m.width) + ")";
+    return false;
+  }
+  m.min_len = r.pod<uint64_t>();
+  const uint64_t n = r.pod<uint64_t>();
+  m.eps = r.pod<double>();
+  if (r.ok && n >= 0x7fffffffull) { *why = "is not a clust-dbscan model (" + std::to_string(n) + " genomes)"; return false; }
+  r.vec(m.labels, n);
+  r.vec(m.core, n);
+  for (uint64_t g = 0; r.ok && g < n; g++) {
+    GenomeInfo gi;
+    gi.id = (int)g;
+    gi.fileName = r.str(); gi.seq0.name = r.str(); gi.seq0.comment = r.str();
+    gi.seq0.length = (int)r.pod<uint64_t>();
+    gi.totalSeqLength = r.pod<uint64_t>();
+    gi.use64 = m.width == 8 && !m.minhash;
+    m.genomes.push_back(gi);
+  }
+  std::vector<uint32_t> lens;
+  r.vec(lens, n);
+  if (m.width == 8) m.h64.resize(r.ok ? n : 0); else m.h32.resize(r.ok ? n : 0);
+  for (uint64_t g = 0; r.ok && g < n; g++) {
+    if (m.width == 8) r.vec(m.h64[g], lens[g]);
+    else r.vec(m.h32[g], lens[g]);
+  }
+  if (!r.ok) { *why = "is truncated"; return false; }
+  if (r.at != blob.size()) { *why = "has " + std::to_string(blob.size() - r.at) + " bytes after its end"; return false; }
+  return true;
+}
+
+void print_dbscan_model_stats(const DbscanModel& m, std::ostream& os) {
+  uint64_t noise = 0, core = 0;
+  for (int32_t l : m.labels) noise += l < 0;
+  for (uint8_t c : m.core) core += c != 0;
+  os << "===== DBSCAN model =====" << std::endl
+     << "  Kind:        " << (m.minhash ? "MinHash" : "KSSD") << std::endl
+     << "  Hash width:  " << m.width << std::endl
+     << "  Kmer size:   " << m.kmer_size << std::endl;
+  if (m.minhash) os << "  Sketch size: " << m.sketch_size << std::endl;
+  else os << "  Half k:      " << m.half_k << std::endl << "  Half subk:   " << m.half_subk << std::endl << "  Drlevel:     " << m.drlevel << std::endl;
+  os << "  Min length:  " << m.min_len << std::endl
+     << "  Eps:         " << m.eps << std::endl
+     << "  MinPts:      " << m.min_pts << std::endl
+     << "  Max posting: " << m.max_posting << std::endl
+     << "  Genomes:     " << m.labels.size() << std::endl
+     << "  Clusters:    " << m.n_clusters << std::endl
+     << "  Noise:       " << noise << std::endl
+     << "  Core points: " << core << std::endl
+     << "========================" << std::endl;
+}
+
 }  // namespace rtc

@@ -273,6 +273,29 @@ bool write_mst_query_tsv(const std::string& path, const MstState& st, const std:
 bool write_mst_assign_tsv(const std::string& path, const MstState& st, const std::vector<std::string>& qnames,
                           const std::vector<rtc_rep_hit>& hits, const std::vector<uint32_t>& per_query, int* n_assigned);
 
+// clust-dbscan --db FILE: a clustered sketch set that new genomes can be placed into (rtc_dbscan_assign).  One binary file,
+// little-endian, INTEGRATION.md section 6 lists it byte by byte.  Written to FILE.tmp and renamed.
+struct DbscanModel {
+  bool minhash = false;   // kind: 0 KSSD, 1 MinHash
+  int width = 4;          // bytes per hash
+  bool sketch_by_file = true;
+  int kmer_size = 0;      // the k of the predicate (and of the MinHash sketches)
+  int half_k = 0, half_subk = 0, drlevel = 0;  // KSSD
+  int sketch_size = 0;    // MinHash
+  int min_pts = 0, max_posting = 0, n_clusters = 0;
+  uint64_t min_len = 0;
+  double eps = 0.0;
+  std::vector<int32_t> labels;
+  std::vector<uint8_t> core;
+  std::vector<GenomeInfo> genomes;
+  std::vector<std::vector<uint32_t>> h32;
+  std::vector<std::vector<uint64_t>> h64;
+};
+bool save_dbscan_model(const std::string& path, const DbscanModel& m);
+// false: *why says what is wrong with the file (cannot open, foreign, version, truncated, bytes after its end)
+bool load_dbscan_model(const std::string& path, DbscanModel& m, std::string* why);
+void print_dbscan_model_stats(const DbscanModel& m, std::ostream& os);
+
 std::string current_date_time();  // src/common.hpp:36-44
 
 // Time the parser threads spent inside gzip decompression (libdeflate or zlib), summed over threads, and the bytes it produced

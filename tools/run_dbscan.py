@@ -20,6 +20,12 @@ Sets (KSSD u32 sketches from synthetic genomes, k 21, drlevel 3, sketched on the
 --repeat warm calls for each of the four configurations -- the wave-cooperative merge and RTC_DBSCAN_MASH_SERIAL=1, each with
 the prefilter and with RTC_DBSCAN_MASH_NOPREFILTER=1 -- and whether the four label sets are identical.
 
+--assign Q times Context.dbscan_assign (clust-dbscan --db --assign): the last Q sketches of a set are the queries, the rest the
+model, clustered once at --eps / --minpts; best of --repeat warm calls with the phases of rtc_dbscan_assign_counters, beside the
+baseline it replaces, Context.dbscan (with --minhash: dbscan_mash) on all n sketches.  --baseline-lib PATH takes that baseline
+from another build of the library, e.g. the parent commit's librtclust_hip.so, in a child process (RTC_HIP_LIB); without it the
+baseline is this build's.
+
 Prints one JSON line per set.  The kernel split under rocprofv3 --kernel-trace --stats comes from a run of its own."""
 import argparse
 import json
@@ -154,6 +160,57 @@ def _minhash_rows(ctx, api, a, n=10_000, fam=10, rate=0.01, L=500_000, s=1000, k
     return row
 
 
+def _head(api, sk, n_db):
+    """the first n_db sketches of a set, over the same hash buffer"""
+    return api.SketchSet(sk.hashes, sk.start[:n_db].contiguous(), sk.len[:n_db].contiguous(), sk.width, sk.k, sk.kind)
+
+
+def _best(fn, repeat):
+    fn()  # warm-up: code objects, scratch
+    ts = []
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        out = fn()
+        ts.append(time.perf_counter() - t0)
+    return min(ts) * 1e3, out
+
+
+def _assign_row(ctx, api, sk, name, kmer, a, sketch_size=None):
+    n, q = sk.n, a.assign
+
+    def cluster(s):
+        if sketch_size:
+            lab, core = ctx.dbscan_mash(s, sketch_size, [a.eps], a.minpts, kmer, return_core=True)
+            return lab[0], core[0]
+        return ctx.dbscan(s, a.eps, a.minpts, kmer, return_core=True)
+    base_ms, _ = _best(lambda: cluster(sk), a.repeat)
+    row = {"set": name, "n": n, "queries": q, "kmer": kmer, "eps": a.eps, "minpts": a.minpts, "recluster_all_ms": round(base_ms, 3)}
+    if a.baseline_only:
+        return row
+    labels, core = cluster(_head(api, sk, n - q))
+    cs = []
+
+    def call():
+        out = ctx.dbscan_assign(sk, n - q, labels, core, a.eps, a.minpts, kmer, sketch_size=sketch_size)
+        cs.append(ctx.dbscan_assign_counters())
+        return out
+    ms, _ = _best(call, a.repeat)
+    c = min(cs[1:], key=lambda x: x["total_ns"])
+    row.update({"assign_ms": round(ms, 3), "library_ms": round(c["total_ns"] / 1e6, 3), "join_ms": round(c["join_ns"] / 1e6, 3),
+                "predicate_ms": round(c["predicate_ns"] / 1e6, 3), "fold_ms": round(c["fold_ns"] / 1e6, 3), "chunks": c["chunks"],
+                "candidates": c["candidates"], "neighbours": c["neighbours"], "placed": c["placed"], "novel": c["novel"],
+                "bridging": c["bridging"], "fold_paths": c["fold_paths"]})
+    if a.baseline_lib:  # the same set in a child that loads the other build
+        import subprocess
+        args = [sys.executable, os.path.abspath(__file__), "--sets", name, "--assign", str(q), "--eps", str(a.eps), "--minpts", str(a.minpts),
+                "--repeat", str(a.repeat), "--baseline-only"] + (["--minhash"] if sketch_size else [])
+        r = subprocess.run(args, capture_output=True, text=True, env=dict(os.environ, RTC_HIP_LIB=a.baseline_lib))
+        lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
+        row["baseline_lib"] = a.baseline_lib
+        row["baseline_lib_recluster_all_ms"] = json.loads(lines[-1])["recluster_all_ms"] if r.returncode == 0 and lines else None
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="dense25k,cfg4_200k")
@@ -166,10 +223,24 @@ def main():
     ap.add_argument("--separate-only", action="store_true")
     ap.add_argument("--hierarchy", action="store_true")
     ap.add_argument("--minhash", action="store_true")
+    ap.add_argument("--assign", type=int, default=0)
+    ap.add_argument("--baseline-lib", default="")
+    ap.add_argument("--baseline-only", action="store_true")
     a = ap.parse_args()
     import torch
     from rabbittclust_amd import api
     ctx = api.Context(0)
+    if a.minhash and a.assign:
+        n, fam, L, s, k = 10_000, 10, 500_000, 1000, 21
+        off = np.arange(n + 1, dtype=np.uint64) * np.uint64(L)
+        order = np.random.default_rng(1).permutation(n)  # the queries come from every family
+        seq = ctx.synth_genomes(api.synth_family_descs(fam, n // fam, global_seed=42, max_rate=0.01)[order], off)
+        sk = ctx.sketch_minhash(seq, off, k=k, size=s)
+        ctx.sync()
+        del seq
+        print(json.dumps(_assign_row(ctx, api, sk, "minhash10k", k, a, sketch_size=s)), flush=True)
+        ctx.close()
+        return
     if a.minhash:
         print(json.dumps(_minhash_rows(ctx, api, a)), flush=True)
         ctx.close()
@@ -183,6 +254,10 @@ def main():
             sk = _synth(ctx, api, n, per, rate, seed)
         kmer = sk.k  # half_k * 2, as clust-dbscan --presketched takes it
         torch.cuda.synchronize()
+        if a.assign:
+            print(json.dumps(_assign_row(ctx, api, sk, name, kmer, a)), flush=True)
+            del sk
+            continue
         if a.sweep:
             print(json.dumps(_sweep_row(ctx, sk, name, n, kmer, [float(x) for x in a.sweep.split(",")], a)), flush=True)
             del sk
