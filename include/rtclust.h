@@ -638,6 +638,61 @@ int rtc_dbscan_assign_counters(const rtc_ctx* ctx, uint64_t out[10]);
  * 256-lane workgroup (the longer ones). */
 int rtc_dbscan_assign_last_path(const rtc_ctx* ctx);
 
+/* ---- clust-leiden --louvain: similarity graph and Louvain ---------------------------------------------- */
+/* The graph of the reference's KssdLeidenCluster (src/leiden.cpp:168-293).  A pair u < v is an edge iff both sketches are
+ * non-empty and share a hash, the size ratio passes -- !(2 min(|u|, |v|) < max(|u|, |v|)), which is the reference's
+ * (double)small / large < 0.5 skip -- and dist < threshold strictly, dist = 1 - rtc_graph_weight(common, |u|, |v|, kmer_size):
+ * calculate_mash_distance_fast (:109-121) with the host's libm.  The device forms no distance: the host finds J*, the least
+ * double whose distance through that very function is below threshold, and the device tests (double)common / (double)union >= J*.
+ * The rounding of 2j / (1 + j) can turn the order of doubles a few ulps apart, so J* is moved past every failing double within
+ * 64 ulps above the bisection's flip: a pair the host function fails is never an edge, and the graph equals the host
+ * function's pair by pair whenever no two pairs' quotients lie within 64 ulps of each other around J* -- guaranteed for
+ * unions below 2^22 hashes (distinct quotients are then more than 256 ulps apart), not beyond.
+ * knn_k > 0: every node u keeps only its knn_k best edges among v > u, the reference's asymmetric rule (:199-221).  The rank is
+ * common / union compared exactly by 64-bit cross-multiplication, larger first, equal ratios to the lower v; the reference ranks
+ * by the rounded distance and leaves equal distances in the order of its heap, so this is one of its possible outcomes.
+ * knn_k = 0: no such filter (the command line cannot ask for that, as the reference's cannot).
+ * h_edges[cap] receives the edges in (u, v) order, *h_n_edges their number.  More than cap: RTC_ERR_OVERFLOW with the needed
+ * count in *h_n_edges.  threshold <= 0 or NaN: RTC_ERR_ARG.  A sketch of 2^31 hashes or more: RTC_ERR_UNSUPPORTED.
+ * RTC_EDGE_BUDGET chunks the rows as in rtc_dbscan; a kept list that does not fit: RTC_ERR_NOMEM, no fallback.  Synchronous. */
+typedef struct { uint32_t u, v, common, pad; } rtc_gedge; /* u < v */
+int rtc_graph_build(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                    double threshold, int kmer_size, uint32_t knn_k, rtc_gedge* h_edges, uint64_t cap, uint64_t* h_n_edges);
+/* host only: 1 - calculate_mash_distance_fast(common, size_u, size_v, kmer_size) */
+double rtc_graph_weight(uint32_t common, uint32_t size_u, uint32_t size_v, int kmer_size);
+/* The last rtc_graph_build: out[0] row chunks, out[1] candidates (pairs sharing a hash), out[2] pairs passing the edge rule,
+ * out[3] edges after the k-NN filter, out[4] nodes the filter cut, out[5] pair ns, out[6] filter ns, out[7] select and sort ns,
+ * out[8] 0, out[9] whole call ns. */
+int rtc_graph_counters(const rtc_ctx* ctx, uint64_t out[10]);
+
+/* Deterministic Louvain in exact integers.  The reference calls igraph_community_multilevel, which visits the nodes in a
+ * shuffled order and is no reproducible target: this is the definition (tests/reflouvain.py restates it).
+ *   - Input: n vertices, m records (u, v, q), q >= 1 the weight in units of 2^-20 -- callers form q = max(1, llround(weight *
+ *     2^20)).  Duplicate (u, v) are summed; u == v adds 2q to the self entry; the adjacency is symmetric.  k_x is x's row sum,
+ *     the self entry included; M2 is the sum of all k_x.  g = llround(resolution * 65536); resolution <= 0, NaN or g >= 2^32:
+ *     RTC_ERR_ARG.  u or v >= n, or q = 0: RTC_ERR_ARG.  M2 >= 2^46: RTC_ERR_UNSUPPORTED (the scores fit 128 signed bits below).
+ *   - A level starts from singletons, community x = {x}, tot_c = the sum of k over c's members.  Round r = 0, 1, ...: every
+ *     vertex decides from the state at the start of the round.  For x in community c and a community d, e_d is the weight from
+ *     x to the members of d other than x, and S(d) = e_d M2 65536 - g k_x (tot_d - [d == c] k_x).  Among the communities d != c
+ *     that hold a neighbour of x, with d < c on even rounds and d > c on odd ones, and S(d) > S(c) strictly, x moves to the one
+ *     with the largest S, equal scores to the smallest d; if there is none it stays.  All moves are applied together and tot is
+ *     rebuilt from the memberships.  The level ends after two rounds in a row without a move, or after 64 rounds.
+ *   - If the level moved nothing, the algorithm stops.  Otherwise the communities are numbered by their smallest member and
+ *     become the vertices of the next level; the weight between two communities is summed, the weight inside one (every entry,
+ *     both directions and the self entries) becomes its self entry.  At most 32 levels.
+ *   - h_labels[n]: the final community of every vertex, communities numbered by their smallest original vertex;
+ *     *h_n_clusters their number; *h_modularity (may be NULL) the sum over c of (in_c M2 65536 - g tot_c^2) divided by
+ *     (M2^2 65536) on the host, for information.  m == 0: every vertex is its own cluster (:286-293).
+ * Every sum is an integer (64-bit integer atomics: order-independent), every score a 128-bit signed integer, so the result does
+ * not depend on the scheduling or on which kernel path a row takes.  Synchronous. */
+typedef struct { uint32_t u, v, q; } rtc_wedge;
+int rtc_louvain(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, uint64_t m, double resolution, int32_t* h_labels,
+                uint32_t* h_n_clusters, double* h_modularity);
+/* The last rtc_louvain: out[0] levels, out[1] rounds (all levels), out[2] moves (all levels), out[3] vertices and out[4]
+ * adjacency entries of the last level, out[5] rows the long paths took (workgroup and global table, all rounds), out[6] move ns,
+ * out[7] aggregate ns, out[8] rows the global-table path took, out[9] whole call ns. */
+int rtc_louvain_counters(const rtc_ctx* ctx, uint64_t out[10]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,8 @@ KDIST_NONE = 0xFFFFFFFF  # neighbour of a point with fewer than minPts - 1 candi
 PLACE_DT = np.dtype([("label", "<i4"), ("label_max", "<i4"), ("n_neighbours", "<u4"), ("n_core", "<u4"), ("nearest", "<u4"),
                      ("common", "<u4"), ("denom", "<u4"), ("flags", "<u4")])
 PLACE_NONE = 0xFFFFFFFF  # nearest of a query that shares no hash with the model
+GEDGE_DT = np.dtype([("u", "<u4"), ("v", "<u4"), ("common", "<u4"), ("pad", "<u4")])  # rtc_gedge
+WEDGE_DT = np.dtype([("u", "<u4"), ("v", "<u4"), ("q", "<u4")])  # rtc_wedge
 HEDGE_DT = np.dtype([("p", "<u4"), ("q", "<u4"), ("common", "<u4"), ("size_p", "<u4"), ("size_q", "<u4")])  # rtc_hedge
 
 
@@ -753,6 +755,52 @@ class Context:
                  "forest_ns", "total_ns")
         return {k: int(a[i]) for i, k in enumerate(names)}
 
+    def graph_build(self, sk, threshold, kmer_size, knn_k=0, cap=None):
+        """clust-leiden's similarity graph (rtc_graph_build; KssdLeidenCluster, src/leiden.cpp:168-293): GEDGE_DT edges (u < v,
+        common) in (u, v) order.  knn_k > 0: every node keeps its knn_k best edges among the higher-numbered neighbours.  cap:
+        room for the edges (None: the call is repeated with the count it reports); an explicit cap that is too small raises
+        RTC_ERR_OVERFLOW, the needed count in self.graph_edges_needed."""
+        n = sk.n
+        room = max(int(cap) if cap is not None else 16 * n, 1)
+        while True:
+            out = np.zeros(room, dtype=GEDGE_DT)
+            ne = C.c_uint64(0)
+            st = self.lib.rtc_graph_build(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n, float(threshold),
+                                          int(kmer_size), int(knn_k), _np_ptr(out), int(cap) if cap is not None else room, C.byref(ne))
+            self.graph_edges_needed = int(ne.value)
+            if st == _lib.RTC_ERR_OVERFLOW and cap is None:
+                room = int(ne.value)
+                continue
+            self.check(st)
+            return out[:ne.value].copy()
+
+    def graph_counters(self):
+        """rtc_graph_counters as a dict (the last graph_build call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_graph_counters(self.h, a))
+        names = ("chunks", "candidates", "passing", "edges", "nodes_cut", "pair_ns", "filter_ns", "select_ns", "unused", "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names) if k != "unused"}
+
+    def louvain(self, n, edges, resolution=1.0, return_modularity=False):
+        """rtc_louvain: the deterministic Louvain include/rtclust.h defines over n vertices and WEDGE_DT records (u, v, q), q the
+        weight in units of 2^-20 (graph_weights forms them).  Returns int32 labels, communities numbered by their smallest
+        vertex; with return_modularity (labels, modularity)."""
+        e = np.ascontiguousarray(np.asarray(edges, dtype=WEDGE_DT))
+        labels = np.zeros(max(int(n), 1), dtype=np.int32)
+        ncl, mod = C.c_uint32(0), C.c_double(0.0)
+        self.check(self.lib.rtc_louvain(self.h, int(n), _np_ptr(e) if e.size else None, int(e.size), float(resolution), _np_ptr(labels),
+                                        C.byref(ncl), C.byref(mod)))
+        self.louvain_clusters = int(ncl.value)
+        return (labels[:n].copy(), float(mod.value)) if return_modularity else labels[:n].copy()
+
+    def louvain_counters(self):
+        """rtc_louvain_counters as a dict (the last louvain call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_louvain_counters(self.h, a))
+        names = ("levels", "rounds", "moves", "last_vertices", "last_entries", "long_rows", "move_ns", "aggregate_ns", "global_rows",
+                 "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
     def dbscan_counters(self):
         """rtc_dbscan_counters as a dict (the last dbscan call)."""
         a = (C.c_uint64 * 10)()
@@ -795,6 +843,23 @@ def hierarchy_flat(forest, core, kmer_size, min_cluster_size, return_stability=F
                                                _np_ptr(labels), _np_ptr(stab), C.byref(ncl)),
                 "hierarchy_flat: min_cluster_size %d, k %d" % (min_cluster_size, kmer_size))
     return (labels[:n].copy(), stab[:ncl.value].copy()) if return_stability else labels[:n].copy()
+
+
+def graph_weight(common, size_u, size_v, kmer_size):
+    """rtc_graph_weight: 1 - calculate_mash_distance_fast (src/leiden.cpp:109-121), the library's host function"""
+    return float(_lib.load().rtc_graph_weight(int(common), int(size_u), int(size_v), int(kmer_size)))
+
+
+def graph_weights(edges, sizes, kmer_size):
+    """WEDGE_DT records of GEDGE_DT edges: q = max(1, llround(weight * 2^20)) of rtc_graph_weight"""
+    out = np.zeros(len(edges), dtype=WEDGE_DT)
+    out["u"], out["v"] = edges["u"], edges["v"]
+    fn = _lib.load().rtc_graph_weight
+    x = np.array([fn(c, sizes[u], sizes[v], kmer_size) for u, v, c in zip(edges["u"].tolist(), edges["v"].tolist(), edges["common"].tolist())],
+                 dtype=np.float64) * 1048576.0
+    low = np.floor(x)  # llround: x - floor(x) is exact, halves go away from zero
+    out["q"] = np.maximum(1, low + (x - low >= 0.5)).astype(np.uint32)
+    return out
 
 
 def kdist_distance(common, size_p, size_q, kmer_size):

@@ -5,8 +5,9 @@
 // records are the genomes (no -l), MinHash
 // and KSSD (--fast) sketching, --presketched / --premsted resume, -e/--no-save, and the same
 // intermediate folder (info.sketch, hash.sketch, minhash.sketch.index, kssd.*, info.mst,
-// edge.mst).  Built three times: -DGREEDY_CLUST gives clust-greedy, -DDBSCAN_CLUST clust-dbscan (KSSD only, src/main.cpp:478-522;
-// rtc_dbscan), otherwise clust-mst (CMakeLists.txt:40-58 of the reference does the same).
+// edge.mst).  Built four times: -DGREEDY_CLUST gives clust-greedy, -DDBSCAN_CLUST clust-dbscan (KSSD only, src/main.cpp:478-522;
+// rtc_dbscan), -DLEIDEN_CLUST clust-leiden (src/main.cpp:391-477; rtc_graph_build + rtc_louvain), otherwise clust-mst
+// (CMakeLists.txt:40-58 of the reference does the same).
 // GPUs: every visible MI355X is used (--gpus LIST / RTC_GPUS to choose): one context + one host thread
 // per GPU, file batches go round-robin to the GPUs, the sketches stay in HBM (copied to the host only
 // to write hash.sketch), are shared among the GPUs with RCCL broadcasts, and the MST runs
@@ -16,6 +17,11 @@
 // --append on MinHash sketches, the dense estimator loops (--inverted-index=false: modifyMST / greedyCluster), and
 // clust-mst's --save-rep state and its MST representative database (--db ..., the search on the GPU: rtc_rep_topk).
 // Single-FASTA input to --append and to --db --build / --append is outside this path and exits with a message.
+#ifdef LEIDEN_CLUST
+// clust-leiden sketches, saves and loads KSSD sketches as clust-dbscan does (compute_kssd_sketches keeps the sketches alone), so
+// it shares that build's plumbing; its own flags, checks and clustering are the LEIDEN_CLUST branches inside
+#define DBSCAN_CLUST
+#endif
 #include <math.h>
 #include <iomanip>
 #include <limits>
@@ -872,7 +878,46 @@ struct Options {
   bool minhash = false;     // clust-dbscan --minhash: MinHashDBSCAN over MinHash sketches (rtc_dbscan_mash) instead of --fast
   bool hasMaxPosting = false;
   int minClusterSize = 0;   // --min-cluster-size (default: --minpts)
+  // clust-leiden (src/main.cpp:184-198)
+  double resolution = 1.0;
+  bool has_resolution = false, louvain = false, has_pregraph = false, saveGraph = false;
+  int knn = 0;
 };
+
+#ifdef LEIDEN_CLUST
+// q of rtc_wedge for a weight: max(1, llround(weight * 2^20)), as include/rtclust.h asks of the callers
+static uint32_t leiden_weight_units(double weight) {
+  const long long q = llround(weight * 1048576.0);
+  return (uint32_t)std::min<long long>(std::max<long long>(q, 1), 0xffffffffll);
+}
+// leiden.graph in the reference's text layout (save_graph_to_file, src/leiden.cpp:474-491): "n m", then "u v weight" per edge,
+// the weight as operator<< prints a double (6 significant digits)
+static bool save_leiden_graph(const string& path, uint32_t n, const vector<rtc_gedge>& edges, const vector<double>& weights) {
+  std::ofstream out(path);
+  if (!out.is_open()) { cerr << "ERROR: Cannot open graph file for writing: " << path << endl; return false; }
+  out << n << " " << edges.size() << "\n";
+  for (size_t e = 0; e < edges.size(); e++) out << edges[e].u << " " << edges[e].v << " " << weights[e] << "\n";
+  out.close();
+  return !out.fail();
+}
+// the file back: every weight becomes q on the value the file holds; a weight <= 0 cannot be an edge's
+static bool load_leiden_graph(const string& path, vector<rtc_wedge>& edges, uint64_t& n, string* why) {
+  std::ifstream in(path);
+  if (!in.is_open()) { *why = "cannot open " + path; return false; }
+  uint64_t m = 0;
+  if (!(in >> n >> m) || n >= 0x7fffffffull) { *why = path + ": no 'nodes edges' header"; return false; }
+  edges.clear();
+  edges.reserve((size_t)std::min<uint64_t>(m, (uint64_t)1 << 28));
+  for (uint64_t e = 0; e < m; e++) {
+    uint64_t u = 0, v = 0;
+    double w = 0.0;
+    if (!(in >> u >> v >> w)) { *why = path + ": " + std::to_string(e) + " of " + std::to_string(m) + " edges"; return false; }
+    if (u >= n || v >= n || !(w > 0.0) || !(w <= 4095.0)) { *why = path + ": edge " + std::to_string(e) + " is out of range"; return false; }
+    edges.push_back(rtc_wedge{(uint32_t)u, (uint32_t)v, leiden_weight_units(w)});
+  }
+  return true;
+}
+#endif
 
 static void unsupported(const char* what) {
   fprintf(stderr, "ERROR: %s is outside the sketch + all-pairs path this build implements\n", what);
@@ -884,7 +929,21 @@ static Options parse(int argc, char** argv) {
   auto need = [&](int& i) -> const char* { if (i + 1 >= argc) { fprintf(stderr, "ERROR: option %s requires a value\n", argv[i]); exit(1); } return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     const string a = argv[i];
-#ifdef DBSCAN_CLUST
+#ifdef LEIDEN_CLUST
+    // the options of the Leiden build (src/main.cpp:184-198) and this build's own --save-graph; none of clust-dbscan's
+    if (a == "--resolution") { o.resolution = atof(need(i)); o.has_resolution = true; continue; }
+    if (a == "--louvain") { o.louvain = true; continue; }
+    if (a == "--knn") { o.knn = atoi(need(i)); continue; }
+    if (a == "--pregraph") { o.folder_path = need(i); o.has_pregraph = true; continue; }
+    if (a == "--save-graph") { o.saveGraph = true; continue; }
+    if (a == "--db" || a == "--build" || a == "--assign" || a == "--stats" || a == "--append" || a == "--save-rep" || a == "--query" ||
+        a == "--top-k" || a == "--dense" || a == "--premsted" || a == "--auto-threshold" || a == "--stability" || a == "--dedup-dist" ||
+        a == "--reps-per-cluster" || a == "--newick-tree" || a == "--phylip-tree" || a == "--nexus-tree" || a == "--linkage-matrix" ||
+        a == "--buildDB" || a == "-s" || a == "--sketch-size" || a == "-c" || a == "--containment" || a.rfind("--inverted-index", 0) == 0) {
+      fprintf(stderr, "ERROR: unknown option %s\n", a.c_str());
+      exit(1);
+    }
+#elif defined(DBSCAN_CLUST)
     // the options of the DBSCAN build (src/main.cpp:173-182); the MST / greedy ones are not defined there.  The common options
     // -c (given to the KSSD tuner, as src/main.cpp:516 does), -s and --save-rep (no effect on DBSCAN) are parsed below.
     if (a == "--eps") { o.dbscanEps = atof(need(i)); continue; }
@@ -964,6 +1023,18 @@ static Options parse(int argc, char** argv) {
     else if (a == "-h" || a == "--help") {
 #ifdef GREEDY_CLUST
       puts("clust-greedy (MI355X build): greedy incremental clustering module");
+#elif defined(LEIDEN_CLUST)
+      puts("clust-leiden (MI355X build): graph-based community detection (Louvain) clustering module, KSSD sketches (--fast)");
+      puts("  -t,--threads N  -m,--min-length N  -k,--kmer-size N (default 19)  -l,--list  -e,--no-save  -d,--threshold X (default 0.05:\n"
+           "  a pair is an edge when its distance is below it)  -o,--output FILE  -i,--input FILE  --presketched DIR  --fast (required)\n"
+           "  --drlevel N  --gpus all|N|i,j,.. (sketching on every GPU, graph and Louvain on the first)\n"
+           "  --louvain (required: Leiden refinement is not in this build)  --resolution X (default 1.0; higher: more clusters)\n"
+           "  --knn K (every genome keeps its K best edges among the higher-numbered genomes; 0 or absent: 1000, 1..9: 50 with a\n"
+           "           warning, as the reference defaults it, so the filter cannot be switched off here)\n"
+           "  --save-graph (leiden.graph into the sketch folder: 'n m', then 'u v weight' per edge; the weights carry 6 significant\n"
+           "                digits, so a --pregraph run is defined on the file's weights, not on the sketches')\n"
+           "  --pregraph DIR (DIR/leiden.graph and the KSSD sketches of DIR: Louvain alone, for another --resolution)");
+      exit(0);
 #elif defined(DBSCAN_CLUST)
       puts("clust-dbscan (MI355X build): DBSCAN density-based clustering module (KSSD with --fast, MinHash with --minhash)");
       puts("  -t,--threads N  -m,--min-length N  -k,--kmer-size N  -l,--list  -e,--no-save  -d,--threshold X (KSSD tuner)\n"
@@ -2002,7 +2073,7 @@ static int append_clust_greedy(const Options& o, vector<Gpu>& gpus) {
 }
 #endif
 
-#ifdef DBSCAN_CLUST
+#if defined(DBSCAN_CLUST) && !defined(LEIDEN_CLUST)
 // KssdDBSCAN's closing lines (src/dbscan.cpp:951-980).  Its progress lines (:918-930) leave std::fixed and precision 1 on cerr
 // once one has been printed, and the core-point percentage comes out in that format then: the walk is replayed from the labels
 // to learn whether it printed one.  After cluster c (opened at its smallest core index s_c) the walk has visited
@@ -2238,7 +2309,41 @@ int main(int argc, char** argv) {
   if (o.has_append && o.has_input) { cerr << "ERROR: --append and -i/--input exclude each other" << endl; return 1; }
   if (o.has_append && !o.has_presketched && o.repdb_path.empty()) { cerr << "ERROR option --append, option --presketched needed" << endl; return 1; }  // src/main.cpp:378-381
 #endif
-#ifdef DBSCAN_CLUST
+#ifdef LEIDEN_CLUST
+  // ---- clust-leiden: the checks of src/main.cpp:391-477 in that order, all before any GPU context exists (the default
+  // threshold 0.05 is set above, as for every command) ----
+  if (o.has_resolution) cerr << "-----Resolution parameter: " << o.resolution << endl;
+  if (!o.louvain) { cerr << "ERROR: Leiden refinement is not in this build; run with --louvain" << endl; return 1; }
+  if (!(o.resolution > 0.0) || !(o.resolution < 65536.0)) { cerr << "ERROR: --resolution must be > 0 and below 65536, got " << o.resolution << endl; return 1; }
+  if (!(o.threshold > 0.0)) { cerr << "ERROR: -d/--threshold must be > 0, got " << o.threshold << endl; return 1; }
+  if (o.knn < 0) { cerr << "ERROR: --knn must be >= 0, got " << o.knn << endl; return 1; }
+  if (o.knn == 0) { o.knn = 1000; cerr << "-----Auto-enabled: edge-parallel + warm-start + knn=" << o.knn << endl; }
+  if (o.knn > 0 && o.knn < 10) { cerr << "WARNING: --knn value too small (" << o.knn << "), recommend at least 50. Using 50." << endl; o.knn = 50; }
+  cerr << "-----Algorithm: Louvain (Optimized)" << endl;
+  cerr << "  - k-NN filtering (k=" << o.knn << ")" << endl;
+  vector<rtc_wedge> pregraph;
+  if (o.has_pregraph) {
+    cerr << "-----Clustering from pre-built graph (fast resolution adjustment)" << endl;
+    o.has_presketched = true;  // the KSSD sketches of the folder name the genomes (clust_from_pregraph_leiden, src/sub_command.cpp:3200-3225)
+    o.is_fast = true;
+    o.saveGraph = false;
+  } else if (!o.is_fast) {
+    cerr << "ERROR: clust-leiden requires --fast option" << endl;
+    return 1;
+  } else if (!o.has_presketched) {
+    if (!o.isSetKmer) { o.kmerSize = 19; cerr << "-----use default kmerSize: " << o.kmerSize << endl; }
+    if (o.drlevel < 0 || o.drlevel > 8) { cerr << "ERROR: invalid drlevel " << o.drlevel << ", should be in [0, 8]" << endl; return 1; }
+  }
+  if (o.saveGraph && o.noSave && !o.has_presketched) { cerr << "ERROR: --save-graph writes into the sketch folder, which -e/--no-save leaves out" << endl; return 1; }
+  uint64_t pregraph_nodes = 0;
+  if (o.has_pregraph) {
+    string why;
+    if (!load_leiden_graph(o.folder_path + "/leiden.graph", pregraph, pregraph_nodes, &why)) {
+      cerr << "ERROR: --pregraph " << o.folder_path << ": " << why << endl;
+      return 1;
+    }
+  }
+#elif defined(DBSCAN_CLUST)
   // ---- clust-dbscan --db: the model file's flows, their flag errors before any GPU context exists ----
   DbscanModel db_model;
   {
@@ -2479,7 +2584,7 @@ int main(int argc, char** argv) {
     for (Gpu& g : gpus) rtc_ctx_destroy(g.ctx);
     return rc;
   }
-#else
+#elif !defined(LEIDEN_CLUST)
   if (o.db_assign) {
     const int rc = dbscan_db_assign(o, gpus, db_model);
     g_metrics.str("command", "clust-dbscan");
@@ -2514,7 +2619,7 @@ int main(int argc, char** argv) {
   if (from_sketches) {
     if (o.is_fast) { if (!load_kssd_sketches(folder_path, genomes, ks, sketchByFile)) return 1; }
     else { if (!load_minhash_sketches(folder_path, genomes, mh, sketchByFile)) return 1; }
-#ifdef DBSCAN_CLUST
+#if defined(DBSCAN_CLUST) && !defined(LEIDEN_CLUST)
     // clust_from_sketch_dbscan prints with the -l of the command line, not the one stored with the sketches (:3237-3240)
     if (sketchByFile != o.sketchByFile) { cerr << "Warning: sketch format mismatch" << endl; dbscan_format_mismatch = true; }
     sketchByFile = o.sketchByFile;
@@ -2656,6 +2761,70 @@ int main(int argc, char** argv) {
   cerr << "========time of greedyCluster is: " << get_sec() - t2 << "========" << endl;
   g_metrics.num("greedyCluster_s", get_sec() - t2);
   g_metrics.num("clusters", (double)cluster.size());
+#elif defined(LEIDEN_CLUST)
+  // ---- clust-leiden --louvain: the graph of KssdLeidenCluster (src/leiden.cpp:168-293) and the library's Louvain on the first
+  // GPU, printKssdResult with the clusters in label order ----
+  const uint32_t n_nodes = (uint32_t)genomes.size();
+  vector<rtc_wedge> wedges;
+  if (o.has_pregraph) {
+    if (pregraph_nodes != n_nodes) {
+      cerr << "ERROR: --pregraph " << folder_path << ": leiden.graph has " << pregraph_nodes << " nodes, the folder " << n_nodes << " sketches" << endl;
+      return 1;
+    }
+    wedges.swap(pregraph);
+    cerr << "-----Loaded graph: " << n_nodes << " nodes, " << wedges.size() << " edges" << endl;
+  } else {
+    DeviceSketches ds;
+    if (rs.ok) resident_sketches(ctx, gpus[0], rs, nullptr, ds);
+    else upload_sketches(ctx, ks.use64 ? &ks.h64 : nullptr, ks.use64 ? nullptr : &ks.h32, ds);
+    cerr << "-----Building similarity graph..." << endl;
+    vector<rtc_gedge> edges((size_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_nodes * (uint64_t)o.knn, (uint64_t)16 * n_nodes)));
+    uint64_t n_edges = 0;
+    int st = rtc_graph_build(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, o.threshold, kmer_size, (uint32_t)o.knn, edges.data(), edges.size(), &n_edges);
+    if (st == RTC_ERR_OVERFLOW) {  // the count is known now
+      edges.resize(n_edges);
+      st = rtc_graph_build(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, o.threshold, kmer_size, (uint32_t)o.knn, edges.data(), edges.size(), &n_edges);
+    }
+    CHECK(ctx, st);
+    edges.resize(n_edges);
+    uint64_t gc[10] = {0};
+    rtc_graph_counters(ctx, gc);
+    cerr << "-----Comparisons: " << gc[1] << endl;
+    cerr << "-----Edges created: " << n_edges << endl;
+    vector<uint32_t> sizes(n_nodes);
+    CHECK(ctx, rtc_copy_d2h(ctx, sizes.data(), ds.d_len, (size_t)n_nodes * 4));
+    vector<double> weights(n_edges);
+    wedges.resize(n_edges);
+    for (uint64_t e = 0; e < n_edges; e++) {
+      weights[e] = rtc_graph_weight(edges[e].common, sizes[edges[e].u], sizes[edges[e].v], kmer_size);
+      wedges[e] = rtc_wedge{edges[e].u, edges[e].v, leiden_weight_units(weights[e])};
+    }
+    g_metrics.num("leiden_graph_s", gc[9] / 1e9);
+    if (o.saveGraph) {
+      const string graph_file = folder_path + "/leiden.graph";
+      if (!save_leiden_graph(graph_file, n_nodes, edges, weights)) return 1;
+      cerr << "-----Graph saved to: " << graph_file << endl;
+    }
+  }
+  if (wedges.empty()) cerr << "-----Warning: No edges! Each sequence in its own cluster." << endl;
+  vector<int32_t> labels(n_nodes);
+  uint32_t ncl = 0;
+  double modularity = 0.0;
+  CHECK(ctx, rtc_louvain(ctx, n_nodes, wedges.data(), wedges.size(), o.resolution, labels.data(), &ncl, &modularity));
+  uint64_t lc[10] = {0};
+  rtc_louvain_counters(ctx, lc);
+  cerr << "-----Louvain: " << lc[0] << " level(s), " << lc[1] << " round(s), modularity " << modularity << endl;
+  vector<vector<int>> cluster(ncl);
+  for (uint32_t x = 0; x < n_nodes; x++) cluster[labels[x]].push_back((int)x);
+  print_result(cluster, genomes, sketchByFile, o.outputFile);
+  cerr << "-----write the cluster result into: " << o.outputFile << endl;
+  cerr << "-----the cluster number of " << o.outputFile << " is: " << cluster.size() << endl;
+  cerr << "========time of Leiden clustering is: " << get_sec() - t2 << "========" << endl;
+  g_metrics.num("leiden_louvain_s", lc[9] / 1e9);
+  g_metrics.num("leiden_edges", (double)wedges.size());
+  g_metrics.num("leiden_levels", (double)lc[0]);
+  g_metrics.num("leiden_clusters", (double)ncl);
+  g_metrics.num("leiden_modularity", modularity);
 #elif defined(DBSCAN_CLUST)
   // ---- clust-dbscan: KssdDBSCAN (src/dbscan.cpp:725-985) on the first GPU, printKssdDBSCANResult (:1212-1310); with
   // --minhash MinHashDBSCAN (:987-1096) and printDBSCANResult (:1102-1210), whose layout is the same ----
@@ -2948,6 +3117,8 @@ int main(int argc, char** argv) {
   const double t_end = get_sec();
 #ifdef GREEDY_CLUST
   g_metrics.str("command", "clust-greedy");
+#elif defined(LEIDEN_CLUST)
+  g_metrics.str("command", "clust-leiden");
 #elif defined(DBSCAN_CLUST)
   g_metrics.str("command", "clust-dbscan");
 #else
