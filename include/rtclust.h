@@ -638,7 +638,7 @@ int rtc_dbscan_assign_counters(const rtc_ctx* ctx, uint64_t out[10]);
  * 256-lane workgroup (the longer ones). */
 int rtc_dbscan_assign_last_path(const rtc_ctx* ctx);
 
-/* ---- clust-leiden --louvain: similarity graph and Louvain ---------------------------------------------- */
+/* ---- clust-leiden: similarity graph, Louvain and Leiden ---------------------------------------------- */
 /* The graph of the reference's KssdLeidenCluster (src/leiden.cpp:168-293).  A pair u < v is an edge iff both sketches are
  * non-empty and share a hash, the size ratio passes -- !(2 min(|u|, |v|) < max(|u|, |v|)), which is the reference's
  * (double)small / large < 0.5 skip -- and dist < threshold strictly, dist = 1 - rtc_graph_weight(common, |u|, |v|, kmer_size):
@@ -692,6 +692,58 @@ int rtc_louvain(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, uint64_t m, 
  * adjacency entries of the last level, out[5] rows the long paths took (workgroup and global table, all rounds), out[6] move ns,
  * out[7] aggregate ns, out[8] rows the global-table path took, out[9] whole call ns. */
 int rtc_louvain_counters(const rtc_ctx* ctx, uint64_t out[10]);
+
+/* Deterministic Leiden in exact integers: clust-leiden --leiden.  The reference calls igraph_community_leiden (src/leiden.cpp:
+ * 337-383) without node weights -- the CPM objective with node weight 1 -- with beta 0.01 and 100 iterations.  igraph visits the
+ * nodes in a random order and draws the refinement's merges at random (with probability ~ exp(gain / beta)); this definition
+ * visits all vertices at once and takes the best merge, so it is no port of igraph's and igraph is no reproducible target:
+ * this is the definition (tests/refleiden.py restates it).
+ *   - Input, k_x, M2, g and the refusals are rtc_louvain's.  objective: RTC_LEIDEN_CPM, as the reference calls igraph, or
+ *     RTC_LEIDEN_MODULARITY; anything else RTC_ERR_ARG.
+ *   - The score.  Vertex x has node weight nu_x; N_d is the sum of nu over community d; e_d the weight from x to the members of
+ *     d other than x.  For x in community c,  S(d) = e_d A - g B nu_x (N_d - [d == c] nu_x)  in 128-bit signed integers, with
+ *         CPM:         nu of an input vertex 1,   A = 65536,      B = 2^20
+ *         modularity:  nu of an input vertex k_x, A = M2 65536,   B = 1     (rtc_louvain's score)
+ *     and nu summed when vertices are merged into one.
+ *   - An iteration runs levels 0, 1, ... (at most 32).  The vertices of a level enter with a coarse community each, named by
+ *     its smallest member at that level: at level 0 singletons in the first iteration, the previous iteration's result after.
+ *     (a) Move phase: rtc_louvain's rounds with the score above, from the partition given instead of from singletons.  Every
+ *         vertex decides from the state at the start of the round; candidates are the communities d != c that hold a
+ *         neighbour, d < c on even rounds and d > c on odd ones, with S(d) > S(c) strictly; the largest S wins, equal scores
+ *         go to the smallest d; all moves are applied together and N is rebuilt.  Two idle rounds in a row or 64 rounds end it.
+ *         A vertex never moves to an empty community.  C(x) below is the coarse community it leaves x in.
+ *     (b) Refinement.  Every vertex starts alone in the refined community R(x) = x.  With in_x the weight from x to C(x) minus
+ *         itself, x is eligible iff in_x A >= g B nu_x (N_C - nu_x), tested once.  A refined community r inside C is an
+ *         eligible target iff E_r A >= g B N_r (N_C - N_r), E_r the weight between r and C minus r, rebuilt every round.  In
+ *         round r = 0, 1, ... every eligible vertex x that is still the only member of R(x) proposes: its candidates are the
+ *         eligible targets d != R(x) that hold a neighbour y of x with C(y) = C(x), d < R(x) on even rounds and d > R(x) on
+ *         odd ones, with S(d) >= 0 (a lone vertex stays at score 0; >= is igraph's rule here); it proposes the one with the
+ *         largest S, equal scores to the smallest d.  A proposal is accepted iff no member of its target proposes in that
+ *         round, so a community either gives up its vertex or receives vertices; accepted moves are applied together.  A
+ *         refined community that has members holds the vertex it is named after, and only that vertex can propose for it.  The
+ *         proposal with the smallest target (even rounds; the largest on odd ones) is always accepted, so a round with a
+ *         proposal makes progress.  Every merge joins a vertex to a community that stays, over a positive edge, inside one
+ *         coarse community: refined communities are connected by construction.  Two rounds in a row without an accepted
+ *         proposal, or 64 rounds, end it.
+ *     (c) If the refinement merged nothing, or this was the 32nd level, the iteration ends and its result is the coarse
+ *         partition of (a) at the input's vertices.  Otherwise the refined communities, numbered by their smallest member,
+ *         are the next level's vertices: nu and the adjacency summed as rtc_louvain aggregates (the weight inside one becomes
+ *         its self entry), the coarse community of a new vertex that of its members.
+ *   - Iterations repeat from the input's graph, each from the result before, until one returns the labels it was given or 100
+ *     have run (:379); they are deterministic, so stopping at the first unchanged one equals running them all.
+ *   - h_labels, *h_n_clusters: as rtc_louvain's.  *h_quality (may be NULL), on the host from the labels, for information:
+ *     CPM the sum over c of (in_c 65536 - g 2^20 size_c^2) divided by (M2 65536), modularity rtc_louvain's.  m == 0: every
+ *     vertex is its own cluster.
+ *   - Under CPM every weight of at most one unit (q <= 2^20) gives e_d 65536 <= g 2^20 nu_x N_d at resolution >= 1: nothing
+ *     moves and every vertex is its own cluster.
+ * As for rtc_louvain, the result depends neither on the scheduling nor on the kernel path of a row.  Synchronous. */
+#define RTC_LEIDEN_CPM 0
+#define RTC_LEIDEN_MODULARITY 1
+int rtc_leiden(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, uint64_t m, double resolution, int objective, int32_t* h_labels,
+               uint32_t* h_n_clusters, double* h_quality);
+/* The last rtc_leiden: out[0] iterations, out[1] levels (all iterations), out[2] move rounds, out[3] moves, out[4] refinement
+ * rounds, out[5] merges accepted, out[6] proposals rejected, out[7] move ns, out[8] refinement ns, out[9] whole call ns. */
+int rtc_leiden_counters(const rtc_ctx* ctx, uint64_t out[10]);
 
 #ifdef __cplusplus
 }

@@ -146,6 +146,8 @@ SIGNATURES = {
     "rtc_graph_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_louvain": (_i, [_vp, _u32, _vp, _u64, C.c_double, _vp, C.POINTER(_u32), C.POINTER(C.c_double)]),
     "rtc_louvain_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_leiden": (_i, [_vp, _u32, _vp, _u64, C.c_double, _i, _vp, C.POINTER(_u32), C.POINTER(C.c_double)]),
+    "rtc_leiden_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_hierarchy_flat": (_i, [_u32, _vp, _u64, _vp, _i, _i, _vp, _vp, C.POINTER(_u32)]),
 }
 

@@ -801,6 +801,27 @@ class Context:
                  "total_ns")
         return {k: int(a[i]) for i, k in enumerate(names)}
 
+    def leiden(self, n, edges, resolution=1.0, objective="cpm", return_quality=False):
+        """rtc_leiden: the deterministic Leiden include/rtclust.h defines over n vertices and WEDGE_DT records (u, v, q).
+        objective "cpm" (node weight 1, as the reference calls igraph; at resolution >= 1 and weights of at most one unit nothing
+        moves) or "modularity"; 0 and 1 are taken too.  Returns int32 labels, communities numbered by their smallest vertex; with
+        return_quality (labels, quality)."""
+        obj = {"cpm": 0, "modularity": 1}.get(objective, objective)
+        e = np.ascontiguousarray(np.asarray(edges, dtype=WEDGE_DT))
+        labels = np.zeros(max(int(n), 1), dtype=np.int32)
+        ncl, quality = C.c_uint32(0), C.c_double(0.0)
+        self.check(self.lib.rtc_leiden(self.h, int(n), _np_ptr(e) if e.size else None, int(e.size), float(resolution), int(obj),
+                                       _np_ptr(labels), C.byref(ncl), C.byref(quality)))
+        self.leiden_clusters = int(ncl.value)
+        return (labels[:n].copy(), float(quality.value)) if return_quality else labels[:n].copy()
+
+    def leiden_counters(self):
+        """rtc_leiden_counters as a dict (the last leiden call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_leiden_counters(self.h, a))
+        names = ("iterations", "levels", "move_rounds", "moves", "refine_rounds", "merges", "rejected", "move_ns", "refine_ns", "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
     def dbscan_counters(self):
         """rtc_dbscan_counters as a dict (the last dbscan call)."""
         a = (C.c_uint64 * 10)()

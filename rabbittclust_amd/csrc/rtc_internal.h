@@ -89,6 +89,7 @@ struct rtc_ctx {
   int dbscan_assign_path = 0;  // rtc_dbscan_assign_last_path
   uint64_t graph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};    // rtc_graph_counters (include/rtclust.h lists them)
   uint64_t louvain[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_louvain_counters (include/rtclust.h lists them)
+  uint64_t leiden[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // rtc_leiden_counters
   int host_threads = 1;     // rtc_ctx_set_host_threads: the host side of rtc_tree_medoids
   // rtc_diag_counters: [0] pair tiles the join took, [1] tiled-kernel tiles, [2] merge-kernel tiles, [3] candidate lists contracted
   // to their forest, [4] greedy runs replayed from ONE global join, [5] greedy query blocks of the block loop, [6] estimates handed

@@ -33,3 +33,19 @@ def generate_shuffle_dim(half_subk):
         assert n == len(sd)
         _shuffle_cache[half_subk] = sd
     return _shuffle_cache[half_subk]
+
+
+def leiden_quantise(u, v, weight, objective):
+    """leiden_quantise (rtc_host.cpp): the q of clust-leiden --leiden's records from double weights; objective 0 CPM (the
+    reference's normalisation, records with q == 0 dropped), 1 modularity.  Returns ((u, v, q) records, narrow range?)."""
+    u = np.ascontiguousarray(u, dtype=np.uint32)
+    v = np.ascontiguousarray(v, dtype=np.uint32)
+    w = np.ascontiguousarray(weight, dtype=np.float64)
+    out = np.zeros(max(len(w), 1), dtype=[("u", "<u4"), ("v", "<u4"), ("q", "<u4")])
+    n_out = C.c_uint64(0)
+    fn = load().rtch_leiden_quantise
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
+    narrow = fn(u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p), len(w), int(objective),
+                out.ctypes.data_as(C.c_void_p), C.byref(n_out))
+    return out[:n_out.value].copy(), bool(narrow)

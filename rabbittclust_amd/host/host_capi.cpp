@@ -187,4 +187,13 @@ int rtch_dbscan_model_resave(const char* in_path, const char* out_path) {
   if (!load_dbscan_model(in_path, m, &why)) return -1;
   return save_dbscan_model(out_path, m) ? 0 : -2;
 }
+
+// leiden_quantise: out[m] receives the records kept, *n_out their number; returns 1 where the weights' range was narrow
+int rtch_leiden_quantise(const uint32_t* u, const uint32_t* v, const double* weight, uint64_t m, int objective, rtc_wedge* out, uint64_t* n_out) {
+  std::vector<rtc_wedge> rec;
+  const bool narrow = leiden_quantise(u, v, weight, m, objective, rec, nullptr, nullptr);
+  for (size_t i = 0; i < rec.size(); i++) out[i] = rec[i];
+  *n_out = rec.size();
+  return narrow ? 1 : 0;
+}
 }

@@ -880,8 +880,9 @@ struct Options {
   int minClusterSize = 0;   // --min-cluster-size (default: --minpts)
   // clust-leiden (src/main.cpp:184-198)
   double resolution = 1.0;
-  bool has_resolution = false, louvain = false, has_pregraph = false, saveGraph = false;
+  bool has_resolution = false, louvain = false, leiden = false, has_pregraph = false, saveGraph = false;
   int knn = 0;
+  string objective = "cpm";  // --objective, with --leiden: cpm as the reference calls igraph, or modularity
 };
 
 #ifdef LEIDEN_CLUST
@@ -900,13 +901,15 @@ static bool save_leiden_graph(const string& path, uint32_t n, const vector<rtc_g
   out.close();
   return !out.fail();
 }
-// the file back: every weight becomes q on the value the file holds; a weight <= 0 cannot be an edge's
-static bool load_leiden_graph(const string& path, vector<rtc_wedge>& edges, uint64_t& n, string* why) {
+// the file back: every weight becomes q on the value the file holds (weights: the values themselves, for --leiden's own
+// quantisation); a weight <= 0 cannot be an edge's
+static bool load_leiden_graph(const string& path, vector<rtc_wedge>& edges, vector<double>& weights, uint64_t& n, string* why) {
   std::ifstream in(path);
   if (!in.is_open()) { *why = "cannot open " + path; return false; }
   uint64_t m = 0;
   if (!(in >> n >> m) || n >= 0x7fffffffull) { *why = path + ": no 'nodes edges' header"; return false; }
   edges.clear();
+  weights.clear();
   edges.reserve((size_t)std::min<uint64_t>(m, (uint64_t)1 << 28));
   for (uint64_t e = 0; e < m; e++) {
     uint64_t u = 0, v = 0;
@@ -914,6 +917,7 @@ static bool load_leiden_graph(const string& path, vector<rtc_wedge>& edges, uint
     if (!(in >> u >> v >> w)) { *why = path + ": " + std::to_string(e) + " of " + std::to_string(m) + " edges"; return false; }
     if (u >= n || v >= n || !(w > 0.0) || !(w <= 4095.0)) { *why = path + ": edge " + std::to_string(e) + " is out of range"; return false; }
     edges.push_back(rtc_wedge{(uint32_t)u, (uint32_t)v, leiden_weight_units(w)});
+    weights.push_back(w);
   }
   return true;
 }
@@ -933,6 +937,8 @@ static Options parse(int argc, char** argv) {
     // the options of the Leiden build (src/main.cpp:184-198) and this build's own --save-graph; none of clust-dbscan's
     if (a == "--resolution") { o.resolution = atof(need(i)); o.has_resolution = true; continue; }
     if (a == "--louvain") { o.louvain = true; continue; }
+    if (a == "--leiden") { o.leiden = true; continue; }
+    if (a == "--objective") { o.objective = need(i); continue; }
     if (a == "--knn") { o.knn = atoi(need(i)); continue; }
     if (a == "--pregraph") { o.folder_path = need(i); o.has_pregraph = true; continue; }
     if (a == "--save-graph") { o.saveGraph = true; continue; }
@@ -1024,16 +1030,23 @@ static Options parse(int argc, char** argv) {
 #ifdef GREEDY_CLUST
       puts("clust-greedy (MI355X build): greedy incremental clustering module");
 #elif defined(LEIDEN_CLUST)
-      puts("clust-leiden (MI355X build): graph-based community detection (Louvain) clustering module, KSSD sketches (--fast)");
+      puts("clust-leiden (MI355X build): graph-based community detection (Leiden, Louvain) clustering module, KSSD sketches (--fast)");
       puts("  -t,--threads N  -m,--min-length N  -k,--kmer-size N (default 19)  -l,--list  -e,--no-save  -d,--threshold X (default 0.05:\n"
            "  a pair is an edge when its distance is below it)  -o,--output FILE  -i,--input FILE  --presketched DIR  --fast (required)\n"
-           "  --drlevel N  --gpus all|N|i,j,.. (sketching on every GPU, graph and Louvain on the first)\n"
-           "  --louvain (required: Leiden refinement is not in this build)  --resolution X (default 1.0; higher: more clusters)\n"
-           "  --knn K (every genome keeps its K best edges among the higher-numbered genomes; 0 or absent: 1000, 1..9: 50 with a\n"
-           "           warning, as the reference defaults it, so the filter cannot be switched off here)\n"
+           "  --drlevel N  --gpus all|N|i,j,.. (sketching on every GPU, graph and clustering on the first)\n"
+           "  --leiden | --louvain (one of the two is required; they exclude each other)  --resolution X (default 1.0; higher: more\n"
+           "  clusters)\n"
+           "  --leiden: the deterministic Leiden of include/rtclust.h (move phase, refinement into connected well-connected pieces,\n"
+           "           aggregation on the refined partition, iterations until the labels repeat)\n"
+           "  --objective cpm|modularity (with --leiden; default cpm, as the reference calls igraph: node weight 1, the weights\n"
+           "           normalised to [0, 1] when their range is below 0.5, the lightest edge dropping out.  Under cpm a --resolution\n"
+           "           of 1 or more -- the default included -- moves nothing and leaves every genome in its own cluster, which is\n"
+           "           what the reference's call does too: use --resolution below 1, or --objective modularity, to get clusters)\n"
+           "  --knn K (every genome keeps its K best edges among the higher-numbered genomes; 0 or absent: 1000 with --louvain, 500\n"
+           "           with --leiden; 1..9: 50 with a warning, as the reference defaults it, so the filter cannot be switched off)\n"
            "  --save-graph (leiden.graph into the sketch folder: 'n m', then 'u v weight' per edge; the weights carry 6 significant\n"
            "                digits, so a --pregraph run is defined on the file's weights, not on the sketches')\n"
-           "  --pregraph DIR (DIR/leiden.graph and the KSSD sketches of DIR: Louvain alone, for another --resolution)");
+           "  --pregraph DIR (DIR/leiden.graph and the KSSD sketches of DIR: the clustering alone, for another --resolution)");
       exit(0);
 #elif defined(DBSCAN_CLUST)
       puts("clust-dbscan (MI355X build): DBSCAN density-based clustering module (KSSD with --fast, MinHash with --minhash)");
@@ -2313,15 +2326,23 @@ int main(int argc, char** argv) {
   // ---- clust-leiden: the checks of src/main.cpp:391-477 in that order, all before any GPU context exists (the default
   // threshold 0.05 is set above, as for every command) ----
   if (o.has_resolution) cerr << "-----Resolution parameter: " << o.resolution << endl;
-  if (!o.louvain) { cerr << "ERROR: Leiden refinement is not in this build; run with --louvain" << endl; return 1; }
+  if (o.leiden && o.louvain) { cerr << "ERROR: --leiden and --louvain exclude each other" << endl; return 1; }
+  if (!o.louvain && !o.leiden) {
+    cerr << "ERROR: Leiden refinement is not in this build; run with --louvain" << endl;
+    cerr << "NOTE: the line above is kept for scripts that match it; name the algorithm: --leiden (the deterministic Leiden) or --louvain" << endl;
+    return 1;
+  }
+  if (o.objective != "cpm" && o.objective != "modularity") { cerr << "ERROR: --objective must be cpm or modularity, got " << o.objective << endl; return 1; }
   if (!(o.resolution > 0.0) || !(o.resolution < 65536.0)) { cerr << "ERROR: --resolution must be > 0 and below 65536, got " << o.resolution << endl; return 1; }
   if (!(o.threshold > 0.0)) { cerr << "ERROR: -d/--threshold must be > 0, got " << o.threshold << endl; return 1; }
   if (o.knn < 0) { cerr << "ERROR: --knn must be >= 0, got " << o.knn << endl; return 1; }
-  if (o.knn == 0) { o.knn = 1000; cerr << "-----Auto-enabled: edge-parallel + warm-start + knn=" << o.knn << endl; }
+  if (o.knn == 0 && o.louvain) { o.knn = 1000; cerr << "-----Auto-enabled: edge-parallel + warm-start + knn=" << o.knn << endl; }
+  if (o.knn == 0) { o.knn = 500; cerr << "-----Auto-selecting k-NN: k=" << o.knn << " (use --knn 0 to disable)" << endl; }
   if (o.knn > 0 && o.knn < 10) { cerr << "WARNING: --knn value too small (" << o.knn << "), recommend at least 50. Using 50." << endl; o.knn = 50; }
-  cerr << "-----Algorithm: Louvain (Optimized)" << endl;
+  cerr << (o.louvain ? "-----Algorithm: Louvain (Optimized)" : "-----Algorithm: Leiden") << endl;
   cerr << "  - k-NN filtering (k=" << o.knn << ")" << endl;
   vector<rtc_wedge> pregraph;
+  vector<double> pregraph_weights;
   if (o.has_pregraph) {
     cerr << "-----Clustering from pre-built graph (fast resolution adjustment)" << endl;
     o.has_presketched = true;  // the KSSD sketches of the folder name the genomes (clust_from_pregraph_leiden, src/sub_command.cpp:3200-3225)
@@ -2338,7 +2359,7 @@ int main(int argc, char** argv) {
   uint64_t pregraph_nodes = 0;
   if (o.has_pregraph) {
     string why;
-    if (!load_leiden_graph(o.folder_path + "/leiden.graph", pregraph, pregraph_nodes, &why)) {
+    if (!load_leiden_graph(o.folder_path + "/leiden.graph", pregraph, pregraph_weights, pregraph_nodes, &why)) {
       cerr << "ERROR: --pregraph " << o.folder_path << ": " << why << endl;
       return 1;
     }
@@ -2766,12 +2787,14 @@ int main(int argc, char** argv) {
   // GPU, printKssdResult with the clusters in label order ----
   const uint32_t n_nodes = (uint32_t)genomes.size();
   vector<rtc_wedge> wedges;
+  vector<double> weights;
   if (o.has_pregraph) {
     if (pregraph_nodes != n_nodes) {
       cerr << "ERROR: --pregraph " << folder_path << ": leiden.graph has " << pregraph_nodes << " nodes, the folder " << n_nodes << " sketches" << endl;
       return 1;
     }
     wedges.swap(pregraph);
+    weights.swap(pregraph_weights);
     cerr << "-----Loaded graph: " << n_nodes << " nodes, " << wedges.size() << " edges" << endl;
   } else {
     DeviceSketches ds;
@@ -2793,7 +2816,7 @@ int main(int argc, char** argv) {
     cerr << "-----Edges created: " << n_edges << endl;
     vector<uint32_t> sizes(n_nodes);
     CHECK(ctx, rtc_copy_d2h(ctx, sizes.data(), ds.d_len, (size_t)n_nodes * 4));
-    vector<double> weights(n_edges);
+    weights.resize(n_edges);
     wedges.resize(n_edges);
     for (uint64_t e = 0; e < n_edges; e++) {
       weights[e] = rtc_graph_weight(edges[e].common, sizes[edges[e].u], sizes[edges[e].v], kmer_size);
@@ -2810,19 +2833,40 @@ int main(int argc, char** argv) {
   vector<int32_t> labels(n_nodes);
   uint32_t ncl = 0;
   double modularity = 0.0;
-  CHECK(ctx, rtc_louvain(ctx, n_nodes, wedges.data(), wedges.size(), o.resolution, labels.data(), &ncl, &modularity));
   uint64_t lc[10] = {0};
-  rtc_louvain_counters(ctx, lc);
-  cerr << "-----Louvain: " << lc[0] << " level(s), " << lc[1] << " round(s), modularity " << modularity << endl;
+  const size_t graph_edges = wedges.size();
+  if (o.leiden) {
+    // --leiden: q from the weights anew (CPM: normalised as src/leiden.cpp:343-366, the records at q == 0 dropped)
+    const int objective = o.objective == "cpm" ? RTC_LEIDEN_CPM : RTC_LEIDEN_MODULARITY;
+    vector<uint32_t> eu(graph_edges), ev(graph_edges);
+    for (size_t e = 0; e < graph_edges; e++) { eu[e] = wedges[e].u; ev[e] = wedges[e].v; }
+    double w_min = 0.0, w_max = 0.0;
+    if (leiden_quantise(eu.data(), ev.data(), weights.data(), graph_edges, objective, wedges, &w_min, &w_max))
+      cerr << "-----Edge weights normalized: [" << w_min << ", " << w_max << "] -> [0, 1]" << endl;
+    if (objective == RTC_LEIDEN_CPM && o.resolution >= 1.0)
+      cerr << "-----Note: under --objective cpm a --resolution of 1 or more leaves every genome in its own cluster" << endl;
+    CHECK(ctx, rtc_leiden(ctx, n_nodes, wedges.data(), wedges.size(), o.resolution, objective, labels.data(), &ncl, &modularity));
+    rtc_leiden_counters(ctx, lc);
+    cerr << "-----Leiden (" << o.objective << "): " << lc[0] << " iteration(s), " << lc[1] << " level(s), " << lc[5] << " merge(s), quality " << modularity << endl;
+  } else {
+    CHECK(ctx, rtc_louvain(ctx, n_nodes, wedges.data(), wedges.size(), o.resolution, labels.data(), &ncl, &modularity));
+    rtc_louvain_counters(ctx, lc);
+    cerr << "-----Louvain: " << lc[0] << " level(s), " << lc[1] << " round(s), modularity " << modularity << endl;
+  }
   vector<vector<int>> cluster(ncl);
   for (uint32_t x = 0; x < n_nodes; x++) cluster[labels[x]].push_back((int)x);
   print_result(cluster, genomes, sketchByFile, o.outputFile);
   cerr << "-----write the cluster result into: " << o.outputFile << endl;
   cerr << "-----the cluster number of " << o.outputFile << " is: " << cluster.size() << endl;
   cerr << "========time of Leiden clustering is: " << get_sec() - t2 << "========" << endl;
-  g_metrics.num("leiden_louvain_s", lc[9] / 1e9);
-  g_metrics.num("leiden_edges", (double)wedges.size());
-  g_metrics.num("leiden_levels", (double)lc[0]);
+  g_metrics.num("leiden_louvain_s", lc[9] / 1e9);  // the clustering call, whichever algorithm
+  g_metrics.num("leiden_edges", (double)graph_edges);
+  g_metrics.num("leiden_levels", (double)(o.leiden ? lc[1] : lc[0]));
+  if (o.leiden) {
+    g_metrics.num("leiden_refine_s", lc[8] / 1e9);
+    g_metrics.num("leiden_iterations", (double)lc[0]);
+    g_metrics.num("leiden_merges", (double)lc[5]);
+  }
   g_metrics.num("leiden_clusters", (double)ncl);
   g_metrics.num("leiden_modularity", modularity);
 #elif defined(DBSCAN_CLUST)

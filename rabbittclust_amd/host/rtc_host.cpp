@@ -2809,4 +2809,28 @@ void print_dbscan_model_stats(const DbscanModel& m, std::ostream& os) {
      << "========================" << std::endl;
 }
 
+bool leiden_quantise(const uint32_t* u, const uint32_t* v, const double* weight, uint64_t m, int objective, std::vector<rtc_wedge>& out,
+                     double* w_min, double* w_max) {
+  out.clear();
+  out.reserve(m);
+  double lo = 1.0, hi = 0.0;
+  for (uint64_t e = 0; e < m; e++) {
+    if (weight[e] < lo) lo = weight[e];
+    if (weight[e] > hi) hi = weight[e];
+  }
+  if (w_min) *w_min = lo;
+  if (w_max) *w_max = hi;
+  const bool cpm = objective == 0;
+  const double range = hi - lo;
+  const bool narrow = cpm && hi - lo < 0.5, scale = narrow && range > 1e-6;
+  for (uint64_t e = 0; e < m; e++) {
+    const double x = scale ? (weight[e] - lo) / range : weight[e];
+    long long q = llround(x * 1048576.0);
+    if (!cpm && q < 1) q = 1;
+    if (q < 1) continue;
+    out.push_back(rtc_wedge{u[e], v[e], (uint32_t)std::min<long long>(q, 0xffffffffll)});
+  }
+  return narrow;
+}
+
 }  // namespace rtc

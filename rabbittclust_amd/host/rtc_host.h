@@ -298,6 +298,16 @@ void print_dbscan_model_stats(const DbscanModel& m, std::ostream& os);
 
 std::string current_date_time();  // src/common.hpp:36-44
 
+// clust-leiden --leiden: the weights of m edges to the q of rtc_wedge (units of 2^-20), in doubles.  objective 0 (CPM): as the
+// reference prepares igraph's weights (src/leiden.cpp:343-366) -- min and max searched from 1.0 and 0.0; when max - min < 0.5
+// and the range is above 1e-6, weight' = (weight - min) / range, otherwise the weights stay -- then q = llround(weight' * 2^20),
+// and a record with q == 0 is dropped (the lightest edge normalises to 0 and carries no weight).  objective 1 (modularity):
+// q = max(1, llround(weight * 2^20)) as the Louvain flow forms it, nothing dropped.  q is capped at 2^32 - 1.
+// Returns whether max - min < 0.5 under CPM (the reference prints its "Edge weights normalized" line then); *w_min and *w_max
+// (may be null) receive the two.
+bool leiden_quantise(const uint32_t* u, const uint32_t* v, const double* weight, uint64_t m, int objective, std::vector<rtc_wedge>& out,
+                     double* w_min, double* w_max);
+
 // Time the parser threads spent inside gzip decompression (libdeflate or zlib), summed over threads, and the bytes it produced
 // since the process started: the command lines report them (RTC_METRICS_JSON: inflate_gb_per_s_per_thread).
 void rtc_host_inflate_stats(double* seconds, uint64_t* bytes_out);
