@@ -483,6 +483,43 @@ int rtc_dbscan(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_
  * out[7] eps filter ns, out[8] components and labels ns, out[9] whole call ns. */
 int rtc_dbscan_counters(const rtc_ctx* ctx, uint64_t out[10]);
 
+/* ---- clust-dbscan --knn: KssdDBSCAN over the reference's k-NN graph ------------------------------------ */
+/* KssdDBSCAN with knn_k > 0 (src/dbscan.cpp:725-982): every point's neighbourhood is cut to its knn_k best-scoring candidates
+ * before the eps test, which makes the relation DIRECTED.  t, the sizes, max_posting and the count `common` are rtc_dbscan's.
+ * Per point p of a u32 set (buildKNNForPoint, :221-360):
+ *   candidates: c != p sharing a kept hash with p, floor(t |p|) <= |c| <= ceil(|p| / t); an empty sketch has none;
+ *   arrival order (the `touched` list, :271-300): ascending by (the smallest index in p's hash list of a kept hash that c
+ *     holds too, c);
+ *   passers (:333-338): the candidates with !(common (1 + t) + 1e-12 < t |p| + t |c|) in double, scored
+ *     (float)common / (float)(|p| + |c| - common), one correctly rounded binary32 division (:341-342);
+ *   selection (:344-349): the passers go in arrival order through a min-heap of (score, id) of capacity knn_k -- pushed while
+ *     it holds fewer, otherwise replacing its minimum (lowest score, then lowest id) only when score > that minimum's score;
+ *   N(p) (:444-454): the heap's members with (double)score >= t -- a second test, not the passers' one: a passer that fails it
+ *     still took a heap slot.
+ * p is a core point when |N(p)| + 1 >= min_pts, and the walk of :813-929 runs over these directed lists.  Both order-dependent
+ * steps are computed by their closed forms, which give the walk's result exactly: with s* the knn_k-th largest
+ * score of a row of more than knn_k passers and T the arrival of the knn_k-th passer at or above s*, the heap ends as every
+ * passer above s* plus the passers at s* that arrive no later than T, without the h of them with the lowest ids, h = the
+ * passers above s* arriving after T; and with edges p -> q for core p and q in N(p), m(v) = the smallest core index u with a
+ * path u -> ... -> v whose vertices other than v are all core (v itself for an empty path), v is noise (-1) when there is no
+ * such u and otherwise in the cluster numbered by the rank of m(v) among the distinct values of m -- core and border points
+ * alike.  h_core[n] (may be NULL): 1 for the core points.
+ * knn_k <= 0 (the reference builds no graph) and width 8 (its u64 brute force never reads the graph, :384-442) are rtc_dbscan's
+ * call with the same arguments.  knn_k < min_pts - 1 is raised to min_pts - 1 (:754-757).  Returns RTC_ERR_UNSUPPORTED for
+ * t <= 1e-12 and ceil(max |p| / t) > INT_MAX as rtc_dbscan does; a pair whose two orientations disagree is NO failure here:
+ * each orientation is evaluated on its own, as the reference does.  RTC_EDGE_BUDGET bounds the candidate edges of one row chunk;
+ * RTC_ERR_NOMEM past the device's memory, no fallback.  Synchronous. */
+int rtc_dbscan_knn(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                   double eps, int min_pts, int kmer_size, int max_posting, int knn_k, int32_t* h_labels, uint8_t* h_core,
+                   uint32_t* h_n_clusters, uint32_t* h_n_noise);
+/* What the last rtc_dbscan_knn call did (all 0 where it was rtc_dbscan's call): out[0] row chunks, out[1] candidate edges,
+ * out[2] directed passers, out[3] rows truncated (more than knn_k passers), out[4] rows that needed arrival keys (more than
+ * knn_k passers at or above s*), out[5] directed neighbour edges kept, out[6] core points, out[7] propagation rounds, out[8]
+ * selection ns (passers, sorts, arrival keys, neighbours), out[9] whole call ns. */
+int rtc_dbscan_knn_counters(const rtc_ctx* ctx, uint64_t out[10]);
+/* The last rtc_dbscan_knn call's propagation and labelling, ns. */
+uint64_t rtc_dbscan_knn_propagate_ns(const rtc_ctx* ctx);
+
 /* ---- clust-dbscan --eps-sweep / --kdist: many eps values and the k-distance curve from one pair phase ---------- */
 /* A point's k-th nearest candidate, k = min_pts - 1: j = common / (size_p + size_q - common).  neighbour = UINT32_MAX: the
  * point has fewer than k candidates (the other fields are 0 but size_p). */

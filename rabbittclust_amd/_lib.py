@@ -126,6 +126,10 @@ SIGNATURES = {
     "rtc_dbscan": (_i, [_vp, _vp, _i, _vp, _vp, _u32, C.c_double, _i, _i, _i, _vp, _vp, C.POINTER(_u32),
                        C.POINTER(_u32)]),
     "rtc_dbscan_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_dbscan_knn": (_i, [_vp, _vp, _i, _vp, _vp, _u32, C.c_double, _i, _i, _i, _i, _vp, _vp, C.POINTER(_u32),
+                           C.POINTER(_u32)]),
+    "rtc_dbscan_knn_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_dbscan_knn_propagate_ns": (_u64, [_vp]),
     "rtc_dbscan_sweep": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _u32, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "rtc_dbscan_sweep_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_dbscan_mash": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _u32, _vp, _u32, _i, _i, _vp, _vp, _vp, _vp]),

@@ -617,6 +617,32 @@ class Context:
             return labels[:n].copy(), core[:n].astype(bool)
         return labels[:n].copy()
 
+    def dbscan_knn(self, sk, eps, min_pts, kmer_size, knn_k, max_posting=0, return_core=False):
+        """clust-dbscan --fast --knn K (rtc_dbscan_knn): KssdDBSCAN over the reference's k-NN graph (src/dbscan.cpp:221-360,
+        :444-454), whose neighbour relation is directed; labels as Context.dbscan's.  knn_k <= 0 and u64 sketches are
+        Context.dbscan's call; knn_k < min_pts - 1 is raised to it.  return_core: (labels, bool core flags)."""
+        n = sk.n
+        labels = np.zeros(max(n, 1), dtype=np.int32)
+        core = np.zeros(max(n, 1), dtype=np.uint8)
+        ncl, nnoise = C.c_uint32(), C.c_uint32()
+        self.check(self.lib.rtc_dbscan_knn(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n, float(eps),
+                                           int(min_pts), int(kmer_size), int(max_posting), int(knn_k), _np_ptr(labels),
+                                           _np_ptr(core), C.byref(ncl), C.byref(nnoise)))
+        self.dbscan_knn_counts = (int(ncl.value), int(nnoise.value))
+        if return_core:
+            return labels[:n].copy(), core[:n].astype(bool)
+        return labels[:n].copy()
+
+    def dbscan_knn_counters(self):
+        """rtc_dbscan_knn_counters as a dict (the last dbscan_knn call), with propagate_ns (rtc_dbscan_knn_propagate_ns)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_dbscan_knn_counters(self.h, a))
+        names = ("chunks", "candidate_edges", "passers", "truncated_rows", "arrival_rows", "neighbour_edges", "core_points",
+                 "rounds", "select_ns", "total_ns")
+        out = {k: int(a[i]) for i, k in enumerate(names)}
+        out["propagate_ns"] = int(self.lib.rtc_dbscan_knn_propagate_ns(self.h))
+        return out
+
     def dbscan_sweep(self, sk, eps_list, min_pts, kmer_size, max_posting=0, return_core=False, kdist=False):
         """clust-dbscan --eps-sweep / --kdist (rtc_dbscan_sweep): Context.dbscan for every eps of eps_list (at most 32, any order)
         from one pair phase.  Returns int32 labels[n_eps, n]; with return_core also bool core[n_eps, n]; with kdist also the

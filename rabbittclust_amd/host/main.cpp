@@ -878,6 +878,7 @@ struct Options {
   bool minhash = false;     // clust-dbscan --minhash: MinHashDBSCAN over MinHash sketches (rtc_dbscan_mash) instead of --fast
   bool hasMaxPosting = false;
   int minClusterSize = 0;   // --min-cluster-size (default: --minpts)
+  int dbscanKnn = 0;        // clust-dbscan --knn: KssdDBSCAN over the k-NN graph (rtc_dbscan_knn); 0: the run without the flag
   // clust-leiden (src/main.cpp:184-198)
   double resolution = 1.0;
   bool has_resolution = false, louvain = false, leiden = false, has_pregraph = false, saveGraph = false;
@@ -974,7 +975,7 @@ static Options parse(int argc, char** argv) {
     if (a == "--kdist") { o.kdist = true; continue; }
     if (a == "--hierarchy") { o.hierarchy = true; continue; }
     if (a == "--min-cluster-size") { o.minClusterSize = atoi(need(i)); o.hasMinClusterSize = true; continue; }
-    if (a == "--knn") unsupported("--knn (approximate k-NN DBSCAN)");
+    if (a == "--knn") { o.dbscanKnn = atoi(need(i)); continue; }
     if (a == "--query" || a == "--top-k" || a == "--dense" ||
         a == "--premsted" || a == "--auto-threshold" || a == "--stability" || a == "--dedup-dist" || a == "--reps-per-cluster" ||
         a == "--newick-tree" || a == "--phylip-tree" || a == "--nexus-tree" || a == "--linkage-matrix" || a == "--buildDB") {
@@ -1066,7 +1067,12 @@ static Options parse(int argc, char** argv) {
            "                     parameters, eps and minpts come from FILE; per query its cluster or novel, bridges, neighbours, core\n"
            "                     neighbours, would_be_core, the nearest genome and its distance)\n"
            "  --db FILE --stats (kind, parameters, genomes, clusters, noise and core points of FILE; no GPU)\n"
-           "  -c,--containment N (KSSD tuner)  -s,--sketch-size N  --save-rep (accepted, no effect on DBSCAN)  --knn: not in this build");
+           "  -c,--containment N (KSSD tuner)  -s,--sketch-size N  --save-rep (accepted, no effect on DBSCAN)\n"
+           "  --knn K (the reference's approximate k-NN DBSCAN, label-identical: every genome keeps its K best-scoring candidates, then\n"
+           "           those within eps; 0: off; K < minpts - 1 is raised to it.  The GPU gains no time from it -- the pair phase\n"
+           "           already produces every candidate -- it is there to reproduce the reference's clusters.  With --fast, lists,\n"
+           "           a single FASTA, --presketched, --max-posting and -c; not with --minhash, --eps-sweep, --kdist, --hierarchy,\n"
+           "           --min-cluster-size or --db)");
       exit(0);
 #else
       puts("clust-mst (MI355X build): minimum-spanning-tree-based module");
@@ -2365,6 +2371,18 @@ int main(int argc, char** argv) {
     }
   }
 #elif defined(DBSCAN_CLUST)
+  // ---- clust-dbscan --knn: defined on the directed k-NN relation, so nothing built on the symmetric one goes with it, and
+  // --assign's border rule reads full neighbourhoods.  Its -i input is opened here: the GPU comes up beside the reading of the
+  // list, and a run that cannot start must say so before any context exists.
+  if (o.dbscanKnn > 0) {
+    const char* bad = o.minhash ? "--minhash" : !o.epsSweep.empty() ? "--eps-sweep" : o.kdist ? "--kdist" : o.hierarchy ? "--hierarchy"
+                      : o.hasMinClusterSize ? "--min-cluster-size" : !o.repdb_path.empty() ? "--db" : nullptr;
+    if (bad) { cerr << "ERROR: --knn does not go with " << bad << endl; return 1; }
+    if (o.has_input && !o.has_presketched && !std::ifstream(o.inputFile)) {
+      cerr << "ERROR: --knn: cannot open the input " << o.inputFile << endl;
+      return 1;
+    }
+  }
   // ---- clust-dbscan --db: the model file's flows, their flag errors before any GPU context exists ----
   DbscanModel db_model;
   {
@@ -2422,6 +2440,7 @@ int main(int argc, char** argv) {
   cerr << "-----Using DBSCAN clustering" << endl;
   cerr << "-----DBSCAN parameters: eps=" << o.dbscanEps << ", minPts=" << o.dbscanMinPts;
   if (o.maxPosting > 0) cerr << ", max-posting=" << o.maxPosting;
+  if (o.dbscanKnn > 0) cerr << ", knn=" << o.dbscanKnn;
   cerr << endl;
   if (!o.isSetKmer) { o.kmerSize = 19; cerr << "-----use default kmerSize: " << o.kmerSize << endl; }
   if (o.drlevel < 0 || o.drlevel > 8) { cerr << "ERROR: invalid drlevel " << o.drlevel << ", should be in [0, 8]" << endl; return 1; }
@@ -2898,7 +2917,29 @@ int main(int argc, char** argv) {
   vector<rtc_hedge> forest(o.hierarchy ? genomes.size() : 0);  // --hierarchy: n - 1 slots, the core triples beside them
   vector<rtc_kdist> hcore(o.hierarchy ? genomes.size() : 0);
   uint64_t n_forest = 0;
-  if (o.minhash && o.epsSweep.empty()) {
+  if (o.dbscanKnn > 0) {  // KssdDBSCAN's lines on its k (src/dbscan.cpp:754-761, :774), then the k-NN call
+    int knn_k = o.dbscanKnn;
+    if (knn_k < o.dbscanMinPts - 1) {
+      cerr << "-----WARNING: knn_k (" << knn_k << ") < minPts-1 (" << (o.dbscanMinPts - 1) << "). Adjusting knn_k to " << (o.dbscanMinPts - 1) << "." << endl;
+      knn_k = o.dbscanMinPts - 1;
+    } else if (knn_k < 5 * (o.dbscanMinPts - 1)) {
+      cerr << "-----WARNING: knn_k (" << knn_k << ") may be too small for stable DBSCAN. Consider knn_k >= " << (5 * (o.dbscanMinPts - 1)) << "." << endl;
+    }
+    cerr << "-----WARNING: k-NN acceleration is approximate for DBSCAN (may miss eps neighbors if k is small)." << endl;
+    CHECK(ctx, rtc_dbscan_knn(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, o.dbscanEps, o.dbscanMinPts, kmer_size, o.maxPosting, knn_k,
+                              labels.data(), core.data(), &ncl, &nnoise));
+    uint64_t kc[10] = {0};
+    rtc_dbscan_knn_counters(ctx, kc);
+    if (getenv("RTC_VERBOSE"))
+      fprintf(stderr, "[knn] k %d: %llu candidate edges in %llu chunk(s), %llu passers, %llu rows truncated (%llu by arrival order), %llu neighbour "
+              "edges, %llu rounds; selection %.3f ms, propagation %.3f ms\n", knn_k, (unsigned long long)kc[1], (unsigned long long)kc[0],
+              (unsigned long long)kc[2], (unsigned long long)kc[3], (unsigned long long)kc[4], (unsigned long long)kc[5], (unsigned long long)kc[7],
+              kc[8] / 1e6, rtc_dbscan_knn_propagate_ns(ctx) / 1e6);
+    g_metrics.num("dbscan_knn_k", (double)knn_k);
+    g_metrics.num("dbscan_knn_select_s", kc[8] / 1e9);
+    g_metrics.num("dbscan_knn_propagate_s", rtc_dbscan_knn_propagate_ns(ctx) / 1e9);
+    g_metrics.num("dbscan_knn_truncated_rows", (double)kc[3]);
+  } else if (o.minhash && o.epsSweep.empty()) {
     dbscan_mash(&o.dbscanEps, 1, labels.data(), core.data(), &ncl, &nnoise);
   } else if (o.epsSweep.empty() && !o.kdist && !o.hierarchy) {
     CHECK(ctx, rtc_dbscan(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, o.dbscanEps, o.dbscanMinPts, kmer_size, o.maxPosting,

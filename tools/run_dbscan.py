@@ -2,7 +2,11 @@
 of the DBSCAN call into the pair phase, the eps filter and the components from rtc_dbscan_counters.
 
     python tools/run_dbscan.py [--sets dense25k,cfg4_200k] [--eps 0.05] [--minpts 5] [--repeat 3] [--sweep e1,e2,...] [--kdist]
-                               [--hierarchy]
+                               [--hierarchy] [--knn K]
+
+--knn K times Context.dbscan_knn (clust-dbscan --knn K) beside Context.dbscan on the same set: the best of --repeat warm calls with
+the counters of rtc_dbscan_knn_counters -- passers, rows truncated, rows that needed arrival keys, neighbour edges, propagation
+rounds -- and the selection's and the propagation's share of the call.
 
 --sweep times one Context.dbscan_sweep over the listed eps values (best of --repeat warm calls) against the same values run as
 separate Context.dbscan calls (the sum of each value's best warm call), with the sweep's phases from rtc_dbscan_sweep_counters;
@@ -224,6 +228,7 @@ def main():
     ap.add_argument("--hierarchy", action="store_true")
     ap.add_argument("--minhash", action="store_true")
     ap.add_argument("--assign", type=int, default=0)
+    ap.add_argument("--knn", type=int, default=0)
     ap.add_argument("--baseline-lib", default="")
     ap.add_argument("--baseline-only", action="store_true")
     a = ap.parse_args()
@@ -276,6 +281,22 @@ def main():
                "components_ms": round(c["components_ns"] / 1e6, 3), "chunks": c["chunks"],
                "candidate_edges": c["candidate_edges"], "eps_edges": c["eps_edges"], "core_points": c["core_points"],
                "hook_rounds": c["hook_rounds"], "clusters": int(lab.max()) + 1, "noise": int((lab < 0).sum())}
+        if a.knn > 0:
+            kcs = []
+
+            def knn_call():
+                out = ctx.dbscan_knn(sk, a.eps, a.minpts, kmer, a.knn)
+                kcs.append(ctx.dbscan_knn_counters())
+                return out
+            knn_ms, klab = _best(knn_call, a.repeat)
+            kc = min(kcs[1:], key=lambda x: x["total_ns"])
+            row["knn"] = {"k": a.knn, "call_ms": round(knn_ms, 3), "library_ms": round(kc["total_ns"] / 1e6, 3),
+                          "select_ms": round(kc["select_ns"] / 1e6, 3), "propagate_ms": round(kc["propagate_ns"] / 1e6, 3),
+                          "chunks": kc["chunks"], "candidate_edges": kc["candidate_edges"], "passers": kc["passers"],
+                          "truncated_rows": kc["truncated_rows"], "arrival_rows": kc["arrival_rows"],
+                          "neighbour_edges": kc["neighbour_edges"], "core_points": kc["core_points"], "rounds": kc["rounds"],
+                          "clusters": int(klab.max(initial=-1)) + 1, "noise": int((klab < 0).sum()),
+                          "points_labelled_differently": int((klab != lab).sum())}
         if not a.no_mst:
             ctx.mst(sk, a.eps)
             tm = []
