@@ -675,6 +675,43 @@ int rtc_dbscan_assign_counters(const rtc_ctx* ctx, uint64_t out[10]);
  * 256-lane workgroup (the longer ones). */
 int rtc_dbscan_assign_last_path(const rtc_ctx* ctx);
 
+/* ---- clust-dbscan --db --update: new points added to a clustered set, exactly ------------------------------ */
+/* The layout is rtc_dbscan_assign's: rows [0, n_old) are the model, rows [n_old, n_old + n_new) the new points, n = their sum.
+ * RESULT: h_labels[n], h_core[n] (may be NULL), *h_n_clusters, *h_n_noise equal those of rtc_dbscan (is_minhash = 0, max_posting 0)
+ * or of rtc_dbscan_mash with this one eps (is_minhash = 1, sketch_size as there) on all n rows -- as long as h_labels_old[n_old]
+ * and h_core_old[n_old] are that call's output on the first n_old rows for the same (eps, min_pts, kmer_size).  Only the rows
+ * that can change anything are joined.  The neighbour relation is the kind's; a point is a core point iff
+ *     KSSD:     |N(v)| + 1 >= min_pts   (the point counts itself; at width 8 the empty sketches are neighbours of each other)
+ *     MinHash:  |N(v)| >= max(min_pts, 0), the point itself not counted (min_pts <= 0: every point is a core point).
+ * The rule.  Neighbour counts only grow, so an old core point stays one.  Two old core points within eps of each other are in
+ * one old cluster already, so every old core-core edge is implied by the old labels: each old core point starts under the
+ * smallest core index of its old cluster.  An old non-core point can become a core point ("promoted") only by a new neighbour.
+ * A non-core point takes the lowest-numbered cluster among its core neighbours', clusters are numbered by their smallest core
+ * index, and a promoted point can renumber them: an old border point needs all of its core neighbours again.  So:
+ *   stage 1: rows = the new points, columns = everything below the row: every new-old and new-new eps edge.  T = the old NOISE
+ *            points with at least one new eps neighbour; B = all old BORDER points (not core, label >= 0).
+ *   stage 2: rows = T u B, columns = the old points; each unordered pair with an end in T u B once.
+ * The core flags are the old ones OR the count rule; the count is complete for the new points, T and B, and an old point
+ * outside them has gained nothing.  Components over the seeds and the kept core-core edges; clusters numbered by their smallest
+ * core index in the original numbering; a non-core point with a core neighbour among the kept edges joins the lowest-numbered
+ * of their clusters; every other point is -1.  Old core points and untouched old noise points are never rows.
+ * n_new = 0: the model unchanged.  n_old = 0: the kind's full call.
+ * Errors.  RTC_ERR_ARG: h_labels_old or h_core_old NULL with n_old > 0, h_labels NULL with n > 0, n >= 2^31 - 1, an old label
+ * below -1, an old core point with label -1, an old cluster among 0 .. max label without a core point; otherwise those of
+ * the kind's full call (MinHash eps < 0 or NaN RTC_ERR_ARG, eps >= 1 RTC_ERR_UNSUPPORTED; KSSD jaccard_min <= 1e-12, a size
+ * bound past INT_MAX at width 4, a pair whose orientations disagree: RTC_ERR_UNSUPPORTED).  Both stages run in row chunks under
+ * RTC_EDGE_BUDGET; RTC_ERR_NOMEM means what it says, there is no fallback.  Old labels that are well-formed but not the full
+ * call's output give labels that mean nothing.  Synchronous. */
+int rtc_dbscan_update(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len,
+                      uint32_t n_old, uint32_t n_new, const int32_t* h_labels_old, const uint8_t* h_core_old,
+                      int is_minhash, uint32_t sketch_size, double eps, int min_pts, int kmer_size,
+                      int32_t* h_labels, uint8_t* h_core, uint32_t* h_n_clusters, uint32_t* h_n_noise);
+/* What the last rtc_dbscan_update call did: out[0] stage-1 rows, out[1] stage-2 rows (|T u B|), out[2] row chunks and out[3]
+ * candidate edges of both stages together, out[4] pairs kept, out[5] promoted points, out[6] old clusters merged away (old
+ * clusters minus the final clusters that hold an old core point), out[7] hook rounds, out[8] join ns, out[9] filter ns, out[10]
+ * components and labels ns, out[11] whole call ns.  Twelve words: the two stages' rows each have their own. */
+int rtc_dbscan_update_counters(const rtc_ctx* ctx, uint64_t out[12]);
+
 /* ---- clust-leiden: similarity graph, Louvain and Leiden ---------------------------------------------- */
 /* The graph of the reference's KssdLeidenCluster (src/leiden.cpp:168-293).  A pair u < v is an edge iff both sketches are
  * non-empty and share a hash, the size ratio passes -- !(2 min(|u|, |v|) < max(|u|, |v|)), which is the reference's

@@ -144,6 +144,9 @@ SIGNATURES = {
     "rtc_dbscan_assign": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _u32, _vp, _vp, _i, _u32, C.c_double, _i, _i, _u32, _vp]),
     "rtc_dbscan_assign_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_dbscan_assign_last_path": (_i, [_vp]),
+    "rtc_dbscan_update": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _u32, _vp, _vp, _i, _u32, C.c_double, _i, _i, _vp, _vp, C.POINTER(_u32),
+                               C.POINTER(_u32)]),
+    "rtc_dbscan_update_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_hierarchy_cut": (_i, [_u32, _vp, _u64, _vp, C.c_double, C.c_double, _i, _vp, _vp, C.POINTER(_u32)]),
     "rtc_graph_build": (_i, [_vp, _vp, _i, _vp, _vp, _u32, C.c_double, _i, _u32, _vp, _u64, C.POINTER(_u64)]),
     "rtc_graph_weight": (C.c_double, [_u32, _u32, _u32, _i]),

@@ -738,6 +738,37 @@ class Context:
         out["fold_paths"] = int(self.lib.rtc_dbscan_assign_last_path(self.h))
         return out
 
+    def dbscan_update(self, sk, n_old, labels, core, eps, min_pts, kmer_size, sketch_size=None):
+        """clust-dbscan --db --update (rtc_dbscan_update): sk holds the n_old model points, then the new ones; labels / core are
+        the model's, from Context.dbscan (sketch_size None) or Context.dbscan_mash (sketch_size: the estimator's) at this eps,
+        min_pts and kmer_size.  Returns (labels, bool core) over all of sk, equal to that call on all of sk; only the new rows and
+        the old noise and border rows that can change are joined.  The cluster and noise counts stay in self.dbscan_update_counts."""
+        n_old, n = int(n_old), sk.n
+        if n_old > n:
+            raise ValueError("n_old exceeds the sketch set")
+        lab = None if labels is None else np.ascontiguousarray(np.asarray(labels, dtype=np.int32))
+        cr = None if core is None else np.ascontiguousarray(np.asarray(core, dtype=np.uint8))
+        if (lab is not None and lab.shape != (n_old,)) or (cr is not None and cr.shape != (n_old,)):
+            raise ValueError("labels and core need one entry per model point")
+        out_l = np.zeros(max(n, 1), dtype=np.int32)
+        out_c = np.zeros(max(n, 1), dtype=np.uint8)
+        ncl, nnoise = C.c_uint32(), C.c_uint32()
+        self.check(self.lib.rtc_dbscan_update(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n_old, n - n_old,
+                                              _np_ptr(lab) if lab is not None else None, _np_ptr(cr) if cr is not None else None,
+                                              0 if sketch_size is None else 1, 0 if sketch_size is None else int(sketch_size),
+                                              float(eps), int(min_pts), int(kmer_size), _np_ptr(out_l), _np_ptr(out_c),
+                                              C.byref(ncl), C.byref(nnoise)))
+        self.dbscan_update_counts = (int(ncl.value), int(nnoise.value))
+        return out_l[:n].copy(), out_c[:n].astype(bool)
+
+    def dbscan_update_counters(self):
+        """rtc_dbscan_update_counters as a dict (the last dbscan_update call)."""
+        a = (C.c_uint64 * 12)()
+        self.check(self.lib.rtc_dbscan_update_counters(self.h, a))
+        names = ("stage1_rows", "stage2_rows", "chunks", "candidate_edges", "kept_edges", "promoted", "merged", "hook_rounds",
+                 "join_ns", "predicate_ns", "components_ns", "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
     def dbscan_hierarchy(self, sk, eps_max, min_pts, kmer_size, max_posting=0):
         """clust-dbscan --hierarchy (rtc_dbscan_hierarchy): the maximum spanning forest of the mutual-reachability relation over
         the pairs Context.dbscan keeps at eps_max, and every point's core triple.  Returns (forest, core): HEDGE_DT edges in the

@@ -263,11 +263,12 @@ struct PlanHold {
 
 // The pair phase of a DBSCAN call: every pair sharing a hash (rtc_pair_edges_dev, radio < 0) over row chunks, the overflow
 // protocol of rtc_candidate_edges_device.  on_chunk(d_cand, count) sees every chunk once, before the next one is produced;
-// the candidate list is released on the way out.  budget: the candidate edges of one chunk.
+// the candidate list is released on the way out.  budget: the candidate edges of one chunk.  first_row: the rows below it are
+// columns only (1: every pair of the set; rtc_dbscan_update joins its row ranges alone).
 struct PairPhase { uint64_t chunks = 0, cand_total = 0, pair_ns = 0; };
 template <class F>
 int dbscan_pair_chunks(rtc_ctx* ctx, DevBuf& db, const void* ph, int width, const uint64_t* pstart, const uint32_t* plen, uint32_t n,
-                       unsigned long long* d_cnt, PairPhase* pp, F&& on_chunk) {
+                       uint32_t first_row, unsigned long long* d_cnt, PairPhase* pp, F&& on_chunk) {
   hipStream_t s = ctx->stream;
   uint64_t budget = (uint64_t)256 << 20;  // candidate edges of one chunk (3 GiB)
   if (ctx->opt.edge_budget) budget = ctx->opt.edge_budget;
@@ -276,7 +277,7 @@ int dbscan_pair_chunks(rtc_ctx* ctx, DevBuf& db, const void* ph, int width, cons
   uint64_t cand_cap = std::min<uint64_t>(budget, std::max<uint64_t>((uint64_t)1 << 20, (uint64_t)n * 160));
   RTC_TRY(db.get(ctx, cand_cap, &d_cand));
   const uint32_t row_end = n;
-  uint32_t r0 = 1, rows_per = n;
+  uint32_t r0 = std::max<uint32_t>(first_row, 1), rows_per = n;
   int redo = 0;
   PlanHold hold{ctx};
   while (r0 < row_end) {
@@ -316,7 +317,7 @@ int dbscan_pair_chunks(rtc_ctx* ctx, DevBuf& db, const void* ph, int width, cons
     redo = 0;
     pp->chunks++;
     pp->cand_total += cnt;
-    RTC_TRY(on_chunk((const rtc_cedge*)d_cand, (uint64_t)cnt));
+    RTC_TRY(on_chunk(d_cand, (uint64_t)cnt));
     r0 = r1;
   }
   db.release(d_cand);

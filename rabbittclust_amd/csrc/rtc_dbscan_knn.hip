@@ -335,7 +335,7 @@ extern "C" int rtc_dbscan_knn(rtc_ctx* ctx, const void* d_hashes, int width, con
     if (!cnt) return RTC_OK;
     return filter_chunk(ctx, db, who, knn_keep_kernel, d_cand, cnt, d_len, lv, 1, 65535u, d_cnt + 1, &kept);
   };
-  RTC_TRY(dbscan_pair_chunks(ctx, db, ph, 4, pstart, plen, n, d_cnt, &pp, on_chunk));
+  RTC_TRY(dbscan_pair_chunks(ctx, db, ph, 4, pstart, plen, n, 1, d_cnt, &pp, on_chunk));
   out[0] = pp.chunks; out[1] = pp.cand_total;
 
   // ---- (a) directed passers, (b) the selection, (c) arrival keys where a row needs them ----

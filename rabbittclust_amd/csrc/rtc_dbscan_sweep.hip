@@ -34,10 +34,15 @@
 // rtc_dbscan_mash (clust-dbscan --minhash) is MinHashDBSCAN (:685-720, :987-1096) through the same dbscan_run: the
 // pair phase and everything from the kept list onward are shared; its predicate (rtc_dbscan_mash.h) takes eps_mask_kernel's
 // place and its core rule counts the neighbours alone (|N(v)| >= minPts, :1017, :1050) where KssdDBSCAN's counts the point too.
+//
+// rtc_dbscan_update (clust-dbscan --db --update) is one level of either kind through the same dbscan_run with an
+// UpdReq: the pair phase runs over the new rows and then over a view of the old noise and border rows that can change
+// (rtc_dbscan_update.h), the old core-core edges are seeds of the union-find, and everything from the kept list onward is shared.
 #include "rtc_dbscan_common.h"
 #include "rtc_topk_select.h"
 #include "rtc_dbscan_hier.h"
 #include "rtc_dbscan_mash.h"
+#include "rtc_dbscan_update.h"
 
 namespace {
 
@@ -305,6 +310,11 @@ struct HierReq { double eps_max; rtc_hedge* h_forest; uint64_t* h_n_forest; rtc_
 // What makes a call MinHashDBSCAN: the estimator's sketch size.  The levels' predicate is then rtc_dbscan_mash.h's, the core
 // rule |N(v)| >= minPts, and the empty sketches are plain points (distance 1 to everything).
 struct MashReq { uint32_t sketch_size; };
+// What makes a call an update (rtc_dbscan_update): rows [0, n_old) carry a clustering -- that of this very call on them alone,
+// which the entry point has checked as far as the host can -- and only the rows that can change anything are joined: stage 1
+// the new rows against everything below them, stage 2 the old noise points that stage 1 touched and the old border points
+// against the old rows.  The old core-core edges are the seeds (rtc_dbscan_update.h).  One level, no curve, no hierarchy.
+struct UpdReq { uint32_t n_old; const int32_t* h_labels_old; const uint8_t* h_core_old; uint32_t n_clusters_old; uint64_t rows2; };
 
 // What one call did.  Every entry point maps it onto its own counter array and touches no other.
 struct DbscanStats {
@@ -320,7 +330,7 @@ struct DbscanStats {
 static int dbscan_run(rtc_ctx* ctx, const char* who, bool single, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len,
                       uint32_t n, const double* h_eps, uint32_t n_eps, int min_pts, int kmer_size, int max_posting, int32_t* h_labels,
                       uint8_t* h_core, uint32_t* h_n_clusters, uint32_t* h_n_noise, rtc_kdist* h_kdist, const HierReq* hq, DbscanStats* st,
-                      const MashReq* mq = nullptr) {
+                      const MashReq* mq = nullptr, UpdReq* uq = nullptr) {
   if (!ctx || (n && (!d_hashes || !d_start || !d_len)) || (width != 4 && width != 8)) return RTC_ERR_ARG;
   if (n_eps > DB_MAX_LEVELS) return rtc_fail(ctx, RTC_ERR_ARG, "%s: %u eps values, at most %u", who, n_eps, DB_MAX_LEVELS);
   if (n_eps == 0 && !h_kdist && !hq) return rtc_fail(ctx, RTC_ERR_ARG, "%s: no eps value and no k-distance curve asked for", who);
@@ -441,7 +451,73 @@ static int dbscan_run(rtc_ctx* ctx, const char* who, bool single, const void* d_
       }
       return RTC_OK;
   };
-  if (n_eps || curve || hq) RTC_TRY(dbscan_pair_chunks(ctx, db, ph, width, pstart, plen, n, d_cnt, &pp, on_chunk));
+  int32_t* d_lab_old = nullptr;
+  uint8_t* d_core_old = nullptr;
+  if (uq) {
+    const uint32_t n_old = uq->n_old;
+    // ---- stage 1: the new rows against everything below them; no view, the rows are last already ----
+    RTC_TRY(dbscan_pair_chunks(ctx, db, ph, width, pstart, plen, n, n_old, d_cnt, &pp, on_chunk));
+    // ---- T u B: the old border points (from the host) and the old noise points at the old end of a kept pair ----
+    uint32_t *d_flag = nullptr, *d_pos = nullptr, *d_perm = nullptr, *d_vlen = nullptr;
+    uint64_t* d_vstart = nullptr;
+    RTC_TRY(db.get(ctx, n_old, &d_lab_old));
+    RTC_TRY(db.get(ctx, n_old, &d_core_old));
+    RTC_TRY(db.get(ctx, n_old, &d_flag));
+    RTC_TRY(db.get(ctx, n_old, &d_pos));
+    std::vector<uint32_t> h_flag(n_old);
+    for (uint32_t v = 0; v < n_old; v++) h_flag[v] = !uq->h_core_old[v] && uq->h_labels_old[v] >= 0;
+    RTC_HIP(ctx, hipMemcpyAsync(d_lab_old, uq->h_labels_old, (size_t)n_old * 4, hipMemcpyHostToDevice, s));
+    RTC_HIP(ctx, hipMemcpyAsync(d_core_old, uq->h_core_old, n_old, hipMemcpyHostToDevice, s));
+    RTC_HIP(ctx, hipMemcpyAsync(d_flag, h_flag.data(), (size_t)n_old * 4, hipMemcpyHostToDevice, s));
+    const dim3 go(blocks_for(n_old, ctx->num_cu)), b(256);
+    if (kept.used) {
+      hipLaunchKernelGGL(upd_touch_kernel, dim3(blocks_for(kept.used, ctx->num_cu)), b, 0, s, (const rtc_cedge*)kept.d, kept.used, n_old,
+                         (const int32_t*)d_lab_old, d_flag);
+      RTC_CHECK_LAUNCH(ctx);
+    }
+    bool new_empty = false;
+    for (uint32_t g = n_old; g < n; g++) new_empty |= h_len[g] == 0;
+    if (empty_root != 0xffffffffu && new_empty) {
+      hipLaunchKernelGGL(upd_touch_empty_kernel, go, b, 0, s, d_len, n_old, (const int32_t*)d_lab_old, d_flag);
+      RTC_CHECK_LAUNCH(ctx);
+    }
+    size_t tb = 0;
+    RTC_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n_old, rocprim::plus<uint32_t>(), s));
+    void* tmp = nullptr;
+    RTC_TRY(rtc_ws(ctx, 5, tb + 256, &tmp));
+    RTC_HIP(ctx, rocprim::exclusive_scan(tmp, tb, (const uint32_t*)d_flag, d_pos, 0u, (size_t)n_old, rocprim::plus<uint32_t>(), s));
+    uint32_t last[2] = {0, 0};
+    RTC_HIP(ctx, hipMemcpyAsync(&last[0], d_pos + (n_old - 1), 4, hipMemcpyDeviceToHost, s));
+    RTC_HIP(ctx, hipMemcpyAsync(&last[1], d_flag + (n_old - 1), 4, hipMemcpyDeviceToHost, s));
+    RTC_HIP(ctx, hipStreamSynchronize(s));  // (h_flag goes away below)
+    const uint32_t k2 = last[0] + last[1];
+    if (k2 > n_old) return rtc_fail(ctx, RTC_ERR_HIP, "%s: %u rows flagged among %u", who, k2, n_old);
+    uq->rows2 = k2;
+    // ---- stage 2: those rows against the old rows, on a view that places them last; its pairs come back in the original numbering ----
+    if (k2 && n_old > 1) {
+      RTC_TRY(db.get(ctx, n_old, &d_perm));
+      RTC_TRY(db.get(ctx, n_old, &d_vlen));
+      RTC_TRY(db.get(ctx, n_old, &d_vstart));
+      hipLaunchKernelGGL(upd_view_kernel, go, b, 0, s, (const uint32_t*)d_flag, (const uint32_t*)d_pos, n_old, k2, pstart, plen, d_vstart, d_vlen, d_perm);
+      RTC_CHECK_LAUNCH(ctx);
+      auto on_view_chunk = [&](rtc_cedge* d_cand, uint64_t cnt) -> int {
+        if (!cnt) return RTC_OK;
+        hipLaunchKernelGGL(upd_unview_kernel, dim3(blocks_for(cnt, ctx->num_cu)), dim3(256), 0, s, d_cand, cnt, n_old, (const uint32_t*)d_perm);
+        RTC_CHECK_LAUNCH(ctx);
+        return on_chunk(d_cand, cnt);
+      };
+      // the join's note of a dense tile is keyed by the hash buffer and the tile, not by start / len: none from another
+      // arrangement of these hashes may speak for the view, and none from the view for a later call
+      ctx->join_dense.hashes = nullptr;
+      const int rc2 = dbscan_pair_chunks(ctx, db, ph, width, (const uint64_t*)d_vstart, (const uint32_t*)d_vlen, n_old, n_old - k2, d_cnt, &pp, on_view_chunk);
+      ctx->join_dense.hashes = nullptr;
+      RTC_TRY(rc2);
+      db.release(d_perm); db.release(d_vlen); db.release(d_vstart);
+    }
+    db.release(d_flag); db.release(d_pos);
+  } else if (n_eps || curve || hq) {
+    RTC_TRY(dbscan_pair_chunks(ctx, db, ph, width, pstart, plen, n, 1, d_cnt, &pp, on_chunk));
+  }
   st->chunks = pp.chunks;
   st->candidates = pp.cand_total;
   st->pair_ns = pp.pair_ns;
@@ -533,6 +609,18 @@ static int dbscan_run(rtc_ctx* ctx, const char* who, bool single, const void* d_
   hipLaunchKernelGGL(core_init_kernel, gv, b, 0, s, (const uint32_t*)d_deg, d_len, n, L, (long long)min_pts, mq ? 0ll : 1ll, empty_root, d_coremask, d_parent,
                      (unsigned long long*)(d_changed + 2));
   RTC_CHECK_LAUNCH(ctx);
+  if (uq) {  // the seeds: every old core point stays one and hangs under its old cluster's smallest core index
+    uint32_t* d_tab = nullptr;
+    const uint32_t nc = uq->n_clusters_old;
+    RTC_TRY(db.get(ctx, std::max<uint32_t>(nc, 1), &d_tab));
+    RTC_HIP(ctx, hipMemsetAsync(d_tab, 0xff, (size_t)std::max<uint32_t>(nc, 1) * 4, s));
+    const dim3 go(blocks_for(uq->n_old, ctx->num_cu));
+    hipLaunchKernelGGL(upd_seed_min_kernel, go, b, 0, s, (const int32_t*)d_lab_old, (const uint8_t*)d_core_old, uq->n_old, nc, d_tab);
+    RTC_CHECK_LAUNCH(ctx);
+    hipLaunchKernelGGL(upd_seed_kernel, go, b, 0, s, (const int32_t*)d_lab_old, (const uint8_t*)d_core_old, uq->n_old, nc, (const uint32_t*)d_tab,
+                       d_coremask, d_parent);
+    RTC_CHECK_LAUNCH(ctx);
+  }
   uint32_t* h_changed = nullptr;
   RTC_TRY(rtc_pinned(ctx, 64, (void**)&h_changed));
   uint64_t rounds = 0;
@@ -655,6 +743,81 @@ extern "C" int rtc_dbscan_mash(rtc_ctx* ctx, const void* d_hashes, int width, co
     std::copy(c, c + 10, ctx->dbscan_mash);
   }
   return rc;
+}
+
+// rtc_dbscan_update: include/rtclust.h is the definition.  The old clustering is checked as far as the host can (RTC_ERR_ARG),
+// then the call is dbscan_run's one level of the model's kind with an UpdReq.
+extern "C" int rtc_dbscan_update(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n_old,
+                                 uint32_t n_new, const int32_t* h_labels_old, const uint8_t* h_core_old, int is_minhash, uint32_t sketch_size,
+                                 double eps, int min_pts, int kmer_size, int32_t* h_labels, uint8_t* h_core, uint32_t* h_n_clusters,
+                                 uint32_t* h_n_noise) {
+  const char* who = "rtc_dbscan_update";
+  if (!ctx) return RTC_ERR_ARG;
+  if ((uint64_t)n_old + n_new >= 0x7fffffffu) return rtc_fail(ctx, RTC_ERR_ARG, "%s: %u + %u points", who, n_old, n_new);
+  const uint32_t n = n_old + n_new;
+  if (n_old && (!h_labels_old || !h_core_old)) return rtc_fail(ctx, RTC_ERR_ARG, "%s: the model's labels or core flags are missing", who);
+  if (n && !h_labels) return rtc_fail(ctx, RTC_ERR_ARG, "%s: no room for the labels", who);
+  // the old clustering: noise is -1, a core point has a cluster, the clusters are 0 .. max and each has a core point
+  int32_t max_label = -1;
+  for (uint32_t v = 0; v < n_old; v++) {
+    if (h_labels_old[v] < -1) return rtc_fail(ctx, RTC_ERR_ARG, "%s: old label %d of point %u", who, h_labels_old[v], v);
+    if (h_core_old[v] && h_labels_old[v] < 0) return rtc_fail(ctx, RTC_ERR_ARG, "%s: old point %u is a core point without a cluster", who, v);
+    max_label = std::max(max_label, h_labels_old[v]);
+  }
+  const uint32_t nc_old = (uint32_t)(max_label + 1);
+  uint32_t noise_old = 0;
+  {
+    std::vector<uint8_t> has_core(nc_old, 0);
+    for (uint32_t v = 0; v < n_old; v++) {
+      if (h_core_old[v]) has_core[h_labels_old[v]] = 1;
+      noise_old += h_labels_old[v] < 0;
+    }
+    for (uint32_t c = 0; c < nc_old; c++)
+      if (!has_core[c]) return rtc_fail(ctx, RTC_ERR_ARG, "%s: old cluster %u of %u has no core point", who, c, nc_old);
+  }
+  const MashReq mq{sketch_size};
+  const int mp = is_minhash ? std::max(min_pts, 0) : min_pts;
+  DbscanStats st;
+  UpdReq uq{n_old, h_labels_old, h_core_old, nc_old, 0};
+  uint64_t rows1 = n_new, promoted = 0, merged = 0;
+  int rc = RTC_OK;
+  if (n_new == 0) {  // the model as it is (after the kind's own argument checks: an empty set passes them alone)
+    rc = dbscan_run(ctx, who, true, nullptr, width, nullptr, nullptr, 0, &eps, 1, mp, kmer_size, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                    &st, is_minhash ? &mq : nullptr);
+    if (rc != RTC_OK) return rc;
+    if (n_old) memcpy(h_labels, h_labels_old, (size_t)n_old * 4);
+    if (n_old && h_core) memcpy(h_core, h_core_old, n_old);
+    if (h_n_clusters) *h_n_clusters = nc_old;
+    if (h_n_noise) *h_n_noise = noise_old;
+    st.total_ns = 0;
+  } else {
+    std::vector<uint8_t> core_own;
+    if (!h_core) { core_own.resize(n); h_core = core_own.data(); }
+    rc = dbscan_run(ctx, who, true, d_hashes, width, d_start, d_len, n, &eps, 1, mp, kmer_size, 0, h_labels, h_core, h_n_clusters, h_n_noise, nullptr,
+                    nullptr, &st, is_minhash ? &mq : nullptr, n_old ? &uq : nullptr);
+    if (rc == RTC_OK && n_old) {
+      std::vector<uint8_t> seen(nc_old ? (size_t)n : 0, 0);  // final labels that old core points carry
+      uint64_t distinct = 0;
+      for (uint32_t v = 0; v < n_old; v++) {
+        promoted += h_core[v] && !h_core_old[v];
+        if (h_core_old[v] && h_labels[v] >= 0 && !seen[h_labels[v]]) { seen[h_labels[v]] = 1; distinct++; }
+      }
+      merged = nc_old - distinct;
+    }
+    if (!n_old) rows1 = n_new ? n_new - 1 : 0;  // the plain call: row 0 has nothing below it
+  }
+  if (st.began) {
+    const uint64_t c[12] = {rows1, uq.rows2, st.chunks, st.candidates, st.kept, promoted, merged, st.rounds, st.pair_ns, st.filter_ns,
+                            st.components_ns, st.total_ns};
+    std::copy(c, c + 12, ctx->dbscan_update);
+  }
+  return rc;
+}
+
+extern "C" int rtc_dbscan_update_counters(const rtc_ctx* ctx, uint64_t out[12]) {
+  if (!ctx || !out) return RTC_ERR_ARG;
+  for (int i = 0; i < 12; i++) out[i] = ctx->dbscan_update[i];
+  return RTC_OK;
 }
 
 extern "C" int rtc_dbscan_mash_counters(const rtc_ctx* ctx, uint64_t out[10]) {

@@ -169,7 +169,7 @@ extern "C" int rtc_graph_build(rtc_ctx* ctx, const void* d_hashes, int width, co
     if (!cnt) return RTC_OK;
     return filter_chunk(ctx, db, who, graph_filter_kernel, d_cand, cnt, d_len, lv, 1, 0xffffffffu, d_cnt + 1, &kept);
   };
-  RTC_TRY(dbscan_pair_chunks(ctx, db, d_hashes, width, d_start, d_len, n, d_cnt, &pp, on_chunk));
+  RTC_TRY(dbscan_pair_chunks(ctx, db, d_hashes, width, d_start, d_len, n, 1, d_cnt, &pp, on_chunk));
 
   const uint64_t t_sel = now_ns();
   rtc_cedge* d_final = kept.d;

@@ -87,6 +87,7 @@ struct rtc_ctx {
   uint64_t dbscan_mash[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // rtc_dbscan_mash_counters (include/rtclust.h lists them)
   uint64_t dbscan_assign[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_dbscan_assign_counters (include/rtclust.h lists them)
   int dbscan_assign_path = 0;  // rtc_dbscan_assign_last_path
+  uint64_t dbscan_update[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_dbscan_update_counters (include/rtclust.h lists them)
   uint64_t dbscan_knn[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_dbscan_knn_counters (include/rtclust.h lists them)
   uint64_t dbscan_knn_propagate_ns = 0;  // rtc_dbscan_knn_propagate_ns
   uint64_t graph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};    // rtc_graph_counters (include/rtclust.h lists them)

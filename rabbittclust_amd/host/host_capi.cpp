@@ -188,6 +188,30 @@ int rtch_dbscan_model_resave(const char* in_path, const char* out_path) {
   return save_dbscan_model(out_path, m) ? 0 : -2;
 }
 
+// clust-dbscan --db --update's rewrite of the model file, in place through FILE.tmp: n_new genomes (names, lengths, the hashes
+// of genome q at hashes[off[q] .. off[q + 1]) in the model's width) appended, labels / core over all genomes and the cluster
+// count replaced.  labels NULL with n_new 0: the model's own.  -1: the file does not load, -2: it was not written, -3: sizes.
+int rtch_dbscan_model_update(const char* path, int n_new, const char** names, const uint64_t* lens, const void* hashes, const uint64_t* off,
+                             const int32_t* labels, const uint8_t* core, int n_clusters) {
+  DbscanModel m;
+  std::string why;
+  if (!load_dbscan_model(path, m, &why)) return -1;
+  std::vector<GenomeInfo> add((size_t)std::max(n_new, 0));
+  std::vector<std::vector<uint64_t>> q64; std::vector<std::vector<uint32_t>> q32;
+  for (int q = 0; q < n_new; q++) {
+    add[q].fileName = names[q]; add[q].seq0.name = names[q]; add[q].seq0.length = (int)lens[q]; add[q].totalSeqLength = lens[q];
+    add[q].use64 = m.width == 8 && !m.minhash;
+    if (m.width == 8) q64.emplace_back((const uint64_t*)hashes + off[q], (const uint64_t*)hashes + off[q + 1]);
+    else q32.emplace_back((const uint32_t*)hashes + off[q], (const uint32_t*)hashes + off[q + 1]);
+  }
+  const size_t n = m.labels.size() + add.size();
+  if (!labels && n_new > 0) return -3;
+  const std::vector<int32_t> lab = labels ? std::vector<int32_t>(labels, labels + n) : m.labels;
+  const std::vector<uint8_t> cr = labels ? std::vector<uint8_t>(core, core + n) : m.core;
+  if (!update_dbscan_model(m, add, &q32, &q64, lab, cr, labels ? n_clusters : m.n_clusters)) return -3;
+  return save_dbscan_model(path, m) ? 0 : -2;
+}
+
 // leiden_quantise: out[m] receives the records kept, *n_out their number; returns 1 where the weights' range was narrow
 int rtch_leiden_quantise(const uint32_t* u, const uint32_t* v, const double* weight, uint64_t m, int objective, rtc_wedge* out, uint64_t* n_out) {
   std::vector<rtc_wedge> rec;

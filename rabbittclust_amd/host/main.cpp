@@ -854,6 +854,7 @@ struct Options {
   bool saveRep = false;     // clust-greedy --fast --save-rep: cluster_state.bin beside the sketches
   string repdb_path;        // clust-greedy --fast --db FILE with one of --build / --query / --assign / --append / --stats
   bool db_build = false, db_query = false, db_assign = false, db_stats = false;
+  bool db_update = false;   // clust-dbscan --db FILE --update
   int topk = 5;             // --top-k of --query
   bool has_topk = false;
   int threads = default_threads();
@@ -976,6 +977,7 @@ static Options parse(int argc, char** argv) {
     if (a == "--hierarchy") { o.hierarchy = true; continue; }
     if (a == "--min-cluster-size") { o.minClusterSize = atoi(need(i)); o.hasMinClusterSize = true; continue; }
     if (a == "--knn") { o.dbscanKnn = atoi(need(i)); continue; }
+    if (a == "--update") { o.db_update = true; continue; }
     if (a == "--query" || a == "--top-k" || a == "--dense" ||
         a == "--premsted" || a == "--auto-threshold" || a == "--stability" || a == "--dedup-dist" || a == "--reps-per-cluster" ||
         a == "--newick-tree" || a == "--phylip-tree" || a == "--nexus-tree" || a == "--linkage-matrix" || a == "--buildDB") {
@@ -1066,6 +1068,11 @@ static Options parse(int argc, char** argv) {
            "  --db FILE --assign (-l -i LIST | -i FASTA) -o assign.tsv (new genomes placed into the model on the GPU: kind, k, sketch\n"
            "                     parameters, eps and minpts come from FILE; per query its cluster or novel, bridges, neighbours, core\n"
            "                     neighbours, would_be_core, the nearest genome and its distance)\n"
+           "  --db FILE --update -l -i LIST -o updated.dbscan (new genomes ADDED to the model: sketched as --assign sketches them, the\n"
+           "                     clustering of all genomes as --build over the old list followed by LIST gives it, byte for byte,\n"
+           "                     but only the new genomes and the old noise and border genomes are measured again; FILE is\n"
+           "                     rewritten in place; -l as the model was built; not with --knn, --eps-sweep, --kdist, --hierarchy or\n"
+           "                     --max-posting, nor for a model built with --max-posting)\n"
            "  --db FILE --stats (kind, parameters, genomes, clusters, noise and core points of FILE; no GPU)\n"
            "  -c,--containment N (KSSD tuner)  -s,--sketch-size N  --save-rep (accepted, no effect on DBSCAN)\n"
            "  --knn K (the reference's approximate k-NN DBSCAN, label-identical: every genome keeps its K best-scoring candidates, then\n"
@@ -2176,33 +2183,42 @@ static void print_dbscan_result(const vector<int32_t>& labels, uint32_t ncl, con
   fclose(fp);
 }
 
-// clust-dbscan --db FILE --assign: the queries sketched as the model's genomes were, placed by rtc_dbscan_assign, one TSV line each
-static int dbscan_db_assign(const Options& o, vector<Gpu>& gpus, const DbscanModel& md) {
-  rtc_ctx* ctx = gpus[0].ctx;
+// The -i input of --db --assign / --update sketched as the model's genomes were: kind, k, sketch parameters and minimum length
+// from the model.  what: whose sketches, for the messages.
+static int dbscan_db_sketch(const Options& o, vector<Gpu>& gpus, const DbscanModel& md, const char* what, vector<GenomeInfo>& q,
+                            MinHashSketchFile& mh, KssdSketchFile& ks) {
   SketchJob job;
   job.kssd = !md.minhash; job.kmerSize = md.kmer_size; job.minLen = md.min_len; job.threads = o.threads;
   if (md.minhash) job.sketchSize = md.sketch_size;
   else job.drlevel = md.drlevel;
-  const double t0 = get_sec();
-  vector<GenomeInfo> q; MinHashSketchFile mh; KssdSketchFile ks; Resident rs;
+  Resident rs;
   if (o.sketchByFile) sketch_files(gpus, o.inputFile, job, q, &mh, &ks, rs, true);
   else {
     vector<FastaRecord> recs; SeqModeSizes sz;
     if (!read_sequences(o.inputFile, md.min_len, recs, sz)) return 1;
     sketch_sequences(gpus, recs, job, q, &mh, &ks);
   }
-  const double t1 = get_sec();
-  g_metrics.num("sketch_queries_s", t1 - t0);
   const int qwidth = md.minhash ? 8 : (ks.use64 ? 8 : 4);
   if (!q.empty() && qwidth != md.width) {
-    cerr << "ERROR: the query sketches have hash width " << qwidth << " but the model has " << md.width << endl;
+    cerr << "ERROR: the " << what << " sketches have hash width " << qwidth << " but the model has " << md.width << endl;
     return 1;
   }
   if (!md.minhash && !q.empty() && (ks.info.half_k != md.half_k || ks.info.half_subk != md.half_subk)) {
-    cerr << "ERROR: the query sketches have half_k " << ks.info.half_k << ", half_subk " << ks.info.half_subk << " but the model has " << md.half_k
+    cerr << "ERROR: the " << what << " sketches have half_k " << ks.info.half_k << ", half_subk " << ks.info.half_subk << " but the model has " << md.half_k
          << ", " << md.half_subk << endl;
     return 1;
   }
+  return 0;
+}
+
+// clust-dbscan --db FILE --assign: the queries sketched as the model's genomes were, placed by rtc_dbscan_assign, one TSV line each
+static int dbscan_db_assign(const Options& o, vector<Gpu>& gpus, const DbscanModel& md) {
+  rtc_ctx* ctx = gpus[0].ctx;
+  const double t0 = get_sec();
+  vector<GenomeInfo> q; MinHashSketchFile mh; KssdSketchFile ks;
+  if (const int rc = dbscan_db_sketch(o, gpus, md, "query", q, mh, ks)) return rc;
+  const double t1 = get_sec();
+  g_metrics.num("sketch_queries_s", t1 - t0);
   const uint32_t N = (uint32_t)md.labels.size(), Q = (uint32_t)q.size();
   cerr << "===== DBSCAN model assignment (" << (md.minhash ? "MinHash" : "KSSD") << ") =====" << endl
        << "  Query genomes:  " << Q << endl << "  Model genomes:  " << N << endl << "  Eps, minPts:    " << md.eps << ", " << md.min_pts << endl;
@@ -2262,6 +2278,67 @@ static int dbscan_db_assign(const Options& o, vector<Gpu>& gpus, const DbscanMod
   fclose(fp);
   cerr << "===== Assignment Results =====" << endl << "  Placed:      " << c[3] << endl << "  Novel:       " << c[4] << endl << "  Bridging:    " << c[5] << endl
        << "  Output:      " << o.outputFile << endl << "==============================" << endl;
+  return 0;
+}
+
+// clust-dbscan --db FILE --update: the new genomes sketched as --assign sketches its queries, rtc_dbscan_update over the model's
+// sketches followed by theirs, the clustering of all genomes in result.dbscan's layout, and the model rewritten in place
+static int dbscan_db_update(const Options& o, vector<Gpu>& gpus, DbscanModel& md) {
+  rtc_ctx* ctx = gpus[0].ctx;
+  const double t0 = get_sec();
+  vector<GenomeInfo> add; MinHashSketchFile mh; KssdSketchFile ks;
+  if (const int rc = dbscan_db_sketch(o, gpus, md, "new", add, mh, ks)) return rc;
+  const double t1 = get_sec();
+  g_metrics.num("sketch_new_s", t1 - t0);
+  const uint32_t N = (uint32_t)md.labels.size(), M = (uint32_t)add.size();
+  cerr << "===== DBSCAN model update (" << (md.minhash ? "MinHash" : "KSSD") << ") =====" << endl
+       << "  New genomes:    " << M << endl << "  Model genomes:  " << N << endl << "  Eps, minPts:    " << md.eps << ", " << md.min_pts << endl;
+  const vector<vector<uint64_t>>& a64 = md.minhash ? mh.hashes : ks.h64;
+  if ((md.width == 8 ? a64.size() : ks.h32.size()) != M) {
+    cerr << "ERROR: --update needs the new sketches on the host (" << (md.width == 8 ? a64.size() : ks.h32.size()) << " of " << M << ")" << endl;
+    return 1;
+  }
+  vector<int32_t> labels((size_t)N + M);
+  vector<uint8_t> core((size_t)N + M);
+  uint32_t ncl = 0, nnoise = 0;
+  uint64_t c[12] = {0};
+  {
+    DeviceSketches ds;
+    if (md.width == 8) {
+      vector<vector<uint64_t>> all(md.h64);
+      all.insert(all.end(), a64.begin(), a64.end());
+      upload_sketches(ctx, &all, nullptr, ds);
+    } else {
+      vector<vector<uint32_t>> all(md.h32);
+      all.insert(all.end(), ks.h32.begin(), ks.h32.end());
+      upload_sketches(ctx, nullptr, &all, ds);
+    }
+    CHECK(ctx, rtc_dbscan_update(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, N, M, md.labels.data(), md.core.data(), md.minhash ? 1 : 0,
+                                 (uint32_t)md.sketch_size, md.eps, md.min_pts, md.kmer_size, labels.data(), core.data(), &ncl, &nnoise));
+    rtc_dbscan_update_counters(ctx, c);
+    (void)rtc_dev_free(ctx, ds.d_hashes); (void)rtc_dev_free(ctx, ds.d_start); (void)rtc_dev_free(ctx, ds.d_len);
+  }
+  const double t2 = get_sec();
+  if (getenv("RTC_VERBOSE"))
+    fprintf(stderr, "[update] rows %llu + %llu, %llu candidates in %llu chunk(s), %llu kept; join %.3f ms, predicate %.3f ms, components %.3f ms\n",
+            (unsigned long long)c[0], (unsigned long long)c[1], (unsigned long long)c[3], (unsigned long long)c[2], (unsigned long long)c[4], c[8] / 1e6,
+            c[9] / 1e6, c[10] / 1e6);
+  g_metrics.num("dbscan_update_s", t2 - t1);
+  g_metrics.num("dbscan_update_join_s", c[8] / 1e9);
+  g_metrics.num("dbscan_update_predicate_s", c[9] / 1e9);
+  g_metrics.num("dbscan_update_components_s", c[10] / 1e9);
+  g_metrics.num("dbscan_update_rows", (double)(c[0] + c[1]));
+  g_metrics.num("dbscan_update_promoted", (double)c[5]);
+  g_metrics.num("dbscan_update_merged", (double)c[6]);
+  g_metrics.num("genomes", (double)N + M);
+  g_metrics.num("clusters", (double)ncl);
+  g_metrics.num("noise", (double)nnoise);
+  if (!update_dbscan_model(md, add, &ks.h32, &a64, labels, core, (int)ncl)) { cerr << "ERROR: --update: the new sketches do not fit the model" << endl; return 1; }
+  print_dbscan_result(labels, ncl, md.genomes, md.sketch_by_file, false, o.outputFile, md.eps, md.min_pts);
+  if (!save_dbscan_model(o.repdb_path, md)) return 1;
+  cerr << "===== Update Results =====" << endl << "  Genomes:     " << (size_t)N + M << endl << "  Clusters:    " << ncl << endl << "  Noise:       " << nnoise << endl
+       << "  Re-measured: " << c[1] << " of " << N << " model genomes" << endl << "  Promoted:    " << c[5] << endl << "  Merged away: " << c[6] << endl
+       << "  Output:      " << o.outputFile << endl << "  Model:       " << o.repdb_path << endl << "==========================" << endl;
   return 0;
 }
 #endif
@@ -2386,15 +2463,21 @@ int main(int argc, char** argv) {
   // ---- clust-dbscan --db: the model file's flows, their flag errors before any GPU context exists ----
   DbscanModel db_model;
   {
-    const int actions = (int)o.db_build + (int)o.db_assign + (int)o.db_stats;
+    const int actions = (int)o.db_build + (int)o.db_assign + (int)o.db_stats + (int)o.db_update;
+    if (o.db_update && o.repdb_path.empty()) { cerr << "ERROR: --update requires --db" << endl; return 1; }
     if (actions && o.repdb_path.empty()) { cerr << "ERROR: --build / --assign / --stats require --db" << endl; return 1; }
     if (!o.repdb_path.empty() && o.has_append) { cerr << "ERROR: --append not supported for DBSCAN clustering" << endl; return 1; }
-    if (!o.repdb_path.empty() && actions != 1) { cerr << "ERROR: --db requires exactly one of --build, --assign, --stats" << endl; return 1; }
+    if (!o.repdb_path.empty() && actions != 1) { cerr << "ERROR: --db requires exactly one of --build, --assign, --stats, --update" << endl; return 1; }
+    if (o.db_update) {
+      const char* bad = !o.epsSweep.empty() ? "--eps-sweep" : o.kdist ? "--kdist" : o.hierarchy ? "--hierarchy" : o.hasMaxPosting ? "--max-posting" : nullptr;
+      if (bad) { cerr << "ERROR: --update does not go with " << bad << endl; return 1; }
+      if (!o.has_input) { cerr << "ERROR: --update requires -i <input_file>" << endl; return 1; }
+    }
     if (o.db_build && o.hasMaxPosting && o.maxPosting > 0) {
       cerr << "ERROR: --build does not go with --max-posting (its pruning depends on posting counts that new genomes would change)" << endl;
       return 1;
     }
-    if (o.db_stats || o.db_assign) {
+    if (o.db_stats || o.db_assign || o.db_update) {
       string why;
       if (!load_dbscan_model(o.repdb_path, db_model, &why)) { cerr << "ERROR: --db " << o.repdb_path << ": " << why << endl; return 1; }
     }
@@ -2415,6 +2498,23 @@ int main(int argc, char** argv) {
       o.is_fast = !db_model.minhash;
       o.minhash = db_model.minhash;
       o.epsSweep.clear(); o.kdist = o.hierarchy = o.hasMinClusterSize = o.isContainment = false;
+      o.dbscanEps = db_model.eps; o.dbscanMinPts = db_model.min_pts;
+    }
+    if (o.db_update) {  // -k, -s, --eps and --minpts have no effect, as beside --assign: the model's hold
+      if (o.is_fast && db_model.minhash) { cerr << "ERROR: --update: --fast given, but " << o.repdb_path << " is a MinHash model" << endl; return 1; }
+      if (o.minhash && !db_model.minhash) { cerr << "ERROR: --update: --minhash given, but " << o.repdb_path << " is a KSSD model" << endl; return 1; }
+      if (db_model.max_posting > 0) {
+        cerr << "ERROR: --update: " << o.repdb_path << " was built with --max-posting " << db_model.max_posting << ", which is out of scope" << endl;
+        return 1;
+      }
+      if (o.sketchByFile != db_model.sketch_by_file) {
+        cerr << "ERROR: --update: " << o.repdb_path << " was built " << (db_model.sketch_by_file ? "with" : "without") << " -l, the new genomes must come the same way"
+             << endl;
+        return 1;
+      }
+      o.is_fast = !db_model.minhash;
+      o.minhash = db_model.minhash;
+      o.hasMinClusterSize = o.isContainment = false;
       o.dbscanEps = db_model.eps; o.dbscanMinPts = db_model.min_pts;
     }
   }
@@ -2515,7 +2615,7 @@ int main(int argc, char** argv) {
 #ifdef GREEDY_CLUST
         o.has_append || !o.repdb_path.empty() || o.has_presketched;
 #elif defined(DBSCAN_CLUST)
-        o.has_presketched || o.db_assign;
+        o.has_presketched || o.db_assign || o.db_update;
 #else
         o.has_append || ((o.dense || !o.useIndex) && o.has_presketched) || !o.repdb_path.empty();
 #endif
@@ -2625,8 +2725,8 @@ int main(int argc, char** argv) {
     return rc;
   }
 #elif !defined(LEIDEN_CLUST)
-  if (o.db_assign) {
-    const int rc = dbscan_db_assign(o, gpus, db_model);
+  if (o.db_assign || o.db_update) {
+    const int rc = o.db_assign ? dbscan_db_assign(o, gpus, db_model) : dbscan_db_update(o, gpus, db_model);
     g_metrics.str("command", "clust-dbscan");
     g_metrics.str("sketch", db_model.minhash ? "minhash" : "kssd");
     g_metrics.write();

@@ -2788,6 +2788,24 @@ bool load_dbscan_model(const std::string& path, DbscanModel& m, std::string* why
   return true;
 }
 
+bool update_dbscan_model(DbscanModel& m, const std::vector<GenomeInfo>& add, const std::vector<std::vector<uint32_t>>* a32,
+                         const std::vector<std::vector<uint64_t>>* a64, const std::vector<int32_t>& labels, const std::vector<uint8_t>& core,
+                         int n_clusters) {
+  const size_t n = m.labels.size() + add.size();
+  if (labels.size() != n || core.size() != n) return false;
+  if (m.width == 8 ? (!a64 || a64->size() != add.size()) : (!a32 || a32->size() != add.size())) return false;
+  for (const GenomeInfo& g : add) {
+    m.genomes.push_back(g);
+    m.genomes.back().id = (int)m.genomes.size() - 1;
+  }
+  if (m.width == 8) m.h64.insert(m.h64.end(), a64->begin(), a64->end());
+  else m.h32.insert(m.h32.end(), a32->begin(), a32->end());
+  m.labels = labels;
+  m.core = core;
+  m.n_clusters = n_clusters;
+  return true;
+}
+
 void print_dbscan_model_stats(const DbscanModel& m, std::ostream& os) {
   uint64_t noise = 0, core = 0;
   for (int32_t l : m.labels) noise += l < 0;

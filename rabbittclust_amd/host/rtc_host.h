@@ -294,6 +294,12 @@ struct DbscanModel {
 bool save_dbscan_model(const std::string& path, const DbscanModel& m);
 // false: *why says what is wrong with the file (cannot open, foreign, version, truncated, bytes after its end)
 bool load_dbscan_model(const std::string& path, DbscanModel& m, std::string* why);
+// clust-dbscan --db FILE --update: the records and sketches of the new genomes appended (a32 or a64, by the model's width), the
+// labels, core flags and cluster count replaced by those of rtc_dbscan_update over all genomes.  The caller saves the model
+// under its own name: the same format and version.  false: the sizes do not fit together.
+bool update_dbscan_model(DbscanModel& m, const std::vector<GenomeInfo>& add, const std::vector<std::vector<uint32_t>>* a32,
+                         const std::vector<std::vector<uint64_t>>* a64, const std::vector<int32_t>& labels, const std::vector<uint8_t>& core,
+                         int n_clusters);
 void print_dbscan_model_stats(const DbscanModel& m, std::ostream& os);
 
 std::string current_date_time();  // src/common.hpp:36-44

@@ -2,7 +2,7 @@
 of the DBSCAN call into the pair phase, the eps filter and the components from rtc_dbscan_counters.
 
     python tools/run_dbscan.py [--sets dense25k,cfg4_200k] [--eps 0.05] [--minpts 5] [--repeat 3] [--sweep e1,e2,...] [--kdist]
-                               [--hierarchy] [--knn K]
+                               [--hierarchy] [--knn K] [--assign Q] [--update M]
 
 --knn K times Context.dbscan_knn (clust-dbscan --knn K) beside Context.dbscan on the same set: the best of --repeat warm calls with
 the counters of rtc_dbscan_knn_counters -- passers, rows truncated, rows that needed arrival keys, neighbour edges, propagation
@@ -30,6 +30,13 @@ baseline it replaces, Context.dbscan (with --minhash: dbscan_mash) on all n sket
 from another build of the library, e.g. the parent commit's librtclust_hip.so, in a child process (RTC_HIP_LIB); without it the
 baseline is this build's.
 
+--update M times Context.dbscan_update (clust-dbscan --db --update): the last M sketches of a set are the new genomes, the rest
+the model, clustered once at --eps / --minpts; best of --repeat warm calls with the counters of rtc_dbscan_update_counters -- the
+rows of both stages, promoted points, clusters merged away, the join, predicate and components times -- beside Context.dbscan on
+all n sketches, and whether the two label vectors are identical.  Its default set is fam20k: 20 000 host-drawn u32 sets of ~600
+hashes in families of ten at three substitution rates (2 %, 10 %, 30 % of a member's hashes replaced) and loners, in shuffled
+order, so the new genomes come from every family.
+
 Prints one JSON line per set.  The kernel split under rocprofv3 --kernel-trace --stats comes from a run of its own."""
 import argparse
 import json
@@ -56,6 +63,22 @@ def _sparse(rng, n, size, per):
         s[flip] = rng.integers(1, (1 << 31) - 1, size=int(flip.sum()), dtype=np.int64)
         out.append(np.unique(s).astype(np.uint32))
     return out
+
+
+def _mixed_families(rng, n, size=600, per=10):
+    """families of `per` at three substitution rates, every tenth family a lone sketch, shuffled"""
+    out, f = [], 0
+    while len(out) < n:
+        base = rng.integers(1, (1 << 31) - 1, size=size, dtype=np.int64)
+        members = 1 if f % 10 == 9 else per
+        rate = (0.02, 0.1, 0.3)[f % 3]
+        for _ in range(min(members, n - len(out))):
+            s = base.copy()
+            flip = rng.random(size) < rate
+            s[flip] = rng.integers(1, (1 << 31) - 1, size=int(flip.sum()), dtype=np.int64)
+            out.append(np.unique(s).astype(np.uint32))
+        f += 1
+    return [out[i] for i in rng.permutation(n)]
 
 
 def _synth(ctx, api, n, per, max_rate, seed, L=2_000_000, batch=25_000):
@@ -215,6 +238,30 @@ def _assign_row(ctx, api, sk, name, kmer, a, sketch_size=None):
     return row
 
 
+def _update_row(ctx, api, sk, name, kmer, a):
+    n, m = sk.n, a.update
+    full_ms, (want, want_core) = _best(lambda: ctx.dbscan(sk, a.eps, a.minpts, kmer, return_core=True), a.repeat)
+    fc = ctx.dbscan_counters()
+    labels, core = ctx.dbscan(_head(api, sk, n - m), a.eps, a.minpts, kmer, return_core=True)
+    cs = []
+
+    def call():
+        out = ctx.dbscan_update(sk, n - m, labels, core, a.eps, a.minpts, kmer)
+        cs.append(ctx.dbscan_update_counters())
+        return out
+    ms, (got, got_core) = _best(call, a.repeat)
+    c = min(cs[1:], key=lambda x: x["total_ns"])
+    return {"set": name, "n": n, "new": m, "kmer": kmer, "eps": a.eps, "minpts": a.minpts, "dbscan_all_ms": round(full_ms, 3),
+            "dbscan_all_pair_ms": round(fc["pair_ns"] / 1e6, 3), "dbscan_all_filter_ms": round(fc["filter_ns"] / 1e6, 3),
+            "dbscan_all_components_ms": round(fc["components_ns"] / 1e6, 3), "dbscan_all_candidate_edges": fc["candidate_edges"],
+            "update_ms": round(ms, 3), "library_ms": round(c["total_ns"] / 1e6, 3), "join_ms": round(c["join_ns"] / 1e6, 3),
+            "predicate_ms": round(c["predicate_ns"] / 1e6, 3), "components_ms": round(c["components_ns"] / 1e6, 3),
+            "stage1_rows": c["stage1_rows"], "stage2_rows": c["stage2_rows"], "chunks": c["chunks"], "candidate_edges": c["candidate_edges"],
+            "kept_edges": c["kept_edges"], "promoted": c["promoted"], "merged": c["merged"], "hook_rounds": c["hook_rounds"],
+            "identical": bool(np.array_equal(got, want) and np.array_equal(got_core, want_core)),
+            "clusters": int(want.max(initial=-1)) + 1, "noise": int((want < 0).sum())}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="dense25k,cfg4_200k")
@@ -229,6 +276,7 @@ def main():
     ap.add_argument("--minhash", action="store_true")
     ap.add_argument("--assign", type=int, default=0)
     ap.add_argument("--knn", type=int, default=0)
+    ap.add_argument("--update", type=int, default=0)
     ap.add_argument("--baseline-lib", default="")
     ap.add_argument("--baseline-only", action="store_true")
     a = ap.parse_args()
@@ -250,8 +298,13 @@ def main():
         print(json.dumps(_minhash_rows(ctx, api, a)), flush=True)
         ctx.close()
         return
+    if a.update and a.sets == ap.get_default("sets"):
+        a.sets = "fam20k"
     for name in a.sets.split(","):
-        if name in SPARSE:
+        if name == "fam20k":
+            n = 20_000
+            sk = api.SketchSet.from_host(_mixed_families(np.random.default_rng(11), n), ctx.device, k=22, kind="kssd", width=4)
+        elif name in SPARSE:
             n, size, per = SPARSE[name]
             sk = api.SketchSet.from_host(_sparse(np.random.default_rng(7), n, size, per), ctx.device, k=22, kind="kssd", width=4)
         else:
@@ -261,6 +314,10 @@ def main():
         torch.cuda.synchronize()
         if a.assign:
             print(json.dumps(_assign_row(ctx, api, sk, name, kmer, a)), flush=True)
+            del sk
+            continue
+        if a.update:
+            print(json.dumps(_update_row(ctx, api, sk, name, kmer, a)), flush=True)
             del sk
             continue
         if a.sweep:
