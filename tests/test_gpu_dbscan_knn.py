@@ -1,7 +1,12 @@
 """clust-dbscan --knn on the GPU (rtc_dbscan_knn): labels, core flags and counts identical to the restated k-NN DBSCAN
 (tests/refdbscan_knn.py: the reference's min-heap and sequential walk) on the sweep's family sets, on a set where every score
 ties and the arrival order decides, on a directed chain many propagation rounds deep, the delegation of u64 sketches and
-knn_k = 0 to rtc_dbscan, and the command line end to end.  Every comparison is exact."""
+knn_k = 0 to rtc_dbscan, and the command line end to end.  Past one wave of 64 lanes (tests/knn_sets.py, whose cases
+tests/test_cpu_dbscan_knn.py proves on the restatement): the star set, whose labels show every hub row's kept neighbours, with
+rows of up to 147 passers, k up to 129, tied groups of 119 and first-shared indices from 63 to past 3 000 -- alone, under row
+chunks and with max_posting pruning -- and bridged stars whose cluster number travels through rows longer than a wave.  Then
+the binary32 eps test of the k-NN branch, u16 saturation inside the score, and the degenerate inputs (one point, no candidate
+pair, knn_k = INT_MAX).  Every comparison is exact."""
 import functools
 import json
 import os
@@ -10,6 +15,7 @@ import struct
 import numpy as np
 import pytest
 
+from tests import knn_sets as K
 from tests import refdbscan as R
 from tests import refdbscan_knn as RK
 from tests import sweep_sets as S
@@ -159,6 +165,105 @@ def test_row_chunks_keep_the_labels(ctx):
     assert np.array_equal(got, want) and c2["chunks"] > 1
     assert {k: c2[k] for k in ("candidate_edges", "passers", "truncated_rows", "arrival_rows", "neighbour_edges")} == \
            {k: c1[k] for k in ("candidate_edges", "passers", "truncated_rows", "arrival_rows", "neighbour_edges")}
+
+
+COUNTERS = ("candidate_edges", "passers", "truncated_rows", "arrival_rows", "neighbour_edges")
+
+
+def _check_rows(ctx, sk, host, eps, min_pts, knn_k, max_posting=0):
+    """_check, and the counters that follow from the restatement's rows"""
+    got, c = _check(ctx, sk, host, eps, min_pts, knn_k, max_posting)
+    k = RK.effective_k(knn_k, min_pts)
+    passers = RK.passers_in_arrival_order(host, eps, S.KMER, max_posting)
+    shapes = [K.row_shape(p, k) for p in passers]
+    assert c["passers"] == sum(len(p) for p in passers)
+    assert c["truncated_rows"] == sum(P > k for P, *_ in shapes)
+    assert c["arrival_rows"] == sum(Q > k for _, _, Q, _, _ in shapes)
+    assert c["neighbour_edges"] == sum(len(x) for x in RK.knn_lists(host, eps, S.KMER, k, max_posting))
+    return got, c
+
+
+@functools.lru_cache(maxsize=None)
+def _star(seed):
+    return K.star_set(seed)[0]
+
+
+@pytest.mark.parametrize("seed", range(1, SOAK_SEEDS + 1))
+@pytest.mark.parametrize("knn_k", K.KS)
+def test_star_set_selection_is_visible_in_the_labels(ctx, seed, knn_k):
+    assert K.KMER == S.KMER
+    host = _star(seed)
+    got, c = _check_rows(ctx, _set(ctx, host), host, K.EPS, K.MIN_PTS, knn_k)
+    assert c["truncated_rows"] >= c["arrival_rows"] >= 1 and c["chunks"] == 1
+    if knn_k == 64:
+        assert c["truncated_rows"] > c["arrival_rows"]  # the row with exactly k passers at or above s*
+    # a pair is a hub and a leaf: every leaf lists its hub, a hub lists the leaves it kept, a leaf not kept is noise
+    assert c["neighbour_edges"] == 2 * c["candidate_edges"] - (got < 0).sum()
+
+
+@pytest.mark.parametrize("knn_k", [64, 100])
+def test_star_set_under_row_chunks(ctx, knn_k):
+    host = K.chunk_star_set(1)[0]
+    n = len(host)
+    sk = _set(ctx, host)
+    want, c1 = _check_rows(ctx, sk, host, K.CHUNK_EPS, K.MIN_PTS, knn_k)
+    assert c1["chunks"] == 1 and c1["candidate_edges"] == n * (n - 1) // 2 and c1["arrival_rows"] >= 1
+    with ctx.env(RTC_EDGE_BUDGET=str(64 * n + 1024)):
+        got, c2 = _check_rows(ctx, sk, host, K.CHUNK_EPS, K.MIN_PTS, knn_k)
+    assert np.array_equal(got, want) and c2["chunks"] > 1
+    assert {x: c2[x] for x in COUNTERS} == {x: c1[x] for x in COUNTERS}
+
+
+@pytest.mark.parametrize("knn_k", [64, 128])
+def test_star_set_with_pruned_postings(ctx, knn_k):
+    host = K.star_set(1, decoy=True)[0]
+    want = RK.labels_of_knn(host, K.EPS, K.MIN_PTS, S.KMER, knn_k, K.DECOY_MAX_POSTING)
+    assert not np.array_equal(want, RK.labels_of_knn(host, K.EPS, K.MIN_PTS, S.KMER, knn_k))  # the pruning changes this result
+    sk = _set(ctx, host)
+    _, c = _check_rows(ctx, sk, host, K.EPS, K.MIN_PTS, knn_k, K.DECOY_MAX_POSTING)
+    assert c["arrival_rows"] >= 1
+    _check_rows(ctx, sk, host, K.EPS, K.MIN_PTS, knn_k)
+
+
+@pytest.mark.parametrize("low,knn_k", [(False, 2), (False, 64), (False, 129), (True, 200)])
+def test_bridged_stars_propagate_through_long_rows(ctx, low, knn_k):
+    host, info = K.bridged_star_set(1, low)
+    got, c = _check_rows(ctx, _set(ctx, host), host, K.EPS, K.MIN_PTS, knn_k)
+    assert (got[info["hubs"] + info["bridges"]] == 0).all() and got.max() == 0
+    print("bridged stars, k %d: %d propagation rounds" % (knn_k, c["rounds"]))
+    assert 2 <= c["rounds"] <= len(host) + 1
+
+
+@pytest.mark.parametrize("a,b,c", K.float_boundary_pairs())
+def test_float_score_decides_the_eps_test(ctx, a, b, c):
+    eps = K.float_boundary_eps(a, b, c)
+    host = K.float_boundary_sketches(a, b, c)
+    sk = _set(ctx, host)
+    got, cnt = _check(ctx, sk, host, eps, 2, 5)
+    assert got.tolist() == [-1, -1]
+    assert cnt["passers"] == 2 and cnt["neighbour_edges"] == 0 and cnt["candidate_edges"] == 1
+    assert ctx.dbscan(sk, eps, 2, S.KMER).tolist() == [0, 0]
+
+
+def test_u16_saturation_changes_the_kept_neighbour(ctx):
+    host = K.saturated_choice_set()
+    got, c = _check(ctx, _set(ctx, host), host, K.SATURATED_EPS, 2, 1)
+    assert got.tolist() == [0, 1, 0]  # exact counts would give 0, 0, 1 (test_cpu_dbscan_knn)
+    assert c["passers"] == 6 and c["truncated_rows"] == 3 and c["neighbour_edges"] == 3
+
+
+def test_degenerate_sets(ctx):
+    one = [np.arange(100, 200, dtype=np.uint32)]
+    got, c = _check(ctx, _set(ctx, one), one, 0.05, 2, 3)
+    assert got.tolist() == [-1] and c["candidate_edges"] == 0 and c["passers"] == 0 and c["rounds"] == 0
+    apart = [np.arange(1000 * g, 1000 * g + 50 + g, dtype=np.uint32) for g in range(1, 4)]
+    for min_pts in (1, 2):  # at minPts 1 every point is a core point and a cluster of its own
+        got, c = _check(ctx, _set(ctx, apart), apart, 0.05, min_pts, 3)
+        assert got.tolist() == ([0, 1, 2] if min_pts == 1 else [-1, -1, -1])
+        assert c["candidate_edges"] == 0 and c["passers"] == 0 and c["neighbour_edges"] == 0
+    host = _star(1)
+    _, c = _check_rows(ctx, _set(ctx, host), host, K.EPS, K.MIN_PTS, 2 ** 31 - 1)
+    assert c["truncated_rows"] == 0 and c["arrival_rows"] == 0 and c["neighbour_edges"] == c["passers"]
 
 
 def _folder_sketches(folder, n):
