@@ -6,7 +6,11 @@ weight in units of 2^-20, counters the ten of rtc_leiden_counters with the three
 asserts that each refined community lies inside one coarse community and is connected over its positive edges.  stats, a dict,
 receives what the counters do not hold: "ineligible" (vertices that failed the eligibility test, all refinements), "split"
 (coarse communities a refinement left in two or more pieces) and "row_lengths" (the set of adjacency row lengths met); a list
-under "trace", if the caller put one there, receives (iteration, level, coarse, refined) after every refinement."""
+under "trace", if the caller put one there, receives (iteration, level, coarse, refined) after every refinement.  Lists, one
+entry per event: "proposer_rows" (the row length, self entry included, of every vertex that proposed, once per proposal),
+"proposer_rows_outside" (the same for proposers with a neighbour outside their coarse community), "proposer_rows_nontarget"
+(for proposers with a neighbouring refined community, inside their coarse community, that is no target in that round),
+"move_rounds" and "refine_rounds" (the rounds of every level's move phase and refinement) and "levels_by_iteration"."""
 
 import math
 
@@ -131,6 +135,12 @@ def _refine(adj, nu, coarse, A, gB, stats):
                 s = e[d] * A - gB * nu[x] * Nr[d]
                 if s >= 0 and s > best_s:
                     best_s, prop[x] = s, d
+            if prop[x] is not None:  # stats only
+                stats.setdefault("proposer_rows", []).append(len(adj[x]))
+                if any(coarse[y] != coarse[x] for y in adj[x]):
+                    stats.setdefault("proposer_rows_outside", []).append(len(adj[x]))
+                if any(d != x and not target[d] for d in e):
+                    stats.setdefault("proposer_rows_nontarget", []).append(len(adj[x]))
         accepted = 0
         for x in range(n):
             if prop[x] is None:
@@ -192,15 +202,18 @@ def _iteration(adj0, nu0, start, A, gB, C, stats):
         coarse, r, moved = _move(adj, nu, coarse, A, gB)
         C[2] += r
         C[3] += moved
+        stats.setdefault("move_rounds", []).append(r)
         R, r, merges, rejected = _refine(adj, nu, coarse, A, gB, stats)
         C[4] += r
         C[5] += merges
+        stats.setdefault("refine_rounds", []).append(r)
         C[6] += rejected
         levels += 1
         C[1] += 1
         if "trace" in stats:
             stats["trace"].append((C[0], levels - 1, list(coarse), list(R)))
         if not merges or levels == MAX_LEVELS:
+            stats.setdefault("levels_by_iteration", []).append(levels)
             return _by_smallest([coarse[v] for v in label])
         newc, count = _by_smallest(R)
         label = [newc[v] for v in label]

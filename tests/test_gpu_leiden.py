@@ -3,6 +3,7 @@ tests/reflouvain.py (the header's definition restated), both exactly."""
 import numpy as np
 import pytest
 
+import community_sets
 import refgraph
 import reflouvain
 
@@ -155,8 +156,7 @@ def _louvain_cases():
     for c in range(30):
         ring += _clique(range(5 * c, 5 * c + 5), one) + [(5 * c + 4, (5 * c + 5) % 150, one)]
     cases["ring"] = (150, ring)
-    cases["duplicates_and_loops"] = (9, _clique(range(4), 10) + _clique(range(4), 7) + [(4, 4, 50), (4, 5, 9), (5, 4, 9), (5, 6, 30), (6, 7, 30),
-                                                                                  (7, 5, 30), (3, 4, 1), (8, 8, 4), (0, 0, 3)])
+    cases["duplicates_and_loops"] = community_sets.loops_and_duplicates()
     return cases
 
 
