@@ -251,7 +251,12 @@ int rtc_boruvka_union_dev(rtc_ctx* ctx, uint32_t n, uint32_t s_fixed, const uint
                           uint64_t* d_nsel, uint32_t* h_added);
 
 /* All rounds on ONE GPU behind one call: the minimum spanning forest (kruskalAlgorithm's result, src/MST.cpp:59-75) of
- * a device-resident candidate list.  d_sel: n entries; *h_n_sel edges are written; h_rounds may be NULL.  Synchronous. */
+ * a device-resident candidate list.  d_sel: n entries; *h_n_sel edges are written; h_rounds may be NULL.  Synchronous.
+ * The forest is the one the strict total order (weight key of the double common / denom, then i, then j) leaves, and d_sel
+ * holds it in that order.  The call reads the smallest and the largest size and takes the round that fits, the forest being
+ * the same in all three: equal sizes whose fused key fits 63 bits, one pass; sizes that vary, with two vertex indices and
+ * the longest size's count in 63 bits, two passes (the edge id carries the count, as in rtc_mst and rtc_mst_sharded);
+ * otherwise three.  Every pair (i, j) occurs once, i > j, and common <= min(size of i, size of j). */
 int rtc_msf_dev(rtc_ctx* ctx, const rtc_cedge* d_edges, uint64_t m, const uint32_t* d_len, uint32_t n, int is_containment,
                 rtc_cedge* d_sel, uint64_t* h_n_sel, int* h_rounds);
 

@@ -394,6 +394,24 @@ class Context:
                                                _t_ptr(count)))
         return edges, int(count.item())
 
+    def msf(self, edges, lens, wmode=0):
+        """rtc_msf_dev: the minimum spanning forest of a candidate list.  edges: (i, j, common) rows, a host array or a device
+        tensor [m, 3] int32; lens: the sizes, one per vertex.  Returns (the forest's CEDGE_DT records in (weight key, i, j)
+        order, the Boruvka rounds the call ran)."""
+        def dev(a):
+            if not torch.is_tensor(a):
+                a = np.ascontiguousarray(a)
+                a = torch.from_numpy((a if a.dtype.itemsize == 4 else a.astype(np.uint32)).view(np.int32).copy())
+            return a.to(self.device).contiguous()
+        edges, lens = dev(edges).reshape(-1, 3), dev(lens).reshape(-1)
+        n, m = int(lens.numel()), int(edges.shape[0])
+        sel = torch.empty((max(n, 1), 3), dtype=torch.int32, device=self.device)
+        nsel, rounds = C.c_uint64(), C.c_int()
+        self.check(self.lib.rtc_msf_dev(self.h, _t_ptr(edges) if m else None, m, _t_ptr(lens), n, int(wmode), _t_ptr(sel),
+                                        C.byref(nsel), C.byref(rounds)))
+        rec = np.ascontiguousarray(sel[:nsel.value].cpu().numpy().view(np.uint32)).view(CEDGE_DT).reshape(-1)
+        return rec, int(rounds.value)
+
     def mst(self, sk, threshold, is_containment=False, start_index=0):
         """compute_minhash_mst / compute_kssd_mst: returns numpy EDGE_DT array (edge.mst records).
         start_index > 0: only rows >= start_index (the --append form, src/MST.cpp:1375-1383)."""

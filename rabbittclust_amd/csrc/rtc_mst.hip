@@ -1185,7 +1185,9 @@ int rtc_msf_dev(rtc_ctx* ctx, const rtc_cedge* d_edges, uint64_t m, const uint32
   RTC_HIP(ctx, hipMemcpyAsync(mm, d_mm, 8, hipMemcpyDeviceToHost, ctx->stream));
   RTC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const uint32_t s_fixed = (mm[0] == mm[1] && mm[0] > 0 && rtc_boruvka_key_bits(n, mm[0])) ? mm[0] : 0;
-  return rtc_msf_device(ctx, d_edges, m, d_len, n, is_containment, s_fixed, nullptr, d_sel, h_n_sel, h_rounds);
+  // sizes that vary: the longest one lets the edge id carry the count (two passes a round, as in rtc_mst / rtc_mst_sharded)
+  return rtc_msf_device(ctx, d_edges, m, d_len, n, is_containment, s_fixed, nullptr, d_sel, h_n_sel, h_rounds, true,
+                        mm[0] != mm[1] ? mm[1] : 0u);
 }
 
 }  // extern "C"

@@ -1,7 +1,9 @@
 """GPU parity: candidate edges and the minimum spanning forest vs the oracle's restatement of
-compute_minhash_mst (src/MST.cpp:1290-1737).  Ties make the edge SET ambiguous (the reference
-uses an unstable sort), so the asserted invariants are: identical sorted multiset of edge
-weights (bit-for-bit doubles), identical partition at the threshold, forest size."""
+compute_minhash_mst (src/MST.cpp:1290-1737).  Ties make the REFERENCE's edge set ambiguous (it
+uses an unstable sort), so against the oracle the asserted invariants are: identical sorted multiset
+of edge weights (bit-for-bit doubles), identical partition at the threshold, forest size.  Our own
+forest is unique (a strict total order on the edges), and three tests hold it, edge for edge, to the
+exact forest of the emitted candidate list (tests/refmsf.py)."""
 import numpy as np
 import pytest
 
@@ -35,6 +37,29 @@ def _clusters_from_edges(edges, thr, n):
     for v in range(n):
         groups.setdefault(find(v), []).append(v)
     return list(groups.values())
+
+
+
+def _assert_forest_edge_for_edge(ctx, sk, got, thr, containment):
+    """The forest is unique -- the strict total order (weight key of the double common / denom, then i, then j) leaves one --
+    so `got` (ctx.mst) has to be the exact forest of the candidate list the pair phase emits at this run's radio
+    (tests/refmsf.py: Kruskal over that order), record for record: the reference's (i, j, common) through the host's distance
+    and output order."""
+    import ctypes as C
+    import refmsf
+    from rabbittclust_amd import api
+    n = sk.n
+    edges, m = ctx.pair_edges(sk, 0, n, 0, n, api.mst_radio(thr, sk.k), cap=n * n // 2 + 1)
+    assert m <= n * n // 2 + 1
+    cand = edges[:m].cpu().numpy().view(np.int32).reshape(-1, 3)
+    lens = np.ascontiguousarray(sk.len.cpu().numpy().view(np.uint32))
+    f = refmsf.forest(n, cand, lens, int(containment))
+    sel = np.zeros(len(f), dtype=api.CEDGE_DT)
+    sel["i"], sel["j"], sel["common"] = f[:, 0], f[:, 1], f[:, 2]
+    want = np.zeros(max(len(f), 1), dtype=api.EDGE_DT)
+    assert ctx.lib.rtc_edges_to_mst_host(sel.ctypes.data_as(C.c_void_p), len(sel), lens.ctypes.data_as(C.c_void_p), sk.k, int(containment),
+                                         want.ctypes.data_as(C.c_void_p)) == 0
+    assert np.array_equal(got, want[:len(f)])
 
 
 def _family_sketches(ctx, n_fam, per, L, size=1000, seed=3):
@@ -78,6 +103,7 @@ def test_mst_random_overlapping_sets_many_ties(ctx, oracle):
         assert np.array_equal(np.sort(got["dist"]).view(np.uint64), np.sort(want["dist"]).view(np.uint64))
         for thr in (0.05, 0.2, 0.4):
             assert _partition(oracle.forest_clusters(want, thr, 200)) == _partition(_clusters_from_edges(got, thr, 200))
+        _assert_forest_edge_for_edge(ctx, dev, got, 0.05, containment)
 
 
 def test_extract_edges_equals_oracle_candidates(ctx, oracle):
@@ -371,6 +397,7 @@ def test_row_sharded_boruvka_equals_single_rank(ctx, oracle, world, fixed):
     assert _partition(oracle.forest_clusters(got, 0.05, n)) == _partition(oracle.forest_clusters(want, 0.05, n))
     single = ctx.mst(sk, 0.05)
     assert np.array_equal(single, got), "sharded forest differs from the single-rank forest"
+    _assert_forest_edge_for_edge(ctx, sk, single, 0.05, False)
 
 
 class _LoopbackDist:
@@ -549,3 +576,4 @@ def test_mst_on_random_sketch_sets(ctx, oracle, seed):
         assert np.array_equal(np.sort(got["dist"]).view(np.uint64), np.sort(want["dist"]).view(np.uint64)), (seed, containment)
         for cut in (thr, 0.2, 0.5):
             assert _partition(oracle.forest_clusters(want, cut, n)) == _partition(_clusters_from_edges(got, cut, n)), (seed, containment, cut)
+        _assert_forest_edge_for_edge(ctx, dev, got, thr, containment)
