@@ -604,6 +604,17 @@ __device__ __forceinline__ void reset_ctrl(const WgState& W, uint64_t Tstart) {
   if (W.t == 0) { W.ctrl->T = Tstart; W.ctrl->T0 = Tstart; W.ctrl->sorted = 0; W.ctrl->count = 0; W.ctrl->overflow = 0; W.ctrl->saw_max = 0; W.ctrl->scan_base = 0; }
 }
 
+// Mode of a walk's first tile (workgroup-uniform).  Without a starting threshold everything passes and the tile floods
+// the buffer: safe mode.  Under one, a tile of tile_bases k-mers expects tile_bases x Tstart / 2^64 candidates; below
+// room / 4 -- the bound end_tile holds every later tile to -- it is walked optimistically like any other.  A tile that
+// overflows all the same (a repeat whose hash lies under the threshold) is caught by tile_overflowed and walked again
+// in safe mode; a restart that lifted Tstart to SENT starts in safe mode again.
+__device__ __forceinline__ bool first_tile_safe(const WgState& W, uint64_t Tstart, uint32_t tile_bases) {
+  // (through a scalar register: Tstart changes on the restart edge, which the compiler takes for divergent, and every
+  // branch on the mode would otherwise be a vector compare under an execution mask)
+  return uniform32(Tstart == SENT || __umul64hi((uint64_t)tile_bases, Tstart) >= (uint64_t)(W.room / 4) ? 1u : 0u) != 0u;
+}
+
 // finishes the queued halves (one lane each), keeps those still below T and appends them with ONE LDS
 // atomic for the whole batch; called where cap - count >= NWAVE * QCAP is guaranteed
 __device__ __forceinline__ void drain_queue(const WgState& W, uint32_t& qn, uint64_t T) {

@@ -65,7 +65,7 @@ restart:
 
   uint64_t T = uniform64(Tstart);  // scalar registers: the threshold compares write wave masks directly
   qn = 0;
-  bool safe_mode = true;
+  bool safe_mode = first_tile_safe(W, Tstart, (uint32_t)TILE_BASES);
 
   uint32_t count_at_tile_start = 0;  // carried in registers: identical in every thread
   for (uint64_t T0 = sg.s_begin & ~15ULL; T0 < sg.s_end && s > 0; T0 += TILE_BASES) {

@@ -27,9 +27,12 @@
 
 namespace {
 
-constexpr int P_NL = 1;                        // 16-byte loads (64 bases) per lane and tile
+constexpr int P_NL = 4;                        // 16-byte loads (64 bases each) per lane and tile
 constexpr int P_CHUNK = 64 * 64;               // bases of one wave load
-constexpr int P_TILE_BASES = WG * 64 * P_NL;   // bases per tile
+constexpr int P_TILE_BASES = WG * 64 * P_NL;   // bases per tile: the workgroup meets its tile protocol once per 131 072 bases
+// The segment plan keeps counting in tiles of one load per lane (min_seg, seg_pref of minhash_run): what a tile costs the
+// walk changed, what a segment should hold did not, and the plans of every shape stay what they were measured with.
+constexpr uint64_t P_PLAN_BASES = (uint64_t)WG * 64;
 
 struct PackedIn {
   const uint8_t* bytes;     // packed bases: base i at bits 2 (i & 3) of bytes[i >> 2]
@@ -51,6 +54,36 @@ __host__ __device__ constexpr uint32_t fwd_roll_sel(int fsb, int q) {
   return sel;
 }
 
+// What a tile's loads ask about it, 32-bit and relative to its first base (extents clamped to +-2^30: a tile is 2^17 bases)
+struct TileView {
+  int rel_lo, rel_hi;   // the tile's owned positions
+  int gb, ge;           // the genome's extent
+  int nb;               // bytes of the buffer from the tile's first byte on
+  int pb;               // first byte offset with eight bytes of buffer in front of it
+};
+__device__ __forceinline__ int clamp30(int64_t x) { return x < -(1 << 30) ? -(1 << 30) : x > (1 << 30) ? (1 << 30) : (int)x; }
+__device__ __forceinline__ TileView tile_view(const Segment& sg, uint64_t TB, uint64_t n_bases) {
+  TileView V;
+  const int lo = clamp30((int64_t)sg.s_begin - (int64_t)TB), hi = clamp30((int64_t)sg.s_end - (int64_t)TB);
+  V.rel_lo = lo < 0 ? 0 : lo;
+  V.rel_hi = hi > P_TILE_BASES ? P_TILE_BASES : hi;
+  V.gb = clamp30((int64_t)sg.g_begin - (int64_t)TB);
+  V.ge = clamp30((int64_t)sg.g_end - (int64_t)TB);
+  V.nb = clamp30((int64_t)(n_bases >> 2) - (int64_t)(TB >> 2));
+  V.pb = TB == 0 ? 8 : 0;  // (a tile starts at a multiple of 64 bases)
+  return V;
+}
+
+// names the fields of a k-mer's table words as values without writing them (no instruction)
+__device__ __forceinline__ void undefined_loads(KmerLoads& L) {
+#pragma unroll
+  for (int w = 0; w < 4; w++) {
+    asm("" : "=v"(L.e[w].x), "=v"(L.e[w].y), "=v"(L.e[w].z), "=v"(L.e[w].w));
+    asm("" : "=v"(L.bl[w]));
+  }
+  asm("" : "=v"(L.dt));
+}
+
 template <int KT, bool PK>  // KT > 0: k known at compile time; 0: runtime k.  PK: packed hash tables (lut_bytes)
 __global__ __launch_bounds__(WG, 6) void sketch_minhash_packed_kernel(PackedIn B, const Segment* __restrict__ segs,
                                                                    const uint2* __restrict__ seg_runs,
@@ -65,6 +98,7 @@ __global__ __launch_bounds__(WG, 6) void sketch_minhash_packed_kernel(PackedIn B
   const WgState W = carve_lds(smem, k, PK, cap, sg.sketch_size);
   uint64_t lo1;  // later passes of a large sketch: only hashes from lo1 up (0: the first pass)
   if (!pass_gate(sg, pass_no, redo, cnt, out, pcnt, lo1)) return;  // workgroup-uniform
+  lo1 = uniform64(lo1);
   const KParams P = make_kparams(k, KT > 0 ? MASH_SEED : seed, PK);  // compile-time k serves the reference's seed only
   const uint32_t lane = W.lane;
   const int wv = (int)uniform32((uint32_t)(W.t >> 6));
@@ -72,7 +106,6 @@ __global__ __launch_bounds__(WG, 6) void sketch_minhash_packed_kernel(PackedIn B
   uint32_t qn = 0;  // entries waiting in this wave's candidate queue (wave-uniform)
   const uint2 sr = seg_runs[blockIdx.x];
   const bool has_runs = sr.x != sr.y;  // workgroup-uniform: most segments of a finished genome meet no run at all
-  const int64_t nbytes = (int64_t)(B.n_bases >> 2);
 
   uint64_t Tstart = (pass_no == 0 && !redo) ? sg.t0 : SENT;  // starting threshold (segment plan); lifted if it proves too optimistic
 restart:
@@ -82,44 +115,67 @@ restart:
 
   uint64_t T = uniform64(Tstart);
   qn = 0;
-  bool safe_mode = true;
+  bool safe_mode = first_tile_safe(W, Tstart, (uint32_t)P_TILE_BASES);
+  uint32_t qlast = 0;    // what this wave's last load left in its queue (wave-uniform)
   uint32_t rcur = sr.x;  // wave-uniform cursor into the run list: every run in front of it ends before anything this wave still looks at
 
   uint32_t count_at_tile_start = 0;
   for (uint64_t TB = sg.s_begin & ~63ULL; TB < sg.s_end && s > 0; TB += P_TILE_BASES) {
-    const int64_t lo64 = (int64_t)sg.s_begin - (int64_t)TB;
-    const int64_t hi64 = (int64_t)sg.s_end - (int64_t)TB;
-    const int rel_lo = lo64 < 0 ? 0 : (int)lo64;
-    const int rel_hi = hi64 > P_TILE_BASES ? P_TILE_BASES : (int)hi64;
-    const bool interior = rel_lo == 0 && rel_hi == P_TILE_BASES;  // every position of the tile is owned
-    const int64_t gb64 = (int64_t)sg.g_begin - (int64_t)TB, ge64 = (int64_t)sg.g_end - (int64_t)TB;
-    const int gb = gb64 < -(1 << 30) ? -(1 << 30) : (int)gb64;   // genome extent in tile coordinates
-    const int ge = ge64 > (1 << 30) ? (1 << 30) : (int)ge64;
-    const int64_t tile_byte = (int64_t)(TB >> 2);                 // wave-uniform
+    // Everything a load asks is 32-bit and relative to the tile.  The express walk reads two scalars of it: the loads
+    // it may take start in [ex_lo, ex_hi - P_CHUNK].
+    const TileView V = tile_view(sg, TB, B.n_bases);
+    const uint8_t* const tile = B.bytes + (TB >> 2);              // wave-uniform
     const uint32_t rcur_tile = rcur;                              // a tile walked again starts from here again
 
     do {
       rcur = rcur_tile;
+      // Express eligibility is a property of the wave's load (4 096 positions), not of the tile: its positions are all
+      // owned ([rel_lo, rel_hi)) and they and their k - 1 predecessors lie in the genome -- so a tile at a segment or
+      // genome edge still walks its clean loads express.  What holds for the whole tile (mode, pass, a high word that
+      // decides) empties the range instead.
+      int ex_lo = 1 << 30, ex_hi = 0;
+      uint32_t Thi1 = 0;
+      if constexpr (KT > 16 && KT <= 28) {
+        const uint32_t Thi_e = (uint32_t)(T >> 32);
+        if (!safe_mode && !lo1 && Thi_e < 0xffffffffu - TEST_SLACK) {
+          ex_lo = V.rel_lo > V.gb + (KT - 1) ? V.rel_lo : V.gb + (KT - 1);
+          ex_hi = V.rel_hi < V.ge ? V.rel_hi : V.ge;
+          Thi1 = Thi_e + TEST_SLACK;
+        }
+      }
+      ex_lo = (int)uniform32((uint32_t)ex_lo);  // scalars by construction: a load's branch is a scalar compare
+      ex_hi = (int)uniform32((uint32_t)ex_hi);
 #pragma unroll 1
       for (int j = 0; j < P_NL; j++) {
-        const int crel = (wv * P_NL + j) * P_CHUNK;   // this wave's load: first base relative to the tile (wave-uniform)
-        const int lrel = crel + 64 * (int)lane;       // the lane's first owned position
+        // this wave's load: first base relative to the tile (wave-uniform).  The waves' loads interleave, so that a tile
+        // only part of which is owned (a segment's last) still spreads over all eight waves; a wave's own loads ascend,
+        // which is all its run cursor asks.
+        const int crel = (j * NWAVE + wv) * P_CHUNK;
+        // Outside safe mode a load that owns no position has nothing to do (the tile behind a segment's end, the loads
+        // in front of its begin); in safe mode every wave meets the barriers of all its steps.
+        if (!safe_mode && (crel >= V.rel_hi || crel + P_CHUNK <= V.rel_lo)) continue;
+        // A queue that the next load could fill is drained in front of it (outside safe mode appends need no barrier: a
+        // buffer that cannot take them raises the overflow flag, and the tile is walked again): as many as three times
+        // what the last load queued, and a few, must fit.  At a tile's end the queue drains as before.
+        if (!safe_mode && qn > 0 && qn + 3 * qlast + 8 > (uint32_t)QCAP) drain_queue(W, qn, T);
+        const uint32_t q_in = qn;
         // ---- the lane's 64 bases and the 32 in front of them (zeros outside the buffer: never part of a counted k-mer) ----
         uint32_t cw[4] = {0u, 0u, 0u, 0u}, p2 = 0u, p3 = 0u;
-        {
-          const int64_t byte = tile_byte + (lrel >> 2);
-          if (byte + 16 <= nbytes) {
-            const uint4 v = *reinterpret_cast<const uint4*>(B.bytes + byte);
+        auto load_guarded = [&](int lrel) __attribute__((always_inline)) {
+          const int lb = lrel >> 2;  // byte of the lane's first base, relative to the tile's
+          if (lb + 16 <= V.nb) {
+            const uint4 v = *reinterpret_cast<const uint4*>(tile + lb);
             cw[0] = v.x; cw[1] = v.y; cw[2] = v.z; cw[3] = v.w;
           }
-          if (byte >= 8 && byte <= nbytes) {
-            const uint2 v = *reinterpret_cast<const uint2*>(B.bytes + byte - 8);
+          if (lb >= V.pb && lb <= V.nb) {
+            const uint2 v = *reinterpret_cast<const uint2*>(tile + (lb - 8));
             p2 = v.x; p3 = v.y;
           }
-        }
+        };
         // ---- can a run touch this wave's bases?  (scalar: the cursor only moves forward) ----
         bool wave_dirty = false;
         if (has_runs) {
+          load_guarded(crel + 64 * (int)lane);  // in flight under the cursor's scalar reads, whichever walk takes the load
           const int64_t first = (int64_t)TB + crel - 32;  // runs that end at or before it are behind this wave for good
           uint32_t rc = rcur;
           while (rc < sr.y) {
@@ -132,28 +188,39 @@ restart:
           wave_dirty = rcur < sr.y && (int64_t)B.runs[2 * (uint64_t)rcur] < (int64_t)TB + crel + P_CHUNK;
         }
 
-        bool done = false;  // wave-uniform: the express walk took this load
+        bool done = false;       // wave-uniform: the express walk took this load
+        bool lost_load = false;  // wave-uniform: ... and gave it back, its queue full
         if constexpr (KT > 16 && KT <= 28) {
-          // The steady state: a wave whose 4 096 bases (and the k - 1 in front) lie inside the genome and clear of runs,
-          // in a tile interior to the segment, outside safe mode, with a threshold whose high word decides, walks its
+          // The steady state: a wave whose 4 096 bases (and the k - 1 in front) lie inside the genome and the segment
+          // and clear of runs, outside safe mode, with a threshold whose high word decides, walks its
           // 64 k-mers per lane as one software pipeline (the table reads of k-mer n + 1 in flight under the arithmetic
           // of k-mer n) -- windows, hash halves, high-word test, possible candidates to the queue.  A full queue hands
           // the whole load to the general walk.
           constexpr int FS = 58 - 2 * KT;           // where a new byte enters the forward window kept top-aligned for a dword's first k-mer
           constexpr int FSB = FS & ~7, FX = FS & 7;  // ... kept at the byte boundary below it; the rest is part of every cut
-          const uint32_t Thi_e = (uint32_t)(T >> 32);
-          if (!safe_mode && !lo1 && interior && Thi_e < 0xffffffffu - TEST_SLACK && !wave_dirty && crel - (KT - 1) >= gb && crel + P_CHUNK <= ge) {
-            const uint32_t Thi1 = Thi_e + TEST_SLACK;
+          if (crel >= ex_lo && crel + P_CHUNK <= ex_hi && !wave_dirty) {
+            // the lane's 64 bases and the 32 in front of them: all inside the buffer (the load lies in the genome, and
+            // not at base 0 of the buffer: k - 1 predecessors lie in the genome too), so nothing is asked per lane
+            uint4 cv = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+            uint2 pv = make_uint2(p2, p3);
+            if (!has_runs) {
+              const uint8_t* const src = tile + (uint32_t)((crel >> 2) + 16 * (int)lane);
+              cv = *reinterpret_cast<const uint4*>(src);
+              pv = *reinterpret_cast<const uint2*>(src - 8);
+            }
             const uint32_t qn0 = qn;
             // both windows from the 32 bases in front: forward F << FSB (first base on top), reverse complement with the
             // newest base's complement on top -- the complemented stream as it lies
-            const uint32_t q2 = pair_rev(p2), q3 = pair_rev(p3);
+            const uint32_t q2 = pair_rev(pv.x), q3 = pair_rev(pv.y);
             uint32_t FThi = FSB ? __builtin_amdgcn_alignbit(q2, q3, 32 - FSB) : q2;
             uint32_t FTlo = FSB ? (q3 << FSB) : q3;
-            uint32_t Rhi = ~p3, Rlo = ~p2;
-            uint32_t w0 = cw[0], w1 = cw[1], w2 = cw[2], w3 = cw[3];
+            uint32_t Rhi = ~pv.y, Rlo = ~pv.x;
+            uint32_t w0 = cv.x, w1 = cv.y, w2 = cv.z, w3 = cv.w;
             bool lost = false;  // wave-uniform: the queue could not take a candidate
-            KmerLoads pend = {};
+            // the pipeline's first k-mer has no predecessor to finish: its slot starts as whatever the registers hold
+            // (named as values, not written: a zero-fill would be twelve moves per load), and is never finished
+            KmerLoads pend;
+            undefined_loads(pend);
             auto finish_pending = [&]() __attribute__((always_inline)) { express_handoff(pend, P, Thi1, W.wq, qn, lost); };
 #pragma unroll 1
             for (int d = 0; d < 4; d++) {
@@ -182,13 +249,20 @@ restart:
               w0 = w1; w1 = w2; w2 = w3;
             }
             finish_pending();
-            if (lost) qn = qn0;  // the candidates this load did queue are found again by the general walk
+            if (lost) { qn = qn0; lost_load = true; }  // the candidates this load did queue are found again by the general walk
             else done = true;
           }
         }
 
         // ---- the general walk: every k, runs, genome and segment edges, safe mode, later passes ----
         if (!done) {  // (safe mode never takes the express walk: every wave meets the barriers of all sixteen steps)
+          // Nothing in here is worked out ahead of the branch (an express load would pay for masks it never reads): the
+          // lane's position passes through an empty asm that stays where it is written, and the masks, the ownership
+          // tests and, in a segment without runs, the loads with their guards all hang on it.
+          int lrel = crel + 64 * (int)lane;  // the lane's first owned position
+          asm volatile("" : "+v"(lrel));
+          if (!has_runs) load_guarded(lrel);
+          const bool owned = crel >= V.rel_lo && crel + P_CHUNK <= V.rel_hi;  // wave-uniform: every position of the load is owned
           // validity of the lane's 96 bases: bit i of (M2 : M1 : M0) set = base lrel - 32 + i lies in a run or outside the genome
           uint32_t M[3] = {0u, 0u, 0u};
           const int wstart = lrel - 32;  // tile coordinates
@@ -202,8 +276,8 @@ restart:
               if (la < lb) M[w] |= (lb - la == 32) ? ~0u : (((1u << (lb - la)) - 1u) << la);
             }
           };
-          if (gb > wstart) mark(0, gb - wstart);
-          if (ge < wstart + 96) mark(ge - wstart, 96);
+          if (V.gb > wstart) mark(0, V.gb - wstart);
+          if (V.ge < wstart + 96) mark(V.ge - wstart, 96);
           if (wave_dirty) {
             const int64_t wabs = (int64_t)TB + wstart;
             for (uint32_t r = first_run_ending_after(B.runs, rcur, sr.y, wabs); r < sr.y; r++) {  // from the first run that ends behind the window's first base
@@ -236,7 +310,7 @@ restart:
               const uint32_t rp = y ^ 0xffu;
               uint64_t canon[4];
               cut_kmers(fwd, rc, pack, rp, P, true, canon);  // ... and rolls the windows on
-              const bool allok = interior && clean;  // wave-uniform: every k-mer of every lane is valid and owned
+              const bool allok = owned && clean;  // wave-uniform: every k-mer of every lane is valid and owned
               // a k-mer that ends at position i of the lane's 64 is valid when the k bits up to bit 32 + i of the mask are clear
               bool ok[4];
 #pragma unroll
@@ -244,12 +318,13 @@ restart:
                 const int i = (i0 & 31) + b;  // position inside Wm's upper word
                 const uint64_t win = (Wm >> (33 + i - k)) & (k == 32 ? 0xffffffffULL : ((1ULL << k) - 1ULL));
                 const int rel = rel0 + b;
-                ok[b] = win == 0 && rel >= rel_lo && rel < rel_hi;
+                ok[b] = win == 0 && rel >= V.rel_lo && rel < V.rel_hi;
               }
               kmer_step4(W, P, canon, allok, T, lo1, qn, safe_mode, [&](int b) __attribute__((always_inline)) { return ok[b]; });
             }
           }
         }
+        qlast = lost_load ? (uint32_t)QCAP : qn - q_in;  // (a drain happens in front of a load only: qn >= q_in)
       }  // loads of the tile
     } while (tile_overflowed(W, T, count_at_tile_start, safe_mode));
     end_tile(W, T, qn, count_at_tile_start, safe_mode);
@@ -296,7 +371,7 @@ extern "C" int rtc_sketch_minhash_packed_dev(rtc_ctx* ctx, const uint8_t* d_pack
     RTC_CHECK_LAUNCH(ctx);
     return RTC_OK;
   };
-  return minhash_run(ctx, h_off, n, k, h_sizes, size, d_out, stride, d_cnt, (uint64_t)P_TILE_BASES, (size_t)MIN_ROOM, prepare, launch);
+  return minhash_run(ctx, h_off, n, k, h_sizes, size, d_out, stride, d_cnt, P_PLAN_BASES, (size_t)MIN_ROOM, prepare, launch);
 }
 
 namespace { __global__ void touch_unit_kernel() {} }
