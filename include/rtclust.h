@@ -824,6 +824,76 @@ int rtc_leiden(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, uint64_t m, d
  * rounds, out[5] merges accepted, out[6] proposals rejected, out[7] move ns, out[8] refinement ns, out[9] whole call ns. */
 int rtc_leiden_counters(const rtc_ctx* ctx, uint64_t out[10]);
 
+/* ---- clust-leiden --db --assign: new genomes placed into the communities of a finished run ------------------- */
+/* The move phase's choice for a vertex that was not there.  The reference has nothing of the kind: this is the definition
+ * (tests/refleiden_assign.py restates it).
+ * A model is the result of one clust-leiden run over n_db KSSD sketches: the labels L[p], numbered as the run numbered its
+ * clusters; the graph parameters threshold, kmer_size, knn_k; the objective (CPM or modularity; rtc_louvain is modularity);
+ * g = llround(resolution 65536); the quantisation the run used -- under CPM the scale flag with lo and range of the host's
+ * leiden_quantise, under modularity none; under CPM the community sizes N_d; under modularity tot_d, the sum over d's members
+ * of the row sums k_p of the very records the run gave rtc_louvain or rtc_leiden (k_x as defined at rtc_louvain), and
+ * M2 = the sum of all tot_d.
+ * For a query x, a sketch that is not in the model:
+ *   - C(x): the model genomes p that share a hash with x and pass rtc_graph_build's edge rule -- both sketches non-empty,
+ *     !(2 min < max) on the sizes, (double)common / (double)union >= J* with rtc_graph_build's J* for (threshold, kmer_size) --
+ *     on the count the pair phase reports, as rtc_graph_build sees it.
+ *   - E(x): the knn_k best of C(x).  The rank is common / union, larger first, compared exactly by 64-bit cross-multiplication,
+ *     equal ratios to the lower p; knn_k = 0 keeps all of C(x).  The build's "higher-numbered neighbours only" rule has no
+ *     meaning for a vertex outside the numbering: a query ranks against all model genomes.
+ *   - q(x, p): the weight rtc_graph_weight(common, |x|, |p|, kmer_size), formed on the host, quantised exactly as the model's
+ *     run quantised its own.  Modularity: max(1, llround(w 2^20)).  CPM: w' = scale ? (w - lo) / range : w, q = llround(w' 2^20)
+ *     capped at 0xffffffff; a record with q < 1 is dropped (w' may lie outside [0, 1] for a query; the same lines apply).
+ *   - k_x = the sum of q over the kept records, e_d = the sum over those with L[p] = d.
+ *   - The score, in 128-bit signed integers: the move phase's for x alone in a community of its own, S(own) = 0, in the model's
+ *     graph with x and its edges added.
+ *         CPM:         S(d) = e_d 65536 - g 2^20 N_d
+ *         modularity:  S(d) = e_d (M2 + 2 k_x) 65536 - g k_x (tot_d + e_d);    M2 + 2 k_x >= 2^46: RTC_ERR_UNSUPPORTED
+ *   - label: the d with e_d > 0 and the largest S(d) > 0 strictly, equal scores to the smallest d; -1 if there is none (the
+ *     command line prints "novel").  runner_up: the next community in that order among those with S > 0, or -1.
+ *   - Queries never see each other, and the model is not changed.  Under CPM with resolution >= 1 and weights of at most one
+ *     unit no score is positive and every query is novel, as every vertex of the build is its own cluster there.
+ * The two calls mirror the build: rtc_graph_build, the host's weights, rtc_louvain.  The device forms no distance.
+ *
+ * rtc_graph_query: E(x) for every query.  The rows [0, n_db) are the model, the rows [n_db, n_db + n_queries) the queries, the
+ * layout of rtc_rep_topk.  h_edges[cap] receives the records in (q, p) order, *h_n_edges their number; more than cap:
+ * RTC_ERR_OVERFLOW with the needed count in *h_n_edges (h_near is complete then).  h_near[q]: nearest, common, denom -- over ALL
+ * candidates (model genomes sharing a hash with q, passing or not) the one with the largest common / (|x| + |p| - common),
+ * compared exactly, equal keys to the lower p; UINT32_MAX and zeros when q shares no hash -- and n_candidates, n_passing = |C(x)|,
+ * n_kept = |E(x)|.  query_chunk: queries per join (0: all); a chunk whose candidates exceed RTC_EDGE_BUDGET or whose join scratch
+ * does not fit is halved, RTC_ERR_NOMEM past one query; no fallback.  Argument errors are rtc_graph_build's (threshold <= 0 or
+ * NaN, kmer_size < 1, n_db + n_queries >= 2^31 - 1, no room: RTC_ERR_ARG; a sketch of 2^31 hashes: RTC_ERR_UNSUPPORTED), and
+ * h_near NULL with n_queries > 0 is RTC_ERR_ARG.  Synchronous. */
+typedef struct { uint32_t q, p, common, pad; } rtc_qedge; /* q: query index, p: model genome */
+typedef struct { uint32_t nearest, common, denom, n_candidates, n_passing, n_kept; } rtc_graph_near;
+int rtc_graph_query(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n_db,
+                    uint32_t n_queries, double threshold, int kmer_size, uint32_t knn_k, uint32_t query_chunk, rtc_qedge* h_edges,
+                    uint64_t cap, uint64_t* h_n_edges, rtc_graph_near* h_near);
+/* The last rtc_graph_query: out[0] query chunks, out[1] candidates, out[2] passing the edge rule, out[3] kept, out[4] queries the
+ * k-NN rule cut, out[5] queries without a candidate, out[6] join ns, out[7] filter and bucketing ns, out[8] select and sort ns,
+ * out[9] whole call ns. */
+int rtc_graph_query_counters(const rtc_ctx* ctx, uint64_t out[10]);
+
+/* rtc_leiden_place: label and runner-up of every query from its quantised records (u: query index, v: model genome, q), in any
+ * order; duplicate (u, v) are summed.  h_labels[n_db] in [0, n_clusters); h_tot[n_clusters] the model's tot_d under modularity,
+ * NULL under CPM (the sizes N_d are counted from the labels); m2 the model's M2 (unused under CPM).  h_out[q]: label, runner_up,
+ * n_edges (distinct model genomes among the records), n_comms (communities they touch), k_x, e_label, e_runner (0 where there
+ * is none).  A query without a record is novel with zeros.
+ * Errors: u >= n_queries, v >= n_db, q = 0, a label outside [0, n_clusters), an objective that is neither RTC_LEIDEN_CPM nor
+ * RTC_LEIDEN_MODULARITY, h_tot NULL under modularity: RTC_ERR_ARG; resolution as rtc_louvain refuses it; M2 + 2 k_x >= 2^46 for
+ * some query under modularity: RTC_ERR_UNSUPPORTED.  Everything is an integer, so the result depends neither on the order of
+ * the records nor on the kernel path of a row.  Synchronous. */
+typedef struct { int32_t label, runner_up; uint32_t n_edges, n_comms; uint64_t k_x, e_label, e_runner; } rtc_leiden_placement;
+int rtc_leiden_place(rtc_ctx* ctx, uint32_t n_db, const int32_t* h_labels, uint32_t n_clusters, const uint64_t* h_tot, uint64_t m2,
+                     double resolution, int objective, uint32_t n_queries, const rtc_wedge* h_edges, uint64_t m,
+                     rtc_leiden_placement* h_out);
+/* The last rtc_leiden_place: out[0] records, out[1] distinct (u, v), out[2] queries with a record, out[3] placed, out[4] novel,
+ * out[5] rows of the wave path, out[6] of the workgroup path, out[7] of the global-table path, out[8] sort and kernel ns,
+ * out[9] whole call ns. */
+int rtc_leiden_place_counters(const rtc_ctx* ctx, uint64_t out[10]);
+/* The row paths of the last rtc_leiden_place: bit 0 one wave with the table in LDS (rows of up to 128 entries), bit 1 a 256-lane
+ * workgroup (up to 2 048), bit 2 the table in global memory (longer rows). */
+int rtc_leiden_place_last_path(const rtc_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif

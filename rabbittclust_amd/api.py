@@ -28,6 +28,11 @@ PLACE_DT = np.dtype([("label", "<i4"), ("label_max", "<i4"), ("n_neighbours", "<
                      ("common", "<u4"), ("denom", "<u4"), ("flags", "<u4")])
 PLACE_NONE = 0xFFFFFFFF  # nearest of a query that shares no hash with the model
 GEDGE_DT = np.dtype([("u", "<u4"), ("v", "<u4"), ("common", "<u4"), ("pad", "<u4")])  # rtc_gedge
+QEDGE_DT = np.dtype([("q", "<u4"), ("p", "<u4"), ("common", "<u4"), ("pad", "<u4")])  # rtc_qedge
+NEAR_DT = np.dtype([("nearest", "<u4"), ("common", "<u4"), ("denom", "<u4"), ("n_candidates", "<u4"), ("n_passing", "<u4"),
+                    ("n_kept", "<u4")])  # rtc_graph_near; nearest PLACE_NONE: no shared hash
+PLACEMENT_DT = np.dtype([("label", "<i4"), ("runner_up", "<i4"), ("n_edges", "<u4"), ("n_comms", "<u4"), ("k_x", "<u8"), ("e_label", "<u8"),
+                         ("e_runner", "<u8")])  # rtc_leiden_placement
 WEDGE_DT = np.dtype([("u", "<u4"), ("v", "<u4"), ("q", "<u4")])  # rtc_wedge
 HEDGE_DT = np.dtype([("p", "<u4"), ("q", "<u4"), ("common", "<u4"), ("size_p", "<u4"), ("size_q", "<u4")])  # rtc_hedge
 
@@ -896,6 +901,65 @@ class Context:
         self.check(self.lib.rtc_leiden_counters(self.h, a))
         names = ("iterations", "levels", "move_rounds", "moves", "refine_rounds", "merges", "rejected", "move_ns", "refine_ns", "total_ns")
         return {k: int(a[i]) for i, k in enumerate(names)}
+
+    def graph_query(self, sk, n_db, threshold, kmer_size, knn_k=0, query_chunk=0, cap=None):
+        """clust-leiden --db --assign, first call (rtc_graph_query): sk holds the n_db model genomes, then the queries.  Returns
+        (edges, near): QEDGE_DT records (q, p, common) in (q, p) order -- every query's knn_k best model genomes among those
+        passing graph_build's edge rule, knn_k 0: all of them -- and NEAR_DT per query.  cap: room for the records (None: the
+        call is repeated with the count it reports); an explicit cap that is too small raises RTC_ERR_OVERFLOW, the needed
+        count in self.graph_edges_needed."""
+        nq = sk.n - int(n_db)
+        if nq < 0:
+            raise ValueError("n_db exceeds the sketch set")
+        room = max(int(cap) if cap is not None else 64 * max(nq, 1), 1)
+        near = np.zeros(max(nq, 1), dtype=NEAR_DT)
+        while True:
+            out = np.zeros(room, dtype=QEDGE_DT)
+            ne = C.c_uint64(0)
+            st = self.lib.rtc_graph_query(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), int(n_db), nq,
+                                          float(threshold), int(kmer_size), int(knn_k), int(query_chunk), _np_ptr(out),
+                                          int(cap) if cap is not None else room, C.byref(ne), _np_ptr(near))
+            self.graph_edges_needed = int(ne.value)
+            if st == _lib.RTC_ERR_OVERFLOW and cap is None:
+                room = int(ne.value)
+                continue
+            self.check(st)
+            return out[:ne.value].copy(), near[:nq].copy()
+
+    def graph_query_counters(self):
+        """rtc_graph_query_counters as a dict (the last graph_query call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_graph_query_counters(self.h, a))
+        names = ("chunks", "candidates", "passing", "kept", "queries_cut", "queries_alone", "join_ns", "filter_ns", "select_ns", "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
+    def leiden_place(self, labels, n_clusters, n_queries, edges, resolution=1.0, objective="cpm", tot=None, m2=0):
+        """clust-leiden --db --assign, second call (rtc_leiden_place): labels are the model's (one per model genome, in
+        [0, n_clusters)), edges WEDGE_DT records (u: query index, v: model genome, q) in any order.  objective "modularity"
+        needs the model's tot (one per cluster) and m2; under "cpm" both are left out.  Returns PLACEMENT_DT per query: label
+        (-1: novel), runner_up, n_edges, n_comms, k_x, e_label, e_runner."""
+        obj = {"cpm": 0, "modularity": 1}.get(objective, objective)
+        lab = np.ascontiguousarray(np.asarray(labels, dtype=np.int32))
+        e = np.ascontiguousarray(np.asarray(edges, dtype=WEDGE_DT))
+        t = None if tot is None else np.ascontiguousarray(np.asarray(tot, dtype=np.uint64))
+        if t is not None and t.shape != (int(n_clusters),):
+            raise ValueError("tot needs one entry per cluster")
+        out = np.zeros(max(int(n_queries), 1), dtype=PLACEMENT_DT)
+        self.check(self.lib.rtc_leiden_place(self.h, int(lab.size), _np_ptr(lab) if lab.size else None, int(n_clusters),
+                                             _np_ptr(t) if t is not None and t.size else None, int(m2), float(resolution), int(obj),
+                                             int(n_queries), _np_ptr(e) if e.size else None, int(e.size), _np_ptr(out)))
+        return out[:int(n_queries)].copy()
+
+    def leiden_place_counters(self):
+        """rtc_leiden_place_counters as a dict (the last leiden_place call); row_paths: bit 0 one wave, bit 1 a 256-lane
+        workgroup, bit 2 the global table (rtc_leiden_place_last_path)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_leiden_place_counters(self.h, a))
+        names = ("records", "entries", "queries_with_records", "placed", "novel", "wave_rows", "workgroup_rows", "global_rows", "kernel_ns",
+                 "total_ns")
+        out = {k: int(a[i]) for i, k in enumerate(names)}
+        out["row_paths"] = int(self.lib.rtc_leiden_place_last_path(self.h))
+        return out
 
     def dbscan_counters(self):
         """rtc_dbscan_counters as a dict (the last dbscan call)."""

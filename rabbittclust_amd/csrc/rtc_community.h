@@ -129,6 +129,136 @@ __global__ __launch_bounds__(BLOCK) void louvain_move_kernel(const uint32_t* __r
   }
 }
 
+// ---- placement (rtc_leiden_place, rtc_leiden_assign.hip): the move kernel's sibling for a vertex that is not in the graph ----
+// The move kernel's table and order, as functions: open addressing over 1 << (32 - shift) slots with its hash, keys all LV_NONE
+// on entry.  Returns community d's slot, claimed if it had none; the caller adds the weight to vals[slot].  (louvain_move_kernel
+// keeps its own lines: written through these functions its instruction stream comes out differently.)
+__device__ __forceinline__ uint32_t lv_table_slot(uint32_t* keys, uint32_t d, uint32_t shift, uint32_t mask) {
+  uint32_t h = (d * 2654435761u) >> shift;
+  for (;;) {
+    const uint32_t old = atomicCAS(&keys[h], LV_NONE, d);
+    if (old == LV_NONE || old == d) break;
+    h = (h + 1) & mask;
+  }
+  return h;
+}
+// the move kernel's order of (score, community): larger score, then smaller community
+__device__ __forceinline__ bool lv_better(i128 sc, uint32_t d, i128 best, uint32_t best_d) { return sc > best || (sc == best && d < best_d); }
+// The two best communities of a row under lv_better, with the weight into each.  d == LV_NONE at score 0: none -- a candidate
+// needs a score above 0, so it beats every such entry and no such entry beats anything.
+struct LvTop2 { i128 s[2]; uint64_t e[2]; uint32_t d[2]; };
+__device__ __forceinline__ void lv_top2_insert(LvTop2& t, i128 sc, uint32_t d, uint64_t e) {
+  if (lv_better(sc, d, t.s[0], t.d[0])) {
+    t.s[1] = t.s[0]; t.d[1] = t.d[0]; t.e[1] = t.e[0];
+    t.s[0] = sc; t.d[0] = d; t.e[0] = e;
+  } else if (lv_better(sc, d, t.s[1], t.d[1])) {
+    t.s[1] = sc; t.d[1] = d; t.e[1] = e;
+  }
+}
+__device__ __forceinline__ i128 lv_shfl_xor(i128 v, int off) {
+  const unsigned long long hi = __shfl_xor((unsigned long long)((unsigned __int128)v >> 64), off);
+  const unsigned long long lo = __shfl_xor((unsigned long long)v, off);
+  return (i128)(((unsigned __int128)hi << 64) | lo);
+}
+
+// Query list[it]'s row holds its records (key: query << 32 | model genome, equal keys summed).  The table is the move kernel's,
+// keyed by the model genome's community; tot[d] is N_d (CPM) or tot_d (modularity).  The score is the one of a vertex alone in
+// a community of its own in the model's graph with the query added (include/rtclust.h: rtc_leiden_place):
+//   CPM         S(d) = e_d 65536 - g 2^20 N_d
+//   modularity  S(d) = e_d (M2 + 2 k_x) 65536 - g k_x (tot_d + e_d),   M2 + 2 k_x < 2^46 (the host refuses more)
+// Lane 0 writes the query's record; nothing else touches it.
+template <int BLOCK, uint32_t SLOTS>
+__global__ __launch_bounds__(BLOCK) void leiden_place_kernel(const uint32_t* __restrict__ list, uint32_t n_list, const uint64_t* __restrict__ row_off,
+                                                             const uint64_t* __restrict__ key, const uint64_t* __restrict__ w,
+                                                             const int32_t* __restrict__ labels, const uint64_t* __restrict__ tot, int modularity,
+                                                             uint64_t g, uint64_t m2, const uint64_t* __restrict__ tab_off,
+                                                             const uint32_t* __restrict__ tab_log2, uint32_t* gkeys, unsigned long long* gvals,
+                                                             rtc_leiden_placement* __restrict__ out) {
+  __shared__ uint32_t s_keys[SLOTS ? SLOTS : 1];
+  __shared__ unsigned long long s_vals[SLOTS ? SLOTS : 1];
+  __shared__ unsigned long long s_k[4];
+  __shared__ uint32_t s_n[4];
+  __shared__ LvTop2 s_top[4];
+  for (uint32_t it = blockIdx.x; it < n_list; it += gridDim.x) {  // uniform over the workgroup
+    const uint32_t x = list[it];
+    uint32_t* keys = s_keys;
+    unsigned long long* vals = s_vals;
+    uint32_t log2_slots = 31 - __builtin_clz(SLOTS ? SLOTS : 1u);
+    if (!SLOTS) {
+      keys = gkeys + tab_off[it];
+      vals = gvals + tab_off[it];
+      log2_slots = tab_log2[it];
+    }
+    const uint32_t slots = 1u << log2_slots, mask = slots - 1, shift = 32 - log2_slots;
+    for (uint32_t s = threadIdx.x; s < slots; s += BLOCK) { keys[s] = LV_NONE; vals[s] = 0ull; }
+    __syncthreads();
+    const uint64_t r0 = row_off[x], r1 = row_off[x + 1];
+    unsigned long long kx = 0;
+    for (uint64_t e = r0 + threadIdx.x; e < r1; e += BLOCK) {
+      const uint64_t we = w[e];
+      const uint32_t h = lv_table_slot(keys, (uint32_t)labels[(uint32_t)key[e]], shift, mask);
+      atomicAdd(&vals[h], (unsigned long long)we);
+      kx += we;
+    }
+    for (int off = 32; off; off >>= 1) kx += __shfl_xor(kx, off);
+    if (BLOCK > 64) {
+      if ((threadIdx.x & 63) == 0) s_k[threadIdx.x / 64] = kx;
+    }
+    __syncthreads();  // the table is complete, and so are the waves' sums
+    if (BLOCK > 64) {
+      kx = 0;
+      for (uint32_t wv = 0; wv < BLOCK / 64; wv++) kx += s_k[wv];
+    }
+    const i128 A = modularity ? (i128)(m2 + 2 * kx) * 65536 : (i128)65536;
+    const i128 gB = modularity ? (i128)g * (i128)kx : (i128)g * 1048576;
+    LvTop2 t;
+    t.s[0] = t.s[1] = 0; t.d[0] = t.d[1] = LV_NONE; t.e[0] = t.e[1] = 0;
+    uint32_t nc = 0;
+    for (uint32_t s = threadIdx.x; s < slots; s += BLOCK) {
+      const uint32_t d = keys[s];
+      if (d == LV_NONE) continue;
+      nc++;
+      const uint64_t ed = vals[s];
+      const i128 sc = (i128)ed * A - gB * (i128)(tot[d] + (modularity ? ed : 0ull));
+      if (sc > 0) lv_top2_insert(t, sc, d, ed);
+    }
+    for (int off = 32; off; off >>= 1) {
+      nc += __shfl_xor(nc, off);
+      LvTop2 o;
+      for (int j = 0; j < 2; j++) {
+        o.s[j] = lv_shfl_xor(t.s[j], off);
+        o.d[j] = __shfl_xor(t.d[j], off);
+        o.e[j] = __shfl_xor((unsigned long long)t.e[j], off);
+      }
+      lv_top2_insert(t, o.s[0], o.d[0], o.e[0]);
+      lv_top2_insert(t, o.s[1], o.d[1], o.e[1]);
+    }
+    if (BLOCK > 64) {
+      if ((threadIdx.x & 63) == 0) { s_top[threadIdx.x / 64] = t; s_n[threadIdx.x / 64] = nc; }
+      __syncthreads();
+      if (threadIdx.x == 0)
+        for (uint32_t wv = 1; wv < BLOCK / 64; wv++) {
+          const LvTop2 o = s_top[wv];
+          lv_top2_insert(t, o.s[0], o.d[0], o.e[0]);
+          lv_top2_insert(t, o.s[1], o.d[1], o.e[1]);
+          nc += s_n[wv];
+        }
+    }
+    if (threadIdx.x == 0) {
+      rtc_leiden_placement r;
+      r.label = t.d[0] == LV_NONE ? -1 : (int32_t)t.d[0];
+      r.runner_up = t.d[1] == LV_NONE ? -1 : (int32_t)t.d[1];
+      r.n_edges = (uint32_t)(r1 - r0);
+      r.n_comms = nc;
+      r.k_x = kx;
+      r.e_label = t.e[0];
+      r.e_runner = t.e[1];
+      out[x] = r;
+    }
+    __syncthreads();  // the table and the wave slots are written again in the next turn
+  }
+}
+
 // level 0: record e as two directed entries (u == v: twice the self entry, 2q in all)
 __global__ __launch_bounds__(256) void louvain_entries_kernel(const rtc_wedge* __restrict__ edges, uint64_t m, uint64_t* __restrict__ key,
                                                               uint64_t* __restrict__ w) {

@@ -128,6 +128,8 @@ int sort_kept(rtc_ctx* ctx, DevBuf& db, rtc_cedge** list, uint64_t m, Less less)
 
 }  // namespace
 
+double rtc_graph_jstar(double threshold, int kmer_size) { return graph_jstar(threshold, kmer_size); }
+
 extern "C" double rtc_graph_weight(uint32_t common, uint32_t size_u, uint32_t size_v, int kmer_size) {
   if (common == 0) return 0.0;  // distance 1
   const uint64_t union_size = (uint64_t)size_u + size_v - common;

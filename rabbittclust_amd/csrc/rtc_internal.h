@@ -93,6 +93,9 @@ struct rtc_ctx {
   uint64_t graph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};    // rtc_graph_counters (include/rtclust.h lists them)
   uint64_t louvain[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_louvain_counters (include/rtclust.h lists them)
   uint64_t leiden[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // rtc_leiden_counters
+  uint64_t graph_query[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // rtc_graph_query_counters (include/rtclust.h lists them)
+  uint64_t leiden_place[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_leiden_place_counters (include/rtclust.h lists them)
+  int leiden_place_path = 0;  // rtc_leiden_place_last_path
   int host_threads = 1;     // rtc_ctx_set_host_threads: the host side of rtc_tree_medoids
   // rtc_diag_counters: [0] pair tiles the join took, [1] tiled-kernel tiles, [2] merge-kernel tiles, [3] candidate lists contracted
   // to their forest, [4] greedy runs replayed from ONE global join, [5] greedy query blocks of the block loop, [6] estimates handed
@@ -188,6 +191,8 @@ int rtc_msf_device(rtc_ctx* ctx, const rtc_cedge* d_edges, uint64_t m, const uin
                    uint64_t* n_sel_out, int* rounds_out, bool sorted = true, uint32_t max_len = 0);
 int rtc_sort_forest_device(rtc_ctx* ctx, rtc_cedge* d_sel, uint64_t ns, const uint32_t* d_len, int wmode);
 int rtc_sort_u32_pairs(rtc_ctx* ctx, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t n);
+// rtc_graph.hip: the least Jaccard quotient whose distance through the host function is below threshold (rtc_graph_build's J*)
+double rtc_graph_jstar(double threshold, int kmer_size);
 uint32_t rtc_fixed_size_of(const uint32_t* h_len, uint32_t n);
 size_t rtc_msf_scratch_bytes(uint32_t n);
 struct rtc_mst_bufs_t { uint32_t* h_len; rtc_cedge* h_sel; rtc_cedge* d_sel; };  // page-locked sizes + forest, device forest list

@@ -49,3 +49,90 @@ def leiden_quantise(u, v, weight, objective):
     narrow = fn(u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p), len(w), int(objective),
                 out.ctypes.data_as(C.c_void_p), C.byref(n_out))
     return out[:n_out.value].copy(), bool(narrow)
+
+
+def leiden_quantiser(weight, objective):
+    """leiden_quantiser (rtc_host.cpp): what a clust-leiden run's quantisation keeps for its model -> (scale, lo, range, narrow)"""
+    w = np.ascontiguousarray(weight, dtype=np.float64)
+    scale, lo, rng = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+    fn = load().rtch_leiden_quantiser
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    narrow = fn(w.ctypes.data_as(C.c_void_p), len(w), int(objective), C.byref(scale), C.byref(lo), C.byref(rng))
+    return bool(scale.value), float(lo.value), float(rng.value), bool(narrow)
+
+
+def leiden_quantise_weight(weight, objective, scale=False, lo=0.0, rng=1.0):
+    """leiden_quantise_weight (rtc_host.cpp): q of one weight as the model's run formed it, 0 where the record drops out"""
+    fn = load().rtch_leiden_quantise_weight
+    fn.restype = C.c_uint32
+    fn.argtypes = [C.c_double, C.c_int, C.c_int, C.c_double, C.c_double]
+    return int(fn(float(weight), int(objective), int(bool(scale)), float(lo), float(rng)))
+
+
+def leiden_assign_weights(edges, model_sizes, query_sizes, kmer_size, objective, scale=False, lo=0.0, rng=1.0, threads=1):
+    """leiden_assign_weights (rtc_host.cpp): the records of Context.graph_query (q, p, common) to (u: query, v: model genome, q)
+    records through rtc_graph_weight and the model's quantisation, on `threads` host threads"""
+    from . import _lib
+    e = np.ascontiguousarray(edges)
+    ms = np.ascontiguousarray(model_sizes, dtype=np.uint32)
+    qs = np.ascontiguousarray(query_sizes, dtype=np.uint32)
+    out = np.zeros(max(len(e), 1), dtype=[("u", "<u4"), ("v", "<u4"), ("q", "<u4")])
+    n_out = C.c_uint64(0)
+    wf = C.cast(_lib.load().rtc_graph_weight, C.c_void_p)
+    fn = load().rtch_leiden_assign_weights
+    fn.restype = None
+    fn.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                   C.c_void_p, C.POINTER(C.c_uint64)]
+    fn(e.ctypes.data_as(C.c_void_p), len(e), ms.ctypes.data_as(C.c_void_p), qs.ctypes.data_as(C.c_void_p), int(kmer_size), wf, int(objective),
+       int(bool(scale)), float(lo), float(rng), int(threads), out.ctypes.data_as(C.c_void_p), C.byref(n_out))
+    return out[:n_out.value].copy()
+
+
+def leiden_model_sums(records, labels, n_clusters):
+    """leiden_model_sums (rtc_host.cpp): (k per genome, tot per cluster, M2, size per cluster) of a run's records and labels"""
+    r = np.ascontiguousarray(records, dtype=[("u", "<u4"), ("v", "<u4"), ("q", "<u4")])
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    n, nc = len(lab), int(n_clusters)
+    k, tot, size, m2 = np.zeros(max(n, 1), np.uint64), np.zeros(max(nc, 1), np.uint64), np.zeros(max(nc, 1), np.uint64), C.c_uint64(0)
+    fn = load().rtch_leiden_model_sums
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    if fn(r.ctypes.data_as(C.c_void_p), len(r), lab.ctypes.data_as(C.c_void_p), n, nc, k.ctypes.data_as(C.c_void_p),
+          tot.ctypes.data_as(C.c_void_p), size.ctypes.data_as(C.c_void_p), C.byref(m2)) != 0:
+        raise ValueError("a record or a label is out of range")
+    return k[:n].copy(), tot[:nc].copy(), int(m2.value), size[:nc].copy()
+
+
+def leiden_model_save(path, head, min_len, threshold, resolution, lo, rng, m2, labels, tot, names, lens, sketches):
+    """save_leiden_model (rtc_host.cpp) from its parts; head: algorithm, objective, width, sketch_by_file, kmer_size, half_k,
+    half_subk, drlevel, knn, n_clusters, scale"""
+    head = np.ascontiguousarray(head, dtype=np.int32)
+    assert head.shape == (11,)
+    width = int(head[2])
+    dt = np.uint64 if width == 8 else np.uint32
+    n = len(labels)
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    t = np.ascontiguousarray(tot, dtype=np.uint64)
+    ln = np.ascontiguousarray(lens, dtype=np.uint64)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(s) for s in sketches])
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=dt) for s in sketches]) if n else np.zeros(1, dtype=dt))
+    arr = (C.c_char_p * max(n, 1))(*[s.encode() for s in names])
+    fn = load().rtch_leiden_model_save
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_uint32, C.c_void_p,
+                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return fn(str(path).encode(), head.ctypes.data_as(C.c_void_p), int(min_len), float(threshold), float(resolution), float(lo), float(rng),
+              int(m2), n, lab.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), arr, ln.ctypes.data_as(C.c_void_p),
+              flat.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p))
+
+
+def leiden_model_resave(in_path, out_path):
+    """load_leiden_model, then save_leiden_model -> (0, "") or (-1, the loader's reason)"""
+    why = C.create_string_buffer(256)
+    fn = load().rtch_leiden_model_resave
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
+    rc = fn(str(in_path).encode(), str(out_path).encode(), why, 256)
+    return rc, why.value.decode()

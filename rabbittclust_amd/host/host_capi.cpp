@@ -220,4 +220,76 @@ int rtch_leiden_quantise(const uint32_t* u, const uint32_t* v, const double* wei
   *n_out = rec.size();
   return narrow ? 1 : 0;
 }
+
+// leiden_quantiser: (scale, lo, range) of the weights; returns leiden_quantise's flag
+int rtch_leiden_quantiser(const double* weight, uint64_t m, int objective, int* scale, double* lo, double* range) {
+  LeidenQuant z;
+  const bool narrow = leiden_quantiser(weight, m, objective, &z, nullptr, nullptr);
+  *scale = z.scale ? 1 : 0; *lo = z.lo; *range = z.range;
+  return narrow ? 1 : 0;
+}
+
+// leiden_quantise_weight: q of one weight, 0 where the record drops out
+uint32_t rtch_leiden_quantise_weight(double weight, int objective, int scale, double lo, double range) {
+  LeidenQuant z;
+  z.objective = objective; z.scale = scale != 0; z.lo = lo; z.range = range;
+  return leiden_quantise_weight(weight, z);
+}
+
+// leiden_assign_weights with the caller's weight function (rtc_graph_weight): out[m], *n_out the records kept
+void rtch_leiden_assign_weights(const rtc_qedge* edges, uint64_t m, const uint32_t* model_sizes, const uint32_t* query_sizes, int kmer_size,
+                                double (*weight_fn)(uint32_t, uint32_t, uint32_t, int), int objective, int scale, double lo, double range,
+                                int threads, rtc_wedge* out, uint64_t* n_out) {
+  LeidenQuant z;
+  z.objective = objective; z.scale = scale != 0; z.lo = lo; z.range = range;
+  std::vector<rtc_wedge> rec;
+  leiden_assign_weights(edges, m, model_sizes, query_sizes, kmer_size, weight_fn, z, threads, rec);
+  for (size_t i = 0; i < rec.size(); i++) out[i] = rec[i];
+  *n_out = rec.size();
+}
+
+// leiden_model_sums: k[n], tot[n_clusters], size[n_clusters], *m2; -1 where a record or a label is out of range
+int rtch_leiden_model_sums(const rtc_wedge* records, uint64_t m, const int32_t* labels, uint32_t n, uint32_t n_clusters, uint64_t* k, uint64_t* tot,
+                           uint64_t* size, uint64_t* m2) {
+  LeidenModelSums s;
+  if (!leiden_model_sums(records, m, labels, n, n_clusters, s)) return -1;
+  std::copy(s.k.begin(), s.k.end(), k);
+  std::copy(s.tot.begin(), s.tot.end(), tot);
+  std::copy(s.size.begin(), s.size.end(), size);
+  *m2 = s.m2;
+  return 0;
+}
+
+// a clust-leiden --db model written from its parts (tests, tools): head = {algorithm, objective, width, sketch_by_file, kmer_size,
+// half_k, half_subk, drlevel, knn, n_clusters, scale}, genome q named names[q] with lens[q] bases and the hashes
+// hashes[off[q] .. off[q + 1]) in the model's width.  0, or -2 where the file was not written.
+int rtch_leiden_model_save(const char* path, const int32_t* head, uint64_t min_len, double threshold, double resolution, double lo, double range,
+                           uint64_t m2, uint32_t n, const int32_t* labels, const uint64_t* tot, const char** names, const uint64_t* lens,
+                           const void* hashes, const uint64_t* off) {
+  LeidenModel m;
+  m.algorithm = head[0]; m.objective = head[1]; m.width = head[2]; m.sketch_by_file = head[3] != 0; m.kmer_size = head[4]; m.half_k = head[5];
+  m.half_subk = head[6]; m.drlevel = head[7]; m.knn = head[8]; m.n_clusters = head[9]; m.scale = head[10] != 0;
+  m.min_len = min_len; m.threshold = threshold; m.resolution = resolution; m.lo = lo; m.range = range; m.m2 = m2;
+  m.labels.assign(labels, labels + n);
+  m.tot.assign(tot, tot + m.n_clusters);
+  m.genomes.resize(n);
+  for (uint32_t q = 0; q < n; q++) {
+    GenomeInfo& g = m.genomes[q];
+    g.id = (int)q; g.fileName = names[q]; g.seq0.name = names[q]; g.seq0.length = (int)lens[q]; g.totalSeqLength = lens[q]; g.use64 = m.width == 8;
+    if (m.width == 8) m.h64.emplace_back((const uint64_t*)hashes + off[q], (const uint64_t*)hashes + off[q + 1]);
+    else m.h32.emplace_back((const uint32_t*)hashes + off[q], (const uint32_t*)hashes + off[q + 1]);
+  }
+  return save_leiden_model(path, m) ? 0 : -2;
+}
+
+// a clust-leiden --db model read and written back; -1 with the loader's reason in why[why_cap] where it does not load
+int rtch_leiden_model_resave(const char* in_path, const char* out_path, char* why, int why_cap) {
+  LeidenModel m;
+  std::string w;
+  if (!load_leiden_model(in_path, m, &w)) {
+    if (why && why_cap > 0) { strncpy(why, w.c_str(), (size_t)why_cap - 1); why[why_cap - 1] = 0; }
+    return -1;
+  }
+  return save_leiden_model(out_path, m) ? 0 : -2;
+}
 }

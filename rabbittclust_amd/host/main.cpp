@@ -944,7 +944,7 @@ static Options parse(int argc, char** argv) {
     if (a == "--knn") { o.knn = atoi(need(i)); continue; }
     if (a == "--pregraph") { o.folder_path = need(i); o.has_pregraph = true; continue; }
     if (a == "--save-graph") { o.saveGraph = true; continue; }
-    if (a == "--db" || a == "--build" || a == "--assign" || a == "--stats" || a == "--append" || a == "--save-rep" || a == "--query" ||
+    if (a == "--append" || a == "--save-rep" || a == "--query" ||
         a == "--top-k" || a == "--dense" || a == "--premsted" || a == "--auto-threshold" || a == "--stability" || a == "--dedup-dist" ||
         a == "--reps-per-cluster" || a == "--newick-tree" || a == "--phylip-tree" || a == "--nexus-tree" || a == "--linkage-matrix" ||
         a == "--buildDB" || a == "-s" || a == "--sketch-size" || a == "-c" || a == "--containment" || a.rfind("--inverted-index", 0) == 0) {
@@ -1049,7 +1049,14 @@ static Options parse(int argc, char** argv) {
            "           with --leiden; 1..9: 50 with a warning, as the reference defaults it, so the filter cannot be switched off)\n"
            "  --save-graph (leiden.graph into the sketch folder: 'n m', then 'u v weight' per edge; the weights carry 6 significant\n"
            "                digits, so a --pregraph run is defined on the file's weights, not on the sketches')\n"
-           "  --pregraph DIR (DIR/leiden.graph and the KSSD sketches of DIR: the clustering alone, for another --resolution)");
+           "  --pregraph DIR (DIR/leiden.graph and the KSSD sketches of DIR: the clustering alone, for another --resolution)\n"
+           "  --db FILE --build (with the flags above: the run as without --db, then the model -- labels, community totals, the\n"
+           "                     run's parameters and quantisation, genome records and all sketches -- into FILE; not with --pregraph)\n"
+           "  --db FILE --assign (-l -i LIST | -i FASTA) -o assign.tsv (new genomes placed into the model's communities on the GPU:\n"
+           "                     k, sketch parameters, threshold, knn, objective and resolution come from FILE; per query its\n"
+           "                     cluster or novel, the runner-up, edges kept, communities touched, the weight to the cluster and\n"
+           "                     its share, the nearest genome and its distance; the model is not changed)\n"
+           "  --db FILE --stats (algorithm, parameters, genomes and clusters of FILE; no GPU, no -o)");
       exit(0);
 #elif defined(DBSCAN_CLUST)
       puts("clust-dbscan (MI355X build): DBSCAN density-based clustering module (KSSD with --fast, MinHash with --minhash)");
@@ -2099,6 +2106,131 @@ static int append_clust_greedy(const Options& o, vector<Gpu>& gpus) {
 }
 #endif
 
+#ifdef DBSCAN_CLUST
+// The -i input of --db --assign / --update sketched as the model's genomes were: kind, k, sketch parameters and minimum length
+// from the model (clust-dbscan's and clust-leiden's alike).  what: whose sketches, for the messages.
+struct ModelSketching { bool minhash; int width, kmer_size, sketch_size, half_k, half_subk, drlevel; uint64_t min_len; };
+static int model_db_sketch(const Options& o, vector<Gpu>& gpus, const ModelSketching& md, const char* what, vector<GenomeInfo>& q,
+                           MinHashSketchFile& mh, KssdSketchFile& ks) {
+  SketchJob job;
+  job.kssd = !md.minhash; job.kmerSize = md.kmer_size; job.minLen = md.min_len; job.threads = o.threads;
+  if (md.minhash) job.sketchSize = md.sketch_size;
+  else job.drlevel = md.drlevel;
+  Resident rs;
+  if (o.sketchByFile) sketch_files(gpus, o.inputFile, job, q, &mh, &ks, rs, true);
+  else {
+    vector<FastaRecord> recs; SeqModeSizes sz;
+    if (!read_sequences(o.inputFile, md.min_len, recs, sz)) return 1;
+    sketch_sequences(gpus, recs, job, q, &mh, &ks);
+  }
+  const int qwidth = md.minhash ? 8 : (ks.use64 ? 8 : 4);
+  if (!q.empty() && qwidth != md.width) {
+    cerr << "ERROR: the " << what << " sketches have hash width " << qwidth << " but the model has " << md.width << endl;
+    return 1;
+  }
+  if (!md.minhash && !q.empty() && (ks.info.half_k != md.half_k || ks.info.half_subk != md.half_subk)) {
+    cerr << "ERROR: the " << what << " sketches have half_k " << ks.info.half_k << ", half_subk " << ks.info.half_subk << " but the model has " << md.half_k
+         << ", " << md.half_subk << endl;
+    return 1;
+  }
+  return 0;
+}
+#endif
+
+#ifdef LEIDEN_CLUST
+// clust-leiden --db FILE --assign: the queries sketched as the model's genomes were; rtc_graph_query, the host's weights on the
+// host threads, rtc_leiden_place; one TSV line each.  The model is read only.
+static int leiden_db_assign(const Options& o, vector<Gpu>& gpus, const LeidenModel& md) {
+  rtc_ctx* ctx = gpus[0].ctx;
+  const double t0 = get_sec();
+  vector<GenomeInfo> q; MinHashSketchFile mh; KssdSketchFile ks;
+  if (const int rc = model_db_sketch(o, gpus, ModelSketching{false, md.width, md.kmer_size, 0, md.half_k, md.half_subk, md.drlevel, md.min_len},
+                                     "query", q, mh, ks))
+    return rc;
+  const double t1 = get_sec();
+  g_metrics.num("sketch_queries_s", t1 - t0);
+  const uint32_t N = (uint32_t)md.labels.size(), Q = (uint32_t)q.size();
+  cerr << "===== Leiden model assignment (" << (md.algorithm == 1 ? "Leiden" : "Louvain") << ", " << (md.objective == 0 ? "cpm" : "modularity") << ") =====" << endl
+       << "  Query genomes:  " << Q << endl << "  Model genomes:  " << N << endl << "  Threshold, knn: " << md.threshold << ", " << md.knn << endl;
+  vector<rtc_graph_near> near(Q);
+  vector<rtc_leiden_placement> place(Q);
+  vector<uint32_t> msize(N), qsize(Q);
+  for (uint32_t p = 0; p < N; p++) msize[p] = (uint32_t)(md.width == 8 ? md.h64[p].size() : md.h32[p].size());
+  uint64_t gc[10] = {0}, pc[10] = {0};
+  double t_weights = 0.0;
+  if (Q) {
+    DeviceSketches ds;
+    if (md.width == 8) {
+      vector<vector<uint64_t>> all(md.h64);
+      all.insert(all.end(), ks.h64.begin(), ks.h64.end());
+      upload_sketches(ctx, &all, nullptr, ds);
+    } else {
+      vector<vector<uint32_t>> all(md.h32);
+      all.insert(all.end(), ks.h32.begin(), ks.h32.end());
+      upload_sketches(ctx, nullptr, &all, ds);
+    }
+    if (ds.n != N + Q) { cerr << "ERROR: --assign needs the query sketches on the host (" << ds.n - N << " of " << Q << ")" << endl; return 1; }
+    for (uint32_t i = 0; i < Q; i++) qsize[i] = (uint32_t)(md.width == 8 ? ks.h64[i].size() : ks.h32[i].size());
+    vector<rtc_qedge> edges((size_t)std::max<uint64_t>(1, (uint64_t)Q * std::min<uint64_t>(md.knn > 0 ? (uint64_t)md.knn : 64, 64)));
+    uint64_t n_edges = 0;
+    int st = rtc_graph_query(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, N, Q, md.threshold, md.kmer_size, (uint32_t)md.knn, 0, edges.data(),
+                             edges.size(), &n_edges, near.data());
+    if (st == RTC_ERR_OVERFLOW) {  // the count is known now
+      edges.resize(n_edges);
+      st = rtc_graph_query(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, N, Q, md.threshold, md.kmer_size, (uint32_t)md.knn, 0, edges.data(),
+                           edges.size(), &n_edges, near.data());
+    }
+    CHECK(ctx, st);
+    edges.resize(n_edges);
+    rtc_graph_query_counters(ctx, gc);
+    (void)rtc_dev_free(ctx, ds.d_hashes); (void)rtc_dev_free(ctx, ds.d_start); (void)rtc_dev_free(ctx, ds.d_len);
+    const double tw = get_sec();
+    LeidenQuant z;
+    z.objective = md.objective; z.scale = md.scale; z.lo = md.lo; z.range = md.range;
+    vector<rtc_wedge> records;
+    leiden_assign_weights(edges.data(), n_edges, msize.data(), qsize.data(), md.kmer_size, rtc_graph_weight, z, o.threads, records);
+    t_weights = get_sec() - tw;
+    CHECK(ctx, rtc_leiden_place(ctx, N, md.labels.data(), (uint32_t)md.n_clusters, md.objective == RTC_LEIDEN_MODULARITY ? md.tot.data() : nullptr, md.m2,
+                                md.resolution, md.objective, Q, records.data(), records.size(), place.data()));
+    rtc_leiden_place_counters(ctx, pc);
+  }
+  if (getenv("RTC_VERBOSE"))
+    fprintf(stderr, "[assign] %llu candidates in %llu chunk(s), %llu passing, %llu kept; query %.3f ms, weights %.3f ms, place %.3f ms\n",
+            (unsigned long long)gc[1], (unsigned long long)gc[0], (unsigned long long)gc[2], (unsigned long long)gc[3], gc[9] / 1e6, t_weights * 1e3, pc[9] / 1e6);
+  uint64_t placed = 0;
+  for (uint32_t i = 0; i < Q; i++) placed += place[i].label >= 0;
+  g_metrics.num("leiden_assign_query_s", gc[9] / 1e9);
+  g_metrics.num("leiden_assign_weights_s", t_weights);
+  g_metrics.num("leiden_assign_place_s", pc[9] / 1e9);
+  g_metrics.num("leiden_assign_placed", (double)placed);
+  g_metrics.num("leiden_assign_novel", (double)(Q - placed));
+  g_metrics.num("genomes", (double)Q);
+  FILE* fp = fopen(o.outputFile.c_str(), "w");
+  if (!fp) { cerr << "ERROR: cannot open file: " << o.outputFile << endl; return 1; }
+  fprintf(fp, "query\tcluster\trunner_up\tedges\tcommunities\tweight\tshare\tnearest\tdistance\n");
+  for (uint32_t i = 0; i < Q; i++) {
+    const rtc_leiden_placement& r = place[i];
+    const string& name = o.sketchByFile ? q[i].fileName : q[i].seq0.name;
+    char cluster[16] = "novel", runner[16] = "-", dist[32] = "inf";
+    if (r.label >= 0) snprintf(cluster, sizeof cluster, "%d", r.label);
+    if (r.runner_up >= 0) snprintf(runner, sizeof runner, "%d", r.runner_up);
+    const double share = (r.label >= 0 && r.k_x) ? (double)r.e_label / (double)r.k_x : 0.0;
+    string nearest = "-";
+    if (near[i].nearest != UINT32_MAX) {
+      const GenomeInfo& g = md.genomes[near[i].nearest];
+      nearest = md.sketch_by_file ? g.fileName : g.seq0.name;
+      snprintf(dist, sizeof dist, "%.6f", 1.0 - rtc_graph_weight(near[i].common, qsize[i], msize[near[i].nearest], md.kmer_size));
+    }
+    fprintf(fp, "%s\t%s\t%s\t%u\t%u\t%.6f\t%.6f\t%s\t%s\n", name.c_str(), cluster, runner, r.n_edges, r.n_comms, (double)r.e_label / 1048576.0, share,
+            nearest.c_str(), dist);
+  }
+  fclose(fp);
+  cerr << "===== Assignment Results =====" << endl << "  Placed:      " << placed << endl << "  Novel:       " << Q - placed << endl
+       << "  Output:      " << o.outputFile << endl << "==============================" << endl;
+  return 0;
+}
+#endif
+
 #if defined(DBSCAN_CLUST) && !defined(LEIDEN_CLUST)
 // KssdDBSCAN's closing lines (src/dbscan.cpp:951-980).  Its progress lines (:918-930) leave std::fixed and precision 1 on cerr
 // once one has been printed, and the core-point percentage comes out in that format then: the walk is replayed from the labels
@@ -2183,32 +2315,10 @@ static void print_dbscan_result(const vector<int32_t>& labels, uint32_t ncl, con
   fclose(fp);
 }
 
-// The -i input of --db --assign / --update sketched as the model's genomes were: kind, k, sketch parameters and minimum length
-// from the model.  what: whose sketches, for the messages.
 static int dbscan_db_sketch(const Options& o, vector<Gpu>& gpus, const DbscanModel& md, const char* what, vector<GenomeInfo>& q,
                             MinHashSketchFile& mh, KssdSketchFile& ks) {
-  SketchJob job;
-  job.kssd = !md.minhash; job.kmerSize = md.kmer_size; job.minLen = md.min_len; job.threads = o.threads;
-  if (md.minhash) job.sketchSize = md.sketch_size;
-  else job.drlevel = md.drlevel;
-  Resident rs;
-  if (o.sketchByFile) sketch_files(gpus, o.inputFile, job, q, &mh, &ks, rs, true);
-  else {
-    vector<FastaRecord> recs; SeqModeSizes sz;
-    if (!read_sequences(o.inputFile, md.min_len, recs, sz)) return 1;
-    sketch_sequences(gpus, recs, job, q, &mh, &ks);
-  }
-  const int qwidth = md.minhash ? 8 : (ks.use64 ? 8 : 4);
-  if (!q.empty() && qwidth != md.width) {
-    cerr << "ERROR: the " << what << " sketches have hash width " << qwidth << " but the model has " << md.width << endl;
-    return 1;
-  }
-  if (!md.minhash && !q.empty() && (ks.info.half_k != md.half_k || ks.info.half_subk != md.half_subk)) {
-    cerr << "ERROR: the " << what << " sketches have half_k " << ks.info.half_k << ", half_subk " << ks.info.half_subk << " but the model has " << md.half_k
-         << ", " << md.half_subk << endl;
-    return 1;
-  }
-  return 0;
+  return model_db_sketch(o, gpus, ModelSketching{md.minhash, md.width, md.kmer_size, md.sketch_size, md.half_k, md.half_subk, md.drlevel, md.min_len},
+                         what, q, mh, ks);
 }
 
 // clust-dbscan --db FILE --assign: the queries sketched as the model's genomes were, placed by rtc_dbscan_assign, one TSV line each
@@ -2408,6 +2518,38 @@ int main(int argc, char** argv) {
 #ifdef LEIDEN_CLUST
   // ---- clust-leiden: the checks of src/main.cpp:391-477 in that order, all before any GPU context exists (the default
   // threshold 0.05 is set above, as for every command) ----
+  // ---- clust-leiden --db: the model file's flows, their flag errors first ----
+  LeidenModel ld_model;
+  {
+    const int actions = (int)o.db_build + (int)o.db_assign + (int)o.db_stats;
+    if (actions > 1) { cerr << "ERROR: --build, --assign and --stats exclude each other" << endl; return 1; }
+    if (actions && o.repdb_path.empty()) { cerr << "ERROR: --build / --assign / --stats require --db" << endl; return 1; }
+    if (!o.repdb_path.empty() && actions != 1) { cerr << "ERROR: --db requires one of --build, --assign, --stats" << endl; return 1; }
+    if (o.db_build && o.has_pregraph) { cerr << "ERROR: --db --build does not go with --pregraph" << endl; return 1; }
+    if (o.db_assign && !o.has_input) { cerr << "ERROR: --assign requires -i <input_file>" << endl; return 1; }
+    if (o.db_assign && (o.has_pregraph || o.saveGraph)) {
+      cerr << "ERROR: --assign does not go with " << (o.has_pregraph ? "--pregraph" : "--save-graph") << endl;
+      return 1;
+    }
+    if (o.db_stats || o.db_assign) {
+      string why;
+      if (!load_leiden_model(o.repdb_path, ld_model, &why)) { cerr << "ERROR: --db " << o.repdb_path << ": " << why << endl; return 1; }
+    }
+    if (o.db_stats) {
+      print_leiden_model_stats(ld_model, std::cout);
+      std::cout.flush();
+      return 0;
+    }
+    if (o.db_assign) {
+      // -k, -d, --resolution, --knn, --objective, --louvain and --leiden beside --assign have no effect: the model's hold
+      o.louvain = ld_model.algorithm == 0; o.leiden = !o.louvain;
+      o.objective = ld_model.objective == 0 ? "cpm" : "modularity";
+      o.resolution = ld_model.resolution; o.has_resolution = false;
+      o.threshold = ld_model.threshold; o.knn = ld_model.knn;
+      o.is_fast = true; o.has_presketched = false;
+      o.kmerSize = ld_model.kmer_size; o.isSetKmer = true; o.drlevel = ld_model.drlevel;
+    }
+  }
   if (o.has_resolution) cerr << "-----Resolution parameter: " << o.resolution << endl;
   if (o.leiden && o.louvain) { cerr << "ERROR: --leiden and --louvain exclude each other" << endl; return 1; }
   if (!o.louvain && !o.leiden) {
@@ -2724,7 +2866,17 @@ int main(int argc, char** argv) {
     for (Gpu& g : gpus) rtc_ctx_destroy(g.ctx);
     return rc;
   }
-#elif !defined(LEIDEN_CLUST)
+#elif defined(LEIDEN_CLUST)
+  if (o.db_assign) {
+    const int rc = leiden_db_assign(o, gpus, ld_model);
+    g_metrics.str("command", "clust-leiden");
+    g_metrics.str("sketch", "kssd");
+    g_metrics.write();
+    for (Gpu& g : gpus) { if (g.comm) rtc_comm_destroy(g.comm); }
+    for (Gpu& g : gpus) rtc_ctx_destroy(g.ctx);
+    return rc;
+  }
+#else
   if (o.db_assign || o.db_update) {
     const int rc = o.db_assign ? dbscan_db_assign(o, gpus, db_model) : dbscan_db_update(o, gpus, db_model);
     g_metrics.str("command", "clust-dbscan");
@@ -2954,12 +3106,14 @@ int main(int argc, char** argv) {
   double modularity = 0.0;
   uint64_t lc[10] = {0};
   const size_t graph_edges = wedges.size();
+  LeidenQuant quant;  // --louvain: modularity's, nothing scaled
   if (o.leiden) {
     // --leiden: q from the weights anew (CPM: normalised as src/leiden.cpp:343-366, the records at q == 0 dropped)
     const int objective = o.objective == "cpm" ? RTC_LEIDEN_CPM : RTC_LEIDEN_MODULARITY;
     vector<uint32_t> eu(graph_edges), ev(graph_edges);
     for (size_t e = 0; e < graph_edges; e++) { eu[e] = wedges[e].u; ev[e] = wedges[e].v; }
     double w_min = 0.0, w_max = 0.0;
+    (void)leiden_quantiser(weights.data(), graph_edges, objective, &quant, nullptr, nullptr);  // what --db --build keeps of it
     if (leiden_quantise(eu.data(), ev.data(), weights.data(), graph_edges, objective, wedges, &w_min, &w_max))
       cerr << "-----Edge weights normalized: [" << w_min << ", " << w_max << "] -> [0, 1]" << endl;
     if (objective == RTC_LEIDEN_CPM && o.resolution >= 1.0)
@@ -2977,6 +3131,27 @@ int main(int argc, char** argv) {
   print_result(cluster, genomes, sketchByFile, o.outputFile);
   cerr << "-----write the cluster result into: " << o.outputFile << endl;
   cerr << "-----the cluster number of " << o.outputFile << " is: " << cluster.size() << endl;
+  if (o.db_build) {  // the model: what --db --assign places new genomes into
+    LeidenModel md;
+    md.algorithm = o.leiden ? 1 : 0;
+    md.objective = o.leiden && o.objective == "cpm" ? RTC_LEIDEN_CPM : RTC_LEIDEN_MODULARITY;
+    md.width = ks.use64 ? 8 : 4; md.sketch_by_file = sketchByFile; md.kmer_size = kmer_size;
+    md.half_k = ks.info.half_k; md.half_subk = ks.info.half_subk; md.drlevel = ks.info.drlevel;
+    md.knn = o.knn; md.n_clusters = (int)ncl; md.min_len = o.minLen; md.threshold = o.threshold; md.resolution = o.resolution;
+    md.scale = quant.scale; md.lo = quant.lo; md.range = quant.range;
+    LeidenModelSums sums;
+    if (!leiden_model_sums(wedges.data(), wedges.size(), labels.data(), n_nodes, ncl, sums)) { cerr << "ERROR: --build: the labels do not fit the graph" << endl; return 1; }
+    md.m2 = md.objective == RTC_LEIDEN_MODULARITY ? sums.m2 : 0;
+    md.tot = md.objective == RTC_LEIDEN_MODULARITY ? sums.tot : sums.size;
+    md.labels = labels; md.genomes = genomes;
+    if (ks.use64) md.h64 = ks.h64; else md.h32 = ks.h32;
+    if ((md.width == 8 ? md.h64.size() : md.h32.size()) != genomes.size()) {
+      cerr << "ERROR: --build needs the sketches on the host (" << (md.width == 8 ? md.h64.size() : md.h32.size()) << " of " << genomes.size() << ")" << endl;
+      return 1;
+    }
+    if (!save_leiden_model(o.repdb_path, md)) return 1;
+    cerr << "-----write the Leiden model (" << genomes.size() << " genomes, " << ncl << " clusters) into: " << o.repdb_path << endl;
+  }
   cerr << "========time of Leiden clustering is: " << get_sec() - t2 << "========" << endl;
   g_metrics.num("leiden_louvain_s", lc[9] / 1e9);  // the clustering call, whichever algorithm
   g_metrics.num("leiden_edges", (double)graph_edges);

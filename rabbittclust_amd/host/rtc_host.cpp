@@ -30,6 +30,7 @@
 #include <iostream>
 #include <limits>
 #include <queue>
+#include <thread>
 
 namespace rtc {
 
@@ -2707,6 +2708,54 @@ struct ModelReader {
 };
 template <typename T> void model_put(std::string& o, const T& v) { o.append((const char*)&v, sizeof(T)); }
 void model_put_str(std::string& o, const std::string& s) { model_put(o, (uint32_t)s.size()); o += s; }
+// the genome records, the sketch lengths and the sketches of n genomes, shared by the model files
+void model_put_genomes(std::string& o, const std::vector<GenomeInfo>& genomes, int width, const std::vector<std::vector<uint32_t>>& h32,
+                       const std::vector<std::vector<uint64_t>>& h64) {
+  const uint64_t n = genomes.size();
+  for (uint64_t g = 0; g < n; g++) {
+    const GenomeInfo& gi = genomes[g];
+    model_put_str(o, gi.fileName); model_put_str(o, gi.seq0.name); model_put_str(o, gi.seq0.comment);
+    model_put(o, (uint64_t)gi.seq0.length);
+    model_put(o, gi.totalSeqLength);
+  }
+  for (uint64_t g = 0; g < n; g++) model_put(o, (uint32_t)(width == 8 ? h64[g].size() : h32[g].size()));
+  for (uint64_t g = 0; g < n; g++) {
+    if (width == 8) o.append((const char*)h64[g].data(), h64[g].size() * 8);
+    else o.append((const char*)h32[g].data(), h32[g].size() * 4);
+  }
+}
+void model_get_genomes(ModelReader& r, uint64_t n, int width, bool use64, std::vector<GenomeInfo>& genomes, std::vector<std::vector<uint32_t>>& h32,
+                       std::vector<std::vector<uint64_t>>& h64) {
+  for (uint64_t g = 0; r.ok && g < n; g++) {
+    GenomeInfo gi;
+    gi.id = (int)g;
+    gi.fileName = r.str(); gi.seq0.name = r.str(); gi.seq0.comment = r.str();
+    gi.seq0.length = (int)r.pod<uint64_t>();
+    gi.totalSeqLength = r.pod<uint64_t>();
+    gi.use64 = use64;
+    genomes.push_back(gi);
+  }
+  std::vector<uint32_t> lens;
+  r.vec(lens, n);
+  if (width == 8) h64.resize(r.ok ? n : 0); else h32.resize(r.ok ? n : 0);
+  for (uint64_t g = 0; r.ok && g < n; g++) {
+    if (width == 8) r.vec(h64[g], lens[g]);
+    else r.vec(h32[g], lens[g]);
+  }
+}
+// the file through FILE.tmp and a rename
+bool model_write(const std::string& path, const std::string& o) {
+  const std::string tmp = path + ".tmp";
+  {
+    std::ofstream f(tmp, std::ios::binary | std::ios::trunc);
+    if (!f) { std::cerr << "ERROR: --db " << path << ": cannot write " << tmp << std::endl; return false; }
+    f.write(o.data(), (std::streamsize)o.size());
+    f.close();
+    if (!f) { std::cerr << "ERROR: --db " << path << ": writing " << tmp << " failed" << std::endl; remove(tmp.c_str()); return false; }
+  }
+  if (rename(tmp.c_str(), path.c_str()) != 0) { std::cerr << "ERROR: --db " << path << ": cannot rename " << tmp << std::endl; remove(tmp.c_str()); return false; }
+  return true;
+}
 }  // namespace
 
 bool save_dbscan_model(const std::string& path, const DbscanModel& m) {
@@ -2720,27 +2769,8 @@ bool save_dbscan_model(const std::string& path, const DbscanModel& m) {
   model_put(o, m.eps);
   o.append((const char*)m.labels.data(), n * 4);
   o.append((const char*)m.core.data(), n);
-  for (uint64_t g = 0; g < n; g++) {
-    const GenomeInfo& gi = m.genomes[g];
-    model_put_str(o, gi.fileName); model_put_str(o, gi.seq0.name); model_put_str(o, gi.seq0.comment);
-    model_put(o, (uint64_t)gi.seq0.length);
-    model_put(o, gi.totalSeqLength);
-  }
-  for (uint64_t g = 0; g < n; g++) model_put(o, (uint32_t)(m.width == 8 ? m.h64[g].size() : m.h32[g].size()));
-  for (uint64_t g = 0; g < n; g++) {
-    if (m.width == 8) o.append((const char*)m.h64[g].data(), m.h64[g].size() * 8);
-    else o.append((const char*)m.h32[g].data(), m.h32[g].size() * 4);
-  }
-  const std::string tmp = path + ".tmp";
-  {
-    std::ofstream f(tmp, std::ios::binary | std::ios::trunc);
-    if (!f) { std::cerr << "ERROR: --db " << path << ": cannot write " << tmp << std::endl; return false; }
-    f.write(o.data(), (std::streamsize)o.size());
-    f.close();
-    if (!f) { std::cerr << "ERROR: --db " << path << ": writing " << tmp << " failed" << std::endl; remove(tmp.c_str()); return false; }
-  }
-  if (rename(tmp.c_str(), path.c_str()) != 0) { std::cerr << "ERROR: --db " << path << ": cannot rename " << tmp << std::endl; remove(tmp.c_str()); return false; }
-  return true;
+  model_put_genomes(o, m.genomes, m.width, m.h32, m.h64);
+  return model_write(path, o);
 }
 
 bool load_dbscan_model(const std::string& path, DbscanModel& m, std::string* why) {
@@ -2767,22 +2797,7 @@ bool load_dbscan_model(const std::string& path, DbscanModel& m, std::string* why
   if (r.ok && n >= 0x7fffffffull) { *why = "is not a clust-dbscan model (" + std::to_string(n) + " genomes)"; return false; }
   r.vec(m.labels, n);
   r.vec(m.core, n);
-  for (uint64_t g = 0; r.ok && g < n; g++) {
-    GenomeInfo gi;
-    gi.id = (int)g;
-    gi.fileName = r.str(); gi.seq0.name = r.str(); gi.seq0.comment = r.str();
-    gi.seq0.length = (int)r.pod<uint64_t>();
-    gi.totalSeqLength = r.pod<uint64_t>();
-    gi.use64 = m.width == 8 && !m.minhash;
-    m.genomes.push_back(gi);
-  }
-  std::vector<uint32_t> lens;
-  r.vec(lens, n);
-  if (m.width == 8) m.h64.resize(r.ok ? n : 0); else m.h32.resize(r.ok ? n : 0);
-  for (uint64_t g = 0; r.ok && g < n; g++) {
-    if (m.width == 8) r.vec(m.h64[g], lens[g]);
-    else r.vec(m.h32[g], lens[g]);
-  }
+  model_get_genomes(r, n, m.width, m.width == 8 && !m.minhash, m.genomes, m.h32, m.h64);
   if (!r.ok) { *why = "is truncated"; return false; }
   if (r.at != blob.size()) { *why = "has " + std::to_string(blob.size() - r.at) + " bytes after its end"; return false; }
   return true;
@@ -2827,10 +2842,16 @@ void print_dbscan_model_stats(const DbscanModel& m, std::ostream& os) {
      << "========================" << std::endl;
 }
 
-bool leiden_quantise(const uint32_t* u, const uint32_t* v, const double* weight, uint64_t m, int objective, std::vector<rtc_wedge>& out,
-                     double* w_min, double* w_max) {
-  out.clear();
-  out.reserve(m);
+uint32_t leiden_quantise_weight(double weight, const LeidenQuant& z) {
+  const bool cpm = z.objective == 0;
+  const double x = (cpm && z.scale) ? (weight - z.lo) / z.range : weight;
+  long long q = llround(x * 1048576.0);
+  if (!cpm && q < 1) q = 1;
+  if (q < 1) return 0;
+  return (uint32_t)std::min<long long>(q, 0xffffffffll);
+}
+
+bool leiden_quantiser(const double* weight, uint64_t m, int objective, LeidenQuant* z, double* w_min, double* w_max) {
   double lo = 1.0, hi = 0.0;
   for (uint64_t e = 0; e < m; e++) {
     if (weight[e] < lo) lo = weight[e];
@@ -2840,15 +2861,157 @@ bool leiden_quantise(const uint32_t* u, const uint32_t* v, const double* weight,
   if (w_max) *w_max = hi;
   const bool cpm = objective == 0;
   const double range = hi - lo;
-  const bool narrow = cpm && hi - lo < 0.5, scale = narrow && range > 1e-6;
+  const bool narrow = cpm && hi - lo < 0.5;
+  z->objective = objective;
+  z->scale = narrow && range > 1e-6;
+  z->lo = lo;
+  z->range = range;
+  return narrow;
+}
+
+bool leiden_quantise(const uint32_t* u, const uint32_t* v, const double* weight, uint64_t m, int objective, std::vector<rtc_wedge>& out,
+                     double* w_min, double* w_max) {
+  out.clear();
+  out.reserve(m);
+  LeidenQuant z;
+  const bool narrow = leiden_quantiser(weight, m, objective, &z, w_min, w_max);
   for (uint64_t e = 0; e < m; e++) {
-    const double x = scale ? (weight[e] - lo) / range : weight[e];
-    long long q = llround(x * 1048576.0);
-    if (!cpm && q < 1) q = 1;
+    const uint32_t q = leiden_quantise_weight(weight[e], z);
     if (q < 1) continue;
-    out.push_back(rtc_wedge{u[e], v[e], (uint32_t)std::min<long long>(q, 0xffffffffll)});
+    out.push_back(rtc_wedge{u[e], v[e], q});
   }
   return narrow;
+}
+
+bool leiden_model_sums(const rtc_wedge* records, uint64_t m, const int32_t* labels, uint32_t n, uint32_t n_clusters, LeidenModelSums& out) {
+  out.k.assign(n, 0);
+  out.tot.assign(n_clusters, 0);
+  out.size.assign(n_clusters, 0);
+  out.m2 = 0;
+  for (uint64_t e = 0; e < m; e++) {
+    if (records[e].u >= n || records[e].v >= n) return false;
+    out.k[records[e].u] += records[e].q;  // u == v: both lines, 2q on the self entry
+    out.k[records[e].v] += records[e].q;
+  }
+  for (uint32_t p = 0; p < n; p++) {
+    if (labels[p] < 0 || (uint32_t)labels[p] >= n_clusters) return false;
+    out.tot[labels[p]] += out.k[p];
+    out.size[labels[p]]++;
+    out.m2 += out.k[p];
+  }
+  return true;
+}
+
+void leiden_assign_weights(const rtc_qedge* edges, uint64_t m, const uint32_t* model_sizes, const uint32_t* query_sizes, int kmer_size,
+                           double (*weight_fn)(uint32_t, uint32_t, uint32_t, int), const LeidenQuant& z, int threads, std::vector<rtc_wedge>& out) {
+  std::vector<uint32_t> q(m);
+  const uint64_t T = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(threads, 1), (m + 4095) / 4096));
+  auto work = [&](uint64_t t) {
+    for (uint64_t e = m * t / T; e < m * (t + 1) / T; e++)
+      q[e] = leiden_quantise_weight(weight_fn(edges[e].common, query_sizes[edges[e].q], model_sizes[edges[e].p], kmer_size), z);
+  };
+  std::vector<std::thread> pool;
+  for (uint64_t t = 1; t < T; t++) pool.emplace_back(work, t);
+  work(0);
+  for (std::thread& th : pool) th.join();
+  out.clear();
+  out.reserve(m);
+  for (uint64_t e = 0; e < m; e++)
+    if (q[e]) out.push_back(rtc_wedge{edges[e].q, edges[e].p, q[e]});
+}
+
+// ---- clust-leiden --db: the model file ----
+namespace {
+const char LEIDEN_MODEL_MAGIC[9] = "RTCLDNM1";
+}
+
+bool save_leiden_model(const std::string& path, const LeidenModel& m) {
+  const uint64_t n = m.labels.size();
+  std::string o(LEIDEN_MODEL_MAGIC, 8);
+  const int32_t head[12] = {1, m.algorithm, m.objective, m.width, m.sketch_by_file ? 1 : 0, m.kmer_size, m.half_k, m.half_subk, m.drlevel, m.knn,
+                            m.n_clusters, m.scale ? 1 : 0};
+  o.append((const char*)head, sizeof head);
+  model_put(o, m.min_len);
+  model_put(o, n);
+  model_put(o, m.threshold);
+  model_put(o, m.resolution);
+  model_put(o, m.lo);
+  model_put(o, m.range);
+  model_put(o, m.m2);
+  o.append((const char*)m.labels.data(), n * 4);
+  o.append((const char*)m.tot.data(), m.tot.size() * 8);
+  model_put_genomes(o, m.genomes, m.width, m.h32, m.h64);
+  return model_write(path, o);
+}
+
+bool load_leiden_model(const std::string& path, LeidenModel& m, std::string* why) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f) { *why = "cannot open"; return false; }
+  std::string blob((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  if (blob.size() < 8 || memcmp(blob.data(), LEIDEN_MODEL_MAGIC, 8) != 0) { *why = "is not a clust-leiden model (bad magic)"; return false; }
+  ModelReader r{blob};
+  r.at = 8;
+  int32_t head[12];
+  for (int i = 0; i < 12; i++) head[i] = r.pod<int32_t>();
+  if (!r.ok) { *why = "is truncated"; return false; }
+  if (head[0] != 1) { *why = "has version " + std::to_string(head[0]) + ", this build reads version 1"; return false; }
+  m = LeidenModel();
+  m.algorithm = head[1]; m.objective = head[2]; m.width = head[3]; m.sketch_by_file = head[4] != 0; m.kmer_size = head[5]; m.half_k = head[6];
+  m.half_subk = head[7]; m.drlevel = head[8]; m.knn = head[9]; m.n_clusters = head[10]; m.scale = head[11] != 0;
+  if ((m.algorithm != 0 && m.algorithm != 1) || (m.objective != 0 && m.objective != 1) || (m.width != 4 && m.width != 8) || m.knn < 0 ||
+      m.n_clusters < 0) {
+    *why = "is not a clust-leiden model (algorithm " + std::to_string(m.algorithm) + ", objective " + std::to_string(m.objective) + ", hash width " +
+           std::to_string(m.width) + ")";
+    return false;
+  }
+  m.min_len = r.pod<uint64_t>();
+  const uint64_t n = r.pod<uint64_t>();
+  m.threshold = r.pod<double>();
+  m.resolution = r.pod<double>();
+  m.lo = r.pod<double>();
+  m.range = r.pod<double>();
+  m.m2 = r.pod<uint64_t>();
+  if (r.ok && (n >= 0x7fffffffull || (uint64_t)m.n_clusters > n)) {
+    *why = "is not a clust-leiden model (" + std::to_string(n) + " genomes, " + std::to_string(m.n_clusters) + " clusters)";
+    return false;
+  }
+  r.vec(m.labels, n);
+  r.vec(m.tot, (uint64_t)m.n_clusters);
+  model_get_genomes(r, n, m.width, m.width == 8, m.genomes, m.h32, m.h64);
+  if (!r.ok) { *why = "is truncated"; return false; }
+  if (r.at != blob.size()) { *why = "has " + std::to_string(blob.size() - r.at) + " bytes after its end"; return false; }
+  for (int32_t l : m.labels)
+    if (l < 0 || l >= m.n_clusters) { *why = "is not a clust-leiden model (label " + std::to_string(l) + ")"; return false; }
+  return true;
+}
+
+void print_leiden_model_stats(const LeidenModel& m, std::ostream& os) {
+  std::vector<uint64_t> size((size_t)m.n_clusters, 0);
+  for (int32_t l : m.labels) size[l]++;
+  uint64_t largest = 0, single = 0;
+  for (uint64_t s : size) { largest = std::max(largest, s); single += s == 1; }
+  os << "===== Leiden model =====" << std::endl
+     << "  Algorithm:   " << (m.algorithm == 1 ? "Leiden" : "Louvain") << std::endl
+     << "  Objective:   " << (m.objective == 0 ? "cpm" : "modularity") << std::endl
+     << "  Hash width:  " << m.width << std::endl
+     << "  Kmer size:   " << m.kmer_size << std::endl
+     << "  Half k:      " << m.half_k << std::endl << "  Half subk:   " << m.half_subk << std::endl << "  Drlevel:     " << m.drlevel << std::endl
+     << "  Min length:  " << m.min_len << std::endl
+     << "  Threshold:   " << m.threshold << std::endl
+     << "  Resolution:  " << m.resolution << std::endl
+     << "  Knn:         " << m.knn << std::endl;
+  if (m.objective == 0) {
+    os << "  Weights:     ";
+    if (m.scale) os << "scaled from [" << m.lo << ", " << m.lo + m.range << "]" << std::endl;
+    else os << "as they are" << std::endl;
+  } else {
+    os << "  Total weight: " << m.m2 << std::endl;
+  }
+  os << "  Genomes:     " << m.labels.size() << std::endl
+     << "  Clusters:    " << m.n_clusters << std::endl
+     << "  Largest:     " << largest << std::endl
+     << "  Singletons:  " << single << std::endl
+     << "========================" << std::endl;
 }
 
 }  // namespace rtc

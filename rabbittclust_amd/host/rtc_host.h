@@ -314,6 +314,62 @@ std::string current_date_time();  // src/common.hpp:36-44
 bool leiden_quantise(const uint32_t* u, const uint32_t* v, const double* weight, uint64_t m, int objective, std::vector<rtc_wedge>& out,
                      double* w_min, double* w_max);
 
+// The quantisation of ONE weight, as a clust-leiden run formed its records: leiden_quantise finds (scale, lo, range) over its
+// weights and calls leiden_quantise_weight for each, and clust-leiden --db --assign calls it with the model's three for the
+// weights of a query, so the two cannot drift.  objective 1 (modularity; --louvain too): max(1, llround(w 2^20)), nothing
+// scaled.  Returns 0 for a record that drops out (CPM, q < 1); q is capped at 2^32 - 1.
+struct LeidenQuant {
+  int objective = 1;
+  bool scale = false;
+  double lo = 0.0, range = 1.0;
+};
+uint32_t leiden_quantise_weight(double weight, const LeidenQuant& z);
+// (scale, lo, range) of m weights under objective; returns leiden_quantise's flag; *w_min, *w_max may be null
+bool leiden_quantiser(const double* weight, uint64_t m, int objective, LeidenQuant* z, double* w_min, double* w_max);
+
+// What a model keeps of the records a run gave rtc_louvain / rtc_leiden and of its labels: k[p] the row sums as the
+// rtc_louvain comment defines them (u == v adds 2q), tot[d] their sum over community d, m2 the sum of all, size[d] the members.
+// false: a record's end or a label is out of range.
+struct LeidenModelSums {
+  std::vector<uint64_t> k, tot, size;
+  uint64_t m2 = 0;
+};
+bool leiden_model_sums(const rtc_wedge* records, uint64_t m, const int32_t* labels, uint32_t n, uint32_t n_clusters, LeidenModelSums& out);
+
+// clust-leiden --db FILE: the communities of one run, with everything a new genome needs to be placed into them
+// (rtc_graph_query, rtc_leiden_place).  One binary file, little-endian, INTEGRATION.md section 8 lists it byte by byte; the
+// genome records, sketch lengths and sketches are section 6's.  Written to FILE.tmp and renamed.
+struct LeidenModel {
+  int algorithm = 0;      // 0 Louvain, 1 Leiden
+  int objective = 1;      // RTC_LEIDEN_CPM / RTC_LEIDEN_MODULARITY (Louvain: modularity)
+  int width = 4;          // bytes per hash
+  bool sketch_by_file = true;
+  int kmer_size = 0, half_k = 0, half_subk = 0, drlevel = 0;
+  int knn = 0;            // the effective value of the run
+  int n_clusters = 0;
+  uint64_t min_len = 0;
+  double threshold = 0.0, resolution = 1.0;
+  bool scale = false;     // the run's quantisation (CPM)
+  double lo = 0.0, range = 1.0;
+  uint64_t m2 = 0;        // modularity
+  std::vector<int32_t> labels;
+  std::vector<uint64_t> tot;  // per cluster: tot_d (modularity) or the size N_d (CPM)
+  std::vector<GenomeInfo> genomes;
+  std::vector<std::vector<uint32_t>> h32;
+  std::vector<std::vector<uint64_t>> h64;
+};
+bool save_leiden_model(const std::string& path, const LeidenModel& m);
+// false: *why says what is wrong with the file (cannot open, foreign, version, truncated, bytes after its end)
+bool load_leiden_model(const std::string& path, LeidenModel& m, std::string* why);
+void print_leiden_model_stats(const LeidenModel& m, std::ostream& os);
+
+// clust-leiden --db --assign between its two device calls: the weight weight_fn(common, |query|, |model genome|, kmer_size) --
+// weight_fn is rtc_graph_weight; this library does not link the GPU library -- of every record of rtc_graph_query on `threads`
+// host threads (n_queries x knn libm calls), quantised by z.  out receives (query, model genome, q) in the records' order, the
+// dropped ones left out.
+void leiden_assign_weights(const rtc_qedge* edges, uint64_t m, const uint32_t* model_sizes, const uint32_t* query_sizes, int kmer_size,
+                           double (*weight_fn)(uint32_t, uint32_t, uint32_t, int), const LeidenQuant& z, int threads, std::vector<rtc_wedge>& out);
+
 // Time the parser threads spent inside gzip decompression (libdeflate or zlib), summed over threads, and the bytes it produced
 // since the process started: the command lines report them (RTC_METRICS_JSON: inflate_gb_per_s_per_thread).
 void rtc_host_inflate_stats(double* seconds, uint64_t* bytes_out);

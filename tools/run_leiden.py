@@ -6,7 +6,14 @@ the objective -- and prints its counters and the whole-call time of rtc_leiden b
 each, after one call to warm up).
 
     python tools/run_leiden.py --families 40 --per-family 12 [--threshold 0.05] [--knn 1000] [--resolution 1.0]
-    python tools/run_leiden.py --leiden [--objective cpm|modularity] [--leiden-resolution 0.5] [--repeat 3]"""
+    python tools/run_leiden.py --leiden [--objective cpm|modularity] [--leiden-resolution 0.5] [--repeat 3]
+
+With --assign M it holds M genomes of the set out, builds the model on the rest (Louvain, or with --leiden the Leiden of
+--objective) and places them (clust-leiden --db --assign: Context.graph_query, the host's weights on --threads host threads,
+Context.leiden_place); it prints the three times, the best of --repeat warm calls each, beside the time of the full run over
+all genomes (graph_build plus the clustering call), and how many held-out genomes came back to the community of their family.
+
+    python tools/run_leiden.py --families 200 --per-family 12 --assign 200 [--leiden --objective modularity] [--threads 16]"""
 import argparse
 import json
 import os
@@ -29,6 +36,8 @@ def main():
     ap.add_argument("--objective", choices=("cpm", "modularity"), default="cpm")
     ap.add_argument("--leiden-resolution", type=float, default=0.5)
     ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--assign", type=int, default=0, metavar="M")
+    ap.add_argument("--threads", type=int, default=16)
     a = ap.parse_args()
     from rabbittclust_amd import api, host
     ctx = api.Context(0)
@@ -58,7 +67,61 @@ def main():
         out.update({"leiden": ctx.leiden_counters(), "leiden_objective": a.objective, "leiden_resolution": a.leiden_resolution,
                     "leiden_records": int(len(lrec)), "leiden_clusters": ctx.leiden_clusters, "leiden_quality": quality,
                     "louvain_call_ms": min(louvain_ns[1:]) / 1e6, "leiden_call_ms": min(leiden_ns[1:]) / 1e6})
+    if a.assign:
+        out["assign"] = assign(ctx, a, sk, kmer, n)
     print(json.dumps(out))
+
+
+def assign(ctx, a, sk, kmer, n):
+    import time
+    from rabbittclust_amd import api, host
+    m = min(a.assign, n - 1)
+    held = set(np.linspace(0, n - 1, m).astype(int).tolist())
+    sets = sk.to_host()
+    keep = [g for g in range(n) if g not in held]
+    hold = sorted(held)
+    model, queries = [sets[g] for g in keep], [sets[g] for g in hold]
+    sk_model = api.SketchSet.from_host(model, ctx.device, k=kmer, kind="kssd", width=sk.width)
+    sk_all = api.SketchSet.from_host(model + queries, ctx.device, k=kmer, kind="kssd", width=sk.width)
+    msz, qsz = [len(s) for s in model], [len(s) for s in queries]
+    objective = (0 if a.objective == "cpm" else 1) if a.leiden else 1
+    resolution = a.leiden_resolution if a.leiden else a.resolution
+
+    def cluster(skx, sizes):
+        """the full run's two device calls -> (labels, clusters, records, weights, ns)"""
+        edges = ctx.graph_build(skx, a.threshold, kmer, a.knn)
+        ns = ctx.graph_counters()["total_ns"]
+        w = [api.graph_weight(c, sizes[u], sizes[v], kmer) for u, v, c in zip(edges["u"].tolist(), edges["v"].tolist(), edges["common"].tolist())]
+        rec, _ = host.leiden_quantise(edges["u"], edges["v"], w, objective)
+        if a.leiden:
+            labels = ctx.leiden(skx.n, rec, resolution, objective)
+            return labels, ctx.leiden_clusters, rec, w, ns + ctx.leiden_counters()["total_ns"]
+        labels = ctx.louvain(skx.n, rec, resolution)
+        return labels, ctx.louvain_clusters, rec, w, ns + ctx.louvain_counters()["total_ns"]
+    full_ns = [cluster(sk, [len(s) for s in sets])[4] for _ in range(a.repeat + 1)]
+    labels, ncl, rec, w, _ = cluster(sk_model, msz)
+    scale, lo, span, _ = host.leiden_quantiser(w, objective)
+    _, tot, m2, _ = host.leiden_model_sums(rec, labels, ncl)
+    query_ns, weight_s, place_ns = [], [], []
+    for _ in range(a.repeat + 1):
+        qe, near = ctx.graph_query(sk_all, len(model), a.threshold, kmer, a.knn)
+        query_ns.append(ctx.graph_query_counters()["total_ns"])
+        t0 = time.perf_counter()
+        qrec = host.leiden_assign_weights(qe, msz, qsz, kmer, objective, scale, lo, span, threads=a.threads)
+        weight_s.append(time.perf_counter() - t0)
+        got = ctx.leiden_place(labels, ncl, len(queries), qrec, resolution, objective, tot=tot if objective else None, m2=m2 if objective else 0)
+        place_ns.append(ctx.leiden_place_counters()["total_ns"])
+    family_label = {}
+    for i, g in enumerate(keep):
+        family_label.setdefault(g // a.per_family, {}).setdefault(int(labels[i]), 0)
+        family_label[g // a.per_family][int(labels[i])] += 1
+    home = sum(1 for i, g in enumerate(hold) if g // a.per_family in family_label and
+               int(got["label"][i]) == max(family_label[g // a.per_family].items(), key=lambda kv: kv[1])[0])
+    return {"model_genomes": len(model), "queries": len(queries), "model_clusters": int(ncl), "algorithm": "leiden" if a.leiden else "louvain",
+            "objective": "cpm" if objective == 0 else "modularity", "records": int(len(qe)), "placed": int((got["label"] >= 0).sum()),
+            "in_family_community": home, "graph_query": ctx.graph_query_counters(), "leiden_place": ctx.leiden_place_counters(),
+            "graph_query_ms": min(query_ns[1:]) / 1e6, "weights_ms": min(weight_s[1:]) * 1e3, "leiden_place_ms": min(place_ns[1:]) / 1e6,
+            "full_run_ms": min(full_ns[1:]) / 1e6}
 
 
 if __name__ == "__main__":
