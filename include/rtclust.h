@@ -734,14 +734,39 @@ int rtc_dbscan_update_counters(const rtc_ctx* ctx, uint64_t out[12]);
  * h_edges[cap] receives the edges in (u, v) order, *h_n_edges their number.  More than cap: RTC_ERR_OVERFLOW with the needed
  * count in *h_n_edges.  threshold <= 0 or NaN: RTC_ERR_ARG.  A sketch of 2^31 hashes or more: RTC_ERR_UNSUPPORTED.
  * RTC_EDGE_BUDGET chunks the rows as in rtc_dbscan; a kept list that does not fit: RTC_ERR_NOMEM, no fallback.  Synchronous. */
-typedef struct { uint32_t u, v, common, pad; } rtc_gedge; /* u < v */
+typedef struct { uint32_t u, v, common, pad; } rtc_gedge; /* u < v; pad: 0 from rtc_graph_build, the truncated denom from rtc_graph_build_mash */
 int rtc_graph_build(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
                     double threshold, int kmer_size, uint32_t knn_k, rtc_gedge* h_edges, uint64_t cap, uint64_t* h_n_edges);
 /* host only: 1 - calculate_mash_distance_fast(common, size_u, size_v, kmer_size) */
 double rtc_graph_weight(uint32_t common, uint32_t size_u, uint32_t size_v, int kmer_size);
-/* The last rtc_graph_build: out[0] row chunks, out[1] candidates (pairs sharing a hash), out[2] pairs passing the edge rule,
- * out[3] edges after the k-NN filter, out[4] nodes the filter cut, out[5] pair ns, out[6] filter ns, out[7] select and sort ns,
- * out[8] 0, out[9] whole call ns. */
+/* clust-leiden --minhash: the same graph over MinHash sketches -- as for rtc_dbscan_mash, ascending lists of distinct hashes of
+ * at most sketch_size elements, shorter and empty ones allowed, width 4 or 8.  A pair u < v is an edge iff both lists are
+ * non-empty, they share a hash and rtc_mash_distance(common, denom, sketch_size, kmer_size) < threshold strictly, (common, denom)
+ * the union-truncated counts of rtc_pair_mash_dev.  There is no size-ratio rule: the reference's skip belongs to KSSD sketches,
+ * whose sizes scale with the genome; MinHash::distance() has none and MinHashDBSCAN applies none.  A pair that shares a hash
+ * only beyond the truncation has common 0, distance 1, and is never an edge.  The device forms no distance: the host builds
+ * cmin[d], d = 0 .. min(sketch_size, 2 * the longest list) -- the least common whose distance through that very host function
+ * is < threshold, d + 1 where none is (rtc_graph_mash_table; rtc_dbscan_mash_table's bisection with < for <=) -- and its suffix
+ * minima for the prefilter on the pair phase's full-set common; the device tests common >= cmin[denom].
+ * knn_k > 0: every node u keeps its knn_k best edges among v > u, ranked by common / denom compared exactly by 64-bit
+ * cross-multiplication (both counts are <= sketch_size < 2^32), larger first, equal ratios to the lower v; knn_k = 0: no filter.
+ * h_edges[cap] receives the edges in (u, v) order with pad = the truncated denom, *h_n_edges their number.  More than cap:
+ * RTC_ERR_OVERFLOW with the needed count in *h_n_edges.  0 < threshold <= 1: threshold <= 0 or NaN returns RTC_ERR_ARG,
+ * threshold > 1 RTC_ERR_UNSUPPORTED (pairs without a shared hash have distance 1 and no candidate list holds them);
+ * sketch_size == 0 or kmer_size < 1: RTC_ERR_ARG.  RTC_EDGE_BUDGET chunks the rows, RTC_ERR_NOMEM without fallback, as
+ * rtc_graph_build.  RTC_DBSCAN_MASH_SERIAL=1 and RTC_DBSCAN_MASH_NOPREFILTER=1 as for rtc_dbscan_mash; results are identical
+ * either way.  Synchronous. */
+int rtc_graph_build_mash(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                         uint32_t sketch_size, double threshold, int kmer_size, uint32_t knn_k, rtc_gedge* h_edges, uint64_t cap,
+                         uint64_t* h_n_edges);
+/* host only: 1 - rtc_mash_distance(common, denom, sketch_size, kmer_size), the weight of a rtc_graph_build_mash edge (> 0) */
+double rtc_graph_weight_mash(uint32_t common, uint32_t denom, uint32_t sketch_size, int kmer_size);
+/* host only, no context: rtc_graph_build_mash's table for one threshold in (0, 1], out[d] for d = 0 .. sketch_size */
+int rtc_graph_mash_table(uint32_t sketch_size, int kmer_size, double threshold, uint32_t* out);
+/* The last rtc_graph_build or rtc_graph_build_mash: out[0] row chunks, out[1] candidates (pairs sharing a hash), out[2] pairs
+ * passing the edge rule, out[3] edges after the k-NN filter, out[4] nodes the filter cut, out[5] pair ns, out[6] filter (MinHash:
+ * prefilter and merge) ns, out[7] select and sort ns, out[8] candidates merged past the prefilter (MinHash; 0 after
+ * rtc_graph_build), out[9] whole call ns. */
 int rtc_graph_counters(const rtc_ctx* ctx, uint64_t out[10]);
 
 /* Deterministic Louvain in exact integers.  The reference calls igraph_community_multilevel, which visits the nodes in a

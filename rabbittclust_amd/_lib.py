@@ -150,6 +150,9 @@ SIGNATURES = {
     "rtc_hierarchy_cut": (_i, [_u32, _vp, _u64, _vp, C.c_double, C.c_double, _i, _vp, _vp, C.POINTER(_u32)]),
     "rtc_graph_build": (_i, [_vp, _vp, _i, _vp, _vp, _u32, C.c_double, _i, _u32, _vp, _u64, C.POINTER(_u64)]),
     "rtc_graph_weight": (C.c_double, [_u32, _u32, _u32, _i]),
+    "rtc_graph_build_mash": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _u32, C.c_double, _i, _u32, _vp, _u64, C.POINTER(_u64)]),
+    "rtc_graph_weight_mash": (C.c_double, [_u32, _u32, _u32, _i]),
+    "rtc_graph_mash_table": (_i, [_u32, _i, C.c_double, _vp]),
     "rtc_graph_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_louvain": (_i, [_vp, _u32, _vp, _u64, C.c_double, _vp, C.POINTER(_u32), C.POINTER(C.c_double)]),
     "rtc_louvain_counters": (_i, [_vp, C.POINTER(_u64)]),

@@ -27,7 +27,7 @@ KDIST_NONE = 0xFFFFFFFF  # neighbour of a point with fewer than minPts - 1 candi
 PLACE_DT = np.dtype([("label", "<i4"), ("label_max", "<i4"), ("n_neighbours", "<u4"), ("n_core", "<u4"), ("nearest", "<u4"),
                      ("common", "<u4"), ("denom", "<u4"), ("flags", "<u4")])
 PLACE_NONE = 0xFFFFFFFF  # nearest of a query that shares no hash with the model
-GEDGE_DT = np.dtype([("u", "<u4"), ("v", "<u4"), ("common", "<u4"), ("pad", "<u4")])  # rtc_gedge
+GEDGE_DT = np.dtype([("u", "<u4"), ("v", "<u4"), ("common", "<u4"), ("pad", "<u4")])  # rtc_gedge; pad: 0 from graph_build, the truncated denom from graph_build_mash (graph_denom reads it)
 QEDGE_DT = np.dtype([("q", "<u4"), ("p", "<u4"), ("common", "<u4"), ("pad", "<u4")])  # rtc_qedge
 NEAR_DT = np.dtype([("nearest", "<u4"), ("common", "<u4"), ("denom", "<u4"), ("n_candidates", "<u4"), ("n_passing", "<u4"),
                     ("n_kept", "<u4")])  # rtc_graph_near; nearest PLACE_NONE: no shared hash
@@ -854,12 +854,33 @@ class Context:
             self.check(st)
             return out[:ne.value].copy()
 
+    def graph_build_mash(self, sk, sketch_size, threshold, kmer_size, knn_k=0, cap=None):
+        """clust-leiden --minhash's similarity graph (rtc_graph_build_mash): GEDGE_DT edges (u < v, common) in (u, v) order over
+        MinHash sketches of at most sketch_size hashes; a pair is an edge iff rtc_mash_distance(common, denom) < threshold, on
+        the union-truncated counts.  The field `pad` holds the truncated denom (graph_denom(edges)).  knn_k and cap as
+        graph_build: the rank is common / denom."""
+        n = sk.n
+        room = max(int(cap) if cap is not None else 16 * n, 1)
+        while True:
+            out = np.zeros(room, dtype=GEDGE_DT)
+            ne = C.c_uint64(0)
+            st = self.lib.rtc_graph_build_mash(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n, int(sketch_size),
+                                               float(threshold), int(kmer_size), int(knn_k), _np_ptr(out), int(cap) if cap is not None else room,
+                                               C.byref(ne))
+            self.graph_edges_needed = int(ne.value)
+            if st == _lib.RTC_ERR_OVERFLOW and cap is None:
+                room = int(ne.value)
+                continue
+            self.check(st)
+            return out[:ne.value].copy()
+
     def graph_counters(self):
-        """rtc_graph_counters as a dict (the last graph_build call)."""
+        """rtc_graph_counters as a dict (the last graph_build or graph_build_mash call; merged: the candidates merged past the
+        prefilter of a MinHash call, 0 after graph_build)."""
         a = (C.c_uint64 * 10)()
         self.check(self.lib.rtc_graph_counters(self.h, a))
-        names = ("chunks", "candidates", "passing", "edges", "nodes_cut", "pair_ns", "filter_ns", "select_ns", "unused", "total_ns")
-        return {k: int(a[i]) for i, k in enumerate(names) if k != "unused"}
+        names = ("chunks", "candidates", "passing", "edges", "nodes_cut", "pair_ns", "filter_ns", "select_ns", "merged", "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
 
     def louvain(self, n, edges, resolution=1.0, return_modularity=False):
         """rtc_louvain: the deterministic Louvain include/rtclust.h defines over n vertices and WEDGE_DT records (u, v, q), q the
@@ -1010,16 +1031,41 @@ def graph_weight(common, size_u, size_v, kmer_size):
     return float(_lib.load().rtc_graph_weight(int(common), int(size_u), int(size_v), int(kmer_size)))
 
 
-def graph_weights(edges, sizes, kmer_size):
-    """WEDGE_DT records of GEDGE_DT edges: q = max(1, llround(weight * 2^20)) of rtc_graph_weight"""
+def _weight_units(edges, weights):
+    """WEDGE_DT records: q = max(1, llround(weight * 2^20))"""
     out = np.zeros(len(edges), dtype=WEDGE_DT)
     out["u"], out["v"] = edges["u"], edges["v"]
-    fn = _lib.load().rtc_graph_weight
-    x = np.array([fn(c, sizes[u], sizes[v], kmer_size) for u, v, c in zip(edges["u"].tolist(), edges["v"].tolist(), edges["common"].tolist())],
-                 dtype=np.float64) * 1048576.0
+    x = np.asarray(weights, dtype=np.float64) * 1048576.0
     low = np.floor(x)  # llround: x - floor(x) is exact, halves go away from zero
     out["q"] = np.maximum(1, low + (x - low >= 0.5)).astype(np.uint32)
     return out
+
+
+def graph_weights(edges, sizes, kmer_size):
+    """WEDGE_DT records of GEDGE_DT edges: q = max(1, llround(weight * 2^20)) of rtc_graph_weight"""
+    fn = _lib.load().rtc_graph_weight
+    return _weight_units(edges, [fn(c, sizes[u], sizes[v], kmer_size)
+                                 for u, v, c in zip(edges["u"].tolist(), edges["v"].tolist(), edges["common"].tolist())])
+
+
+def graph_denom(edges):
+    """the truncated denom of graph_build_mash's edges (rtc_gedge.pad)"""
+    return edges["pad"]
+
+
+def graph_weight_mash(common, denom, sketch_size, kmer_size):
+    """rtc_graph_weight_mash: 1 - rtc_mash_distance(common, denom), the library's host function"""
+    return float(_lib.load().rtc_graph_weight_mash(int(common), int(denom), int(sketch_size), int(kmer_size)))
+
+
+def graph_weights_mash(edges, sketch_size, kmer_size, return_weights=False):
+    """WEDGE_DT records of graph_build_mash's edges: q = max(1, llround(w * 2^20)), w = rtc_graph_weight_mash(common, denom);
+    return_weights: also the doubles w"""
+    fn = _lib.load().rtc_graph_weight_mash
+    w = np.array([fn(c, d, int(sketch_size), int(kmer_size)) for c, d in zip(edges["common"].tolist(), graph_denom(edges).tolist())],
+                 dtype=np.float64)
+    out = _weight_units(edges, w)
+    return (out, w) if return_weights else out
 
 
 def kdist_distance(common, size_p, size_q, kmer_size):

@@ -144,22 +144,26 @@ struct DevBuf {  // hipMalloc'd scratch released on every way out
   }
 };
 
-// A device list of pairs that a filter kernel appends to chunk by chunk, and what the filter has found so far
-struct KeptList {
-  rtc_cedge* d = nullptr;
+// A device list of pairs that a filter kernel appends to chunk by chunk, and what the filter has found so far.  R: the record
+// (rtc_cedge everywhere but in rtc_graph_build_mash, whose 16-byte record carries the truncated denom beside the common).
+template <class R>
+struct KeptListOf {
+  R* d = nullptr;
   uint64_t cap = 0, used = 0, asym = 0, first_asym = ~0ull, asym_levels = 0, ns = 0;
 };
+using KeptList = KeptListOf<rtc_cedge>;
 using FilterKernel = void (*)(const rtc_cedge*, uint64_t, const uint32_t*, EpsLevels, uint32_t, uint32_t, rtc_cedge*, uint64_t, unsigned long long*);
 
 // Room for `need` pairs in the list before a filter runs, so the kernel never runs past it and runs once: doubled while that
 // covers the need, so many row chunks move the list a few times, and the exact size where the doubled list is too small or
 // does not fit.
-int kept_reserve(rtc_ctx* ctx, DevBuf& db, KeptList* L, uint64_t need) {
+template <class R>
+int kept_reserve(rtc_ctx* ctx, DevBuf& db, KeptListOf<R>* L, uint64_t need) {
   if (need <= L->cap) return RTC_OK;
   auto regrow = [&](uint64_t want) -> int {
-    rtc_cedge* nd = nullptr;
+    R* nd = nullptr;
     RTC_TRY(db.get(ctx, want, &nd));
-    if (L->used) RTC_HIP(ctx, hipMemcpyAsync(nd, L->d, L->used * sizeof(rtc_cedge), hipMemcpyDeviceToDevice, ctx->stream));
+    if (L->used) RTC_HIP(ctx, hipMemcpyAsync(nd, L->d, L->used * sizeof(R), hipMemcpyDeviceToDevice, ctx->stream));
     RTC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     db.release(L->d);
     L->d = nd; L->cap = want;

@@ -14,7 +14,11 @@
 //     in the union, which decides whether it lies among the first sketch_size.  Serial (RTC_DBSCAN_MASH_SERIAL=1): every lane
 //     merges its own candidate with rtc_mash_merge, the baseline.  Either way lane k then holds candidate k's counts and the
 //     epilogue is lane-parallel: the counts go to the caller (rtc_pair_mash_edges_dev) or through the tables into the kept list.
+// rtc_graph_build_mash (rtc_graph.hip) runs the same candidates through the same merge with one strict table
+// (mash_tables<true>) and an epilogue of its own: the kept record is a rtc_medge, which carries both counts.
 #pragma once
+#include <type_traits>
+
 #include "rtc_dbscan_common.h"
 #include "rtc_mash_merge.h"
 
@@ -25,17 +29,25 @@ namespace {
 
 constexpr uint32_t MASH_LDS_ELEMS = 1024;  // the second list is staged in LDS up to this length (8 KiB of u64 per wave)
 
+// What rtc_graph_build_mash keeps of a passing pair (i > j): the truncated counts, both of them -- the rank and the weight need
+// the denom, and rtc_cedge has no room for it
+struct rtc_medge { uint32_t i, j, common, denom; };
+
 // cmin[0 .. D] for one eps: least common with distance(common, d) <= eps, d + 1 where there is none.  For a fixed d the
 // distance does not increase with common: j = common / d grows by a relative step of at least 1 / common, far above the
 // rounding of 2j / (1 + j), and the C library's log is monotone.  pass(0) is false (distance 1 > eps) and pass(d) true
 // (distance 0), so the bisection keeps lo failing and hi passing: both sides of the boundary have been evaluated when it ends.
+// STRICT: distance < eps, the edge rule of rtc_graph_build_mash, for 0 < eps <= 1: pass(0) is false (1 < eps never) and pass(d)
+// true (0 < eps), and the argument is the same.
+template <bool STRICT = false>
 inline void mash_cmin_row(uint32_t D, uint32_t sketch_size, int kmer_size, double eps, uint32_t* row) {
   row[0] = 1;  // denom 0: two empty lists, j = 0, distance 1
   for (uint32_t d = 1; d <= D; d++) {
     uint32_t lo = 0, hi = d;
     while (hi - lo > 1) {
       const uint32_t mid = lo + (hi - lo) / 2;
-      if (rtc_mash_distance_host(mid, d, sketch_size, kmer_size) <= eps) hi = mid; else lo = mid;
+      const double dist = rtc_mash_distance_host(mid, d, sketch_size, kmer_size);
+      if (STRICT ? dist < eps : dist <= eps) hi = mid; else lo = mid;
     }
     row[d] = hi;
   }
@@ -96,13 +108,15 @@ __device__ __forceinline__ void mash_merge_wave(const T* __restrict__ a, uint32_
   *denom = u < s ? (uint32_t)u : s;
 }
 
-// One wave per block, 64 candidates per wave and round.  cnt[0]: pairs kept (wave_append), cnt[1]: candidates merged.
-template <typename T, bool SERIAL>
+// One wave per block, 64 candidates per wave and round.  cnt[0]: pairs kept (wave_append), cnt[1]: candidates merged.  R: the
+// kept record -- rtc_cedge with the levels' mask in `common` (rtc_dbscan_mash), or rtc_medge with the counts themselves
+// (rtc_graph_build_mash: one level).
+template <typename T, bool SERIAL, class R>
 __global__ __launch_bounds__(64) void mash_edges_kernel(const T* __restrict__ hashes, const uint64_t* __restrict__ start,
                                                         const uint32_t* __restrict__ len, uint32_t sketch_size,
                                                         const rtc_cedge* __restrict__ cand, uint64_t m, MashParams P,
                                                         uint32_t* __restrict__ common_out, uint32_t* __restrict__ denom_out,
-                                                        rtc_cedge* __restrict__ kept, uint64_t cap, unsigned long long* __restrict__ cnt) {
+                                                        R* __restrict__ kept, uint64_t cap, unsigned long long* __restrict__ cnt) {
   __shared__ T sb[MASH_LDS_ELEMS];
   const uint32_t lane = threadIdx.x;
   for (uint64_t base = (uint64_t)blockIdx.x * 64; base < m; base += (uint64_t)gridDim.x * 64) {  // uniform
@@ -138,14 +152,20 @@ __global__ __launch_bounds__(64) void mash_edges_kernel(const T* __restrict__ ha
       continue;
     }
     if (lane == 0 && todo) atomicAdd(&cnt[1], (unsigned long long)__popcll(todo));
-    uint32_t mask = 0;
-    if (merge) {
-      const uint32_t d = denom < P.D ? denom : P.D;  // denom <= D by construction
-      for (uint32_t l = 0; l < P.n_lv; l++)
-        if (common >= P.cmin[(uint64_t)l * (P.D + 1) + d]) mask |= 1u << l;
+    if constexpr (std::is_same<R, rtc_medge>::value) {
+      bool keep = false;
+      if (merge) keep = common >= P.cmin[denom < P.D ? denom : P.D];  // denom <= D by construction; cmin >= 1: a shared hash among the first s
+      wave_append(keep, rtc_medge{c.i, c.j, common, denom}, kept, cap, &cnt[0]);
+    } else {
+      uint32_t mask = 0;
+      if (merge) {
+        const uint32_t d = denom < P.D ? denom : P.D;  // denom <= D by construction
+        for (uint32_t l = 0; l < P.n_lv; l++)
+          if (common >= P.cmin[(uint64_t)l * (P.D + 1) + d]) mask |= 1u << l;
+      }
+      c.common = mask;
+      wave_append(mask != 0, c, kept, cap, &cnt[0]);
     }
-    c.common = mask;
-    wave_append(mask != 0, c, kept, cap, &cnt[0]);
   }
 }
 
@@ -153,20 +173,21 @@ inline uint32_t mash_blocks(uint64_t m, int num_cu) {
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((m + 63) / 64, (uint64_t)num_cu * 64));
 }
 
-template <bool SERIAL>
+template <bool SERIAL, class R>
 void mash_edges_launch(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t sketch_size,
-                       const rtc_cedge* d_cand, uint64_t m, const MashParams& P, uint32_t* d_common, uint32_t* d_denom, rtc_cedge* d_kept,
+                       const rtc_cedge* d_cand, uint64_t m, const MashParams& P, uint32_t* d_common, uint32_t* d_denom, R* d_kept,
                        uint64_t cap, unsigned long long* d_cnt) {
   const dim3 g(mash_blocks(m, ctx->num_cu)), b(64);
   if (width == 8)
-    hipLaunchKernelGGL((mash_edges_kernel<uint64_t, SERIAL>), g, b, 0, ctx->stream, (const uint64_t*)d_hashes, d_start, d_len, sketch_size, d_cand, m, P,
+    hipLaunchKernelGGL((mash_edges_kernel<uint64_t, SERIAL, R>), g, b, 0, ctx->stream, (const uint64_t*)d_hashes, d_start, d_len, sketch_size, d_cand, m, P,
                        d_common, d_denom, d_kept, cap, d_cnt);
   else
-    hipLaunchKernelGGL((mash_edges_kernel<uint32_t, SERIAL>), g, b, 0, ctx->stream, (const uint32_t*)d_hashes, d_start, d_len, sketch_size, d_cand, m, P,
+    hipLaunchKernelGGL((mash_edges_kernel<uint32_t, SERIAL, R>), g, b, 0, ctx->stream, (const uint32_t*)d_hashes, d_start, d_len, sketch_size, d_cand, m, P,
                        d_common, d_denom, d_kept, cap, d_cnt);
 }
 
-// cmin and smin for the levels of a call, on the device
+// cmin and smin for the levels of a call, on the device (STRICT: mash_cmin_row's)
+template <bool STRICT = false>
 int mash_tables(rtc_ctx* ctx, DevBuf& db, uint32_t sketch_size, uint32_t max_len, int kmer_size, const double* h_eps, uint32_t n_eps,
                 MashTables* T) {
   T->D = (uint32_t)std::min<uint64_t>(sketch_size, 2ull * max_len);
@@ -174,7 +195,7 @@ int mash_tables(rtc_ctx* ctx, DevBuf& db, uint32_t sketch_size, uint32_t max_len
   std::vector<uint32_t> cmin(W * n_eps), smin(W * n_eps);
   for (uint32_t e = 0; e < n_eps; e++) {
     uint32_t* row = cmin.data() + W * e;
-    mash_cmin_row(T->D, sketch_size, kmer_size, h_eps[e], row);
+    mash_cmin_row<STRICT>(T->D, sketch_size, kmer_size, h_eps[e], row);
     uint32_t best = 0xffffffffu;
     for (size_t d = W; d-- > 0;) {
       if (row[d] <= d) best = std::min(best, row[d]);
@@ -191,9 +212,10 @@ int mash_tables(rtc_ctx* ctx, DevBuf& db, uint32_t sketch_size, uint32_t max_len
 
 // One chunk of candidates through the predicate into the kept list: filter_chunk's protocol (the list grown first to hold the
 // whole chunk, one launch) with the recount in the filter's place.  d_fc: cnt[0..1] of mash_edges_kernel.
+template <class R>
 int mash_filter_chunk(rtc_ctx* ctx, DevBuf& db, const char* who, const void* d_hashes, int width, const uint64_t* d_start,
                       const uint32_t* d_len, uint32_t sketch_size, const rtc_cedge* d_cand, uint64_t m, const MashTables& T, uint32_t n_lv,
-                      unsigned long long* d_fc, KeptList* L, uint64_t* merged) {
+                      unsigned long long* d_fc, KeptListOf<R>* L, uint64_t* merged) {
   hipStream_t s = ctx->stream;
   const uint64_t t0 = now_ns();
   RTC_TRY(kept_reserve(ctx, db, L, L->used + m));

@@ -848,9 +848,9 @@ extern "C" int rtc_pair_mash_edges_dev(rtc_ctx* ctx, const void* d_hashes, int w
   RTC_HIP(ctx, hipSetDevice(ctx->device));
   const MashParams P{nullptr, nullptr, 0, 0};
   if (ctx->opt.dbscan_mash_serial)
-    mash_edges_launch<true>(ctx, d_hashes, width, d_start, d_len, sketch_size, d_edges, m, P, d_common, d_denom, nullptr, 0, nullptr);
+    mash_edges_launch<true>(ctx, d_hashes, width, d_start, d_len, sketch_size, d_edges, m, P, d_common, d_denom, (rtc_cedge*)nullptr, 0, nullptr);
   else
-    mash_edges_launch<false>(ctx, d_hashes, width, d_start, d_len, sketch_size, d_edges, m, P, d_common, d_denom, nullptr, 0, nullptr);
+    mash_edges_launch<false>(ctx, d_hashes, width, d_start, d_len, sketch_size, d_edges, m, P, d_common, d_denom, (rtc_cedge*)nullptr, 0, nullptr);
   RTC_CHECK_LAUNCH(ctx);
   return RTC_OK;
 }

@@ -3,7 +3,10 @@
 // list (filter_chunk's protocol), one rocPRIM merge sort by (u, rank, v) with an exact comparator and a segment-position kernel
 // for the per-node top-k, and a final sort by (u, v).  The device forms no distance: the host bisects the least Jaccard value
 // that passes through the very host function (graph_jstar) and the kernel compares one IEEE quotient with it.
-#include "rtc_dbscan_common.h"
+// rtc_graph_build_mash (clust-leiden --minhash) is the same graph over MinHash sketches: the candidates of
+// the same pair phase go through the union-truncated merge of rtc_dbscan_mash.h, the rule is rtc_mash_distance < threshold
+// decided by one host-built table of counts, and the kept record carries (common, denom); kept list, top-k and sorts are shared.
+#include "rtc_dbscan_mash.h"
 
 namespace {
 
@@ -80,20 +83,31 @@ struct RankLess {
     return x.i < y.i;
   }
 };
+// the MinHash graph's rank: common / denom of the truncated merge, both at most sketch_size < 2^32
+struct MashRankLess {
+  __device__ bool operator()(const rtc_medge& x, const rtc_medge& y) const {
+    if (x.j != y.j) return x.j < y.j;
+    const uint64_t l = (uint64_t)x.common * y.denom, r = (uint64_t)y.common * x.denom;
+    if (l != r) return l > r;
+    return x.i < y.i;
+  }
+};
 struct PairLess {
-  __device__ bool operator()(const rtc_cedge& x, const rtc_cedge& y) const { return x.j != y.j ? x.j < y.j : x.i < y.i; }
+  template <class R>
+  __device__ bool operator()(const R& x, const R& y) const { return x.j != y.j ? x.j < y.j : x.i < y.i; }
 };
 
 // The list sorted by RankLess: record idx is kept when fewer than knn_k records of its u come before it.  The segment's start
 // is the lower bound of u in the list.  cnt[0]: kept so far (wave_append), cnt[1]: nodes that lost an edge.
-__global__ __launch_bounds__(256) void graph_topk_kernel(const rtc_cedge* __restrict__ sorted, uint64_t m, uint32_t knn_k,
-                                                         rtc_cedge* __restrict__ out, uint64_t cap, unsigned long long* __restrict__ cnt) {
+template <class R>
+__global__ __launch_bounds__(256) void graph_topk_kernel(const R* __restrict__ sorted, uint64_t m, uint32_t knn_k,
+                                                         R* __restrict__ out, uint64_t cap, unsigned long long* __restrict__ cnt) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   const uint64_t rounds = (m + stride - 1) / stride;
   for (uint64_t r = 0; r < rounds; r++) {
     const uint64_t idx = r * stride + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool keep = false;
-    rtc_cedge c{0, 0, 0};
+    R c{};
     if (idx < m) {
       c = sorted[idx];
       uint64_t lo = 0, hi = idx;  // first record of u: sorted[lo - 1].j < u <= sorted[hi].j
@@ -109,13 +123,13 @@ __global__ __launch_bounds__(256) void graph_topk_kernel(const rtc_cedge* __rest
 }
 
 // *list sorted by `less` into a list of its own; the unsorted one is released
-template <class Less>
-int sort_kept(rtc_ctx* ctx, DevBuf& db, rtc_cedge** list, uint64_t m, Less less) {
+template <class R, class Less>
+int sort_kept(rtc_ctx* ctx, DevBuf& db, R** list, uint64_t m, Less less) {
   if (m < 2) return RTC_OK;
   size_t tb = 0;
-  RTC_HIP(ctx, rocprim::merge_sort(nullptr, tb, (rtc_cedge*)nullptr, (rtc_cedge*)nullptr, (size_t)m, less, ctx->stream));
+  RTC_HIP(ctx, rocprim::merge_sort(nullptr, tb, (R*)nullptr, (R*)nullptr, (size_t)m, less, ctx->stream));
   char* tmp = nullptr;
-  rtc_cedge* d_sorted = nullptr;
+  R* d_sorted = nullptr;
   RTC_TRY(db.get(ctx, tb, &tmp));
   RTC_TRY(db.get(ctx, m, &d_sorted));
   RTC_HIP(ctx, rocprim::merge_sort(tmp, tb, *list, d_sorted, (size_t)m, less, ctx->stream));
@@ -124,6 +138,29 @@ int sort_kept(rtc_ctx* ctx, DevBuf& db, rtc_cedge** list, uint64_t m, Less less)
   db.release(*list);
   *list = d_sorted;
   return RTC_OK;
+}
+
+// The kept list to the call's edges: with knn_k > 0 the sort by `rank` and the position test, then the sort by (u, v).  The
+// list passed in is released or handed on in *d_final.  d_fc: two device counters.
+template <class R, class Rank>
+int select_edges(rtc_ctx* ctx, DevBuf& db, R* d_kept, uint64_t used, uint32_t knn_k, Rank rank, unsigned long long* d_fc, R** d_final,
+                 uint64_t* n_final, uint64_t* cut) {
+  hipStream_t s = ctx->stream;
+  *d_final = d_kept; *n_final = used; *cut = 0;
+  if (knn_k > 0 && used) {
+    RTC_TRY(sort_kept(ctx, db, &d_kept, used, rank));
+    R* d_top = nullptr;
+    RTC_TRY(db.get(ctx, used, &d_top));
+    unsigned long long fc[2] = {0ull, 0ull};
+    RTC_HIP(ctx, hipMemcpyAsync(d_fc, fc, sizeof fc, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(graph_topk_kernel<R>, dim3(blocks_for(used, ctx->num_cu)), dim3(256), 0, s, (const R*)d_kept, used, knn_k, d_top, used, d_fc);
+    RTC_CHECK_LAUNCH(ctx);
+    RTC_HIP(ctx, hipMemcpyAsync(fc, d_fc, sizeof fc, hipMemcpyDeviceToHost, s));
+    RTC_HIP(ctx, hipStreamSynchronize(s));
+    db.release(d_kept);
+    *d_final = d_top; *n_final = fc[0]; *cut = fc[1];
+  }
+  return sort_kept(ctx, db, d_final, *n_final, PairLess{});
 }
 
 }  // namespace
@@ -174,23 +211,9 @@ extern "C" int rtc_graph_build(rtc_ctx* ctx, const void* d_hashes, int width, co
   RTC_TRY(dbscan_pair_chunks(ctx, db, d_hashes, width, d_start, d_len, n, 1, d_cnt, &pp, on_chunk));
 
   const uint64_t t_sel = now_ns();
-  rtc_cedge* d_final = kept.d;
-  uint64_t n_final = kept.used, cut = 0;
-  if (knn_k > 0 && kept.used) {
-    RTC_TRY(sort_kept(ctx, db, &kept.d, kept.used, RankLess{d_len}));
-    rtc_cedge* d_top = nullptr;
-    RTC_TRY(db.get(ctx, kept.used, &d_top));
-    unsigned long long fc[2] = {0ull, 0ull};
-    RTC_HIP(ctx, hipMemcpyAsync(d_cnt + 1, fc, sizeof fc, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(graph_topk_kernel, dim3(blocks_for(kept.used, ctx->num_cu)), dim3(256), 0, s, (const rtc_cedge*)kept.d, kept.used, knn_k,
-                       d_top, kept.used, d_cnt + 1);
-    RTC_CHECK_LAUNCH(ctx);
-    RTC_HIP(ctx, hipMemcpyAsync(fc, d_cnt + 1, sizeof fc, hipMemcpyDeviceToHost, s));
-    RTC_HIP(ctx, hipStreamSynchronize(s));
-    db.release(kept.d);
-    d_final = d_top; n_final = fc[0]; cut = fc[1];
-  }
-  RTC_TRY(sort_kept(ctx, db, &d_final, n_final, PairLess{}));
+  rtc_cedge* d_final = nullptr;
+  uint64_t n_final = 0, cut = 0;
+  RTC_TRY(select_edges(ctx, db, kept.d, kept.used, knn_k, RankLess{d_len}, d_cnt + 1, &d_final, &n_final, &cut));
   const uint64_t t_out = now_ns();
   *h_n_edges = n_final;
   uint64_t* g = ctx->graph;
@@ -206,6 +229,78 @@ extern "C" int rtc_graph_build(rtc_ctx* ctx, const void* d_hashes, int width, co
     RTC_HIP(ctx, hipStreamSynchronize(s));
   }
   for (uint64_t e = 0; e < n_final; e++) h_edges[e] = rtc_gedge{h[e].j, h[e].i, h[e].common, 0};
+  g[9] = now_ns() - t_begin;
+  return RTC_OK;
+}
+
+extern "C" double rtc_graph_weight_mash(uint32_t common, uint32_t denom, uint32_t sketch_size, int kmer_size) {
+  return 1.0 - rtc_mash_distance_host(common, denom, sketch_size, kmer_size);
+}
+
+// rtc_graph_build_mash's table for one threshold, on the host alone: out[d] for d = 0 .. sketch_size
+extern "C" int rtc_graph_mash_table(uint32_t sketch_size, int kmer_size, double threshold, uint32_t* out) {
+  if (!out || sketch_size == 0 || kmer_size < 1 || !(threshold > 0.0) || threshold > 1.0) return RTC_ERR_ARG;
+  mash_cmin_row<true>(sketch_size, sketch_size, kmer_size, threshold, out);
+  return RTC_OK;
+}
+
+extern "C" int rtc_graph_build_mash(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                                    uint32_t sketch_size, double threshold, int kmer_size, uint32_t knn_k, rtc_gedge* h_edges, uint64_t cap,
+                                    uint64_t* h_n_edges) {
+  const char* who = "rtc_graph_build_mash";
+  if (!ctx || !h_n_edges || (n && (!d_hashes || !d_start || !d_len)) || (width != 4 && width != 8) || (cap && !h_edges)) return RTC_ERR_ARG;
+  if (!(threshold > 0.0)) return rtc_fail(ctx, RTC_ERR_ARG, "%s: threshold %g", who, threshold);
+  if (threshold > 1.0)  // pairs without a shared hash have distance 1 and no candidate list holds them
+    return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "%s: threshold %g above 1 would make edges of pairs that share no hash", who, threshold);
+  if (sketch_size == 0) return rtc_fail(ctx, RTC_ERR_ARG, "%s: sketch size 0", who);
+  if (kmer_size < 1) return rtc_fail(ctx, RTC_ERR_ARG, "%s: k-mer size %d", who, kmer_size);
+  if (n >= 0x7fffffffu) return rtc_fail(ctx, RTC_ERR_ARG, "%s: %u points", who, n);
+  *h_n_edges = 0;
+  memset(ctx->graph, 0, sizeof ctx->graph);
+  if (n < 2) return RTC_OK;
+  RTC_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const uint64_t t_begin = now_ns();
+  std::vector<uint32_t> h_len(n);
+  RTC_HIP(ctx, hipMemcpyAsync(h_len.data(), d_len, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  RTC_HIP(ctx, hipStreamSynchronize(s));
+  const uint32_t max_len = *std::max_element(h_len.begin(), h_len.end());
+
+  DevBuf db;
+  MashTables mt;
+  RTC_TRY(mash_tables<true>(ctx, db, sketch_size, max_len, kmer_size, &threshold, 1, &mt));
+  unsigned long long* d_cnt = nullptr;  // [0] pair count, [1..2] the counters of the kernel in flight
+  RTC_TRY(db.get(ctx, 8, &d_cnt));
+  KeptListOf<rtc_medge> kept;
+  kept.cap = std::max<uint64_t>((uint64_t)1 << 16, (uint64_t)n * 16);
+  RTC_TRY(db.get(ctx, kept.cap, &kept.d));
+  PairPhase pp;
+  uint64_t merged = 0;
+  auto on_chunk = [&](const rtc_cedge* d_cand, uint64_t cnt) -> int {
+    if (!cnt) return RTC_OK;
+    return mash_filter_chunk(ctx, db, who, d_hashes, width, d_start, d_len, sketch_size, d_cand, cnt, mt, 1, d_cnt + 1, &kept, &merged);
+  };
+  RTC_TRY(dbscan_pair_chunks(ctx, db, d_hashes, width, d_start, d_len, n, 1, d_cnt, &pp, on_chunk));
+
+  const uint64_t t_sel = now_ns();
+  rtc_medge* d_final = nullptr;
+  uint64_t n_final = 0, cut = 0;
+  RTC_TRY(select_edges(ctx, db, kept.d, kept.used, knn_k, MashRankLess{}, d_cnt + 1, &d_final, &n_final, &cut));
+  const uint64_t t_out = now_ns();
+  *h_n_edges = n_final;
+  uint64_t* g = ctx->graph;
+  g[0] = pp.chunks; g[1] = pp.cand_total; g[2] = kept.used; g[3] = n_final; g[4] = cut;
+  g[5] = pp.pair_ns; g[6] = kept.ns; g[7] = t_out - t_sel; g[8] = merged;
+  if (n_final > cap) {
+    g[9] = now_ns() - t_begin;
+    return rtc_fail(ctx, RTC_ERR_OVERFLOW, "%s: %llu edges, room for %llu", who, (unsigned long long)n_final, (unsigned long long)cap);
+  }
+  std::vector<rtc_medge> h(n_final);
+  if (n_final) {
+    RTC_HIP(ctx, hipMemcpyAsync(h.data(), d_final, n_final * sizeof(rtc_medge), hipMemcpyDeviceToHost, s));
+    RTC_HIP(ctx, hipStreamSynchronize(s));
+  }
+  for (uint64_t e = 0; e < n_final; e++) h_edges[e] = rtc_gedge{h[e].j, h[e].i, h[e].common, h[e].denom};
   g[9] = now_ns() - t_begin;
   return RTC_OK;
 }

@@ -876,7 +876,8 @@ struct Options {
   bool kdist = false;       // clust-dbscan --kdist: the k-distance curve, k = minPts - 1
   bool hierarchy = false;   // clust-dbscan --hierarchy: the density hierarchy below --eps (rtc_dbscan_hierarchy) and its flat clustering
   bool hasMinClusterSize = false;
-  bool minhash = false;     // clust-dbscan --minhash: MinHashDBSCAN over MinHash sketches (rtc_dbscan_mash) instead of --fast
+  bool minhash = false;     // clust-dbscan --minhash: MinHashDBSCAN over MinHash sketches (rtc_dbscan_mash) instead of --fast;
+                            // clust-leiden --minhash: the graph over MinHash sketches (rtc_graph_build_mash) instead of --fast
   bool hasMaxPosting = false;
   int minClusterSize = 0;   // --min-cluster-size (default: --minpts)
   int dbscanKnn = 0;        // clust-dbscan --knn: KssdDBSCAN over the k-NN graph (rtc_dbscan_knn); 0: the run without the flag
@@ -885,6 +886,8 @@ struct Options {
   bool has_resolution = false, louvain = false, leiden = false, has_pregraph = false, saveGraph = false;
   int knn = 0;
   string objective = "cpm";  // --objective, with --leiden: cpm as the reference calls igraph, or modularity
+  bool hasDrlevel = false;
+  string minhashOnly;        // clust-leiden: the first of -s / -c as spelled, which only --minhash gives a meaning
 };
 
 #ifdef LEIDEN_CLUST
@@ -944,10 +947,12 @@ static Options parse(int argc, char** argv) {
     if (a == "--knn") { o.knn = atoi(need(i)); continue; }
     if (a == "--pregraph") { o.folder_path = need(i); o.has_pregraph = true; continue; }
     if (a == "--save-graph") { o.saveGraph = true; continue; }
+    if (a == "--minhash") { o.minhash = true; continue; }
+    if ((a == "-s" || a == "--sketch-size" || a == "-c" || a == "--containment") && o.minhashOnly.empty()) o.minhashOnly = a;
     if (a == "--append" || a == "--save-rep" || a == "--query" ||
         a == "--top-k" || a == "--dense" || a == "--premsted" || a == "--auto-threshold" || a == "--stability" || a == "--dedup-dist" ||
         a == "--reps-per-cluster" || a == "--newick-tree" || a == "--phylip-tree" || a == "--nexus-tree" || a == "--linkage-matrix" ||
-        a == "--buildDB" || a == "-s" || a == "--sketch-size" || a == "-c" || a == "--containment" || a.rfind("--inverted-index", 0) == 0) {
+        a == "--buildDB" || a.rfind("--inverted-index", 0) == 0) {
       fprintf(stderr, "ERROR: unknown option %s\n", a.c_str());
       exit(1);
     }
@@ -1007,7 +1012,7 @@ static Options parse(int argc, char** argv) {
     else if (a == "--assign") o.db_assign = true;
     else if (a == "--stats") o.db_stats = true;
     else if (a == "--top-k") { o.topk = atoi(need(i)); o.has_topk = true; }
-    else if (a == "--drlevel") o.drlevel = atoi(need(i));
+    else if (a == "--drlevel") { o.drlevel = atoi(need(i)); o.hasDrlevel = true; }
     else if (a == "--gpus") o.gpus = need(i);
 #ifndef GREEDY_CLUST
     else if (a == "--dense") o.dense = true;
@@ -1033,10 +1038,16 @@ static Options parse(int argc, char** argv) {
 #ifdef GREEDY_CLUST
       puts("clust-greedy (MI355X build): greedy incremental clustering module");
 #elif defined(LEIDEN_CLUST)
-      puts("clust-leiden (MI355X build): graph-based community detection (Leiden, Louvain) clustering module, KSSD sketches (--fast)");
+      puts("clust-leiden (MI355X build): graph-based community detection (Leiden, Louvain) clustering module, KSSD sketches (--fast)\n"
+           "or MinHash sketches (--minhash)");
       puts("  -t,--threads N  -m,--min-length N  -k,--kmer-size N (default 19)  -l,--list  -e,--no-save  -d,--threshold X (default 0.05:\n"
-           "  a pair is an edge when its distance is below it)  -o,--output FILE  -i,--input FILE  --presketched DIR  --fast (required)\n"
-           "  --drlevel N  --gpus all|N|i,j,.. (sketching on every GPU, graph and clustering on the first)\n"
+           "  a pair is an edge when its distance is below it)  -o,--output FILE  -i,--input FILE  --presketched DIR\n"
+           "  --fast | --minhash (one of the two is required)  --drlevel N (--fast)\n"
+           "  --gpus all|N|i,j,.. (sketching on every GPU, graph and clustering on the first)\n"
+           "  --minhash (instead of --fast: MinHash sketches as clust-mst makes and saves them, -k / -s,--sketch-size / -m and the\n"
+           "             tuner as there, or a MinHash --presketched DIR, k and s from it; a pair is an edge when MinHash::distance()\n"
+           "             on the union-truncated counts is below -d, 0 < d <= 1, with no size-ratio rule; --knn ranks by common / denom;\n"
+           "             not with --fast, -c, --drlevel or --db)\n"
            "  --leiden | --louvain (one of the two is required; they exclude each other)  --resolution X (default 1.0; higher: more\n"
            "  clusters)\n"
            "  --leiden: the deterministic Leiden of include/rtclust.h (move phase, refinement into connected well-connected pieces,\n"
@@ -1049,7 +1060,8 @@ static Options parse(int argc, char** argv) {
            "           with --leiden; 1..9: 50 with a warning, as the reference defaults it, so the filter cannot be switched off)\n"
            "  --save-graph (leiden.graph into the sketch folder: 'n m', then 'u v weight' per edge; the weights carry 6 significant\n"
            "                digits, so a --pregraph run is defined on the file's weights, not on the sketches')\n"
-           "  --pregraph DIR (DIR/leiden.graph and the KSSD sketches of DIR: the clustering alone, for another --resolution)\n"
+           "  --pregraph DIR (DIR/leiden.graph and the KSSD sketches of DIR -- with --minhash its MinHash sketches: the clustering\n"
+           "                  alone, for another --resolution)\n"
            "  --db FILE --build (with the flags above: the run as without --db, then the model -- labels, community totals, the\n"
            "                     run's parameters and quantisation, genome records and all sketches -- into FILE; not with --pregraph)\n"
            "  --db FILE --assign (-l -i LIST | -i FASTA) -o assign.tsv (new genomes placed into the model's communities on the GPU:\n"
@@ -2518,6 +2530,14 @@ int main(int argc, char** argv) {
 #ifdef LEIDEN_CLUST
   // ---- clust-leiden: the checks of src/main.cpp:391-477 in that order, all before any GPU context exists (the default
   // threshold 0.05 is set above, as for every command) ----
+  // ---- clust-leiden --minhash: this build's own flag, what it excludes named first.  -s and -c mean something beside it alone
+  if (!o.minhash && !o.minhashOnly.empty()) { fprintf(stderr, "ERROR: unknown option %s\n", o.minhashOnly.c_str()); return 1; }
+  if (o.minhash) {
+    const char* bad = o.is_fast ? "--fast (the two sketch kinds exclude each other)" : o.isContainment ? "-c/--containment" : o.hasDrlevel ? "--drlevel"
+                      : !o.repdb_path.empty() ? "--db (models of MinHash sketches are out of scope)" : nullptr;
+    if (bad) { cerr << "ERROR: --minhash does not go with " << bad << endl; return 1; }
+    if (!(o.threshold > 0.0 && o.threshold <= 1.0)) { cerr << "ERROR: --minhash needs 0 < -d/--threshold <= 1, got " << o.threshold << endl; return 1; }
+  }
   // ---- clust-leiden --db: the model file's flows, their flag errors first ----
   LeidenModel ld_model;
   {
@@ -2570,14 +2590,16 @@ int main(int argc, char** argv) {
   vector<double> pregraph_weights;
   if (o.has_pregraph) {
     cerr << "-----Clustering from pre-built graph (fast resolution adjustment)" << endl;
-    o.has_presketched = true;  // the KSSD sketches of the folder name the genomes (clust_from_pregraph_leiden, src/sub_command.cpp:3200-3225)
-    o.is_fast = true;
+    // the sketches of the folder name the genomes (clust_from_pregraph_leiden, src/sub_command.cpp:3200-3225): KSSD ones, with
+    // --minhash the MinHash ones
+    o.has_presketched = true;
+    o.is_fast = !o.minhash;
     o.saveGraph = false;
-  } else if (!o.is_fast) {
+  } else if (!o.is_fast && !o.minhash) {
     cerr << "ERROR: clust-leiden requires --fast option" << endl;
     return 1;
   } else if (!o.has_presketched) {
-    if (!o.isSetKmer) { o.kmerSize = 19; cerr << "-----use default kmerSize: " << o.kmerSize << endl; }
+    if (!o.isSetKmer) { o.kmerSize = 19; cerr << "-----use default kmerSize: " << o.kmerSize << endl; }  // as clust-dbscan, --minhash included
     if (o.drlevel < 0 || o.drlevel > 8) { cerr << "ERROR: invalid drlevel " << o.drlevel << ", should be in [0, 8]" << endl; return 1; }
   }
   if (o.saveGraph && o.noSave && !o.has_presketched) { cerr << "ERROR: --save-graph writes into the sketch folder, which -e/--no-save leaves out" << endl; return 1; }
@@ -3068,16 +3090,24 @@ int main(int argc, char** argv) {
     weights.swap(pregraph_weights);
     cerr << "-----Loaded graph: " << n_nodes << " nodes, " << wedges.size() << " edges" << endl;
   } else {
+    if (o.minhash && mh.isContainment) { cerr << "ERROR: --minhash: " << folder_path << " holds containment sketches (-c), which are out of scope" << endl; return 1; }
     DeviceSketches ds;
     if (rs.ok) resident_sketches(ctx, gpus[0], rs, nullptr, ds);
+    else if (o.minhash) upload_sketches(ctx, &mh.hashes, nullptr, ds);
     else upload_sketches(ctx, ks.use64 ? &ks.h64 : nullptr, ks.use64 ? nullptr : &ks.h32, ds);
-    cerr << "-----Building similarity graph..." << endl;
+    cerr << "-----Building similarity graph" << (o.minhash ? " (MinHash)" : "") << "..." << endl;
     vector<rtc_gedge> edges((size_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_nodes * (uint64_t)o.knn, (uint64_t)16 * n_nodes)));
     uint64_t n_edges = 0;
-    int st = rtc_graph_build(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, o.threshold, kmer_size, (uint32_t)o.knn, edges.data(), edges.size(), &n_edges);
+    auto build = [&]() {  // --minhash: the edge rule and the rank on MinHash::distance()'s (common, denom)
+      return o.minhash ? rtc_graph_build_mash(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, (uint32_t)mh.sketchSize, o.threshold, kmer_size,
+                                              (uint32_t)o.knn, edges.data(), edges.size(), &n_edges)
+                       : rtc_graph_build(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, o.threshold, kmer_size, (uint32_t)o.knn, edges.data(),
+                                         edges.size(), &n_edges);
+    };
+    int st = build();
     if (st == RTC_ERR_OVERFLOW) {  // the count is known now
       edges.resize(n_edges);
-      st = rtc_graph_build(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, o.threshold, kmer_size, (uint32_t)o.knn, edges.data(), edges.size(), &n_edges);
+      st = build();
     }
     CHECK(ctx, st);
     edges.resize(n_edges);
@@ -3085,15 +3115,21 @@ int main(int argc, char** argv) {
     rtc_graph_counters(ctx, gc);
     cerr << "-----Comparisons: " << gc[1] << endl;
     cerr << "-----Edges created: " << n_edges << endl;
+    if (getenv("RTC_VERBOSE") && o.minhash)
+      fprintf(stderr, "[minhash] %llu candidate edges in %llu chunk(s), %llu merged, %llu passing, %llu edges; pair %.3f ms, filter + merge %.3f ms, "
+              "select %.3f ms\n", (unsigned long long)gc[1], (unsigned long long)gc[0], (unsigned long long)gc[8], (unsigned long long)gc[2],
+              (unsigned long long)gc[3], gc[5] / 1e6, gc[6] / 1e6, gc[7] / 1e6);
     vector<uint32_t> sizes(n_nodes);
     CHECK(ctx, rtc_copy_d2h(ctx, sizes.data(), ds.d_len, (size_t)n_nodes * 4));
     weights.resize(n_edges);
     wedges.resize(n_edges);
     for (uint64_t e = 0; e < n_edges; e++) {
-      weights[e] = rtc_graph_weight(edges[e].common, sizes[edges[e].u], sizes[edges[e].v], kmer_size);
+      weights[e] = o.minhash ? rtc_graph_weight_mash(edges[e].common, edges[e].pad, (uint32_t)mh.sketchSize, kmer_size)
+                             : rtc_graph_weight(edges[e].common, sizes[edges[e].u], sizes[edges[e].v], kmer_size);
       wedges[e] = rtc_wedge{edges[e].u, edges[e].v, leiden_weight_units(weights[e])};
     }
     g_metrics.num("leiden_graph_s", gc[9] / 1e9);
+    g_metrics.num("leiden_graph_merged", (double)gc[8]);
     if (o.saveGraph) {
       const string graph_file = folder_path + "/leiden.graph";
       if (!save_leiden_graph(graph_file, n_nodes, edges, weights)) return 1;

@@ -13,7 +13,14 @@ With --assign M it holds M genomes of the set out, builds the model on the rest 
 Context.leiden_place); it prints the three times, the best of --repeat warm calls each, beside the time of the full run over
 all genomes (graph_build plus the clustering call), and how many held-out genomes came back to the community of their family.
 
-    python tools/run_leiden.py --families 200 --per-family 12 --assign 200 [--leiden --objective modularity] [--threads 16]"""
+    python tools/run_leiden.py --families 200 --per-family 12 --assign 200 [--leiden --objective modularity] [--threads 16]
+
+With --minhash the genomes are sketched with MinHash (-k 21, --sketch-size hashes) and the graph is clust-leiden --minhash's
+(Context.graph_build_mash): it prints the graph's counter set (the call with the least whole-call time of --repeat warm calls)
+and Louvain's, and beside them the counters of Context.dbscan_mash on the same sketches at eps = --threshold (min_pts 2), whose
+pair phase and merge kernel the graph shares.
+
+    python tools/run_leiden.py --minhash [--sketch-size 1000] [--threshold 0.05] [--knn 1000]"""
 import argparse
 import json
 import os
@@ -38,7 +45,11 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--assign", type=int, default=0, metavar="M")
     ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--minhash", action="store_true")
+    ap.add_argument("--sketch-size", type=int, default=1000)
     a = ap.parse_args()
+    if a.minhash and (a.leiden or a.assign):
+        ap.error("--minhash prints the graph's and Louvain's counters alone")
     from rabbittclust_amd import api, host
     ctx = api.Context(0)
     desc = api.synth_family_descs(a.families, a.per_family, global_seed=11)
@@ -46,6 +57,8 @@ def main():
     off = np.arange(n + 1, dtype=np.uint64) * a.length
     seq = ctx.synth_genomes(desc, off)
     kmer = 21
+    if a.minhash:
+        return minhash(ctx, a, seq, off, kmer, n)
     sk = ctx.sketch_kssd(seq, off, host.generate_shuffle_dim(6), kmer_size=kmer, drlevel=3)
     ctx.sync()
     sizes = sk.len.cpu().numpy().tolist()
@@ -69,6 +82,32 @@ def main():
                     "louvain_call_ms": min(louvain_ns[1:]) / 1e6, "leiden_call_ms": min(leiden_ns[1:]) / 1e6})
     if a.assign:
         out["assign"] = assign(ctx, a, sk, kmer, n)
+    print(json.dumps(out))
+
+
+def minhash(ctx, a, seq, off, kmer, n):
+    from rabbittclust_amd import api
+    sk = ctx.sketch_minhash(seq, off, k=kmer, size=a.sketch_size)
+    ctx.sync()
+    graph = None
+    for i in range(a.repeat + 1):  # the first call warms up
+        edges = ctx.graph_build_mash(sk, a.sketch_size, a.threshold, kmer, a.knn)
+        c = ctx.graph_counters()
+        if i and (graph is None or c["total_ns"] < graph["total_ns"]):
+            graph = c
+    rec = api.graph_weights_mash(edges, a.sketch_size, kmer)
+    _, modularity = ctx.louvain(n, rec, a.resolution, return_modularity=True)
+    out = {"sketch": "minhash", "sketch_size": a.sketch_size, "genomes": n, "edges": int(len(edges)), "clusters": ctx.louvain_clusters,
+           "modularity": modularity, "graph": graph, "louvain": ctx.louvain_counters(),
+           "graph_ms": {k[:-3]: graph[k] / 1e6 for k in ("pair_ns", "filter_ns", "select_ns", "total_ns")}}
+    if a.threshold < 1.0:
+        best = None
+        for i in range(a.repeat + 1):
+            ctx.dbscan_mash(sk, a.sketch_size, [a.threshold], 2, kmer)
+            c = ctx.dbscan_mash_counters()
+            if i and (best is None or c["total_ns"] < best["total_ns"]):
+                best = c
+        out["dbscan_mash"] = best
     print(json.dumps(out))
 
 
