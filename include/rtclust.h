@@ -919,6 +919,54 @@ int rtc_leiden_place_counters(const rtc_ctx* ctx, uint64_t out[10]);
  * workgroup (up to 2 048), bit 2 the table in global memory (longer rows). */
 int rtc_leiden_place_last_path(const rtc_ctx* ctx);
 
+/* ---- clust-mst --linkage complete: complete linkage inside the single-linkage clusters ------------------------- */
+/* clust-mst is single linkage: a chain of close pairs ends in one cluster whose far ends may be far apart.  Complete linkage inside
+ * each of its clusters gives a diameter instead: every two members of a result cluster are within the threshold.  The Mash
+ * distance is monotone in the Jaccard quotient and complete linkage takes only minima and maxima, so the device works on exact
+ * rationals and forms no distance; this is the definition (tests/reflinkage.py restates it).
+ *
+ * Key of a pair.  kappa(u, v) = common / denom, common as rtc_pair_common_dev reports it, denom = |u| + |v| - common: the
+ *     set-Jaccard of the index path.  A record is rtc_lkey {common, denom}.  Keys are compared exactly, common_x denom_y against
+ *     common_y denom_x in 64 bits; denom == 0 (two empty sketches) counts as kappa = 0.
+ * Agglomeration of one set of m points, given its symmetric m x m key matrix (the diagonal is ignored).  Every point starts as a
+ *     cluster named by its index.  K(X, Y) is the minimum key over the pairs between X and Y in the order kappa ascending, then
+ *     denom ascending (the reported counts are unique).  Each step takes the active pair (a, b), a < b, with the largest
+ *     kappa(K(a, b)), ties to the smallest a, then the smallest b.  If that kappa is 0 or below the stop bound kmin_num / kmin_den
+ *     (cross-multiplied; 0 / 1: no bound) the agglomeration ends.  Otherwise the step emits rtc_lmerge {a, b, common, denom,
+ *     size}, size the member count of the new cluster; K(a, c) = min(K(a, c), K(b, c)) for every other active c, b is retired
+ *     and the cluster keeps the name a.  At most m - 1 merges, in step order.
+ * The cut is the host's: rtc_linkage_distance gives a merge the distance of its key through the function that weighs the MST's
+ *     edges (same expression order), and a component's merges apply in order up to, not including, the first whose distance is
+ *     > threshold.  Minimum keys never grow from step to step, so the cut is where a bound at or below the true one stops.
+ *
+ * Two kernel paths, each a component's whole dendrogram in one launch: m <= 64 one wave with the matrix in LDS, m > 64 one
+ * 256-lane workgroup with the matrix in global memory.  Nothing is summed: the merge list depends on neither. */
+typedef struct { uint32_t common, denom; } rtc_lkey;
+typedef struct { uint32_t a, b, common, denom, size; } rtc_lmerge;
+/* One matrix that is already on the device: d_key[i * ld + j], 8-byte aligned, ld >= m; it is read and overwritten.
+ * h_merges[m - 1], *h_n_merges their number.  kmin_den == 0, ld < m, m >= 2^31 - 1, NULLs: RTC_ERR_ARG.  Synchronous. */
+int rtc_linkage_dev(rtc_ctx* ctx, uint32_t m, rtc_lkey* d_key, uint64_t ld, uint32_t kmin_num, uint32_t kmin_den,
+                    rtc_lmerge* h_merges, uint32_t* h_n_merges);
+/* Every component of a labelling of n sketches.  h_comp[g] is the component of genome g, any labelling; components are numbered
+ * in order of their smallest member and their members taken in ascending genome order.  The key blocks of the components are
+ * filled from rtc_pair_common_dev over row bands and agglomerated in batches under a byte budget (RTC_LINKAGE_BYTES, default half
+ * the free HBM).  h_merges[cap]: the merges of component 0, then 1, ..., a and b as genome indices; *h_n_merges their number;
+ * h_first[c] is where component c's merges start, h_first[n_comp] == *h_n_merges -- room for n_comp + 1 entries, n + 1 always
+ * suffices.  Components of one member cost nothing.
+ * A component whose 8 m^2 bytes and one band exceed the budget: RTC_ERR_NOMEM, the message naming m and the bytes; no fallback.
+ * More merges than cap: RTC_ERR_OVERFLOW with the needed count in *h_n_merges (h_first is complete then).  width not 4 or 8,
+ * NULLs, n >= 2^31 - 1, kmin_den == 0: RTC_ERR_ARG.  Synchronous. */
+int rtc_linkage_complete(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                         const uint32_t* h_comp, uint32_t kmin_num, uint32_t kmin_den, rtc_lmerge* h_merges, uint64_t cap,
+                         uint64_t* h_n_merges, uint64_t* h_first);
+/* The last rtc_linkage_complete (or rtc_linkage_dev): out[0] components agglomerated (m >= 2), out[1] wave-path components,
+ * out[2] workgroup-path components, out[3] merges, out[4] row rescans (rows whose best was looked for again after a merge),
+ * out[5] batches, out[6] fill ns, out[7] agglomeration ns, out[8] largest m, out[9] whole call ns. */
+int rtc_linkage_counters(const rtc_ctx* ctx, uint64_t out[10]);
+/* The distance of a key: 1 for kappa = 0, 0 for kappa = 1, otherwise -ln(2j / (1 + j)) / kmer_size, j = common / denom in double,
+ * with the host's libm; denom up to 2^31 - 1, the range of the MST's own weights.  Host only. */
+double rtc_linkage_distance(uint32_t common, uint32_t denom, int kmer_size);
+
 #ifdef __cplusplus
 }
 #endif

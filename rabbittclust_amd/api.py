@@ -34,6 +34,8 @@ NEAR_DT = np.dtype([("nearest", "<u4"), ("common", "<u4"), ("denom", "<u4"), ("n
 PLACEMENT_DT = np.dtype([("label", "<i4"), ("runner_up", "<i4"), ("n_edges", "<u4"), ("n_comms", "<u4"), ("k_x", "<u8"), ("e_label", "<u8"),
                          ("e_runner", "<u8")])  # rtc_leiden_placement
 WEDGE_DT = np.dtype([("u", "<u4"), ("v", "<u4"), ("q", "<u4")])  # rtc_wedge
+LKEY_DT = np.dtype([("common", "<u4"), ("denom", "<u4")])  # rtc_lkey
+LMERGE_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("common", "<u4"), ("denom", "<u4"), ("size", "<u4")])  # rtc_lmerge
 HEDGE_DT = np.dtype([("p", "<u4"), ("q", "<u4"), ("common", "<u4"), ("size_p", "<u4"), ("size_q", "<u4")])  # rtc_hedge
 
 
@@ -923,6 +925,51 @@ class Context:
         names = ("iterations", "levels", "move_rounds", "moves", "refine_rounds", "merges", "rejected", "move_ns", "refine_ns", "total_ns")
         return {k: int(a[i]) for i, k in enumerate(names)}
 
+    def linkage(self, keys, kmin=(0, 1)):
+        """rtc_linkage_dev: the complete-linkage agglomeration include/rtclust.h defines over one symmetric m x m key matrix --
+        an array [m, m, 2] of (common, denom), or LKEY_DT [m, m] -- uploaded for the call.  kmin: the stop bound (num, den),
+        (0, 1) none.  Returns LMERGE_DT records (a, b, common, denom, size) in step order, a and b as matrix indices."""
+        k = np.ascontiguousarray(keys)
+        if k.dtype == LKEY_DT:
+            k = k.view(np.uint32).reshape(k.shape + (2,))
+        k = np.ascontiguousarray(k, dtype=np.uint32)
+        m = int(k.shape[0])
+        if k.ndim != 3 or k.shape[1] != m or k.shape[2] != 2:
+            raise ValueError("keys must be [m, m, 2]")
+        d = torch.from_numpy(k.view(np.int32).reshape(-1).copy()).to(self.device) if m else torch.zeros(2, dtype=torch.int32, device=self.device)
+        out = np.zeros(max(m - 1, 1), dtype=LMERGE_DT)
+        nm = C.c_uint32(0)
+        self.check(self.lib.rtc_linkage_dev(self.h, m, _t_ptr(d), m, int(kmin[0]), int(kmin[1]), _np_ptr(out), C.byref(nm)))
+        return out[:nm.value].copy()
+
+    def linkage_complete(self, sk, comp, kmin=(0, 1), cap=None):
+        """rtc_linkage_complete: the agglomeration inside every component of the labelling comp[g] of sk's sketches (any labels;
+        components are numbered by their smallest member).  Returns (merges, first): LMERGE_DT records with a and b as genome
+        indices, component after component, and first[c] where component c's merges start (len(first) - 1 components).  cap:
+        room for the merges (None: n - 1, which always suffices); too small raises RTC_ERR_OVERFLOW, the needed count in
+        self.linkage_merges_needed."""
+        n = sk.n
+        lab = np.ascontiguousarray(np.asarray(comp).astype(np.int64).astype(np.uint32))
+        if lab.shape != (n,):
+            raise ValueError("comp must hold one label per sketch")
+        room = max(n - 1, 1) if cap is None else int(cap)
+        out = np.zeros(max(room, 1), dtype=LMERGE_DT)
+        first = np.zeros(n + 1, dtype=np.uint64)
+        nm = C.c_uint64(0)
+        st = self.lib.rtc_linkage_complete(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n, _np_ptr(lab),
+                                           int(kmin[0]), int(kmin[1]), _np_ptr(out), room, C.byref(nm), _np_ptr(first))
+        self.linkage_merges_needed = int(nm.value)
+        self.check(st)
+        return out[:nm.value].copy(), first[:len(np.unique(lab)) + 1].copy()
+
+    def linkage_counters(self):
+        """rtc_linkage_counters as a dict (the last linkage or linkage_complete call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_linkage_counters(self.h, a))
+        names = ("components", "wave_components", "workgroup_components", "merges", "rescans", "batches", "fill_ns", "agglomerate_ns",
+                 "largest_m", "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
     def graph_query(self, sk, n_db, threshold, kmer_size, knn_k=0, query_chunk=0, cap=None):
         """clust-leiden --db --assign, first call (rtc_graph_query): sk holds the n_db model genomes, then the queries.  Returns
         (edges, near): QEDGE_DT records (q, p, common) in (q, p) order -- every query's knn_k best model genomes among those
@@ -1066,6 +1113,18 @@ def graph_weights_mash(edges, sketch_size, kmer_size, return_weights=False):
                  dtype=np.float64)
     out = _weight_units(edges, w)
     return (out, w) if return_weights else out
+
+
+def linkage_distance(common, denom, kmer_size):
+    """rtc_linkage_distance: the distance the host gives a complete-linkage merge of key common / denom"""
+    return float(_lib.load().rtc_linkage_distance(int(common), int(denom), int(kmer_size)))
+
+
+def linkage_bound(threshold, kmer_size):
+    """the conservative stop bound (num, den) clust-mst --linkage complete passes: J = 1 / (2 exp(k d) - 1), times (1 - 2^-20),
+    as floor(J 2^31) / 2^31"""
+    j = 1.0 / (2.0 * np.exp(float(kmer_size) * float(threshold)) - 1.0) * (1.0 - 2.0 ** -20)
+    return (int(np.floor(j * 2147483648.0)) if j > 0 else 0, 1 << 31)
 
 
 def kdist_distance(common, size_p, size_q, kmer_size):

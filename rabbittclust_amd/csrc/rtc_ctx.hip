@@ -100,6 +100,8 @@ void rtc_options_from_env(rtc_options* o) {
   o->dedup_gpu = (int)num("RTC_DEDUP_GPU", 1);
   o->dbscan_mash_serial = flag("RTC_DBSCAN_MASH_SERIAL");
   o->dbscan_mash_noprefilter = flag("RTC_DBSCAN_MASH_NOPREFILTER");
+  o->linkage_span = (uint32_t)std::min<long long>(std::max<long long>(0, num("RTC_LINKAGE_SPAN", 0)), 262140);
+  if (const char* e = getenv("RTC_LINKAGE_BYTES")) o->linkage_bytes = std::max<uint64_t>(strtoull(e, nullptr, 10), 1);
 }
 
 extern "C" {

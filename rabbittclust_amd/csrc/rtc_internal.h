@@ -36,6 +36,8 @@ struct rtc_options {
   int dedup_gpu = 1;               // RTC_DEDUP_GPU: 0 never, 1 groups from the measured cutoff up, 2 every group of two or more
   int dbscan_mash_serial = 0;      // RTC_DBSCAN_MASH_SERIAL: the per-thread merge instead of the wave-cooperative one
   int dbscan_mash_noprefilter = 0;  // RTC_DBSCAN_MASH_NOPREFILTER: every candidate is merged
+  uint32_t linkage_span = 0;       // RTC_LINKAGE_SPAN: the rows of a band that small components share in the fill (0: default)
+  uint64_t linkage_bytes = 0;      // RTC_LINKAGE_BYTES: the byte budget of a batch of rtc_linkage_complete (0: half the free HBM)
 };
 void rtc_options_from_env(rtc_options* o);
 
@@ -96,6 +98,7 @@ struct rtc_ctx {
   uint64_t graph_query[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // rtc_graph_query_counters (include/rtclust.h lists them)
   uint64_t leiden_place[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_leiden_place_counters (include/rtclust.h lists them)
   int leiden_place_path = 0;  // rtc_leiden_place_last_path
+  uint64_t linkage[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_linkage_counters (include/rtclust.h lists them)
   int host_threads = 1;     // rtc_ctx_set_host_threads: the host side of rtc_tree_medoids
   // rtc_diag_counters: [0] pair tiles the join took, [1] tiled-kernel tiles, [2] merge-kernel tiles, [3] candidate lists contracted
   // to their forest, [4] greedy runs replayed from ONE global join, [5] greedy query blocks of the block loop, [6] estimates handed

@@ -390,6 +390,12 @@ double rtc_mash_distance_host(uint32_t common, uint32_t denom, uint32_t sketch_s
   return host_mst_distance((int)common, (int)denom, (int)common, kmer_size, 2 | (int)(sketch_size << 2));
 }
 
+// rtc_linkage_distance: the distance of a key common / denom of the complete-linkage refinement, through the function that weighs
+// the MST's edges on the index path (sizes (denom, common) give its set-Jaccard the denominator denom + common - common)
+extern "C" double rtc_linkage_distance(uint32_t common, uint32_t denom, int kmer_size) {
+  return host_mst_distance((int)common, (int)denom, (int)common, kmer_size, 0);
+}
+
 // the union step of a round (hook + relabel + the counter read back): rtc_boruvka_union_dev and the multi-GPU rounds
 static int boruvka_union_round(rtc_ctx* ctx, uint32_t n, const RoundKeys& K, uint32_t* d_comp, uint32_t* d_succ, rtc_cedge* d_sel,
                                uint64_t* d_nsel, uint32_t* h_added) {

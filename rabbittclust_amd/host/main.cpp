@@ -888,6 +888,7 @@ struct Options {
   string objective = "cpm";  // --objective, with --leiden: cpm as the reference calls igraph, or modularity
   bool hasDrlevel = false;
   string minhashOnly;        // clust-leiden: the first of -s / -c as spelled, which only --minhash gives a meaning
+  bool linkageComplete = false;  // clust-mst --linkage complete: complete linkage inside every cluster (rtc_linkage_complete)
 };
 
 #ifdef LEIDEN_CLUST
@@ -1034,6 +1035,12 @@ static Options parse(int argc, char** argv) {
     else if (a == "--dedup-dist") o.dedupDist = atof(need(i));
     else if (a == "--reps-per-cluster") o.repsPerCluster = atoi(need(i));
 #endif
+#if !defined(GREEDY_CLUST) && !defined(DBSCAN_CLUST) && !defined(LEIDEN_CLUST)
+    else if (a == "--linkage") {
+      if (strcmp(need(i), "complete") != 0) { fprintf(stderr, "ERROR: --linkage must be complete\n"); exit(1); }
+      o.linkageComplete = true;
+    }
+#endif
     else if (a == "-h" || a == "--help") {
 #ifdef GREEDY_CLUST
       puts("clust-greedy (MI355X build): greedy incremental clustering module");
@@ -1111,6 +1118,8 @@ static Options parse(int argc, char** argv) {
            "  --premsted DIR  --append LIST (with --presketched/--premsted DIR)\n"
            "  --auto-threshold  --stability  --dedup-dist D  --reps-per-cluster K (with --fast: <output>.dedup / .reps)\n"
            "  --save-rep (mst_cluster_state.bin beside the sketches; a later --append measures against its representatives)\n"
+           "  --linkage complete (complete linkage inside every cluster of the run: <output>.complete, where every two members of\n"
+           "             a cluster are within -d, and <output>.complete.linkage.txt; with --fast or MinHash on the index path)\n"
            "  [--fast] --db FILE --build|--query|--assign|--append LIST|--stats [--top-k N] (MST representative database)"
 #else
            "  --append LIST (with --presketched DIR)  --save-rep (cluster_state.bin beside the sketches)\n"
@@ -1211,6 +1220,82 @@ static void write_trees(const Options& o, const vector<GenomeInfo>& genomes, con
   if (o.nexus) { const string f = o.outputFile + ".nexus.tree"; print_nexus_tree(genomes, mst, byFile, f); cerr << "-----write the NEXUS tree into: " << f << endl; }
   if (o.linkage) { const string f = o.outputFile + ".linkage.txt"; print_linkage_matrix((int)genomes.size(), mst, f); cerr << "-----write the linkage matrix into: " << f << endl; }
 }
+
+#if !defined(GREEDY_CLUST) && !defined(DBSCAN_CLUST) && !defined(LEIDEN_CLUST)
+// --linkage complete: complete linkage inside every cluster of the plain run (include/rtclust.h has the definition).  The device
+// hands back every component's merges on exact keys; the host gives each its distance through the function that weighs the
+// MST's edges and applies a component's merges up to, not including, the first one past the threshold (generate_forest's <=).
+// <base>.complete: the refined clusters in print_result's layout, by smallest member; <base>.complete.linkage.txt: the kept
+// merges as print_linkage_matrix writes them, leaves as genome indices, new ids N, N + 1, ... in file order.
+static void linkage_complete_and_print(rtc_ctx* ctx, const DeviceSketches& ds, const vector<vector<int>>& clusters, const vector<GenomeInfo>& genomes,
+                                       bool sketchByFile, const string& base, double threshold, int kmer_size) {
+  const uint32_t n = (uint32_t)genomes.size();
+  vector<uint32_t> comp(n, 0);
+  for (size_t c = 0; c < clusters.size(); c++) for (int g : clusters[c]) comp[g] = (uint32_t)c;
+  // the stop bound: conservative, any bound at or below the true one gives the same cut
+  const double j = 1.0 / (2.0 * exp((double)kmer_size * threshold) - 1.0) * (1.0 - 1.0 / 1048576.0);
+  const double jn = floor(j * 2147483648.0);
+  const uint32_t kmin_num = !(jn > 0.0) ? 0u : jn >= 2147483648.0 ? 2147483648u : (uint32_t)jn;
+  vector<rtc_lmerge> merges(n > 1 ? n - 1 : 1);
+  vector<uint64_t> first((size_t)n + 1, 0);
+  uint64_t n_merges = 0;
+  CHECK(ctx, rtc_linkage_complete(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, n, comp.data(), kmin_num, 2147483648u, merges.data(), merges.size(),
+                                  &n_merges, first.data()));
+  uint64_t cnt[10];
+  CHECK(ctx, rtc_linkage_counters(ctx, cnt));
+  // components arrive in order of their smallest member; so do the clusters generate_cluster_with_bfs numbers, but do not rely on it
+  vector<size_t> order(clusters.size());
+  for (size_t c = 0; c < order.size(); c++) order[c] = c;
+  vector<int> smallest(clusters.size());
+  for (size_t c = 0; c < clusters.size(); c++) smallest[c] = *std::min_element(clusters[c].begin(), clusters[c].end());
+  std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return smallest[x] < smallest[y]; });
+  const string f_lk = base + ".complete.linkage.txt";
+  FILE* fp = fopen(f_lk.c_str(), "w");
+  if (!fp) { cerr << "ERROR: cannot open file: " << f_lk << endl; join_warmup(); exit(1); }
+  vector<vector<int>> out;
+  vector<int> cid(n), head(n);  // the linkage id of the cluster named g; the result cluster (index into out) named g
+  for (uint32_t g = 0; g < n; g++) cid[g] = (int)g;
+  int next_id = (int)n;
+  uint64_t kept = 0;
+  for (size_t q = 0; q < order.size(); q++) {
+    const vector<int>& mem = clusters[order[q]];
+    vector<int> sorted_mem(mem);
+    std::sort(sorted_mem.begin(), sorted_mem.end());
+    const size_t out0 = out.size();
+    for (int g : sorted_mem) { head[g] = (int)out.size(); out.push_back({g}); }
+    for (uint64_t e = first[q]; e < first[q + 1]; e++) {
+      const rtc_lmerge& mg = merges[e];
+      const double dist = rtc_linkage_distance(mg.common, mg.denom, kmer_size);
+      if (dist > threshold) break;
+      fprintf(fp, "%d\t%d\t%.6f\t%d\n", cid[mg.a], cid[mg.b], dist, (int)mg.size);
+      cid[mg.a] = next_id++;
+      vector<int>& A = out[head[mg.a]];
+      vector<int>& Bv = out[head[mg.b]];
+      A.insert(A.end(), Bv.begin(), Bv.end());
+      Bv.clear();
+      kept++;
+    }
+    // the component's clusters: members ascending, clusters by smallest member
+    vector<vector<int>> part;
+    for (size_t i = out0; i < out.size(); i++) if (!out[i].empty()) { std::sort(out[i].begin(), out[i].end()); part.push_back(std::move(out[i])); }
+    std::sort(part.begin(), part.end(), [](const vector<int>& x, const vector<int>& y) { return x[0] < y[0]; });
+    out.resize(out0);
+    for (auto& c : part) out.push_back(std::move(c));
+  }
+  fclose(fp);
+  std::sort(out.begin(), out.end(), [](const vector<int>& x, const vector<int>& y) { return x[0] < y[0]; });
+  const string f_cl = base + ".complete";
+  print_result(out, genomes, sketchByFile, f_cl, threshold);
+  cerr << "-----write the complete-linkage cluster result into: " << f_cl << endl;
+  cerr << "-----the cluster number of: " << f_cl << " is: " << out.size() << endl;
+  cerr << "-----write the complete-linkage matrix into: " << f_lk << endl;
+  g_metrics.num("linkage_fill_s", 1e-9 * (double)cnt[6]);
+  g_metrics.num("linkage_agglomerate_s", 1e-9 * (double)cnt[7]);
+  g_metrics.num("linkage_components", (double)cnt[0]);
+  g_metrics.num("linkage_merges", (double)kept);
+  g_metrics.num("linkage_clusters", (double)out.size());
+}
+#endif
 
 #if !defined(GREEDY_CLUST) && !defined(DBSCAN_CLUST)
 // append_clust_mst / append_clust_mst_fast (src/sub_command.cpp:1532-1759): sketch the new genomes with the
@@ -2711,6 +2796,15 @@ int main(int argc, char** argv) {
   if (o.has_append) { cerr << "ERROR: --append not supported for DBSCAN clustering" << endl; return 1; }
 #endif
 #if !defined(GREEDY_CLUST) && !defined(DBSCAN_CLUST)
+#ifndef LEIDEN_CLUST
+  // ---- --linkage complete: what it does not go with, before any GPU is asked for ----
+  if (o.linkageComplete) {
+    const char* bad = o.isContainment ? "-c/--containment" : !o.useIndex ? "--inverted-index=false" : o.has_append ? "--append"
+                      : o.has_premsted ? "--premsted" : !o.repdb_path.empty() ? "--db" : o.dense ? "--dense"
+                      : o.autoThreshold ? "--auto-threshold" : o.stability ? "--stability" : nullptr;
+    if (bad) { cerr << "ERROR: --linkage does not go with " << bad << endl; return 1; }
+  }
+#endif
   // ---- MST RepDB mode: --db FILE (src/main.cpp:213-254, :525-600) ----
   if (o.has_topk && !o.db_query) { cerr << "ERROR: --top-k requires --query" << endl; return 1; }
   const bool db_action = o.db_build || o.db_query || o.db_assign || o.db_stats;
@@ -3503,6 +3597,10 @@ int main(int argc, char** argv) {
     return 1;
   // --dedup-dist / --reps-per-cluster: the KSSD flows only (compute_kssd_clusters, clust_from_sketch_fast)
   if (o.is_fast) dedup_and_reps(ctx, o.dedupDist, o.repsPerCluster, o.threads, forest, clusters, genomes, sketchByFile, o.outputFile);
+  if (o.linkageComplete) {
+    if (is_containment) { cerr << "ERROR: --linkage does not go with containment sketches" << endl; return 1; }
+    linkage_complete_and_print(ctx, dss[0], clusters, genomes, sketchByFile, o.outputFile, o.threshold, kmer_size);
+  }
   if (o.dense) {
     if (!o.noSave && !from_sketches) { save_ani(folder_path, ani); save_dense(folder_path, dense, DENSE_SPAN, (int)genomes.size()); }
     remove_noise_and_print(mst, genomes, sketchByFile, o.outputFile, o.threshold, dense, DENSE_SPAN, &forest, &clusters);
