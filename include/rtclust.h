@@ -967,6 +967,48 @@ int rtc_linkage_counters(const rtc_ctx* ctx, uint64_t out[10]);
  * with the host's libm; denom up to 2^31 - 1, the range of the MST's own weights.  Host only. */
 double rtc_linkage_distance(uint32_t common, uint32_t denom, int kmer_size);
 
+/* ---- clust-mst --nj-tree / --nj-all: neighbour-joining trees ------------------------------------------------------ */
+/* Neighbour joining (Saitou-Nei, with Studier-Keppler's Q) of one set of m points over a symmetric m x m matrix D of finite
+ * doubles; the diagonal is ignored.  This is the definition (tests/refnj.py restates it).  Every operation is one IEEE-754 double
+ * operation in the order written: no contraction into FMA, no reassociation.
+ *
+ * Start.  Every point is an active node named by its index, r = m.  R[i] is the sum of D[i][j] over j != i in ascending j, added
+ *     one after the other starting from 0.0 -- the only ordered sum, and it happens once.
+ * While r > 3.  Q(i, j) = ((double)(r - 2) * D[i][j] - R[i]) - R[j] for active i < j; the pair with the least Q is joined, equal
+ *     Q going to the smallest i, then the smallest j (comparisons of doubles are exact, so the choice does not depend on how the
+ *     search is split).  dij = D[i][j], delta = (R[i] - R[j]) / (double)(2 (r - 2)), len_i = 0.5 * dij + delta,
+ *     len_j = dij - len_i.  For every other active k: duk = 0.5 * ((D[i][k] + D[j][k]) - dij),
+ *     R[k] = ((R[k] - D[i][k]) - D[j][k]) + duk, D[i][k] = D[k][i] = duk.  Then R[i] = 0.5 * ((R[i] + R[j]) - (double)r * dij)
+ *     with the r from before the join, j is retired, the new node keeps the name i and r drops by one.  The step emits
+ *     rtc_njoin {a = i, b = j, c = UINT32_MAX, len_a = len_i, len_b = len_j, len_c = 0}.
+ * At r == 3, active i < j < k: one record {i, j, k, 0.5 * ((D[i][j] + D[i][k]) - D[j][k]), 0.5 * ((D[i][j] + D[j][k]) - D[i][k]),
+ *     0.5 * ((D[i][k] + D[j][k]) - D[i][j])}.
+ * m >= 3 gives m - 2 records, m == 2 the one record {0, 1, UINT32_MAX, 0.5 * d, d - 0.5 * d, 0}, m <= 1 none.  Branch lengths
+ *     are not clamped: negative ones come out as they are.  Non-finite input is undefined.
+ *
+ * Three kernel paths, chosen per component: m <= 64 one wave with D and R in LDS; larger ones a 256-lane workgroup with D in
+ * global memory, the whole tree in one launch; from RTC_NJ_GRID_MIN points on (default 256; set, it holds down to 4) the whole
+ * device, two launches a join, all of them enqueued without a read-back.  The records are the same on every path. */
+typedef struct { uint32_t a, b, c, pad; double len_a, len_b, len_c; } rtc_njoin;
+/* One matrix that is already on the device: d_dist[i * ld + j], ld >= m; it is read and overwritten.  h_joins: room for
+ * max(m - 2, 1) records, *h_n_joins their number.  ld < m, m >= 2^31 - 1, NULLs: RTC_ERR_ARG.  Synchronous. */
+int rtc_nj_dev(rtc_ctx* ctx, uint32_t m, double* d_dist, uint64_t ld, rtc_njoin* h_joins, uint32_t* h_n_joins);
+/* One tree per component of a labelling of n sketches: component numbering, member order, h_first and RTC_ERR_OVERFLOW as
+ * rtc_linkage_complete has them; a component of m >= 3 has m - 2 records, one of two has one, a, b and c are genome indices.  The
+ * key blocks are rtc_linkage_complete's; each batch is copied to the host, every entry becomes
+ * rtc_linkage_distance(common, denom, kmer_size) -- 1 for common == 0 or denom == 0 -- with the host's libm on the context's host
+ * threads (rtc_ctx_set_host_threads), the doubles go back into the same 8-byte cells and the device joins.  The byte budget of a
+ * batch is RTC_NJ_BYTES (default half the free HBM); a component whose 8 m^2 bytes and one band exceed it: RTC_ERR_NOMEM, the
+ * message naming m and the bytes; no fallback.  Argument errors as rtc_linkage_complete; kmer_size < 1: RTC_ERR_ARG. */
+int rtc_nj_clusters(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                    const uint32_t* h_comp, int kmer_size, rtc_njoin* h_joins, uint64_t cap, uint64_t* h_n_joins, uint64_t* h_first);
+/* The last rtc_nj_clusters (or rtc_nj_dev): out[0] components joined (m >= 2), out[1] on the wave path, out[2] on the workgroup
+ * path, out[3] on the grid path, out[4] records, out[5] batches, out[6] fill ns, out[7] host distance ns (copies included),
+ * out[8] joining ns, out[9] whole call ns. */
+int rtc_nj_counters(const rtc_ctx* ctx, uint64_t out[10]);
+/* The paths of the last call: bit 0 the wave path, bit 1 the workgroup path, bit 2 the grid path. */
+int rtc_nj_last_path(const rtc_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif

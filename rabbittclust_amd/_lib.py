@@ -167,6 +167,10 @@ SIGNATURES = {
     "rtc_linkage_complete": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _u64, C.POINTER(_u64), _vp]),
     "rtc_linkage_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_linkage_distance": (C.c_double, [_u32, _u32, _i]),
+    "rtc_nj_dev": (_i, [_vp, _u32, _vp, _u64, _vp, C.POINTER(_u32)]),
+    "rtc_nj_clusters": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _i, _vp, _u64, C.POINTER(_u64), _vp]),
+    "rtc_nj_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_nj_last_path": (_i, [_vp]),
     "rtc_hierarchy_flat": (_i, [_u32, _vp, _u64, _vp, _i, _i, _vp, _vp, C.POINTER(_u32)]),
 }
 

@@ -36,6 +36,9 @@ PLACEMENT_DT = np.dtype([("label", "<i4"), ("runner_up", "<i4"), ("n_edges", "<u
 WEDGE_DT = np.dtype([("u", "<u4"), ("v", "<u4"), ("q", "<u4")])  # rtc_wedge
 LKEY_DT = np.dtype([("common", "<u4"), ("denom", "<u4")])  # rtc_lkey
 LMERGE_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("common", "<u4"), ("denom", "<u4"), ("size", "<u4")])  # rtc_lmerge
+NJOIN_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("c", "<u4"), ("pad", "<u4"), ("len_a", "<f8"), ("len_b", "<f8"), ("len_c", "<f8")])  # rtc_njoin
+NJ_PATH_WAVE, NJ_PATH_WORKGROUP, NJ_PATH_GRID = 1, 2, 4  # rtc_nj_last_path
+NJ_GRID_MIN = 256  # the library's default RTC_NJ_GRID_MIN (rtc_nj.hip: NJ_GRID_MIN)
 HEDGE_DT = np.dtype([("p", "<u4"), ("q", "<u4"), ("common", "<u4"), ("size_p", "<u4"), ("size_q", "<u4")])  # rtc_hedge
 
 
@@ -969,6 +972,51 @@ class Context:
         names = ("components", "wave_components", "workgroup_components", "merges", "rescans", "batches", "fill_ns", "agglomerate_ns",
                  "largest_m", "total_ns")
         return {k: int(a[i]) for i, k in enumerate(names)}
+
+    def nj(self, matrix, ld=None):
+        """rtc_nj_dev: the neighbour joining include/rtclust.h defines over one symmetric m x m matrix of doubles, uploaded for the
+        call.  ld: the row stride when the array is [m, ld] with ld > m.  Returns NJOIN_DT records in step order, a, b and c as
+        matrix indices (c is 0xFFFFFFFF but in the last record of m >= 3)."""
+        d = np.ascontiguousarray(matrix, dtype=np.float64)
+        m = int(d.shape[0])
+        ld = int(d.shape[1]) if d.ndim == 2 and m else m
+        if d.ndim != 2 or ld < m:
+            raise ValueError("matrix must be [m, ld] with ld >= m")
+        t = torch.from_numpy(d.reshape(-1).copy()).to(self.device) if m else torch.zeros(2, dtype=torch.float64, device=self.device)
+        out = np.zeros(max(m - 2, 1), dtype=NJOIN_DT)
+        nj = C.c_uint32(0)
+        self.check(self.lib.rtc_nj_dev(self.h, m, _t_ptr(t), ld, _np_ptr(out), C.byref(nj)))
+        return out[:nj.value].copy()
+
+    def nj_clusters(self, sk, comp, kmer_size, cap=None):
+        """rtc_nj_clusters: one neighbour-joining tree per component of the labelling comp[g] of sk's sketches (any labels;
+        components are numbered by their smallest member) over rtc_linkage_distance of the exact keys.  Returns (joins, first):
+        NJOIN_DT records with a, b and c as genome indices, component after component, and first[c] where component c's records
+        start.  cap: room for the records (None: n, which always suffices); too small raises RTC_ERR_OVERFLOW, the needed count
+        in self.nj_records_needed."""
+        n = sk.n
+        lab = np.ascontiguousarray(np.asarray(comp).astype(np.int64).astype(np.uint32))
+        if lab.shape != (n,):
+            raise ValueError("comp must hold one label per sketch")
+        room = max(n, 1) if cap is None else int(cap)
+        out = np.zeros(max(room, 1), dtype=NJOIN_DT)
+        first = np.zeros(n + 1, dtype=np.uint64)
+        nj = C.c_uint64(0)
+        st = self.lib.rtc_nj_clusters(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n, _np_ptr(lab), int(kmer_size),
+                                      _np_ptr(out), room, C.byref(nj), _np_ptr(first))
+        self.nj_records_needed = int(nj.value)
+        self.check(st)
+        return out[:nj.value].copy(), first[:len(np.unique(lab)) + 1].copy()
+
+    def nj_counters(self):
+        """rtc_nj_counters as a dict (the last nj or nj_clusters call), and "paths": rtc_nj_last_path's bits."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_nj_counters(self.h, a))
+        names = ("components", "wave_components", "workgroup_components", "grid_components", "records", "batches", "fill_ns", "distance_ns",
+                 "join_ns", "total_ns")
+        out = {k: int(a[i]) for i, k in enumerate(names)}
+        out["paths"] = int(self.lib.rtc_nj_last_path(self.h))
+        return out
 
     def graph_query(self, sk, n_db, threshold, kmer_size, knn_k=0, query_chunk=0, cap=None):
         """clust-leiden --db --assign, first call (rtc_graph_query): sk holds the n_db model genomes, then the queries.  Returns

@@ -102,6 +102,8 @@ void rtc_options_from_env(rtc_options* o) {
   o->dbscan_mash_noprefilter = flag("RTC_DBSCAN_MASH_NOPREFILTER");
   o->linkage_span = (uint32_t)std::min<long long>(std::max<long long>(0, num("RTC_LINKAGE_SPAN", 0)), 262140);
   if (const char* e = getenv("RTC_LINKAGE_BYTES")) o->linkage_bytes = std::max<uint64_t>(strtoull(e, nullptr, 10), 1);
+  if (const char* e = getenv("RTC_NJ_BYTES")) o->nj_bytes = std::max<uint64_t>(strtoull(e, nullptr, 10), 1);
+  if (getenv("RTC_NJ_GRID_MIN")) o->nj_grid_min = (uint32_t)std::min<long long>(std::max<long long>(4, num("RTC_NJ_GRID_MIN", 4)), 0x7fffffff);
 }
 
 extern "C" {

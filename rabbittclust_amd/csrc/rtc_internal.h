@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -38,6 +39,8 @@ struct rtc_options {
   int dbscan_mash_noprefilter = 0;  // RTC_DBSCAN_MASH_NOPREFILTER: every candidate is merged
   uint32_t linkage_span = 0;       // RTC_LINKAGE_SPAN: the rows of a band that small components share in the fill (0: default)
   uint64_t linkage_bytes = 0;      // RTC_LINKAGE_BYTES: the byte budget of a batch of rtc_linkage_complete (0: half the free HBM)
+  uint64_t nj_bytes = 0;           // RTC_NJ_BYTES: the byte budget of a batch of rtc_nj_clusters (0: half the free HBM)
+  uint32_t nj_grid_min = 0;        // RTC_NJ_GRID_MIN: components of at least this many points (down to 4) take the grid path (0: default)
 };
 void rtc_options_from_env(rtc_options* o);
 
@@ -99,7 +102,9 @@ struct rtc_ctx {
   uint64_t leiden_place[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_leiden_place_counters (include/rtclust.h lists them)
   int leiden_place_path = 0;  // rtc_leiden_place_last_path
   uint64_t linkage[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_linkage_counters (include/rtclust.h lists them)
-  int host_threads = 1;     // rtc_ctx_set_host_threads: the host side of rtc_tree_medoids
+  uint64_t nj[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_nj_counters (include/rtclust.h lists them)
+  int nj_path = 0;          // rtc_nj_last_path
+  int host_threads = 1;     // rtc_ctx_set_host_threads: the host side of rtc_tree_medoids and of rtc_nj_clusters' distances
   // rtc_diag_counters: [0] pair tiles the join took, [1] tiled-kernel tiles, [2] merge-kernel tiles, [3] candidate lists contracted
   // to their forest, [4] greedy runs replayed from ONE global join, [5] greedy query blocks of the block loop, [6] estimates handed
   // back instead of a launch (rtc_pair_edges_dev's overflow protocol)
@@ -202,6 +207,32 @@ struct rtc_mst_bufs_t { uint32_t* h_len; rtc_cedge* h_sel; rtc_cedge* d_sel; }; 
 int rtc_mst_bufs(rtc_ctx* ctx, uint32_t n, rtc_mst_bufs_t* b);
 int rtc_edges_to_mst_host_fixed(const rtc_cedge* h_sel, uint64_t m, const uint32_t* h_len, int kmer_size, int is_containment,
                                 uint32_t s_fixed, rtc_edge* h_out);
+
+// rtc_linkage.hip: the exact m x m key blocks (common, denom) of the components of a labelling, formed on the device in batches
+// under a byte budget -- what rtc_linkage_complete agglomerates and rtc_nj_clusters joins.  Components are numbered by their
+// smallest member, members taken in ascending genome order; the members of the components of two or more, component after
+// component, are the permuted set perm, cfirst[c] where component c starts in it.
+struct rtc_kb_comp {
+  uint64_t key_off;      // first record of the block in the batch's buffer
+  uint64_t ld;           // records per row of the block
+  uint64_t merge_off;    // first output record (the consumer's)
+  uint64_t scratch_off;  // the consumer's scratch
+  uint32_t m, pad;
+};
+struct rtc_kb_batch {
+  rtc_lkey* d_keys;                  // the blocks of the batch, both halves filled, the diagonal untouched; NULL: no component of two or more
+  uint64_t n_keys;                   // records in d_keys
+  std::vector<rtc_kb_comp>* comps;   // the components of two or more of [c, ce), key_off / ld / m set
+  size_t c, ce;                      // the components of the batch, those of one member included
+  uint64_t fill_ns;
+  const std::vector<uint32_t>*csize, *cfirst, *perm;
+};
+// on_batch is called for every batch in component order, the stream idle and the blocks complete; it may overwrite them.
+// budget_opt 0: half the free HBM.  h_first[0 .. n_comp] is zeroed.  A component whose 8 m^2 bytes and one band exceed the budget:
+// RTC_ERR_NOMEM, the message starting with who.
+int rtc_key_blocks(rtc_ctx* ctx, const char* who, uint64_t budget_opt, const void* d_hashes, int width, const uint64_t* d_start,
+                   const uint32_t* d_len, uint32_t n, const uint32_t* h_comp, uint64_t* h_first,
+                   const std::function<int(const rtc_kb_batch&)>& on_batch);
 
 #define RTC_HIP(ctx, call)                                                                  \
   do {                                                                                      \

@@ -26,13 +26,7 @@ constexpr uint32_t LK_WAVE_MAX = 64;          // the wave path's largest m
 constexpr uint32_t LK_BAND_SPAN = 4096;       // components of up to this many sketches share a band of the fill (RTC_LINKAGE_SPAN)
 constexpr uint64_t LK_BAND_BYTES = (uint64_t)64 << 20;  // the u32 temporary of one band
 
-struct lk_comp {
-  uint64_t key_off;      // first key of the block, in records
-  uint64_t ld;           // records per row of the block
-  uint64_t merge_off;    // first merge record
-  uint64_t scratch_off;  // workgroup path: first u32 of the row-bests
-  uint32_t m, pad;
-};
+using lk_comp = rtc_kb_comp;  // key_off, ld and m come from the fill; merge_off and scratch_off (workgroup path: first u32 of the row-bests) are set here
 
 struct lk_cand { uint32_t c, d, a, b; };
 
@@ -378,23 +372,11 @@ extern "C" int rtc_linkage_dev(rtc_ctx* ctx, uint32_t m, rtc_lkey* d_key, uint64
   return RTC_OK;
 }
 
-extern "C" int rtc_linkage_complete(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
-                                    const uint32_t* h_comp, uint32_t kmin_num, uint32_t kmin_den, rtc_lmerge* h_merges, uint64_t cap,
-                                    uint64_t* h_n_merges, uint64_t* h_first) {
-  if (!ctx || !h_n_merges || !h_first) return RTC_ERR_ARG;
-  *h_n_merges = 0;
-  h_first[0] = 0;
-  if (width != 4 && width != 8) return rtc_fail(ctx, RTC_ERR_ARG, "width must be 4 or 8");
-  RTC_TRY(lk_check_bound(ctx, kmin_num, kmin_den));
-  if (n >= 0x7fffffffu) return rtc_fail(ctx, RTC_ERR_ARG, "rtc_linkage_complete: n must be below 2^31 - 1");
-  if (cap && !h_merges) return RTC_ERR_ARG;
-  for (int i = 0; i < 10; i++) ctx->linkage[i] = 0;
-  if (n == 0) return RTC_OK;
-  if (!d_start || !d_len || !h_comp) return RTC_ERR_ARG;
-  RTC_HIP(ctx, hipSetDevice(ctx->device));
-  const uint64_t t0 = lk_now_ns();
-  uint64_t* C = ctx->linkage;
-
+// The key blocks of every component, batch after batch (rtc_internal.h): what rtc_linkage_complete agglomerates and
+// rtc_nj_clusters joins.
+int rtc_key_blocks(rtc_ctx* ctx, const char* who, uint64_t budget_opt, const void* d_hashes, int width, const uint64_t* d_start,
+                   const uint32_t* d_len, uint32_t n, const uint32_t* h_comp, uint64_t* h_first,
+                   const std::function<int(const rtc_kb_batch&)>& on_batch) {
   // ---- components in order of their smallest member; members in ascending genome order ----
   std::vector<uint32_t> by_label(n);
   std::iota(by_label.begin(), by_label.end(), 0u);
@@ -425,7 +407,7 @@ extern "C" int rtc_linkage_complete(rtc_ctx* ctx, const void* d_hashes, int widt
   }
   const uint32_t np = (uint32_t)perm.size();
   for (size_t c = 0; c <= n_comp; c++) h_first[c] = 0;
-  if (np == 0) { C[9] = lk_now_ns() - t0; return RTC_OK; }
+  if (np == 0) return RTC_OK;
   if (!d_hashes) return RTC_ERR_ARG;
 
   lk_bufs B;
@@ -442,15 +424,21 @@ extern "C" int rtc_linkage_complete(rtc_ctx* ctx, const void* d_hashes, int widt
   RTC_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
   // ---- batches under the byte budget: the blocks of a batch and one band of the fill ----
-  const uint64_t budget = std::min<uint64_t>(ctx->opt.linkage_bytes ? ctx->opt.linkage_bytes : std::max<uint64_t>(rtc_free_hbm(ctx) / 2, 1), (uint64_t)1 << 61);
+  const uint64_t budget = std::min<uint64_t>(budget_opt ? budget_opt : std::max<uint64_t>(rtc_free_hbm(ctx) / 2, 1), (uint64_t)1 << 61);
   auto block_bytes = [](uint64_t m) { return m > ((uint64_t)1 << 28) ? (uint64_t)1 << 62 : 8 * m * m; };  // past any budget, and no overflow
   auto min_band = [](uint64_t m) { return 4 * m * std::min<uint64_t>(m, 64); };
-  uint64_t total = 0;
-  bool overflow = false;
   std::vector<lk_row> rows(np);
+  std::vector<lk_comp> comps;
+  rtc_kb_batch batch = {nullptr, 0, &comps, 0, 0, 0, &csize, &cfirst, &perm};
   size_t c = 0;
   while (c < n_comp) {
-    if (csize[c] < 2) { h_first[c + 1] = total; c++; continue; }
+    comps.clear();
+    if (csize[c] < 2) {
+      batch.d_keys = nullptr; batch.n_keys = 0; batch.c = c; batch.ce = c + 1; batch.fill_ns = 0;
+      RTC_TRY(on_batch(batch));
+      c++;
+      continue;
+    }
     // the batch [c, ce)
     uint64_t kb = 0, band = 0;
     size_t ce = c;
@@ -460,7 +448,7 @@ extern "C" int rtc_linkage_complete(rtc_ctx* ctx, const void* d_hashes, int widt
         const uint64_t nb = std::max(band, min_band(m));
         if (kb + block_bytes(m) + nb > budget) {
           if (kb == 0)
-            return rtc_fail(ctx, RTC_ERR_NOMEM, "rtc_linkage_complete: a component of m = %llu needs %llu bytes (8 m^2 and one band), the budget is %llu",
+            return rtc_fail(ctx, RTC_ERR_NOMEM, "%s: a component of m = %llu needs %llu bytes (8 m^2 and one band), the budget is %llu", who,
                             (unsigned long long)m, (unsigned long long)(block_bytes(m) + min_band(m)), (unsigned long long)budget);
           break;
         }
@@ -470,12 +458,10 @@ extern "C" int rtc_linkage_complete(rtc_ctx* ctx, const void* d_hashes, int widt
       ce++;
     }
     const uint64_t temp_cap = std::max(band, std::min<uint64_t>(LK_BAND_BYTES, budget - kb));
-    C[5]++;
     const uint64_t tf0 = lk_now_ns();
     rtc_lkey* d_keys = nullptr;
     uint32_t* d_tmp = nullptr;
     RTC_TRY(B.get(ctx, kb, (void**)&d_keys));
-    std::vector<lk_comp> comps;
     std::vector<size_t> comp_of;  // comps[i] is component comp_of[i]
     {
       uint64_t off = 0;
@@ -523,17 +509,48 @@ extern "C" int rtc_linkage_complete(rtc_ctx* ctx, const void* d_hashes, int widt
       RTC_CHECK_LAUNCH(ctx);
     }
     RTC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const uint64_t tf1 = lk_now_ns();
-    C[6] += tf1 - tf0;
-    std::vector<rtc_lmerge> mg;
-    std::vector<uint32_t> nm, nres;
-    RTC_TRY(lk_agglomerate(ctx, d_keys, comps, kmin_num, kmin_den, mg, nm, nres));
-    C[7] += lk_now_ns() - tf1;
+    batch.d_keys = d_keys; batch.n_keys = kb / 8; batch.c = c; batch.ce = ce; batch.fill_ns = lk_now_ns() - tf0;
+    RTC_TRY(on_batch(batch));
     B.drop(d_tmp);
     B.drop(d_keys);
+    c = ce;
+  }
+  return RTC_OK;
+}
+
+extern "C" int rtc_linkage_complete(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                                    const uint32_t* h_comp, uint32_t kmin_num, uint32_t kmin_den, rtc_lmerge* h_merges, uint64_t cap,
+                                    uint64_t* h_n_merges, uint64_t* h_first) {
+  if (!ctx || !h_n_merges || !h_first) return RTC_ERR_ARG;
+  *h_n_merges = 0;
+  h_first[0] = 0;
+  if (width != 4 && width != 8) return rtc_fail(ctx, RTC_ERR_ARG, "width must be 4 or 8");
+  RTC_TRY(lk_check_bound(ctx, kmin_num, kmin_den));
+  if (n >= 0x7fffffffu) return rtc_fail(ctx, RTC_ERR_ARG, "rtc_linkage_complete: n must be below 2^31 - 1");
+  if (cap && !h_merges) return RTC_ERR_ARG;
+  for (int i = 0; i < 10; i++) ctx->linkage[i] = 0;
+  if (n == 0) return RTC_OK;
+  if (!d_start || !d_len || !h_comp) return RTC_ERR_ARG;
+  RTC_HIP(ctx, hipSetDevice(ctx->device));
+  const uint64_t t0 = lk_now_ns();
+  uint64_t* C = ctx->linkage;
+  uint64_t total = 0;
+  bool overflow = false;
+  RTC_TRY(rtc_key_blocks(ctx, "rtc_linkage_complete", ctx->opt.linkage_bytes, d_hashes, width, d_start, d_len, n, h_comp, h_first, [&](const rtc_kb_batch& b) -> int {
+    std::vector<lk_comp>& comps = *b.comps;
+    std::vector<rtc_lmerge> mg;
+    std::vector<uint32_t> nm, nres;
+    if (b.d_keys) {
+      C[5]++;
+      C[6] += b.fill_ns;
+      const uint64_t tf1 = lk_now_ns();
+      RTC_TRY(lk_agglomerate(ctx, b.d_keys, comps, kmin_num, kmin_den, mg, nm, nres));
+      C[7] += lk_now_ns() - tf1;
+    }
     // the merge lists in component order, local indices turned into genome indices
+    const std::vector<uint32_t>&csize = *b.csize, &cfirst = *b.cfirst, &perm = *b.perm;
     size_t i = 0;
-    for (size_t q = c; q < ce; q++) {
+    for (size_t q = b.c; q < b.ce; q++) {
       if (csize[q] >= 2) {
         const lk_comp& cp = comps[i];
         C[0]++; C[cp.m <= LK_WAVE_MAX ? 1 : 2]++; C[3] += nm[i]; C[4] += nres[i]; C[8] = std::max<uint64_t>(C[8], cp.m);
@@ -550,8 +567,8 @@ extern "C" int rtc_linkage_complete(rtc_ctx* ctx, const void* d_hashes, int widt
       }
       h_first[q + 1] = total;
     }
-    c = ce;
-  }
+    return RTC_OK;
+  }));
   *h_n_merges = total;
   C[9] = lk_now_ns() - t0;
   if (overflow) return rtc_fail(ctx, RTC_ERR_OVERFLOW, "rtc_linkage_complete: %llu merges, room for %llu", (unsigned long long)total, (unsigned long long)cap);

@@ -136,3 +136,19 @@ def leiden_model_resave(in_path, out_path):
     fn.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
     rc = fn(str(in_path).encode(), str(out_path).encode(), why, 256)
     return rc, why.value.decode()
+
+
+def nj_newick(labels, members, joins):
+    """get_nj_newick (rtc_host.cpp): the Newick text of one neighbour-joining tree.  labels[g]: the label of genome g; members: the
+    genome indices of the tree; joins: its rtc_njoin records (api.NJOIN_DT), a, b and c as genome indices."""
+    mem = np.ascontiguousarray(sorted(int(g) for g in members), dtype=np.uint32)
+    j = np.ascontiguousarray(joins)
+    assert j.dtype.itemsize == 40
+    arr = (C.c_char_p * max(len(labels), 1))(*[s.encode() for s in labels])
+    fn = load().rtch_nj_newick
+    fn.restype = C.c_long
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_long]
+    need = fn(arr, mem.ctypes.data_as(C.c_void_p), len(mem), j.ctypes.data_as(C.c_void_p), len(j), None, 0)
+    buf = C.create_string_buffer(max(int(need), 1))
+    fn(arr, mem.ctypes.data_as(C.c_void_p), len(mem), j.ctypes.data_as(C.c_void_p), len(j), buf, need)
+    return buf.raw[:need].decode()

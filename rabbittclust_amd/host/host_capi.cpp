@@ -292,4 +292,12 @@ int rtch_leiden_model_resave(const char* in_path, const char* out_path, char* wh
   }
   return save_leiden_model(out_path, m) ? 0 : -2;
 }
+// get_nj_newick over plain arrays: labels[g] for every genome index the members name, members[m] ascending, joins[n_joins] with
+// genome indices.  Returns the text's length; the text itself when it fits cap (no terminator).
+long rtch_nj_newick(const char* const* labels, const uint32_t* members, uint64_t m, const rtc_njoin* joins, uint64_t n_joins, char* out, long cap) {
+  const std::string text = nj_newick_text([&](uint32_t v) { return std::string(labels[v]); }, members, (size_t)m, joins, (size_t)n_joins);
+  if (out && (long)text.size() <= cap) memcpy(out, text.data(), text.size());
+  return (long)text.size();
+}
+
 }

@@ -889,6 +889,7 @@ struct Options {
   bool hasDrlevel = false;
   string minhashOnly;        // clust-leiden: the first of -s / -c as spelled, which only --minhash gives a meaning
   bool linkageComplete = false;  // clust-mst --linkage complete: complete linkage inside every cluster (rtc_linkage_complete)
+  bool njTree = false, njAll = false;  // clust-mst --nj-tree / --nj-all: neighbour-joining trees of the clusters / of all genomes (rtc_nj_clusters)
 };
 
 #ifdef LEIDEN_CLUST
@@ -1040,6 +1041,8 @@ static Options parse(int argc, char** argv) {
       if (strcmp(need(i), "complete") != 0) { fprintf(stderr, "ERROR: --linkage must be complete\n"); exit(1); }
       o.linkageComplete = true;
     }
+    else if (a == "--nj-tree") o.njTree = true;
+    else if (a == "--nj-all") o.njAll = true;
 #endif
     else if (a == "-h" || a == "--help") {
 #ifdef GREEDY_CLUST
@@ -1120,6 +1123,9 @@ static Options parse(int argc, char** argv) {
            "  --save-rep (mst_cluster_state.bin beside the sketches; a later --append measures against its representatives)\n"
            "  --linkage complete (complete linkage inside every cluster of the run: <output>.complete, where every two members of\n"
            "             a cluster are within -d, and <output>.complete.linkage.txt; with --fast or MinHash on the index path)\n"
+           "  --nj-tree (a neighbour-joining tree of every cluster over the exact set-Jaccard distances, joined on the GPU:\n"
+           "             <output>.nj.newick, one tree a line in the order of <output>; with --fast or MinHash on the index path)\n"
+           "  --nj-all (one neighbour-joining tree over all genomes: <output>.nj.all.newick; genomes that share no hash are at distance 1)\n"
            "  [--fast] --db FILE --build|--query|--assign|--append LIST|--stats [--top-k N] (MST representative database)"
 #else
            "  --append LIST (with --presketched DIR)  --save-rep (cluster_state.bin beside the sketches)\n"
@@ -1294,6 +1300,43 @@ static void linkage_complete_and_print(rtc_ctx* ctx, const DeviceSketches& ds, c
   g_metrics.num("linkage_components", (double)cnt[0]);
   g_metrics.num("linkage_merges", (double)kept);
   g_metrics.num("linkage_clusters", (double)out.size());
+}
+
+// --nj-tree / --nj-all: neighbour joining (include/rtclust.h has the definition) over the distances the host forms from the exact
+// keys of the index path.  --nj-tree: every cluster of the plain run is a component, <base>.nj.newick holds one tree a line in
+// the order <base> lists the clusters; --nj-all: all genomes are one component, <base>.nj.all.newick.  A tree that does not fit
+// the device (RTC_ERR_NOMEM, no fallback) is reported after everything else has been written: returns 1.
+static int nj_trees_and_print(rtc_ctx* ctx, const DeviceSketches& ds, const vector<vector<int>>& clusters, const vector<GenomeInfo>& genomes,
+                              bool sketchByFile, const string& base, int kmer_size, int threads, bool per_cluster, bool all) {
+  const uint32_t n = (uint32_t)genomes.size();
+  CHECK(ctx, rtc_ctx_set_host_threads(ctx, threads > 0 ? threads : 1));
+  uint64_t sum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int pass = 0; pass < 2; pass++) {
+    if (!(pass == 0 ? per_cluster : all)) continue;
+    vector<uint32_t> comp(n, 0);
+    vector<vector<int>> whole(1);
+    if (pass == 0) { for (size_t c = 0; c < clusters.size(); c++) for (int g : clusters[c]) comp[g] = (uint32_t)c; }
+    else for (uint32_t g = 0; g < n; g++) whole[0].push_back((int)g);
+    vector<rtc_njoin> joins(n > 0 ? n : 1);
+    vector<uint64_t> first((size_t)n + 1, 0);
+    uint64_t n_joins = 0;
+    const int st = rtc_nj_clusters(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, n, comp.data(), kmer_size, joins.data(), joins.size(), &n_joins,
+                                   first.data());
+    if (st == RTC_ERR_NOMEM) { cerr << "ERROR: " << rtc_last_error(ctx) << endl; return 1; }
+    CHECK(ctx, st);
+    uint64_t cnt[10];
+    CHECK(ctx, rtc_nj_counters(ctx, cnt));
+    for (int i = 0; i < 10; i++) sum[i] += cnt[i];
+    const string f = base + (pass == 0 ? ".nj.newick" : ".nj.all.newick");
+    print_nj_newick(genomes, pass == 0 ? clusters : whole, joins, first, sketchByFile, f);
+    cerr << "-----write the neighbour-joining " << (pass == 0 ? "trees of the clusters" : "tree of all genomes") << " into: " << f << endl;
+  }
+  g_metrics.num("nj_fill_s", 1e-9 * (double)sum[6]);
+  g_metrics.num("nj_distance_s", 1e-9 * (double)sum[7]);
+  g_metrics.num("nj_join_s", 1e-9 * (double)sum[8]);
+  g_metrics.num("nj_components", (double)sum[0]);
+  g_metrics.num("nj_records", (double)sum[4]);
+  return 0;
 }
 #endif
 
@@ -2804,6 +2847,13 @@ int main(int argc, char** argv) {
                       : o.autoThreshold ? "--auto-threshold" : o.stability ? "--stability" : nullptr;
     if (bad) { cerr << "ERROR: --linkage does not go with " << bad << endl; return 1; }
   }
+  // ---- --nj-tree / --nj-all: the same company, refused before any GPU is asked for ----
+  if (o.njTree || o.njAll) {
+    const char* bad = o.isContainment ? "-c/--containment" : !o.useIndex ? "--inverted-index=false" : o.has_append ? "--append"
+                      : o.has_premsted ? "--premsted" : !o.repdb_path.empty() ? "--db" : o.dense ? "--dense"
+                      : o.autoThreshold ? "--auto-threshold" : o.stability ? "--stability" : nullptr;
+    if (bad) { cerr << "ERROR: " << (o.njTree ? "--nj-tree" : "--nj-all") << " does not go with " << bad << endl; return 1; }
+  }
 #endif
   // ---- MST RepDB mode: --db FILE (src/main.cpp:213-254, :525-600) ----
   if (o.has_topk && !o.db_query) { cerr << "ERROR: --top-k requires --query" << endl; return 1; }
@@ -3600,6 +3650,13 @@ int main(int argc, char** argv) {
   if (o.linkageComplete) {
     if (is_containment) { cerr << "ERROR: --linkage does not go with containment sketches" << endl; return 1; }
     linkage_complete_and_print(ctx, dss[0], clusters, genomes, sketchByFile, o.outputFile, o.threshold, kmer_size);
+  }
+  if (o.njTree || o.njAll) {
+    if (is_containment) { cerr << "ERROR: " << (o.njTree ? "--nj-tree" : "--nj-all") << " does not go with containment sketches" << endl; return 1; }
+    if (nj_trees_and_print(ctx, dss[0], clusters, genomes, sketchByFile, o.outputFile, kmer_size, o.threads, o.njTree, o.njAll) != 0) {
+      join_warmup();
+      return 1;
+    }
   }
   if (o.dense) {
     if (!o.noSave && !from_sketches) { save_ani(folder_path, ani); save_dense(folder_path, dense, DENSE_SPAN, (int)genomes.size()); }

@@ -24,6 +24,7 @@
 #endif
 
 #include <algorithm>
+#include <unordered_map>
 #include <type_traits>
 #include <fstream>
 #include <iomanip>
@@ -1218,6 +1219,62 @@ std::string get_newick_tree(const std::vector<GenomeInfo>& g, const std::vector<
   return text + ";";
 }
 
+// Newick text of one neighbour-joining tree from its records (include/rtclust.h: rtc_njoin; a, b and c are genome indices).
+// text(x) is the subtree currently named x: a leaf at first, after a join {a, b} the node "(text(a):len_a,text(b):len_b)" under
+// the name a; the last record of three or more members has three children and closes the tree.  One member: "label;", two:
+// "(a:x,b:y);".  The nodes live in one flat array and the text is written by an explicit stack, as get_newick_tree's.
+std::string nj_newick_text(const std::function<std::string(uint32_t)>& label, const uint32_t* members, size_t m, const rtc_njoin* joins,
+                           size_t n_joins) {
+  if (m == 0) return ";";
+  if (m == 1 || n_joins == 0) return label(members[0]) + ";";
+  struct Node { int kid[3]; double len[3]; int nk; };
+  std::vector<Node> nodes;
+  nodes.reserve(n_joins);
+  std::unordered_map<uint32_t, int> named;  // the node a name stands for: below m the leaf members[.], from m on nodes[. - m]
+  named.reserve(2 * m);
+  for (size_t v = 0; v < m; v++) named[members[v]] = (int)v;
+  for (size_t e = 0; e < n_joins; e++) {
+    const rtc_njoin& r = joins[e];
+    Node nd;
+    nd.nk = r.c == 0xFFFFFFFFu ? 2 : 3;
+    const uint32_t name[3] = {r.a, r.b, r.c};
+    const double len[3] = {r.len_a, r.len_b, r.len_c};
+    for (int s = 0; s < 3; s++) { nd.kid[s] = s < nd.nk ? named.at(name[s]) : -1; nd.len[s] = len[s]; }
+    nodes.push_back(nd);
+    named[r.a] = (int)(m + nodes.size() - 1);
+  }
+  const int leaves = (int)m;
+  std::string text;
+  struct Visit { int node; int done; };  // done: how many of an inner node's branches are written
+  std::vector<Visit> path{{leaves + (int)nodes.size() - 1, 0}};
+  while (!path.empty()) {
+    Visit& v = path.back();
+    if (v.node < leaves) {
+      text += label(members[v.node]);
+    } else if (v.done < nodes[v.node - leaves].nk) {
+      text += v.done == 0 ? "(" : ",";
+      const int kid = nodes[v.node - leaves].kid[v.done++];
+      path.push_back({kid, 0});
+      continue;
+    } else {
+      text += ")";
+    }
+    path.pop_back();
+    if (!path.empty()) {  // the subtree just closed hangs on branch done-1 of the node now on top
+      const Visit& up = path.back();
+      text += ":" + std::to_string(nodes[up.node - leaves].len[up.done - 1]);
+    }
+  }
+  return text + ";";
+}
+
+std::string get_nj_newick(const std::vector<GenomeInfo>& g, const std::vector<int>& members, const rtc_njoin* joins, size_t n_joins,
+                          bool sketchByFile) {
+  std::vector<uint32_t> mem(members.begin(), members.end());
+  std::sort(mem.begin(), mem.end());
+  return nj_newick_text([&](uint32_t v) { return sketchByFile ? g[v].fileName : g[v].seq0.name; }, mem.data(), mem.size(), joins, n_joins);
+}
+
 static FILE* open_out(const std::string& output, const char* who) {
   FILE* fp = fopen(output.c_str(), "w");
   if (!fp) { std::cerr << "ERROR: " << who << "(), cannot write file: " << output << std::endl; exit(1); }
@@ -1227,6 +1284,23 @@ static FILE* open_out(const std::string& output, const char* who) {
 void print_newick_tree(const std::vector<GenomeInfo>& g, const std::vector<rtc_edge>& mst, bool sketchByFile, const std::string& output) {
   FILE* fp = open_out(output, "print_newick_tree");
   fprintf(fp, "%s\n", get_newick_tree(g, mst, sketchByFile).c_str());
+  fclose(fp);
+}
+
+// One tree a line, one line a cluster, in the order of `clusters`; first[q] .. first[q + 1] are the records of the cluster whose
+// smallest member is the q-th smallest (rtc_nj_clusters' component order).
+void print_nj_newick(const std::vector<GenomeInfo>& g, const std::vector<std::vector<int>>& clusters, const std::vector<rtc_njoin>& joins,
+                     const std::vector<uint64_t>& first, bool sketchByFile, const std::string& output) {
+  std::vector<size_t> order(clusters.size()), rank(clusters.size());
+  std::vector<int> smallest(clusters.size());
+  for (size_t c = 0; c < clusters.size(); c++) { order[c] = c; smallest[c] = *std::min_element(clusters[c].begin(), clusters[c].end()); }
+  std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return smallest[x] < smallest[y]; });
+  for (size_t q = 0; q < order.size(); q++) rank[order[q]] = q;
+  FILE* fp = open_out(output, "print_nj_newick");
+  for (size_t c = 0; c < clusters.size(); c++) {
+    const size_t q = rank[c];
+    fprintf(fp, "%s\n", get_nj_newick(g, clusters[c], joins.data() + first[q], (size_t)(first[q + 1] - first[q]), sketchByFile).c_str());
+  }
   fclose(fp);
 }
 

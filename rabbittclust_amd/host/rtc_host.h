@@ -4,6 +4,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <functional>
 #include <ostream>
 #include <string>
 #include <vector>
@@ -168,6 +169,15 @@ void print_newick_tree(const std::vector<GenomeInfo>& g, const std::vector<rtc_e
 void print_phylip_tree(const std::vector<GenomeInfo>& g, const std::vector<rtc_edge>& mst, bool sketchByFile, const std::string& output);
 void print_nexus_tree(const std::vector<GenomeInfo>& g, const std::vector<rtc_edge>& mst, bool sketchByFile, const std::string& output);
 void print_linkage_matrix(int n, const std::vector<rtc_edge>& mst, const std::string& output);  // c1 \t c2 \t dist \t size
+
+// ---- clust-mst --nj-tree / --nj-all: Newick text of the neighbour-joining records of rtc_nj_clusters (include/rtclust.h).  Leaves are
+// labelled as get_newick_tree labels them, lengths printed with std::to_string, negative ones as they are. ----
+std::string nj_newick_text(const std::function<std::string(uint32_t)>& label, const uint32_t* members, size_t m, const rtc_njoin* joins,
+                           size_t n_joins);
+std::string get_nj_newick(const std::vector<GenomeInfo>& g, const std::vector<int>& members, const rtc_njoin* joins, size_t n_joins,
+                          bool sketchByFile);
+void print_nj_newick(const std::vector<GenomeInfo>& g, const std::vector<std::vector<int>>& clusters, const std::vector<rtc_njoin>& joins,
+                     const std::vector<uint64_t>& first, bool sketchByFile, const std::string& output);
 
 // ---- clust-mst --auto-threshold / --stability: the MST edge-length analysis (src/MST.cpp:1743-2376, structs src/MST.h:77-100) ----
 struct EdgeLengthStats {
