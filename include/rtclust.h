@@ -849,6 +849,53 @@ int rtc_leiden(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, uint64_t m, d
  * rounds, out[5] merges accepted, out[6] proposals rejected, out[7] move ns, out[8] refinement ns, out[9] whole call ns. */
 int rtc_leiden_counters(const rtc_ctx* ctx, uint64_t out[10]);
 
+/* Markov clustering (MCL, van Dongen's flow simulation) in exact integers: clust-leiden --mcl.  MCL is usually run in floating
+ * point; this is a definition in fixed point, so that the result depends neither on the scheduling nor on the kernel path of a
+ * column (tests/refmcl.py restates it).  ONE = 2^30.  h = inflation_x2 is twice the inflation, 3 <= h <= 16 (1.5, 2, 2.5 .. 8);
+ * S = select, 1 <= S <= 4096; T = max_iter.  Every quantity is an unsigned 64-bit integer, / is floor division, and no step forms
+ * a floating-point value.
+ *   - Input: n vertices, m records (u, v, q) as rtc_louvain takes them.  Duplicates of an unordered pair are summed, records
+ *     with u == v are ignored, A is the symmetric adjacency.  u or v >= n, or q == 0: RTC_ERR_ARG.  A summed entry >= 2^32:
+ *     RTC_ERR_UNSUPPORTED.  h or S out of range: RTC_ERR_ARG.
+ *   - select(column): of the column's entries (i, x) the S largest stay, in the order x descending, then i ascending (all, if
+ *     there are no more than S).  With X the sum of the x that stay, each becomes p = x ONE / X; entries with p == 0 drop out.
+ *     The keys (x, i) are distinct, so the selection is unique.
+ *   - Start: column j is A's column j and the loop (j, L), L the largest entry of A's column j, or 1 if it is empty;
+ *     M[j] = select(column j).
+ *   - One iteration, for every column j:
+ *       1. Expand: s_i = the sum over the k of column j of M[i,k] M[k,j] (at most 2^60; one integer sum, so order-free);
+ *          e_i = s_i >> 30; rows with e_i == 0 drop out.
+ *       2. Rescale: with E the largest e_i of the column, e'_i = e_i ONE / E -- the largest becomes ONE exactly, so inflation
+ *          never empties a column.
+ *       3. Inflate: y = e'; then h / 2 - 1 times y = (y e') >> 30; if h is odd once more y = (y isqrt(e' << 30)) >> 30, isqrt the
+ *          floor of the exact square root.  Rows with y == 0 drop out.
+ *       4. N[j] = select({(i, y_i)}).
+ *   - Stop after the first iteration with N == M, columns compared as sets of (row, value): that iteration counts and
+ *     *h_converged = 1.  Otherwise after T iterations, *h_converged = 0.  T == 0 returns the start matrix.
+ *   - Clusters, on the host from the final matrix: a is an attractor iff M[a,a] > 0.  Every attractor is united with every
+ *     attractor among the rows of its column.  Every other vertex j is united with one row of its column: the attractor row
+ *     with the largest p, the lowest i among equals; if its column holds no attractor -- possible only without convergence --
+ *     that row among all its rows.  h_labels[x] is the smallest member of x's cluster, so the clusters come in the order in
+ *     which rtc_louvain numbers its communities; *h_n_clusters their number.  No record (or only u == v): every vertex is its own
+ *     cluster, after one iteration.
+ *   - h_matrix (may be NULL): the final matrix in (col, row) order, *h_nnz its entries; cap < *h_nnz: RTC_ERR_OVERFLOW with the
+ *     count in *h_nnz (labels, iterations and converged are set).  h_iterations, h_converged, h_nnz may be NULL without h_matrix.
+ * The device holds two matrices of n columns of min(S, n) slots, 16 n min(S, n) bytes, and the long path's tables; if they do
+ * not fit the free memory: RTC_ERR_NOMEM with the bytes in the message, no fallback.  A column takes one of three kernel paths
+ * by its work W, the number of products its expansion gathers (rabbittclust_amd/csrc/rtc_mcl.h: W <= 256 one wave, W <= 3072 a
+ * 256-lane workgroup, both with the table in LDS; beyond, a table in global memory).  RTC_MCL_GLOBAL=1 sends every column
+ * through the last; results are identical.  Synchronous. */
+typedef struct { uint32_t col, row, value, pad; } rtc_mcl_entry;
+int rtc_mcl(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, uint64_t m, int inflation_x2, uint32_t select, uint32_t max_iter,
+            int32_t* h_labels, uint32_t* h_n_clusters, uint32_t* h_iterations, int* h_converged, rtc_mcl_entry* h_matrix, uint64_t cap,
+            uint64_t* h_nnz);
+/* The last rtc_mcl: out[0] iterations, out[1] converged, out[2] entries of the final matrix, out[3] attractors, out[4] / out[5] /
+ * out[6] columns x iterations on the wave / workgroup / long path, out[7] columns where select cut something (the start and all
+ * iterations), out[8] ns between the first and the last column launch of the iterations (device clock), out[9] whole call ns. */
+int rtc_mcl_counters(const rtc_ctx* ctx, uint64_t out[10]);
+/* the column paths of the last rtc_mcl: bit 0 one wave, bit 1 a 256-lane workgroup, bit 2 the table in global memory */
+int rtc_mcl_last_path(const rtc_ctx* ctx);
+
 /* ---- clust-leiden --db --assign: new genomes placed into the communities of a finished run ------------------- */
 /* The move phase's choice for a vertex that was not there.  The reference has nothing of the kind: this is the definition
  * (tests/refleiden_assign.py restates it).

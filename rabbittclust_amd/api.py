@@ -40,6 +40,12 @@ NJOIN_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("c", "<u4"), ("pad", "<u4"), (
 NJ_PATH_WAVE, NJ_PATH_WORKGROUP, NJ_PATH_GRID = 1, 2, 4  # rtc_nj_last_path
 NJ_GRID_MIN = 256  # the library's default RTC_NJ_GRID_MIN (rtc_nj.hip: NJ_GRID_MIN)
 HEDGE_DT = np.dtype([("p", "<u4"), ("q", "<u4"), ("common", "<u4"), ("size_p", "<u4"), ("size_q", "<u4")])  # rtc_hedge
+MCL_ENTRY_DT = np.dtype([("col", "<u4"), ("row", "<u4"), ("value", "<u4"), ("pad", "<u4")])  # rtc_mcl_entry
+MCL_PATH_WAVE, MCL_PATH_WORKGROUP, MCL_PATH_GLOBAL = 1, 2, 4  # rtc_mcl_last_path
+# the column kernel's path boundaries (csrc/rtc_mcl.h): a column whose expansion gathers at most MCL_WAVE_WORK products takes one
+# wave, at most MCL_BLOCK_WORK a 256-lane workgroup, more the table in global memory
+MCL_WAVE_WORK = 256
+MCL_BLOCK_WORK = 3072
 
 
 def _np_ptr(a):
@@ -927,6 +933,45 @@ class Context:
         self.check(self.lib.rtc_leiden_counters(self.h, a))
         names = ("iterations", "levels", "move_rounds", "moves", "refine_rounds", "merges", "rejected", "move_ns", "refine_ns", "total_ns")
         return {k: int(a[i]) for i, k in enumerate(names)}
+
+    def mcl(self, n, edges, inflation=2.0, select=1024, max_iter=100, return_matrix=False):
+        """rtc_mcl: the Markov clustering include/rtclust.h defines in fixed point over n vertices and WEDGE_DT records (u, v, q).
+        inflation: a multiple of 0.5 from 1.5 to 8 (the library takes twice the value as an integer).  Returns int32 labels, every
+        vertex labelled by the smallest member of its cluster; with return_matrix (labels, matrix), the final matrix as
+        MCL_ENTRY_DT records in (col, row) order.  mcl_iterations, mcl_converged and mcl_clusters hold the rest of the result."""
+        h = int(round(float(inflation) * 2))
+        if h != float(inflation) * 2:
+            raise ValueError(f"inflation {inflation} is no multiple of 0.5")
+        e = np.ascontiguousarray(np.asarray(edges, dtype=WEDGE_DT))
+        labels = np.zeros(max(int(n), 1), dtype=np.int32)
+        ncl, its, nnz, conv = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_int(0)
+
+        def call(mat):
+            return self.lib.rtc_mcl(self.h, int(n), _np_ptr(e) if e.size else None, int(e.size), h, int(select), int(max_iter), _np_ptr(labels),
+                                    C.byref(ncl), C.byref(its), C.byref(conv), _np_ptr(mat) if mat is not None else None,
+                                    int(mat.size) if mat is not None else 0, C.byref(nnz))
+        mat = None
+        if return_matrix:  # room for what the columns can hold, up to 64 MiB; a larger matrix names its size and the call is repeated
+            mat = np.zeros(max(min(int(n) * min(int(select), max(int(n), 1)), 1 << 22), 1), dtype=MCL_ENTRY_DT)
+        st = call(mat)
+        if st == _lib.RTC_ERR_OVERFLOW and return_matrix and int(nnz.value) > mat.size:
+            mat = np.zeros(int(nnz.value), dtype=MCL_ENTRY_DT)
+            st = call(mat)
+        self.check(st)
+        self.mcl_clusters, self.mcl_iterations, self.mcl_converged = int(ncl.value), int(its.value), int(conv.value)
+        return (labels[:n].copy(), mat[:int(nnz.value)].copy()) if return_matrix else labels[:n].copy()
+
+    def mcl_counters(self):
+        """rtc_mcl_counters as a dict (the last mcl call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_mcl_counters(self.h, a))
+        names = ("iterations", "converged", "entries", "attractors", "wave_columns", "workgroup_columns", "global_columns", "cut_columns",
+                 "expand_ns", "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
+    def mcl_last_path(self):
+        """rtc_mcl_last_path: MCL_PATH_WAVE | MCL_PATH_WORKGROUP | MCL_PATH_GLOBAL, the column paths of the last mcl call"""
+        return int(self.lib.rtc_mcl_last_path(self.h))
 
     def linkage(self, keys, kmin=(0, 1)):
         """rtc_linkage_dev: the complete-linkage agglomeration include/rtclust.h defines over one symmetric m x m key matrix --

@@ -886,6 +886,11 @@ struct Options {
   bool has_resolution = false, louvain = false, leiden = false, has_pregraph = false, saveGraph = false;
   int knn = 0;
   string objective = "cpm";  // --objective, with --leiden: cpm as the reference calls igraph, or modularity
+  bool has_objective = false;
+  // clust-leiden --mcl: Markov clustering (rtc_mcl) as the third algorithm
+  bool mcl = false;
+  string inflation = "2.0", mclSelect = "1024", mclIterations = "100";  // as spelled: the refusals name them
+  const char* mclOnly = nullptr;  // the first of --inflation / --mcl-select / --mcl-iterations, which only --mcl gives a meaning
   bool hasDrlevel = false;
   string minhashOnly;        // clust-leiden: the first of -s / -c as spelled, which only --minhash gives a meaning
   bool linkageComplete = false;  // clust-mst --linkage complete: complete linkage inside every cluster (rtc_linkage_complete)
@@ -945,7 +950,11 @@ static Options parse(int argc, char** argv) {
     if (a == "--resolution") { o.resolution = atof(need(i)); o.has_resolution = true; continue; }
     if (a == "--louvain") { o.louvain = true; continue; }
     if (a == "--leiden") { o.leiden = true; continue; }
-    if (a == "--objective") { o.objective = need(i); continue; }
+    if (a == "--objective") { o.objective = need(i); o.has_objective = true; continue; }
+    if (a == "--mcl") { o.mcl = true; continue; }
+    if (a == "--inflation") { o.inflation = need(i); if (!o.mclOnly) o.mclOnly = "--inflation"; continue; }
+    if (a == "--mcl-select") { o.mclSelect = need(i); if (!o.mclOnly) o.mclOnly = "--mcl-select"; continue; }
+    if (a == "--mcl-iterations") { o.mclIterations = need(i); if (!o.mclOnly) o.mclOnly = "--mcl-iterations"; continue; }
     if (a == "--knn") { o.knn = atoi(need(i)); continue; }
     if (a == "--pregraph") { o.folder_path = need(i); o.has_pregraph = true; continue; }
     if (a == "--save-graph") { o.saveGraph = true; continue; }
@@ -1066,8 +1075,15 @@ static Options parse(int argc, char** argv) {
            "           normalised to [0, 1] when their range is below 0.5, the lightest edge dropping out.  Under cpm a --resolution\n"
            "           of 1 or more -- the default included -- moves nothing and leaves every genome in its own cluster, which is\n"
            "           what the reference's call does too: use --resolution below 1, or --objective modularity, to get clusters)\n"
+           "  --mcl (the third algorithm: Markov clustering in the fixed point of include/rtclust.h -- expansion, inflation and\n"
+           "         selection of the graph's flow matrix until it repeats; no objective and no resolution: not with --louvain,\n"
+           "         --leiden, --resolution, --objective or --db --build)\n"
+           "  --inflation X (with --mcl; default 2.0; a multiple of 0.5 between 1.5 and 8; higher: more clusters)\n"
+           "  --mcl-select S (with --mcl; default 1024; a column of the matrix keeps its S largest entries, 1 .. 4096)\n"
+           "  --mcl-iterations T (with --mcl; default 100; a run that has not converged by then warns and writes what it has)\n"
            "  --knn K (every genome keeps its K best edges among the higher-numbered genomes; 0 or absent: 1000 with --louvain, 500\n"
-           "           with --leiden; 1..9: 50 with a warning, as the reference defaults it, so the filter cannot be switched off)\n"
+           "           with --leiden and --mcl; 1..9: 50 with a warning, as the reference defaults it, so the filter cannot be\n"
+           "           switched off)\n"
            "  --save-graph (leiden.graph into the sketch folder: 'n m', then 'u v weight' per edge; the weights carry 6 significant\n"
            "                digits, so a --pregraph run is defined on the file's weights, not on the sketches')\n"
            "  --pregraph DIR (DIR/leiden.graph and the KSSD sketches of DIR -- with --minhash its MinHash sketches: the clustering\n"
@@ -2666,6 +2682,29 @@ int main(int argc, char** argv) {
     if (bad) { cerr << "ERROR: --minhash does not go with " << bad << endl; return 1; }
     if (!(o.threshold > 0.0 && o.threshold <= 1.0)) { cerr << "ERROR: --minhash needs 0 < -d/--threshold <= 1, got " << o.threshold << endl; return 1; }
   }
+  // ---- clust-leiden --mcl: the third algorithm has neither an objective nor a resolution, and the placement rule of --db is
+  // defined on modularity / CPM scores.  Beside --assign / --stats it has no effect, as --louvain / --leiden have none there.
+  int mcl_h = 4;
+  uint32_t mcl_select = 1024, mcl_iterations = 100;
+  if (!o.mcl && o.mclOnly) { cerr << "ERROR: " << o.mclOnly << " needs --mcl" << endl; return 1; }
+  if (o.mcl) {
+    const char* bad = o.louvain ? "--louvain" : o.leiden ? "--leiden" : o.has_resolution ? "--resolution" : o.has_objective ? "--objective"
+                      : o.db_build ? "--db --build" : nullptr;
+    if (bad) { cerr << "ERROR: --mcl does not go with " << bad << endl; return 1; }
+    char* end = nullptr;
+    const double x2 = strtod(o.inflation.c_str(), &end) * 2.0;
+    if (end == o.inflation.c_str() || *end || !(x2 >= 3.0 && x2 <= 16.0) || x2 != floor(x2)) {
+      cerr << "ERROR: --inflation must be a multiple of 0.5 between 1.5 and 8, got " << o.inflation << endl;
+      return 1;
+    }
+    mcl_h = (int)x2;
+    const long long sel = strtoll(o.mclSelect.c_str(), &end, 10);
+    if (end == o.mclSelect.c_str() || *end || sel < 1 || sel > 4096) { cerr << "ERROR: --mcl-select must be between 1 and 4096, got " << o.mclSelect << endl; return 1; }
+    mcl_select = (uint32_t)sel;
+    const long long its = strtoll(o.mclIterations.c_str(), &end, 10);
+    if (end == o.mclIterations.c_str() || *end || its < 0 || its > 0x7fffffffll) { cerr << "ERROR: --mcl-iterations must be 0 or more, got " << o.mclIterations << endl; return 1; }
+    mcl_iterations = (uint32_t)its;
+  }
   // ---- clust-leiden --db: the model file's flows, their flag errors first ----
   LeidenModel ld_model;
   {
@@ -2690,7 +2729,7 @@ int main(int argc, char** argv) {
     }
     if (o.db_assign) {
       // -k, -d, --resolution, --knn, --objective, --louvain and --leiden beside --assign have no effect: the model's hold
-      o.louvain = ld_model.algorithm == 0; o.leiden = !o.louvain;
+      o.louvain = ld_model.algorithm == 0; o.leiden = !o.louvain; o.mcl = false;
       o.objective = ld_model.objective == 0 ? "cpm" : "modularity";
       o.resolution = ld_model.resolution; o.has_resolution = false;
       o.threshold = ld_model.threshold; o.knn = ld_model.knn;
@@ -2700,9 +2739,9 @@ int main(int argc, char** argv) {
   }
   if (o.has_resolution) cerr << "-----Resolution parameter: " << o.resolution << endl;
   if (o.leiden && o.louvain) { cerr << "ERROR: --leiden and --louvain exclude each other" << endl; return 1; }
-  if (!o.louvain && !o.leiden) {
+  if (!o.louvain && !o.leiden && !o.mcl) {
     cerr << "ERROR: Leiden refinement is not in this build; run with --louvain" << endl;
-    cerr << "NOTE: the line above is kept for scripts that match it; name the algorithm: --leiden (the deterministic Leiden) or --louvain" << endl;
+    cerr << "NOTE: the line above is kept for scripts that match it; name the algorithm: --leiden (the deterministic Leiden), --louvain or --mcl (Markov clustering)" << endl;
     return 1;
   }
   if (o.objective != "cpm" && o.objective != "modularity") { cerr << "ERROR: --objective must be cpm or modularity, got " << o.objective << endl; return 1; }
@@ -2712,7 +2751,8 @@ int main(int argc, char** argv) {
   if (o.knn == 0 && o.louvain) { o.knn = 1000; cerr << "-----Auto-enabled: edge-parallel + warm-start + knn=" << o.knn << endl; }
   if (o.knn == 0) { o.knn = 500; cerr << "-----Auto-selecting k-NN: k=" << o.knn << " (use --knn 0 to disable)" << endl; }
   if (o.knn > 0 && o.knn < 10) { cerr << "WARNING: --knn value too small (" << o.knn << "), recommend at least 50. Using 50." << endl; o.knn = 50; }
-  cerr << (o.louvain ? "-----Algorithm: Louvain (Optimized)" : "-----Algorithm: Leiden") << endl;
+  if (o.mcl) cerr << "-----Algorithm: MCL (inflation " << mcl_h / 2.0 << ", select " << mcl_select << ")" << endl;
+  else cerr << (o.louvain ? "-----Algorithm: Louvain (Optimized)" : "-----Algorithm: Leiden") << endl;
   cerr << "  - k-NN filtering (k=" << o.knn << ")" << endl;
   vector<rtc_wedge> pregraph;
   vector<double> pregraph_weights;
@@ -3287,7 +3327,22 @@ int main(int argc, char** argv) {
   uint64_t lc[10] = {0};
   const size_t graph_edges = wedges.size();
   LeidenQuant quant;  // --louvain: modularity's, nothing scaled
-  if (o.leiden) {
+  uint32_t mcl_its = 0;
+  int mcl_converged = 0;
+  if (o.mcl) {
+    // --mcl: --louvain's records; the labels name a cluster by its smallest member, in rtc_louvain's cluster order
+    CHECK(ctx, rtc_mcl(ctx, n_nodes, wedges.data(), wedges.size(), mcl_h, mcl_select, mcl_iterations, labels.data(), &ncl, &mcl_its, &mcl_converged,
+                       nullptr, 0, nullptr));
+    rtc_mcl_counters(ctx, lc);
+    cerr << "-----MCL: " << mcl_its << " iteration(s), " << (mcl_converged ? "converged" : "NOT converged") << ", " << lc[3] << " attractor(s)" << endl;
+    if (!mcl_converged)
+      cerr << "-----Warning: MCL did not converge in " << mcl_iterations << " iteration(s) (--mcl-iterations); the clusters are those of the last matrix" << endl;
+    vector<int32_t> dense(n_nodes, -1);  // cluster c of the result: the c-th smallest label
+    int32_t next = 0;
+    for (uint32_t x = 0; x < n_nodes; x++)
+      if (labels[x] == (int32_t)x) dense[x] = next++;
+    for (uint32_t x = 0; x < n_nodes; x++) labels[x] = dense[labels[x]];
+  } else if (o.leiden) {
     // --leiden: q from the weights anew (CPM: normalised as src/leiden.cpp:343-366, the records at q == 0 dropped)
     const int objective = o.objective == "cpm" ? RTC_LEIDEN_CPM : RTC_LEIDEN_MODULARITY;
     vector<uint32_t> eu(graph_edges), ev(graph_edges);
@@ -3335,14 +3390,21 @@ int main(int argc, char** argv) {
   cerr << "========time of Leiden clustering is: " << get_sec() - t2 << "========" << endl;
   g_metrics.num("leiden_louvain_s", lc[9] / 1e9);  // the clustering call, whichever algorithm
   g_metrics.num("leiden_edges", (double)graph_edges);
-  g_metrics.num("leiden_levels", (double)(o.leiden ? lc[1] : lc[0]));
+  if (o.mcl) {
+    g_metrics.num("mcl_iterations", (double)mcl_its);
+    g_metrics.num("mcl_converged", (double)mcl_converged);
+    g_metrics.num("mcl_entries", (double)lc[2]);
+    g_metrics.num("mcl_expand_s", lc[8] / 1e9);
+  } else {
+    g_metrics.num("leiden_levels", (double)(o.leiden ? lc[1] : lc[0]));
+  }
   if (o.leiden) {
     g_metrics.num("leiden_refine_s", lc[8] / 1e9);
     g_metrics.num("leiden_iterations", (double)lc[0]);
     g_metrics.num("leiden_merges", (double)lc[5]);
   }
   g_metrics.num("leiden_clusters", (double)ncl);
-  g_metrics.num("leiden_modularity", modularity);
+  if (!o.mcl) g_metrics.num("leiden_modularity", modularity);
 #elif defined(DBSCAN_CLUST)
   // ---- clust-dbscan: KssdDBSCAN (src/dbscan.cpp:725-985) on the first GPU, printKssdDBSCANResult (:1212-1310); with
   // --minhash MinHashDBSCAN (:987-1096) and printDBSCANResult (:1102-1210), whose layout is the same ----

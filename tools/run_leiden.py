@@ -20,7 +20,13 @@ With --minhash the genomes are sketched with MinHash (-k 21, --sketch-size hashe
 and Louvain's, and beside them the counters of Context.dbscan_mash on the same sketches at eps = --threshold (min_pts 2), whose
 pair phase and merge kernel the graph shares.
 
-    python tools/run_leiden.py --minhash [--sketch-size 1000] [--threshold 0.05] [--knn 1000]"""
+    python tools/run_leiden.py --minhash [--sketch-size 1000] [--threshold 0.05] [--knn 1000]
+
+With --mcl it also runs the Markov clustering (Context.mcl) on Louvain's records of the same graph and prints its counter set,
+the column paths it took and the whole-call time of rtc_mcl beside rtc_louvain's (the best of --repeat calls each, after one
+call to warm up), and how many families came back whole.
+
+    python tools/run_leiden.py --mcl [--inflation 2.0] [--mcl-select 1024] [--mcl-iterations 100] [--repeat 3]"""
 import argparse
 import json
 import os
@@ -47,8 +53,12 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--minhash", action="store_true")
     ap.add_argument("--sketch-size", type=int, default=1000)
+    ap.add_argument("--mcl", action="store_true")
+    ap.add_argument("--inflation", type=float, default=2.0)
+    ap.add_argument("--mcl-select", type=int, default=1024)
+    ap.add_argument("--mcl-iterations", type=int, default=100)
     a = ap.parse_args()
-    if a.minhash and (a.leiden or a.assign):
+    if a.minhash and (a.leiden or a.assign or a.mcl):
         ap.error("--minhash prints the graph's and Louvain's counters alone")
     from rabbittclust_amd import api, host
     ctx = api.Context(0)
@@ -80,6 +90,17 @@ def main():
         out.update({"leiden": ctx.leiden_counters(), "leiden_objective": a.objective, "leiden_resolution": a.leiden_resolution,
                     "leiden_records": int(len(lrec)), "leiden_clusters": ctx.leiden_clusters, "leiden_quality": quality,
                     "louvain_call_ms": min(louvain_ns[1:]) / 1e6, "leiden_call_ms": min(leiden_ns[1:]) / 1e6})
+    if a.mcl:
+        louvain_ns, mcl_ns = [], []
+        for i in range(a.repeat + 1):  # the first call of each warms up
+            ctx.louvain(n, rec, a.resolution)
+            louvain_ns.append(ctx.louvain_counters()["total_ns"])
+            mlabels = ctx.mcl(n, rec, a.inflation, a.mcl_select, a.mcl_iterations)
+            mcl_ns.append(ctx.mcl_counters()["total_ns"])
+        whole = sum(1 for f in range(a.families) if len(set(mlabels[f * a.per_family:(f + 1) * a.per_family].tolist())) == 1)
+        out.update({"mcl": ctx.mcl_counters(), "mcl_paths": ctx.mcl_last_path(), "mcl_inflation": a.inflation, "mcl_select": a.mcl_select,
+                    "mcl_clusters": ctx.mcl_clusters, "mcl_families_whole": whole, "louvain_call_ms": min(louvain_ns[1:]) / 1e6,
+                    "mcl_call_ms": min(mcl_ns[1:]) / 1e6})
     if a.assign:
         out["assign"] = assign(ctx, a, sk, kmer, n)
     print(json.dumps(out))
