@@ -124,6 +124,11 @@ int rtc_sketch_minhash_packed_dev(rtc_ctx* ctx, const uint8_t* d_packed, uint64_
                                   const uint32_t* h_sizes, uint32_t size, uint64_t* d_out, uint32_t stride,
                                   uint32_t* d_cnt);
 
+/* What the two calls above plan for a batch whose largest sketch size is `size` at this k (both plan alike): workgroups
+ * per CU, whether the hash tables take the packed LDS layout, and the dynamic LDS of a workgroup.  Pure host arithmetic
+ * (tests and tuning ask it where a layout boundary lies); ctx may be NULL: the options are read from the environment. */
+int rtc_sketch_minhash_plan(rtc_ctx* ctx, int k, uint32_t size, int* wgs_per_cu, int* packed_tables, uint64_t* lds_bytes);
+
 /* ---- KSSD sketching (--fast) ------------------------------------------------------------- */
 /* Replaces the per-file body of sketchFileWithKssd (src/SketchInfo.cpp:994-1252): 2-bit rolling
  * k-mer (k rounded up to even, :1019-1020), canonical min, shuffled-dimension filter, dr_tuple,

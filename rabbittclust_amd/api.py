@@ -240,6 +240,12 @@ class Context:
         start = torch.arange(n, dtype=torch.int64, device=self.device) * stride
         return SketchSet(out.view(-1), start, cnt[:n], 8, k, "minhash")
 
+    def sketch_minhash_plan(self, k=21, size=1000):
+        """What the MinHash sketch calls plan for a largest sketch size `size`: dict(wgs_per_cu, packed_tables, lds_bytes)."""
+        wgs, pk, lds = C.c_int(0), C.c_int(0), C.c_uint64(0)
+        self.check(self.lib.rtc_sketch_minhash_plan(self.h, int(k), int(size), C.byref(wgs), C.byref(pk), C.byref(lds)))
+        return {"wgs_per_cu": wgs.value, "packed_tables": bool(pk.value), "lds_bytes": lds.value}
+
     def sketch_minhash_into(self, seq, off, out, cnt, k=21, size=1000, sizes=None, seed=42):
         """Same as sketch_minhash, into caller-provided rows: `out` (len(off)-1, stride) int64 and `cnt`
         int32 views (used by the multi-GPU step, which sketches in two parts so that the all-gather

@@ -24,8 +24,9 @@ __host__ __device__ constexpr int warm_dw(int kt) { return (kt > 0 && kt <= 21) 
 static_assert((RUN_DW + warm_dw(21)) % 4 == 0 && (RUN_DW + warm_dw(0)) % 4 == 0, "a lane's window must be whole 16-byte loads");
 constexpr int TILE_BASES = WG * RUN_DW * 4;           // bases per tile
 // Safe mode appends ONE k-mer per lane between two looks at the candidate count (four until round 5): the room the buffer
-// has to guarantee is a quarter, and a third workgroup per CU fits up to s = 3 318 at k = 21 (3 574 with the packed tables)
-// instead of 1 782 (2 038) -- clust-greedy's containment sketches of 2 - 3.5 Mbp genomes, and BASELINE config 4's sketches
+// has to guarantee is a quarter, and a third workgroup per CU fits up to s = 3 190 at k = 21 (3 574 with the packed tables;
+// 3 318 until the k2-type word's second-half table grew to 8-byte entries) instead of 1 782 (2 038) -- clust-greedy's
+// containment sketches of 2 - 3.5 Mbp genomes, and BASELINE config 4's sketches
 // no longer need the packed layout (its stride-16 reads cost bank conflicts): 115.6 -> 112.5 ms there, 85.8 -> 81.0 ms at s = 3000.
 constexpr int STEP_APPENDS = WG;                      // worst-case appends between two looks at the count in safe mode
 constexpr int MIN_ROOM = STEP_APPENDS;                // candidate room the buffer always offers
@@ -35,8 +36,17 @@ constexpr int QCAP = 32;                              // entries per wave
 constexpr int QDRAIN = 16;                            // drained at a tile end once this many wait
 constexpr size_t QUEUE_BYTES = (size_t)NWAVE * QCAP * 16;
 // hash tables in LDS (see kmer_hash_parts): per 8 bases of k one 256-entry table of 16-byte entries
-// (first four bases of the word) and, where the word has more than four bases, one of 4-byte entries
+// (first four bases of the word) and, where the word has more than four bases, one for its second four: 4-byte
+// entries lo(b * c) for the k1-type words (even w), 8-byte entries {lo(b * c), lo(b * c) * hi(2 c1)} for the k2-type
+// ones (odd w) -- the second dword is the part of word_k2's cross product that is linear in the table index
 constexpr size_t LUT_LO_BYTES = 256 * 16, LUT_HI_BYTES = 256 * 4;
+// second-half tables of the plain layout: offset of word w's behind the 16-byte tables (one unit per k1-type word
+// in front of it, two per k2-type one), and the bytes of the first `his` of them
+// (xt, "cross term tabulated": the compile-time-k kernels.  The runtime-k kernels keep 4-byte entries for every word and
+// multiply -- their general walk holds four k-mers' table words at once and spilt the extra dword inside its loop: k = 15
+// from packed bases 148.7 against 145.5 ms.  The host plans every launch with the larger tables.)
+__host__ __device__ constexpr size_t lut_hi_off(int w, bool xt = true) { return (size_t)(w + (xt ? w / 2 : 0)) * LUT_HI_BYTES; }
+__host__ __device__ constexpr size_t lut_hi_bytes(int his, bool xt = true) { return lut_hi_off(his, xt); }
 // A last word of at most five bases has a table of its own instead: 4^bases entries of 8 bytes holding the
 // finished contribution (at most 8 KiB), one ds_read_b64 and two VALU instructions for the word.
 __host__ __device__ constexpr int lut_words(int k) { return (k + 7) / 8; }
@@ -44,12 +54,13 @@ __host__ __device__ constexpr int lut_last_nb(int k) { return k - 8 * (lut_words
 __host__ __device__ constexpr bool lut_direct(int k) { return lut_last_nb(k) <= 5; }
 __host__ __device__ constexpr int lut_los(int k) { return lut_words(k) - (lut_direct(k) ? 1 : 0); }  // words with the table pair
 __host__ __device__ constexpr int lut_his(int k) { return lut_direct(k) ? lut_los(k) : (k + 3) / 8; }  // word w has a second half iff k > 8w + 4
-// Packed layout (pk): lo(b * c) of the 4-byte tables sits in the spare fourth dword of the 16-byte entries instead --
-// lut_his(k) KiB less LDS, stride-16 reads (more bank conflicts: the headline shape loses 1.9 %, k = 23 6.5 %).  The
-// launch picks it only where it buys a workgroup per CU (k = 21: 3318 < s <= 3574).
+// Packed layout (pk): lo(b * c) of the second-half tables sits in the spare fourth dword of the 16-byte entries instead
+// (there is no fifth for a k2-type word's cross term: that layout keeps the four-instruction word_k2) -- 1 KiB less LDS
+// per k1-type word and 2 per k2-type one, stride-16 reads (more bank conflicts: the headline shape loses 1.9 %,
+// k = 23 6.5 %).  The launch picks it only where it buys a workgroup per CU (k = 21: 3190 < s <= 3574).
 __host__ __device__ constexpr size_t lut_direct_bytes(int k) { return lut_direct(k) ? ((size_t)8 << (2 * lut_last_nb(k))) : 0; }
 __host__ __device__ constexpr size_t lut_bytes(int k, bool pk) {
-  return (size_t)lut_los(k) * LUT_LO_BYTES + (pk ? 0 : (size_t)lut_his(k) * LUT_HI_BYTES) + lut_direct_bytes(k);
+  return (size_t)lut_los(k) * LUT_LO_BYTES + (pk ? 0 : lut_hi_bytes(lut_his(k))) + lut_direct_bytes(k);
 }
 
 struct Segment {
@@ -86,6 +97,7 @@ typedef RTC_LDS Ctrl* lds_ctrl_ptr;
 typedef RTC_LDS unsigned char* lds_byte_ptr;
 struct MergeResult { uint32_t count; uint64_t T; };
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // plain vector (HIP's uint4 is a class, unusable through LDS pointers)
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 // ---- MurmurHash3_x64_128 (first output word) of the canonical k-mer's ASCII bytes ----------------
 // MurmurHash3 turns every 64-bit input word w into  rotl(w * c, r) * c'  (c, r, c' = c1, 31, c2 for the
@@ -155,6 +167,7 @@ __device__ __forceinline__ uint32_t hash_test_word(const HashParts& p) {
 }
 
 constexpr uint64_t MM_C1 = 0x87c37b91114253d5ULL, MM_C2 = 0x4cf5ad432745937fULL;
+constexpr uint32_t K2_CROSS = (uint32_t)((MM_C1 << 1) >> 32);  // hi(2 c1): the cross-product constant of a k2-type word (word_k2)
 constexpr uint32_t MASH_SEED = 42;  // the seed of every reference call site (Sketch::MinHash)
 
 __device__ __forceinline__ uint32_t codes_to_ascii(uint32_t e) {
@@ -171,20 +184,21 @@ struct KParams {
   int rc_shift;        // 2k - 2
   uint64_t kmask;      // low 2k bits
   bool packed;         // table layout, see lut_bytes
+  bool cross_tab;      // plain layout only: the k2-type words' cross term comes out of the tables (word_k2, lut_hi_off)
 };
 
-__device__ __forceinline__ KParams make_kparams(int k, uint32_t seed, bool packed) {
+__device__ __forceinline__ KParams make_kparams(int k, uint32_t seed, bool packed, bool cross_tab) {
   KParams P;
-  P.k = k; P.seed = seed; P.use64 = k > 16 ? 1u : 0u; P.packed = packed;
+  P.k = k; P.seed = seed; P.use64 = k > 16 ? 1u : 0u; P.packed = packed; P.cross_tab = cross_tab && !packed;
   P.lshift = 64 - 2 * k; P.rc_shift = 2 * k - 2;
   P.kmask = k == 32 ? ~0ULL : ((1ULL << (2 * k)) - 1);
   return P;
 }
 
 // Called by all WG threads; the first 256 fill one column each.  Layout: lut_los(k) tables of
-// {u64 P, u32 AH, pad} at w * LUT_LO_BYTES, then lut_his(k) tables of u32 BL, then the last word's own table
+// {u64 P, u32 AH, pad} at w * LUT_LO_BYTES, then lut_his(k) tables of u32 BL (even w) or {u32 BL, u32 BLc} (odd w), then the last word's own table
 // (lut_direct(k)): entry i = rotl(w * c, r) * c' of the word whose bases are the 2-bit codes of i.
-__device__ __forceinline__ void build_kmer_lut(lds_byte_ptr lut, int k, bool pk) {
+__device__ __forceinline__ void build_kmer_lut(lds_byte_ptr lut, int k, bool pk, bool xt) {
   const uint32_t e = threadIdx.x;
   if (e >= 256) return;
   const uint32_t a4 = codes_to_ascii(e);
@@ -192,7 +206,7 @@ __device__ __forceinline__ void build_kmer_lut(lds_byte_ptr lut, int k, bool pk)
   if (lut_direct(k)) {
     const int wl = lut_words(k) - 1, nb = lut_last_nb(k);
     typedef RTC_LDS uint64_t* lds_u64w_ptr;
-    const lds_u64w_ptr dt = (lds_u64w_ptr)(lut + hi_base + (pk ? 0 : (size_t)lut_his(k) * LUT_HI_BYTES));
+    const lds_u64w_ptr dt = (lds_u64w_ptr)(lut + hi_base + (pk ? 0 : lut_hi_bytes(lut_his(k), xt)));
     for (uint32_t i = e; i < (1u << (2 * nb)); i += 256) {
       const uint32_t e4 = nb >= 4 ? ((i >> (2 * nb - 8)) & 0xffu) : ((i << (8 - 2 * nb)) & 0xffu);   // first four bases, first on top
       const uint32_t am = nb >= 4 ? 0xffffffffu : ((1u << (8 * nb)) - 1u);
@@ -218,11 +232,22 @@ __device__ __forceinline__ void build_kmer_lut(lds_byte_ptr lut, int k, bool pk)
     typedef RTC_LDS u32x4* lds_u4_ptr;
     const uint32_t bm = nb >= 8 ? 0xffffffffu : (nb > 4 ? ((1u << (8 * (nb - 4))) - 1u) : 0u);
     const uint32_t BL = (a4 & bm) * (uint32_t)c;  // lo(b * c) of the word whose SECOND four bases are e's codes
-    const u32x4 ent = {(uint32_t)P, (uint32_t)(P >> 32), AH, pk ? BL : 0u};
+    // Plain layout, k2-type word: word_k2's cross product (AH + BL) * hi(2 c1) is linear in its two table indices
+    // mod 2^32 -- the AH term rides in P.hi (the v_mad_u64_u32's addend carries it), the BL term (of the same masked
+    // BL) beside BL.  The packed layout has no dword for the latter: its P.hi stays plain and its word_k2 multiplies.
+    const bool fold = (w & 1) && !pk && xt;
+    const uint32_t Phi = (uint32_t)(P >> 32) + (fold ? AH * K2_CROSS : 0u);
+    const u32x4 ent = {(uint32_t)P, Phi, AH, pk ? BL : 0u};
     *(lds_u4_ptr)(lut + (size_t)w * LUT_LO_BYTES + (size_t)e * 16) = ent;
     if (nb > 4 && !pk) {
-      typedef RTC_LDS uint32_t* lds_u32_ptr;
-      *(lds_u32_ptr)(lut + hi_base + (size_t)w * LUT_HI_BYTES + (size_t)e * 4) = BL;
+      if (fold) {
+        typedef RTC_LDS u32x2* lds_u2_ptr;
+        const u32x2 ent2 = {BL, BL * K2_CROSS};
+        *(lds_u2_ptr)(lut + hi_base + lut_hi_off(w, xt) + (size_t)e * 8) = ent2;
+      } else {
+        typedef RTC_LDS uint32_t* lds_u32_ptr;
+        *(lds_u32_ptr)(lut + hi_base + lut_hi_off(w, xt) + (size_t)e * 4) = BL;
+      }
     }
   }
 }
@@ -254,14 +279,21 @@ __device__ __forceinline__ uint64_t times5(uint64_t x) {
   return r;
 }
 
-// byte B of w, shifted left by `three` (the byte offset of a table entry), as one SDWA shift
-template <int B>
-__device__ __forceinline__ uint32_t byte_x8(uint32_t w, uint32_t three) {
+// byte B of w, shifted left by log2 of a table's entry size (the byte offset of a table entry), as one SDWA shift.  The
+// three shift amounts a k-mer's offsets need (16-, 4- and 8-byte entries) are the bytes of ONE register, picked by the
+// shift operand's own byte select: a register per amount was two for every kernel and would be three with the 8-byte
+// second-half tables, and these kernels sit at their 80-VGPR bound.
+constexpr uint32_t ENTRY_SHIFTS = 0x00030204u;
+enum EntryShift { SH16 = 0, SH4 = 1, SH8 = 2 };  // byte of ENTRY_SHIFTS
+template <int B, int S>
+__device__ __forceinline__ uint32_t byte_x8(uint32_t w, uint32_t shifts) {
   uint32_t r;
-  if (B == 0) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(r) : "v"(three), "v"(w));
-  if (B == 1) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(r) : "v"(three), "v"(w));
-  if (B == 2) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(r) : "v"(three), "v"(w));
-  if (B == 3) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(r) : "v"(three), "v"(w));
+#define RTC_SDWA_SHIFT(SS, BB) \
+  if (S == SS && B == BB) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_" #SS " src1_sel:BYTE_" #BB : "=v"(r) : "v"(shifts), "v"(w))
+  RTC_SDWA_SHIFT(0, 0); RTC_SDWA_SHIFT(0, 1); RTC_SDWA_SHIFT(0, 2); RTC_SDWA_SHIFT(0, 3);
+  RTC_SDWA_SHIFT(1, 0); RTC_SDWA_SHIFT(1, 1); RTC_SDWA_SHIFT(1, 2); RTC_SDWA_SHIFT(1, 3);
+  RTC_SDWA_SHIFT(2, 0); RTC_SDWA_SHIFT(2, 1); RTC_SDWA_SHIFT(2, 2); RTC_SDWA_SHIFT(2, 3);
+#undef RTC_SDWA_SHIFT
   return r;
 }
 
@@ -277,13 +309,24 @@ __device__ __forceinline__ uint64_t word_k1(const u32x4 e, uint32_t BL) {
   return __builtin_bit_cast(uint64_t, make_uint2((uint32_t)R, hi));
 }
 // rotl(S, 33) * c1 for a k2 word: (S.hi * c1) << 1 + P = S.hi * (2 c1 mod 2^64) + P, the table value as the
-// addend of the v_mad_u64_u32 and the constant's high word as one cross product
-__device__ __forceinline__ uint64_t word_k2(const u32x4 e, uint32_t BL) {
+// addend of the v_mad_u64_u32; the constant's high word is one cross product, S.hi * hi(2 c1) into the top word.
+// Only its low 32 bits count, and mod 2^32 it is linear in S.hi = AH + BL: AH * hi(2 c1) + BL * hi(2 c1), one table
+// index each.  The plain layout's tables hold both terms (build_kmer_lut: the first inside P.hi, the second as
+// bl.y beside BL), so the word is add, mad, add.  S.hi is still summed and still feeds the 64 x 32 product: no carry
+// to mend.  mul: the tables hold neither term, bl.y is not read, the sum is multiplied -- the packed layout, which has
+// no dword for the second term, and the runtime-k kernels (KParams::cross_tab, lut_hi_off).
+__device__ __forceinline__ uint64_t word_k2(const u32x4 e, const u32x2 bl, bool mul) {
   constexpr uint64_t C1X2 = MM_C1 << 1;
-  const uint32_t SH = e.z + BL;
+  const uint32_t SH = e.z + bl.x;
   const uint64_t R = (uint64_t)SH * (uint32_t)C1X2 + __builtin_bit_cast(uint64_t, make_uint2(e.x, e.y));  // v_mad_u64_u32
-  uint32_t cross = SH * (uint32_t)(C1X2 >> 32);
-  asm("" : "+v"(cross));  // keep it a v_mul_lo_u32 + v_add_u32: fused into a second v_mad_u64_u32 it costs two extra moves
+  uint32_t cross;
+  if (mul) {
+    cross = SH * K2_CROSS;
+    asm("" : "+v"(cross));  // keep it a v_mul_lo_u32 + v_add_u32: fused into a second v_mad_u64_u32 it costs two extra moves
+  } else {
+    cross = bl.y;
+    asm("" : "+v"(cross));  // keep it a v_add_u32 behind the mad: folded into the addend's high word it costs an add in front and moves
+  }
   return __builtin_bit_cast(uint64_t, make_uint2((uint32_t)R, (uint32_t)(R >> 32) + cross));
 }
 
@@ -292,7 +335,7 @@ __device__ __forceinline__ uint64_t word_k2(const u32x4 e, uint32_t BL) {
 // kmer_loads issues them (offsets + ds_read), kmer_hash_finish consumes them.
 struct KmerLoads {
   u32x4 e[4];       // 16-byte entries {P.lo, P.hi, AH, (BL)} of the words with a table pair
-  uint32_t bl[4];   // lo(b * c) of their second halves
+  u32x2 bl[4];      // x: lo(b * c) of their second halves; y: the k2-type words' cross term (plain layout: the two dwords of one ds_read_b64)
   uint64_t dt;      // the last word's own table entry (lut_direct)
 };
 // x: canonical k-mer, 2 bits per base, first base in the top bits (canon << (64 - 2k))
@@ -300,15 +343,15 @@ __device__ __forceinline__ KmerLoads kmer_loads(uint64_t x, const KParams& P) {
   const uint32_t hi = (uint32_t)(x >> 32), lo = (uint32_t)x;
   const int k = P.k;
   // the tables start at LDS address 0 (checked at kernel entry), so an LDS address is a table offset:
-  // entry offset = code byte << 4 (16-byte entries) or << 2 (4-byte entries), one SDWA shift each;
+  // entry offset = code byte << 4 (16-byte entries), << 3 (8-byte entries) or << 2 (4-byte entries), one SDWA shift each;
   // the table bases fold into the ds_read immediates
   typedef const RTC_LDS u32x4* lds_u4_cptr;
   typedef const RTC_LDS uint32_t* lds_u32_cptr;
-  const uint32_t four = 4, two = 2;
+  typedef const RTC_LDS u32x2* lds_u2_cptr;
+  const bool pk = P.packed, xt = P.cross_tab;
+  const uint32_t sh = pk ? 4u : ENTRY_SHIFTS;  // (a VGPR either way: SDWA takes no constants.  The packed layout has 16-byte entries only and picks byte 0: the parent's `four`)
   const uint32_t hi_base = (uint32_t)(lut_los(k) * LUT_LO_BYTES);
-  const bool pk = P.packed;
-  const uint32_t dt_base = hi_base + (pk ? 0u : (uint32_t)(lut_his(k) * LUT_HI_BYTES));
-  const uint32_t hsh = pk ? four : two;  // shift of the second-half offsets
+  const uint32_t dt_base = hi_base + (pk ? 0u : (uint32_t)lut_hi_bytes(lut_his(k), xt));
   // the last word's own table: its 2nb bits sit at the top of the word's 16-bit slot (whatever lies below them is
   // not part of the k-mer and is cut off), entry offset = field << 3
   typedef const RTC_LDS uint64_t* lds_u64_cptr;
@@ -316,18 +359,28 @@ __device__ __forceinline__ KmerLoads kmer_loads(uint64_t x, const KParams& P) {
 #define RTC_DT(H, odd) (*(lds_u64_cptr)(uintptr_t)(dt_base + ((odd) ? (__builtin_amdgcn_ubfe((H), 16 - 2 * dnb, 2 * dnb) << 3) \
                                                                      : (((H) >> (32 - 2 * dnb)) << 3))))
 #define RTC_LO(w, off) (*(lds_u4_cptr)(uintptr_t)((off) + (uint32_t)((w) * LUT_LO_BYTES)))
-#define RTC_HI(w, off) (*(lds_u32_cptr)(uintptr_t)((off) + (pk ? (uint32_t)((w) * LUT_LO_BYTES) + 12u : hi_base + (uint32_t)((w) * LUT_HI_BYTES))))
+#define RTC_HI(w, off) (*(lds_u32_cptr)(uintptr_t)((off) + (pk ? (uint32_t)((w) * LUT_LO_BYTES) + 12u : hi_base + (uint32_t)lut_hi_off(w, xt))))
+  // a k2-type word's second half: {BL, BLc} as one 8-byte read (plain layout), BL alone out of the 16-byte entry (packed)
+#define RTC_HI2(w, off) (!xt ? u32x2{RTC_HI(w, off), 0u} : *(lds_u2_cptr)(uintptr_t)((off) + hi_base + (uint32_t)lut_hi_off(w, true)))
+  // a second half's offset: its own entry size in the plain layout, the 16-byte entry's in the packed one
+#define RTC_OFF16(B, H) byte_x8<B, SH16>((H), sh)
+#define RTC_OFF(B, H, S) (pk ? RTC_OFF16(B, H) : byte_x8<B, S>((H), sh))
+#define RTC_OFF8X(B, H) (xt ? RTC_OFF(B, H, SH8) : RTC_OFF(B, H, SH4))  // a k2-type word's second half
   KmerLoads L = {};
   const int dw = lut_direct(k) ? lut_words(k) - 1 : -1;  // the word that has a table of its own
   if (dw == 0) L.dt = RTC_DT(hi, false);
-  else { L.e[0] = RTC_LO(0, byte_x8<3>(hi, four)); if (k > 4) L.bl[0] = RTC_HI(0, byte_x8<2>(hi, hsh)); }
+  else { L.e[0] = RTC_LO(0, RTC_OFF16(3, hi)); if (k > 4) L.bl[0].x = RTC_HI(0, RTC_OFF(2, hi, SH4)); }
   if (dw == 1) L.dt = RTC_DT(hi, true);
-  else if (k > 8) { L.e[1] = RTC_LO(1, byte_x8<1>(hi, four)); if (k > 12) L.bl[1] = RTC_HI(1, byte_x8<0>(hi, hsh)); }
+  else if (k > 8) { L.e[1] = RTC_LO(1, RTC_OFF16(1, hi)); if (k > 12) L.bl[1] = RTC_HI2(1, RTC_OFF8X(0, hi)); }
   if (dw == 2) L.dt = RTC_DT(lo, false);
-  else if (k > 16) { L.e[2] = RTC_LO(2, byte_x8<3>(lo, four)); if (k > 20) L.bl[2] = RTC_HI(2, byte_x8<2>(lo, hsh)); }
+  else if (k > 16) { L.e[2] = RTC_LO(2, RTC_OFF16(3, lo)); if (k > 20) L.bl[2].x = RTC_HI(2, RTC_OFF(2, lo, SH4)); }
   if (dw == 3) L.dt = RTC_DT(lo, true);
-  else if (k > 24) { L.e[3] = RTC_LO(3, byte_x8<1>(lo, four)); if (k > 28) L.bl[3] = RTC_HI(3, byte_x8<0>(lo, hsh)); }
+  else if (k > 24) { L.e[3] = RTC_LO(3, RTC_OFF16(1, lo)); if (k > 28) L.bl[3] = RTC_HI2(3, RTC_OFF8X(0, lo)); }
+#undef RTC_OFF8X
+#undef RTC_OFF
+#undef RTC_OFF16
 #undef RTC_LO
+#undef RTC_HI2
 #undef RTC_HI
 #undef RTC_DT
   return L;
@@ -346,13 +399,13 @@ __device__ __forceinline__ HashParts kmer_hash_finish(const KmerLoads& L, const 
     if (dw != 3 && k > 24) asm volatile("" :: "v"(L.e[3].w));
   }
   if (dw == 0) K0 = L.dt;
-  else K0 = word_k1(L.e[0], k > 4 ? L.bl[0] : 0u);
+  else K0 = word_k1(L.e[0], k > 4 ? L.bl[0].x : 0u);
   if (dw == 1) K1 = L.dt;
-  else if (k > 8) K1 = word_k2(L.e[1], k > 12 ? L.bl[1] : 0u);
+  else if (k > 8) K1 = word_k2(L.e[1], k > 12 ? L.bl[1] : u32x2{0u, 0u}, !P.cross_tab);
   if (dw == 2) K2 = L.dt;
-  else if (k > 16) K2 = word_k1(L.e[2], k > 20 ? L.bl[2] : 0u);
+  else if (k > 16) K2 = word_k1(L.e[2], k > 20 ? L.bl[2].x : 0u);
   if (dw == 3) K3 = L.dt;
-  else if (k > 24) K3 = word_k2(L.e[3], k > 28 ? L.bl[3] : 0u);
+  else if (k > 24) K3 = word_k2(L.e[3], k > 28 ? L.bl[3] : u32x2{0u, 0u}, !P.cross_tab);
   uint64_t h1 = P.seed, h2 = P.seed;
   uint64_t t0 = K0, t1 = K1;  // tail contributions
   if (k >= 16) {
@@ -979,6 +1032,34 @@ struct MinhashLaunch {     // one launch of the sketch kernel
   }
 #define RTC_PICK_K(KERN, K) case K: return packed ? KERN<K, true> : KERN<K, false>;
 
+// Candidate buffer of the sketch kernel: s entries + room, as large as the LDS share of a workgroup
+// allows at the best occupancy that still leaves MIN_ROOM (3, 2 or 1 workgroups per CU; the sort
+// works on the live count, so the capacity need not be a power of two), and the table layout that goes with it:
+// packed only where it buys a workgroup per CU.  At k = 21 the plain tables are 19 KiB (two 16-byte tables, 1 + 2 KiB
+// of second halves, the 8 KiB tail table) and three workgroups fit up to s = (53 248 - 19 456 - 80 - 4 096) / 8 - 512
+// = 3 190; the packed ones are 16 KiB and reach s = 3 574.  cap == 0: the chunk does not fit at all.
+constexpr uint32_t PASS_CHUNK = 6144;  // hashes one pass selects per genome (minhash_run)
+struct MinhashLayout { int cap, wgs_per_cu; bool packed; };
+inline MinhashLayout minhash_layout(const rtc_options& opt, int k, uint32_t chunk_max, size_t min_room) {
+  MinhashLayout lay{0, 1, false};
+  for (int wgs = 3; wgs >= 1 && lay.cap == 0; wgs--) {
+    // 52 / 78 / 156 KiB: measured on MI355X, a 53.3 KiB allocation no longer runs three workgroups per CU
+    const size_t share = ((size_t)156 * 1024 / wgs) & ~(size_t)2047;
+    for (int pk = 0; pk < 2 && lay.cap == 0; pk++) {
+      // (tests: both layouts are exercised for every k by forcing one of them; either gives the same sketches)
+      if (pk && (lut_his(k) == 0 || opt.sketch_no_packed)) break;
+      if (!pk && opt.sketch_packed && lut_his(k) > 0) continue;
+      const size_t fixed = lut_bytes(k, pk != 0) + ((sizeof(Ctrl) + 15) & ~(size_t)15) + QUEUE_BYTES;
+      // (round 1 measured ~3000 entries of room as the break-even against lost occupancy; with the merge sorting
+      // only the new candidates and the express walk a third workgroup per CU wins down to the minimum room:
+      // s = 2000 at 10 000 x 5 Mbp 114.5 -> 102.1 ms, the containment sketches of config 4 190 -> 164 ms)
+      const size_t want_room = min_room;  // what the kernel's safe mode may append between two looks at the count
+      if (share > fixed && (share - fixed) / 8 >= (size_t)chunk_max + want_room) lay = MinhashLayout{(int)((share - fixed) / 8), wgs, pk != 0};
+    }
+  }
+  return lay;
+}
+
 // tile_bases: bases a workgroup takes per tile (the unit the segment lengths are planned in); min_room: candidate slots the
 // kernel's buffer must offer beyond the sketch size.  prepare(MinhashPlanInfo)
 // and launch(MinhashLaunch) return a status; everything is enqueued on the context stream.
@@ -996,31 +1077,12 @@ int minhash_run(rtc_ctx* ctx, const uint64_t* h_off, uint32_t n, int k, const ui
   }
   // One pass selects up to CHUNK hashes per genome in LDS; larger sketches take ceil(s/CHUNK) passes
   // over ascending hash ranges (pass p admits only hashes above everything kept so far).
-  const uint32_t CHUNK = 6144;
+  const uint32_t CHUNK = PASS_CHUNK;
   const uint32_t chunk_max = std::min(smax, CHUNK);
   const uint32_t npass = smax == 0 ? 1 : (smax + CHUNK - 1) / CHUNK;
-  // Candidate buffer of the sketch kernel: s entries + room, as large as the LDS share of a workgroup
-  // allows at the best occupancy that still leaves MIN_ROOM (3, 2 or 1 workgroups per CU; the sort
-  // works on the live count, so the capacity need not be a power of two).  Partial-merge kernel:
-  // two s-lists.
-  int cap = 0, wgs_per_cu = 1;
-  bool packed = false;  // table layout (lut_bytes): packed only where it buys a workgroup per CU
-  int wgs_lo = 1, wgs_hi = 3;
-  for (int wgs = wgs_hi; wgs >= wgs_lo && cap == 0; wgs--) {
-    // 52 / 78 / 156 KiB: measured on MI355X, a 53.3 KiB allocation no longer runs three workgroups per CU
-    const size_t share = ((size_t)156 * 1024 / wgs) & ~(size_t)2047;
-    for (int pk = 0; pk < 2 && cap == 0; pk++) {
-    // (tests: both layouts are exercised for every k by forcing one of them; either gives the same sketches)
-    if (pk && (lut_his(k) == 0 || ctx->opt.sketch_no_packed)) break;
-    if (!pk && ctx->opt.sketch_packed && lut_his(k) > 0) continue;
-    const size_t fixed = lut_bytes(k, pk != 0) + ((sizeof(Ctrl) + 15) & ~(size_t)15) + QUEUE_BYTES;
-    // (round 1 measured ~3000 entries of room as the break-even against lost occupancy; with the merge sorting
-    // only the new candidates and the express walk a third workgroup per CU wins down to the minimum room:
-    // s = 2000 at 10 000 x 5 Mbp 114.5 -> 102.1 ms, the containment sketches of config 4 190 -> 164 ms)
-    const size_t want_room = min_room;  // what the kernel's safe mode may append between two looks at the count
-    if (share > fixed && (share - fixed) / 8 >= (size_t)chunk_max + want_room) { cap = (int)((share - fixed) / 8); wgs_per_cu = wgs; packed = pk != 0; }
-    }
-  }
+  const MinhashLayout lay = minhash_layout(ctx->opt, k, chunk_max, min_room);
+  const int cap = lay.cap, wgs_per_cu = lay.wgs_per_cu;
+  const bool packed = lay.packed;
   if (cap == 0) return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "sketch chunk %u does not fit the LDS", chunk_max);
   // partial-sketch merge: two lists fit 2*chunk_max; twice that lets the rank merge work out of place
   const int cap_merge = (int)std::max<uint32_t>(std::max<uint32_t>(2 * chunk_max, std::min<uint32_t>(4 * chunk_max, 16384)), 1024);

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(WG, 6) void sketch_minhash_kernel(const uint8_t* __
   // compile-time-k instantiations serve the reference's seed only (MASH_SEED, the launch sends any other seed to the
   // runtime-k kernel): as an inline constant the two seed xors per k-mer stay fast-class VALU (an SGPR source makes
   // v_xor_b32 a 4.4-cycle instruction, profiles/r03_valu_issue_cost2.txt)
-  const KParams P = make_kparams(k, KT > 0 ? MASH_SEED : seed, PK);
+  const KParams P = make_kparams(k, KT > 0 ? MASH_SEED : seed, PK, KT > 0);
   const int t = W.t;
   const uint32_t s = W.s;
   const bool fastroll = true;     // four bases per step: 64-bit extended windows for k <= 28, 128-bit ones above
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(WG, 6) void sketch_minhash_kernel(const uint8_t* __
   uint64_t Tstart = (pass_no == 0 && !redo) ? sg.t0 : SENT;
 restart:
   reset_ctrl(W, Tstart);
-  build_kmer_lut(W.lut, k, PK);
+  build_kmer_lut(W.lut, k, PK, P.cross_tab);
   __syncthreads();
 
   uint64_t T = uniform64(Tstart);  // scalar registers: the threshold compares write wave masks directly
@@ -254,6 +254,18 @@ extern "C" int rtc_sketch_minhash_dev(rtc_ctx* ctx, const uint8_t* d_seq, const 
     return RTC_OK;
   };
   return minhash_run(ctx, h_off, n, k, h_sizes, size, d_out, stride, d_cnt, (uint64_t)TILE_BASES, (size_t)MIN_ROOM, prepare, launch);
+}
+
+extern "C" int rtc_sketch_minhash_plan(rtc_ctx* ctx, int k, uint32_t size, int* wgs_per_cu, int* packed_tables, uint64_t* lds_bytes) {
+  if (k < 1 || k > 32) return ctx ? rtc_fail(ctx, RTC_ERR_ARG, "k=%d outside 1..32", k) : RTC_ERR_ARG;
+  rtc_options env;
+  if (!ctx) rtc_options_from_env(&env);
+  const MinhashLayout lay = minhash_layout(ctx ? ctx->opt : env, k, std::min(size, PASS_CHUNK), (size_t)MIN_ROOM);
+  if (lay.cap == 0) return ctx ? rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "sketch chunk %u does not fit the LDS", std::min(size, PASS_CHUNK)) : RTC_ERR_UNSUPPORTED;
+  if (wgs_per_cu) *wgs_per_cu = lay.wgs_per_cu;
+  if (packed_tables) *packed_tables = lay.packed ? 1 : 0;
+  if (lds_bytes) *lds_bytes = (uint64_t)lay.cap * 8 + lut_bytes(k, lay.packed) + ((sizeof(Ctrl) + 15) & ~(size_t)15) + QUEUE_BYTES;
+  return RTC_OK;
 }
 
 namespace { __global__ void touch_unit_kernel() {} }

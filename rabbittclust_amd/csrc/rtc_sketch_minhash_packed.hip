@@ -79,7 +79,7 @@ __device__ __forceinline__ void undefined_loads(KmerLoads& L) {
 #pragma unroll
   for (int w = 0; w < 4; w++) {
     asm("" : "=v"(L.e[w].x), "=v"(L.e[w].y), "=v"(L.e[w].z), "=v"(L.e[w].w));
-    asm("" : "=v"(L.bl[w]));
+    asm("" : "=v"(L.bl[w].x), "=v"(L.bl[w].y));
   }
   asm("" : "=v"(L.dt));
 }
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(WG, 6) void sketch_minhash_packed_kernel(PackedIn B
   uint64_t lo1;  // later passes of a large sketch: only hashes from lo1 up (0: the first pass)
   if (!pass_gate(sg, pass_no, redo, cnt, out, pcnt, lo1)) return;  // workgroup-uniform
   lo1 = uniform64(lo1);
-  const KParams P = make_kparams(k, KT > 0 ? MASH_SEED : seed, PK);  // compile-time k serves the reference's seed only
+  const KParams P = make_kparams(k, KT > 0 ? MASH_SEED : seed, PK, KT > 0);  // compile-time k serves the reference's seed only
   const uint32_t lane = W.lane;
   const int wv = (int)uniform32((uint32_t)(W.t >> 6));
   const uint32_t s = W.s;
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(WG, 6) void sketch_minhash_packed_kernel(PackedIn B
   uint64_t Tstart = (pass_no == 0 && !redo) ? sg.t0 : SENT;  // starting threshold (segment plan); lifted if it proves too optimistic
 restart:
   reset_ctrl(W, Tstart);
-  build_kmer_lut(W.lut, k, PK);
+  build_kmer_lut(W.lut, k, PK, P.cross_tab);
   __syncthreads();
 
   uint64_t T = uniform64(Tstart);

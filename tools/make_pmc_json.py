@@ -64,13 +64,10 @@ for name in want:
         k["hbm_bytes_per_launch"] = (2.0 * k["FETCH_SIZE_per_launch"] + k["WRITE_SIZE_per_launch"]) * 1024.0
     if name in ("sketch_minhash_kernel", "sketch_minhash_packed_kernel", "sketch_kssd") and "SQ_INSTS_VALU_per_launch" in k:
         steps = G * L / 64.0
-        k["derived"] = {
-            "kmer_wave_steps": steps,
-            "valu_insts_per_step": k["SQ_INSTS_VALU_per_launch"] / steps,
-            "salu_insts_per_step": k.get("SQ_INSTS_SALU_per_launch", 0) / steps,
-            "lds_insts_per_step": k.get("SQ_INSTS_LDS_per_launch", 0) / steps,
-            "wave_cycles_per_step": k.get("SQ_WAVE_CYCLES_per_launch", 0) / steps,
-        }
+        k["derived"] = {"kmer_wave_steps": steps, "valu_insts_per_step": k["SQ_INSTS_VALU_per_launch"] / steps}
+        for fig, ctr in (("salu_insts_per_step", "SQ_INSTS_SALU"), ("lds_insts_per_step", "SQ_INSTS_LDS"), ("wave_cycles_per_step", "SQ_WAVE_CYCLES")):
+            if ctr + "_per_launch" in k:  # a pass that did not collect the counter has no such figure (not a zero)
+                k["derived"][fig] = k[ctr + "_per_launch"] / steps
     out["kernels"][name] = k
 if "synth_kernel" in out["kernels"] and "WRITE_SIZE_per_launch" in out["kernels"]["synth_kernel"]:
     out["write_size_calibration"] = {"synth_bytes_written": float(G) * L,
