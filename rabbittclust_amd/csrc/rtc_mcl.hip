@@ -24,7 +24,6 @@
 namespace {
 
 constexpr uint64_t MCL_ONE = 1ull << 30;
-constexpr uint32_t MCL_GOLDEN = 2654435761u;
 // the state words of a call on the device
 enum { MCL_CHANGED = 0, MCL_LIST0 = 1, MCL_CUT = 4, MCL_TOO_LARGE = 5, MCL_STATE_WORDS = 8 };
 
@@ -415,7 +414,7 @@ extern "C" int rtc_mcl(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, uint6
     const uint32_t stride = std::min(select, n);
     const int all_global = ctx->opt.mcl_global;
     // the global tables: one per workgroup of the long launch, for the largest column there can be
-    const uint32_t long_wgs = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->num_cu * 4);
+    const uint32_t long_wgs = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->num_cu * MCL_GLOBAL_WGS_PER_CU);
     uint32_t gtab_log2 = MCL_GLOBAL_LOG2_MIN;
     while (gtab_log2 < 31 && (1ull << gtab_log2) < 2 * std::min<uint64_t>((uint64_t)stride * stride, n)) gtab_log2++;
     const uint64_t mat_bytes = 16ull * n * stride, tab_bytes = 12ull * long_wgs << gtab_log2, small_bytes = 28ull * n + 4096;
@@ -455,7 +454,7 @@ extern "C" int rtc_mcl(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, uint6
       RTC_CHECK_LAUNCH(ctx);
       RTC_TRY(L.build(n, E0, &E));
       RTC_HIP(ctx, hipMemsetAsync(d_state, 0, sizeof state, s));
-      hipLaunchKernelGGL(mcl_start_kernel, dim3(std::min<uint32_t>(n, (uint32_t)ctx->num_cu * 8)), dim3(256), 0, s, (const uint64_t*)L.row_off,
+      hipLaunchKernelGGL(mcl_start_kernel, dim3(std::min<uint32_t>(n, (uint32_t)ctx->num_cu * MCL_START_WGS_PER_CU)), dim3(256), 0, s, (const uint64_t*)L.row_off,
                          (const uint64_t*)L.key, (const uint64_t*)L.w, n, stride, select, A, d_state);
       RTC_CHECK_LAUNCH(ctx);
       RTC_HIP(ctx, hipMemcpyAsync(state, d_state, sizeof state, hipMemcpyDeviceToHost, s));
@@ -472,11 +471,11 @@ extern "C" int rtc_mcl(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, uint6
                          d_list[0], d_list[1], d_list[2], d_state);
       RTC_CHECK_LAUNCH(ctx);
       RTC_HIP(ctx, hipEventRecord(ev.a, s));
-      hipLaunchKernelGGL((mcl_column_kernel<64, MCL_WAVE_SLOTS>), dim3(std::min<uint32_t>(n, (uint32_t)ctx->num_cu * 32)), dim3(64), 0, s,
+      hipLaunchKernelGGL((mcl_column_kernel<64, MCL_WAVE_SLOTS>), dim3(std::min<uint32_t>(n, (uint32_t)ctx->num_cu * MCL_WAVE_WGS_PER_CU)), dim3(64), 0, s,
                          (const uint32_t*)d_list[0], (const uint32_t*)(d_state + MCL_LIST0), *M, *N, n, stride, select, inflation_x2,
                          (const uint32_t*)d_work, (uint32_t*)nullptr, (unsigned long long*)nullptr, 0u, d_state);
       RTC_CHECK_LAUNCH(ctx);
-      hipLaunchKernelGGL((mcl_column_kernel<256, MCL_BLOCK_SLOTS>), dim3(std::min<uint32_t>(n, (uint32_t)ctx->num_cu * 3)), dim3(256), 0, s,
+      hipLaunchKernelGGL((mcl_column_kernel<256, MCL_BLOCK_SLOTS>), dim3(std::min<uint32_t>(n, (uint32_t)ctx->num_cu * MCL_BLOCK_WGS_PER_CU)), dim3(256), 0, s,
                          (const uint32_t*)d_list[1], (const uint32_t*)(d_state + MCL_LIST0 + 1), *M, *N, n, stride, select, inflation_x2,
                          (const uint32_t*)d_work, (uint32_t*)nullptr, (unsigned long long*)nullptr, 0u, d_state);
       RTC_CHECK_LAUNCH(ctx);

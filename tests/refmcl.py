@@ -67,7 +67,12 @@ def inflate(e1, h):
 
 
 def iterate(M, h, S):
-    N = []
+    return iterate_counting(M, h, S)[0]
+
+
+def iterate_counting(M, h, S):
+    """-> (the next matrix, the columns that select cut: those with more than S rows alive after the inflation)"""
+    N, cut = [], 0
     for j in range(len(M)):
         s = {}
         for k, pkj in M[j].items():
@@ -83,8 +88,9 @@ def iterate(M, h, S):
             yi = inflate(ei * ONE // E, h)
             if yi:
                 y[i] = yi
+        cut += len(y) > S
         N.append(select(y.items(), S))
-    return N
+    return N, cut
 
 
 def clusters(M):

@@ -80,6 +80,13 @@ def test_constants_agree_with_the_header():
     from rabbittclust_amd import api
     assert (api.MCL_WAVE_WORK, api.MCL_BLOCK_WORK) == S.boundaries()
     assert api.MCL_WAVE_WORK < api.MCL_BLOCK_WORK
+    # what the turn sets are built from: the tables' sizes, the hash's multiplier and the launches' workgroups a CU.  A change
+    # of one of these asks for the sets to be sized again.
+    c = S.constants()
+    assert (c["MCL_WAVE_SLOTS"], c["MCL_BLOCK_SLOTS"], c["MCL_GLOBAL_LOG2_MIN"], c["MCL_GOLDEN"]) == (512, 4096, 10, 2654435761)
+    assert S.grids(S.CUS, S.TURNS_N) == (8 * S.CUS, 32 * S.CUS, 3 * S.CUS, 4 * S.CUS)
+    assert S.grids(2, 5) == (5, 5, 5, 5)
+    assert not set(S.turn_sets()) & set(S.every_set())
 
 
 def test_boundary_sets_hold_the_three_works():
@@ -139,6 +146,95 @@ def test_fallback_rule_without_convergence():
     n, rec, sel = S.path9()
     labels, iterations, converged, M = R.mcl(n, rec, 4, sel, 2)
     assert (iterations, converged) == (2, 0) and labels == R.clusters(M)
+
+
+# ---- the turn sets hold their cases (tests/test_gpu_mcl_turns.py runs them) ----
+def test_turn_sets_give_every_launch_more_columns_than_workgroups():
+    """on the 256 CUs of an MI355X: more vertices than mcl_start_kernel has workgroups, in every early iteration more wave
+    columns than the wave launch has workgroups and more workgroup columns than the workgroup launch has, and at S = 8
+    every column on the wave path, a good part of them cut"""
+    T = S.turn_sets()
+    wave_work, block_work = S.boundaries()
+    start, wave, block, glob = S.grids(S.CUS, S.TURNS_N)
+    n, rec, sel = T["turns_10k"]
+    assert n == S.TURNS_N > start and sel == 1024
+    mats, _ = S.trajectory("turns_10k", 4, T, upto=3)
+    counts = [S.path_counts(M) for M in mats[:3]]  # of the iterations 1, 2 and 3
+    assert all(sum(c) == n for c in counts)
+    assert counts[0][0] > wave and counts[0][1] > block and counts[0][2] == 0
+    for c in counts[1:]:
+        assert c[0] > wave and c[1] > block and 0 < c[2] < glob  # the global launch takes a second turn under the switch only,
+    assert n > glob                                             # where it gets all n columns
+    assert S.cuts("turns_10k", 4, 3, T) == 0
+    # from the second iteration the global columns take tables of more than one size, the largest there is among them; under
+    # the switch the others take the smallest
+    for M in mats[1:3]:
+        W = S.work(M)
+        sizes = {S.table_log2(w, n, sel) for w in W if w > block_work}
+        assert len(sizes) > 1 and max(sizes) == 15 and min(sizes) > 10
+        assert all(2 * min(w, n) > 1024 for w in W if w > block_work)
+        assert {S.table_log2(w, n, sel) for w in W} >= sizes | {10}
+    assert T["turns_10k_s8"][:2] == (n, rec) and T["turns_10k_s8"][2] == 8
+    mats8, _ = S.trajectory("turns_10k_s8", 4, T, upto=3)
+    assert all(S.path_counts(M) == (n, 0, 0) for M in mats8[:3]) and n > wave
+    cut = [S.cuts("turns_10k_s8", 4, t, T) for t in range(4)]
+    assert cut[0] > 1000 and all(b - a > 1000 for a, b in zip(cut, cut[1:]))
+    assert all(len(col) <= 8 for M in mats8 for col in M) and not any(len(col) == 0 for M in mats + mats8 for col in M)
+
+
+def test_wrap_cliques_run_off_the_last_slot():
+    """the row set of every column of the two wrap cliques, put into its table by linear probing: slot 0 ends up holding a
+    row whose home is among the table's last slots -- in the LDS table of its path and in the smallest global table"""
+    T = S.turn_sets()
+    wave_work, block_work = S.boundaries()
+    wave_ids, block_ids = S.wrap_ids()
+    assert len(wave_ids) == 12 and len(block_ids) == 18 and not set(wave_ids) & set(block_ids)
+    assert max(wave_ids + block_ids) < S.TURNS_N
+    # (log2 of the table's slots, the slots at its end that hold the homes); at S = 8 every column takes the wave table
+    for name, cases in (("turns_10k", ((wave_ids, ((9, 4), (10, 8))), (block_ids, ((12, 8), (10, 8))))),
+                        ("turns_10k_s8", ((wave_ids, ((9, 4),)), (block_ids, ((9, 4),))))):
+        M = S.trajectory(name, 4, T, upto=0)[0][0]
+        for ids, tables in cases:
+            for j in ids:
+                rows = set().union(*(M[k] for k in M[j]))  # the rows that column j's expansion reaches in the first iteration
+                W = sum(len(M[k]) for k in M[j])
+                if name == "turns_10k":
+                    assert rows == set(ids) and W == len(ids) ** 2
+                    assert W <= wave_work if ids is wave_ids else wave_work < W <= block_work
+                else:
+                    assert rows <= set(ids) and len(rows) >= 8 and W <= wave_work
+                for log2, tail in tables:
+                    slots = S.probe_fill(sorted(rows), log2)
+                    assert sorted(slots.values()) == sorted(rows)
+                    assert (1 << log2) - 1 in slots and 0 in slots and S.home(slots[0], log2) >= (1 << log2) - tail, (name, j, log2)
+
+
+def test_hub_300_is_cut_among_equals_past_one_turn_of_the_lanes():
+    T = S.turn_sets()
+    n, rec, _ = T["hub_300_s64"]
+    assert T["hub_300_s1024"][:2] == (n, rec)
+    adj = R.adjacency(n, rec)
+    hub = S.HUB_300
+    assert len(adj[hub]) == 300 > 256  # the lanes of mcl_start_kernel
+    keys = sorted(list(adj[hub].items()) + [(hub, max(adj[hub].values()))], key=lambda e: (-e[1], e[0]))
+    assert keys[63][1] == keys[64][1] and keys[63][0] < keys[64][0]  # the 64th and the 65th differ by the row alone
+    assert sorted(R.start(n, rec, 64)[hub]) == sorted(i for i, _ in keys[:64]) and hub in R.start(n, rec, 64)[hub]
+    assert len(R.start(n, rec, 1024)[hub]) == 301
+    assert (S.cuts("hub_300_s64", 4, 0, T), S.cuts("hub_300_s1024", 4, 0, T)) == (1, 0)
+    assert S.cuts("hub_300_s64", 4, 1, T) > 1 and S.cuts("hub_300_s1024", 4, 1, T) == 0
+
+
+@pytest.mark.parametrize("h", range(6, 17))
+def test_high_inflation_leaves_no_column_empty(h):
+    """inflation 3 to 8: the product loop of mcl_inflate takes two to seven turns.  The largest entry of a column inflates to
+    ONE, so no column empties and every set reaches its fixed point.  One turn of the loop fewer gives another matrix after the
+    first iteration already (but for the clique of equal weights, whose entries all are the largest), so a kernel that took
+    a wrong number of turns would not meet the restatement."""
+    for name in S.HIGH_INFLATION_SETS:
+        mats, converged = S.trajectory(name, h)
+        assert converged and len(mats) >= 2, name
+        assert all(col for M in mats for col in M), name
+        assert mats[1] != S.trajectory(name, h - 2)[0][1] or name == "tied_clique_s8", name
 
 
 # ---- the command line ----

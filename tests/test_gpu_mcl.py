@@ -27,9 +27,9 @@ def _got(ctx, n, rec, h, sel, T):
     return labels.tolist(), ctx.mcl_iterations, ctx.mcl_converged, list(zip(mat["col"].tolist(), mat["row"].tolist(), mat["value"].tolist()))
 
 
-def _check(ctx, name, h, T, rec=None):
-    n, records, sel = S.every_set()[name]
-    want = S.expected(name, h, T)
+def _check(ctx, name, h, T, rec=None, sets=None):
+    n, records, sel = (sets or S.every_set())[name]
+    want = S.expected(name, h, T, sets)
     got = _got(ctx, n, records if rec is None else rec, h, sel, T)
     assert got[3] == want[3], (name, h, T)
     assert got[:3] == want[:3], (name, h, T)
