@@ -1,9 +1,10 @@
 // rtc_dbscan_assign.hip -- clust-dbscan --db --assign: new points placed into a clustered sketch set by DBSCAN's border rule
 // (include/rtclust.h defines the rule).  The set on the device is the model's rows [0, n_db) followed by the
-// queries' rows, the layout of rtc_rep_topk.  A chunk of queries goes through four steps on the device:
-//   1. join     rtc_pair_edges_join with the columns [0, n_db) only: (n_db + q, p, common) for every pair that shares a hash.
-//               Queries never see each other.
-//   2. bucket   count (tk_count_kernel), scan (tk_scan_kernel), scatter: a record (p, common, denom, in N(q)) per candidate into
+// queries' rows, the layout of rtc_rep_topk.  A chunk of queries (for_query_chunks, rtc_query_chunks.h) goes through four steps
+// on the device:
+//   1. join     query_candidates: rtc_pair_edges_join with the columns [0, n_db) only, (n_db + q, p, common) for every pair that
+//               shares a hash.  Queries never see each other.
+//   2. bucket   query_segments (count, scan), then the scatter: a record (p, common, denom, in N(q)) per candidate into
 //               its query's segment.  The scatter evaluates the model's predicate -- KSSD: eps_level_mask at one level, the
 //               predicate block of rtc_dbscan's filter; MinHash: the wave-cooperative truncated merge (mash_merge_wave) and one
 //               level's cmin table, without a prefilter because `nearest` needs every candidate's counts.  The atomic order of
@@ -11,13 +12,13 @@
 //   3. fold     a workgroup per query -- one wave for segments of up to AS_WAVE_TILE records, 256 lanes for the longer ones --
 //               strides over the segment; every lane keeps the neighbour count, the core count, min / max label over the core
 //               neighbours and its best record under rtc_rep_topk's exact order, and cross-lane shuffles (then four partials in
-//               LDS) reduce them.  No atomics on a query's record: a query inside a family of 1 000 would serialise them.
-//               min / max / sum are order-free and the order of the records is total, so the result is the same for every
-//               scatter order.
+//               LDS) reduce them: tk_fold_segment (rtc_topk_select.h) over AsFold.  No atomics on a query's record: a query
+//               inside a family of 1 000 would serialise them.  min / max / sum are order-free and the order of the records
+//               is total, so the result is the same for every scatter order.
 //   4. read     the chunk's fixed-size records.
 // A chunk whose candidates exceed the edge budget or whose join scratch does not fit is halved; RTC_ERR_NOMEM past one query.
 #include "rtc_dbscan_mash.h"
-#include "rtc_topk_select.h"
+#include "rtc_query_chunks.h"
 
 namespace {
 
@@ -84,18 +85,30 @@ __global__ __launch_bounds__(64) void as_mash_scatter_kernel(const T* __restrict
   }
 }
 
-// What a lane, a wave and then the workgroup hold of a query's segment
+// What a lane, a wave and then the workgroup hold of a query's segment (tk_fold_segment's F)
 struct AsFold {
   uint32_t nn, nc;     // |N(q)|, the core points among them
   int32_t lmin, lmax;  // over the core points of N(q)
   TkRec best;          // over every candidate
+  __device__ __forceinline__ void take(const TkRec& x, const int32_t* __restrict__ labels, const uint8_t* __restrict__ core) {
+    if (x.pad & 1u) {
+      nn++;
+      if (core[x.slot]) {
+        const int32_t l = labels[x.slot];
+        nc++;
+        lmin = l < lmin ? l : lmin;
+        lmax = l > lmax ? l : lmax;
+      }
+    }
+    if (tk_beats(x, best)) best = x;
+  }
+  __device__ __forceinline__ void merge(const AsFold& b) {
+    nn += b.nn; nc += b.nc;
+    lmin = b.lmin < lmin ? b.lmin : lmin;
+    lmax = b.lmax > lmax ? b.lmax : lmax;
+    if (tk_beats(b.best, best)) best = b.best;
+  }
 };
-__device__ __forceinline__ void as_merge(AsFold& a, const AsFold& b) {
-  a.nn += b.nn; a.nc += b.nc;
-  a.lmin = b.lmin < a.lmin ? b.lmin : a.lmin;
-  a.lmax = b.lmax > a.lmax ? b.lmax : a.lmax;
-  if (tk_beats(b.best, a.best)) a.best = b.best;
-}
 
 // a workgroup of B lanes per query whose segment length lies in [lo, hi].  need: q would be a core point with that many neighbours.
 template <int B>
@@ -110,34 +123,7 @@ __global__ __launch_bounds__(B) void as_fold_kernel(const TkRec* __restrict__ se
   // no candidate: denom 1 keeps the key 0 / 1 below every real record's.  A MinHash candidate whose truncated common is 0 has
   // that key too and must still win: equal keys go to the lower index, and every real slot is below AS_NONE because
   // rtc_dbscan_assign refuses n_db + n_queries >= 2^31 - 1.
-  AsFold f{0, 0, 0x7fffffff, -1, TkRec{AS_NONE, 0, 1, 0}};
-  for (uint64_t idx = s0 + threadIdx.x; idx < s1; idx += B) {
-    const TkRec x = seg[idx];
-    if (x.pad & 1u) {
-      f.nn++;
-      if (core[x.slot]) {
-        const int32_t l = labels[x.slot];
-        f.nc++;
-        f.lmin = l < f.lmin ? l : f.lmin;
-        f.lmax = l > f.lmax ? l : f.lmax;
-      }
-    }
-    if (tk_beats(x, f.best)) f.best = x;
-  }
-  for (int d = 32; d; d >>= 1) {
-    AsFold o;
-    o.nn = __shfl_xor(f.nn, d); o.nc = __shfl_xor(f.nc, d);
-    o.lmin = __shfl_xor(f.lmin, d); o.lmax = __shfl_xor(f.lmax, d);
-    o.best.slot = __shfl_xor(f.best.slot, d); o.best.common = __shfl_xor(f.best.common, d);
-    o.best.denom = __shfl_xor(f.best.denom, d); o.best.pad = 0;
-    as_merge(f, o);
-  }
-  if (B > 64) {
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = f;
-    __syncthreads();
-    if (threadIdx.x == 0)
-      for (int w = 1; w < B / 64; w++) as_merge(f, part[w]);
-  }
+  const AsFold f = tk_fold_segment<B>(seg, s0, s1, AsFold{0, 0, 0x7fffffff, -1, TkRec{AS_NONE, 0, 1, 0}}, part, labels, core);
   if (threadIdx.x == 0) {
     rtc_dbscan_place r;
     const bool none = f.best.slot == AS_NONE;
@@ -164,73 +150,37 @@ struct AsStats { uint64_t candidates = 0, merged = 0, asym = 0, first_asym = ~0u
 int assign_chunk(rtc_ctx* ctx, const AsArgs& A, const std::vector<uint32_t>& h_len, uint32_t q0, uint32_t q1, rtc_dbscan_place* h_out,
                  AsStats* st) {
   const uint32_t R = A.n_db, row0 = R + q0, row1 = R + q1, nq = q1 - q0;
-  uint64_t k_cols = 0, k_rows = 0;
-  for (uint32_t g = 0; g < R; g++) k_cols += h_len[g];
-  for (uint32_t g = row0; g < row1; g++) k_rows += h_len[g];
-  if (R == 0 || k_cols == 0 || k_rows == 0) return RTC_OK;  // nothing can share a hash (the join declines such sets)
+  if (query_rows_alone(h_len, R, row0, row1)) return RTC_OK;
   hipStream_t s = ctx->stream;
   DevBuf db;
   const uint64_t t0 = now_ns();
-  // ---- 1. candidates (row, p, common) from the join; the list is grown to the count when it was too short ----
+  // ---- 1. candidates (row, p, common) from the join ----
   rtc_cedge* d_edges = nullptr;
-  unsigned long long* d_m = nullptr;
-  RTC_TRY(db.get(ctx, 2, &d_m));
-  uint64_t cap = std::min<uint64_t>(A.budget, std::max<uint64_t>(1u << 16, (uint64_t)nq * 64)), m = 0;
-  for (int attempt = 0; attempt < 3; attempt++) {
-    if (d_edges) db.release(d_edges);
-    RTC_TRY(db.get(ctx, cap, &d_edges));
-    RTC_HIP(ctx, hipMemsetAsync(d_m, 0, 16, s));
-    int handled = 0;
-    RTC_TRY(rtc_pair_edges_join(ctx, A.d_hashes, A.width, A.d_start, A.d_len, A.n, row0, row1, 0, R, -1, d_edges, cap, (uint64_t*)d_m, -1.0,
-                                &handled));
-    if (!handled) return rtc_fail(ctx, RTC_ERR_NOMEM, "rtc_dbscan_assign: the join's scratch does not fit %u queries", nq);
-    RTC_HIP(ctx, hipMemcpyAsync(&m, d_m, 8, hipMemcpyDeviceToHost, s));
-    RTC_HIP(ctx, hipStreamSynchronize(s));
-    if (m <= cap) break;
-    if (m > A.budget)
-      return rtc_fail(ctx, RTC_ERR_NOMEM, "rtc_dbscan_assign: %llu candidates of %u queries, edge budget %llu", (unsigned long long)m, nq,
-                      (unsigned long long)A.budget);
-    cap = std::max<uint64_t>(m, std::min<uint64_t>(A.budget, m + m / 8));
-    m = 0;
-    if (attempt == 2) return rtc_fail(ctx, RTC_ERR_OVERFLOW, "rtc_dbscan_assign: candidate list kept growing");
-  }
+  uint64_t m = 0;
+  RTC_TRY(query_candidates(ctx, db, "rtc_dbscan_assign", A.d_hashes, A.width, A.d_start, A.d_len, A.n, row0, row1, R, A.budget, &d_edges, &m));
   const uint64_t t1 = now_ns();
   st->join_ns += t1 - t0;
   if (m == 0) return RTC_OK;
   // ---- 2. count, scan, predicate + scatter ----
-  uint32_t* d_cnt = nullptr;  // counts, then the scatter's cursors
-  uint64_t* d_off = nullptr;  // off[nq + 1], koff[nq + 1] (tk_scan_kernel's second sum, unused here)
-  RTC_TRY(db.get(ctx, (size_t)nq * 2, &d_cnt));
-  RTC_TRY(db.get(ctx, (size_t)(nq + 1) * 2, &d_off));
-  uint32_t* d_cur = d_cnt + nq;
-  RTC_HIP(ctx, hipMemsetAsync(d_cnt, 0, (size_t)nq * 8, s));
-  const uint32_t blocks = (uint32_t)((m + 255) / 256);
-  hipLaunchKernelGGL(tk_count_kernel, dim3(blocks), dim3(256), 0, s, (const rtc_cedge*)d_edges, m, row0, nq, R, (const uint8_t*)nullptr, d_cnt);
-  RTC_CHECK_LAUNCH(ctx);
-  hipLaunchKernelGGL(tk_scan_kernel, dim3(1), dim3(TK_SCAN_THREADS), 0, s, (const uint32_t*)d_cnt, nq, 0u, d_off, d_off + nq + 1);
-  RTC_CHECK_LAUNCH(ctx);
-  std::vector<uint32_t> h_cnt(nq);
-  uint64_t T = 0;
-  RTC_HIP(ctx, hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-  RTC_HIP(ctx, hipMemcpyAsync(&T, d_off + nq, 8, hipMemcpyDeviceToHost, s));
-  RTC_HIP(ctx, hipStreamSynchronize(s));
-  st->candidates += T;
-  if (T == 0) return RTC_OK;
+  QuerySegments S;
+  RTC_TRY(query_segments(ctx, db, d_edges, m, row0, nq, R, nullptr, 0u, &S));
+  st->candidates += S.T;
+  if (S.T == 0) return RTC_OK;
   TkRec* d_seg = nullptr;
-  RTC_TRY(db.get(ctx, T, &d_seg));
+  RTC_TRY(db.get(ctx, S.T, &d_seg));
   unsigned long long fc[4] = {0ull, 0ull, ~0ull, 0ull};
   RTC_HIP(ctx, hipMemcpyAsync(A.d_fc, fc, sizeof fc, hipMemcpyHostToDevice, s));
   if (A.minhash) {
     const dim3 g(mash_blocks(m, ctx->num_cu)), b(64);
     if (A.width == 8)
       hipLaunchKernelGGL(as_mash_scatter_kernel<uint64_t>, g, b, 0, s, (const uint64_t*)A.d_hashes, A.d_start, A.d_len, A.sketch_size,
-                         (const rtc_cedge*)d_edges, m, row0, nq, R, A.d_cmin, A.D, (const uint64_t*)d_off, d_cur, d_seg, A.d_fc);
+                         (const rtc_cedge*)d_edges, m, row0, nq, R, A.d_cmin, A.D, (const uint64_t*)S.d_off, S.d_cur, d_seg, A.d_fc);
     else
       hipLaunchKernelGGL(as_mash_scatter_kernel<uint32_t>, g, b, 0, s, (const uint32_t*)A.d_hashes, A.d_start, A.d_len, A.sketch_size,
-                         (const rtc_cedge*)d_edges, m, row0, nq, R, A.d_cmin, A.D, (const uint64_t*)d_off, d_cur, d_seg, A.d_fc);
+                         (const rtc_cedge*)d_edges, m, row0, nq, R, A.d_cmin, A.D, (const uint64_t*)S.d_off, S.d_cur, d_seg, A.d_fc);
   } else {
-    hipLaunchKernelGGL(as_kssd_scatter_kernel, dim3(blocks), dim3(256), 0, s, (const rtc_cedge*)d_edges, m, row0, nq, R, A.d_len, A.lv, A.sat,
-                       (const uint64_t*)d_off, d_cur, d_seg, A.d_fc);
+    hipLaunchKernelGGL(as_kssd_scatter_kernel, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, s, (const rtc_cedge*)d_edges, m, row0, nq, R, A.d_len, A.lv, A.sat,
+                       (const uint64_t*)S.d_off, S.d_cur, d_seg, A.d_fc);
   }
   RTC_CHECK_LAUNCH(ctx);
   RTC_HIP(ctx, hipMemcpyAsync(fc, A.d_fc, sizeof fc, hipMemcpyDeviceToHost, s));
@@ -243,16 +193,16 @@ int assign_chunk(rtc_ctx* ctx, const AsArgs& A, const std::vector<uint32_t>& h_l
   st->bucket_ns += t2 - t1;
   // ---- 3. fold, 4. the records ----
   uint64_t n_long = 0, n_short = 0;
-  for (uint32_t q = 0; q < nq; q++) { n_long += h_cnt[q] > AS_WAVE_TILE; n_short += h_cnt[q] && h_cnt[q] <= AS_WAVE_TILE; }
+  for (uint32_t q = 0; q < nq; q++) { n_long += S.h_cnt[q] > AS_WAVE_TILE; n_short += S.h_cnt[q] && S.h_cnt[q] <= AS_WAVE_TILE; }
   rtc_dbscan_place* d_out = nullptr;
   RTC_TRY(db.get(ctx, nq, &d_out));
   if (n_long < nq) {
-    hipLaunchKernelGGL(as_fold_kernel<64>, dim3(nq), dim3(64), 0, s, (const TkRec*)d_seg, (const uint64_t*)d_off, nq, 0u, AS_WAVE_TILE, A.d_labels,
+    hipLaunchKernelGGL(as_fold_kernel<64>, dim3(nq), dim3(64), 0, s, (const TkRec*)d_seg, (const uint64_t*)S.d_off, nq, 0u, AS_WAVE_TILE, A.d_labels,
                        A.d_core, A.need, d_out);
     RTC_CHECK_LAUNCH(ctx);
   }
   if (n_long) {
-    hipLaunchKernelGGL(as_fold_kernel<256>, dim3(nq), dim3(256), 0, s, (const TkRec*)d_seg, (const uint64_t*)d_off, nq, AS_WAVE_TILE + 1, 0xffffffffu,
+    hipLaunchKernelGGL(as_fold_kernel<256>, dim3(nq), dim3(256), 0, s, (const TkRec*)d_seg, (const uint64_t*)S.d_off, nq, AS_WAVE_TILE + 1, 0xffffffffu,
                        A.d_labels, A.d_core, A.need, d_out);
     RTC_CHECK_LAUNCH(ctx);
   }
@@ -332,24 +282,19 @@ extern "C" int rtc_dbscan_assign(rtc_ctx* ctx, const void* d_hashes, int width, 
     A.d_cmin = mt.d_cmin; A.D = mt.D;
   }
   AsStats st;
+  AsStats before;
   uint64_t chunks = 0;
-  uint32_t chunk = query_chunk ? std::min(query_chunk, n_queries) : n_queries;
-  for (uint32_t q0 = 0; q0 < n_queries;) {
-    const uint32_t q1 = std::min(n_queries, q0 + chunk);
-    const AsStats before = st;
-    const int rc = assign_chunk(ctx, A, h_len, q0, q1, h_out + q0, &st);
-    if (rc == RTC_ERR_NOMEM && q1 - q0 > 1) {  // half the queries: fewer candidates, a smaller join
-      st = before;
-      std::fill(h_out + q0, h_out + q1, none);
-      chunk = std::max<uint32_t>(1, (q1 - q0) / 2);
-      ctx->err.clear();
-      (void)hipGetLastError();
-      continue;
-    }
-    if (rc != RTC_OK) return rc;
-    chunks++;
-    q0 = q1;
-  }
+  RTC_TRY(for_query_chunks(
+      ctx, n_queries, query_chunk,
+      [&](uint32_t q0, uint32_t q1) {
+        before = st;
+        return assign_chunk(ctx, A, h_len, q0, q1, h_out + q0, &st);
+      },
+      [&](uint32_t q0, uint32_t q1) {
+        st = before;
+        std::fill(h_out + q0, h_out + q1, none);
+      },
+      &chunks));
   if (st.asym)
     return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "%s: %llu pairs whose eps test depends on the orientation, e.g. (query %u, model point %u)", who,
                     (unsigned long long)st.asym, (uint32_t)(st.first_asym >> 32) - n_db, (uint32_t)st.first_asym);

@@ -127,20 +127,26 @@ __global__ __launch_bounds__(256) void posting_rows_kernel(const uint64_t* __res
   }
 }
 
-struct DevBuf {  // hipMalloc'd scratch released on every way out
+struct DevBuf {  // hipMalloc'd scratch released on every way out; the context's free-memory figure stays current, as with rtc_dev_alloc / rtc_dev_free
+  rtc_ctx* ctx = nullptr;
   std::vector<void*> p;
-  ~DevBuf() { for (void* q : p) (void)hipFree(q); }
-  template <class T> int get(rtc_ctx* ctx, size_t count, T** out) {
+  ~DevBuf() {
+    for (void* q : p) (void)hipFree(q);
+    if (ctx) ctx->free_hbm_at = -1.0;
+  }
+  template <class T> int get(rtc_ctx* c, size_t count, T** out) {
     void* q = nullptr;
     const hipError_t e = hipMalloc(&q, std::max<size_t>(count * sizeof(T), 256));
-    if (e != hipSuccess) return rtc_fail(ctx, RTC_ERR_NOMEM, "rtc_dbscan: %zu bytes: %s", count * sizeof(T), hipGetErrorString(e));
+    if (e != hipSuccess) return rtc_fail(c, RTC_ERR_NOMEM, "device scratch: %zu bytes: %s", count * sizeof(T), hipGetErrorString(e));
     p.push_back(q);
+    ctx = c;
     ctx->free_hbm_at = -1.0;
     *out = (T*)q;
     return RTC_OK;
   }
   void release(void* q) {
     for (auto& x : p) if (x == q) { (void)hipFree(x); x = nullptr; }
+    if (ctx) ctx->free_hbm_at = -1.0;
   }
 };
 

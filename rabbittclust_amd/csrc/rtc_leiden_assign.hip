@@ -3,13 +3,14 @@
 // rtc_graph_build, weights, rtc_louvain.
 //
 // rtc_graph_query: the set on the device is the model's rows [0, n_db) followed by the queries' rows, the layout of
-// rtc_rep_topk.  A chunk of queries goes through five steps on the device:
-//   1. join     rtc_pair_edges_join with the columns [0, n_db) only, as rtc_dbscan_assign's step 1.
-//   2. bucket   tk_count_kernel and tk_scan_kernel: the segment of every query.
+// rtc_rep_topk.  A chunk of queries (for_query_chunks, rtc_query_chunks.h) goes through five steps on the device:
+//   1. join     query_candidates: rtc_pair_edges_join with the columns [0, n_db) only.
+//   2. bucket   query_segments: the segment of every query.
 //   3. scatter  a lane per candidate evaluates rtc_graph_build's edge rule, writes (p, common, union, pass) into the query's
 //               segment and appends the passing ones, with their query, to one list (wave_append).  A workgroup per query then
 //               folds the segment -- one wave up to TK_LONG records, 256 lanes beyond -- into the passing count and the nearest
-//               candidate by cross-lane shuffles, as as_fold_kernel does: no atomics on a query's record.
+//               candidate by cross-lane shuffles (tk_fold_segment over LqFold, as as_fold_kernel over AsFold): no atomics on a
+//               query's record.
 //   4. select   knn_k is typically 500 or 1 000, past what the running selection of rtc_topk_select.h holds (TK_KMAX = 256: two
 //               tables and a tile of 16-byte records in LDS, and every survivor of a tile ranked against every other one, k
 //               comparisons a record).  So the passing list is sorted once by (q, rank, p) with the exact comparator -- the
@@ -21,7 +22,7 @@
 // rtc_leiden_place: the records (query, model genome, q) become a CSR by one radix sort and one reduce_by_key (equal pairs
 // summed), the rows are split by length as a level's rows are (RowPaths) and leiden_place_kernel (rtc_community.h) scores them.
 #include "rtc_community.h"
-#include "rtc_topk_select.h"
+#include "rtc_query_chunks.h"
 
 namespace {
 
@@ -57,43 +58,36 @@ __global__ __launch_bounds__(256) void lq_scatter_kernel(const rtc_cedge* __rest
   }
 }
 
+// What a lane, a wave and then the workgroup hold of a query's segment (tk_fold_segment's F)
+struct LqFold {
+  TkRec best;   // over every candidate
+  uint32_t np;  // the passing ones
+  __device__ __forceinline__ void take(const TkRec& x) {
+    np += x.pad & 1u;
+    if (tk_beats(x, best)) best = x;
+  }
+  __device__ __forceinline__ void merge(const LqFold& b) {
+    np += b.np;
+    if (tk_beats(b.best, best)) best = b.best;
+  }
+};
+
 // a workgroup of B lanes per query whose segment length lies in [lo, hi]
 template <int B>
 __global__ __launch_bounds__(B) void lq_fold_kernel(const TkRec* __restrict__ seg, const uint64_t* __restrict__ off, uint32_t nq, uint32_t lo,
                                                     uint32_t hi, rtc_graph_near* __restrict__ out) {
-  __shared__ TkRec part[B > 64 ? B / 64 : 1];
-  __shared__ uint32_t part_n[B > 64 ? B / 64 : 1];
+  __shared__ LqFold part[B > 64 ? B / 64 : 1];
   const uint32_t q = blockIdx.x;
   if (q >= nq) return;
   const uint64_t s0 = off[q], s1 = off[q + 1];
   if (s1 - s0 < lo || s1 - s0 > hi) return;  // uniform across the workgroup
-  TkRec best{LQ_NONE, 0, 1, 0};  // key 0 / 1: below every candidate's, each shares a hash
-  uint32_t np = 0;
-  for (uint64_t idx = s0 + threadIdx.x; idx < s1; idx += B) {
-    const TkRec x = seg[idx];
-    np += x.pad & 1u;
-    if (tk_beats(x, best)) best = x;
-  }
-  for (int d = 32; d; d >>= 1) {
-    TkRec o;
-    o.slot = __shfl_xor(best.slot, d); o.common = __shfl_xor(best.common, d); o.denom = __shfl_xor(best.denom, d); o.pad = 0;
-    np += __shfl_xor(np, d);
-    if (tk_beats(o, best)) best = o;
-  }
-  if (B > 64) {
-    if ((threadIdx.x & 63) == 0) { part[threadIdx.x >> 6] = best; part_n[threadIdx.x >> 6] = np; }
-    __syncthreads();
-    if (threadIdx.x == 0)
-      for (int w = 1; w < B / 64; w++) {
-        np += part_n[w];
-        if (tk_beats(part[w], best)) best = part[w];
-      }
-  }
+  // key 0 / 1: below every candidate's, each shares a hash
+  const LqFold f = tk_fold_segment<B>(seg, s0, s1, LqFold{TkRec{LQ_NONE, 0, 1, 0}, 0}, part);
   if (threadIdx.x == 0) {
-    const bool none = best.slot == LQ_NONE;
+    const bool none = f.best.slot == LQ_NONE;
     rtc_graph_near r;
-    r.nearest = best.slot; r.common = none ? 0u : best.common; r.denom = none ? 0u : best.denom;
-    r.n_candidates = (uint32_t)(s1 - s0); r.n_passing = np; r.n_kept = np;
+    r.nearest = f.best.slot; r.common = none ? 0u : f.best.common; r.denom = none ? 0u : f.best.denom;
+    r.n_candidates = (uint32_t)(s1 - s0); r.n_passing = f.np; r.n_kept = f.np;
     out[q] = r;
   }
 }
@@ -165,56 +159,21 @@ int query_chunk_run(rtc_ctx* ctx, const LqArgs& A, const std::vector<uint32_t>& 
                     std::vector<rtc_qedge>* edges, LqStats* st) {
   const char* who = "rtc_graph_query";
   const uint32_t R = A.n_db, row0 = R + q0, row1 = R + q1, nq = q1 - q0;
-  uint64_t k_cols = 0, k_rows = 0;
-  for (uint32_t g = 0; g < R; g++) k_cols += h_len[g];
-  for (uint32_t g = row0; g < row1; g++) k_rows += h_len[g];
-  if (R == 0 || k_cols == 0 || k_rows == 0) return RTC_OK;  // nothing can share a hash (the join declines such sets)
+  if (query_rows_alone(h_len, R, row0, row1)) return RTC_OK;
   hipStream_t s = ctx->stream;
   DevBuf db;
   const uint64_t t0 = now_ns();
-  // ---- 1. candidates (row, p, common) from the join; the list is grown to the count when it was too short ----
+  // ---- 1. candidates (row, p, common) from the join ----
   rtc_cedge* d_edges = nullptr;
-  unsigned long long* d_m = nullptr;
-  RTC_TRY(db.get(ctx, 2, &d_m));
-  uint64_t cap = std::min<uint64_t>(A.budget, std::max<uint64_t>(1u << 16, (uint64_t)nq * 64)), m = 0;
-  for (int attempt = 0; attempt < 3; attempt++) {
-    if (d_edges) db.release(d_edges);
-    RTC_TRY(db.get(ctx, cap, &d_edges));
-    RTC_HIP(ctx, hipMemsetAsync(d_m, 0, 16, s));
-    int handled = 0;
-    RTC_TRY(rtc_pair_edges_join(ctx, A.d_hashes, A.width, A.d_start, A.d_len, A.n, row0, row1, 0, R, -1, d_edges, cap, (uint64_t*)d_m, -1.0,
-                                &handled));
-    if (!handled) return rtc_fail(ctx, RTC_ERR_NOMEM, "%s: the join's scratch does not fit %u queries", who, nq);
-    RTC_HIP(ctx, hipMemcpyAsync(&m, d_m, 8, hipMemcpyDeviceToHost, s));
-    RTC_HIP(ctx, hipStreamSynchronize(s));
-    if (m <= cap) break;
-    if (m > A.budget)
-      return rtc_fail(ctx, RTC_ERR_NOMEM, "%s: %llu candidates of %u queries, edge budget %llu", who, (unsigned long long)m, nq,
-                      (unsigned long long)A.budget);
-    cap = std::max<uint64_t>(m, std::min<uint64_t>(A.budget, m + m / 8));
-    m = 0;
-    if (attempt == 2) return rtc_fail(ctx, RTC_ERR_OVERFLOW, "%s: candidate list kept growing", who);
-  }
+  uint64_t m = 0;
+  RTC_TRY(query_candidates(ctx, db, who, A.d_hashes, A.width, A.d_start, A.d_len, A.n, row0, row1, R, A.budget, &d_edges, &m));
   const uint64_t t1 = now_ns();
   st->join_ns += t1 - t0;
   if (m == 0) return RTC_OK;
   // ---- 2. count, scan; 3. edge rule + scatter, fold ----
-  uint32_t* d_cnt = nullptr;  // counts, then the scatter's cursors
-  uint64_t* d_off = nullptr;  // off[nq + 1], koff[nq + 1] (tk_scan_kernel's second sum, unused here)
-  RTC_TRY(db.get(ctx, (size_t)nq * 2, &d_cnt));
-  RTC_TRY(db.get(ctx, (size_t)(nq + 1) * 2, &d_off));
-  uint32_t* d_cur = d_cnt + nq;
-  RTC_HIP(ctx, hipMemsetAsync(d_cnt, 0, (size_t)nq * 8, s));
-  const uint32_t blocks = (uint32_t)((m + 255) / 256);
-  hipLaunchKernelGGL(tk_count_kernel, dim3(blocks), dim3(256), 0, s, (const rtc_cedge*)d_edges, m, row0, nq, R, (const uint8_t*)nullptr, d_cnt);
-  RTC_CHECK_LAUNCH(ctx);
-  hipLaunchKernelGGL(tk_scan_kernel, dim3(1), dim3(TK_SCAN_THREADS), 0, s, (const uint32_t*)d_cnt, nq, 0u, d_off, d_off + nq + 1);
-  RTC_CHECK_LAUNCH(ctx);
-  std::vector<uint32_t> h_cnt(nq);
-  uint64_t T = 0;
-  RTC_HIP(ctx, hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-  RTC_HIP(ctx, hipMemcpyAsync(&T, d_off + nq, 8, hipMemcpyDeviceToHost, s));
-  RTC_HIP(ctx, hipStreamSynchronize(s));
+  QuerySegments S;
+  RTC_TRY(query_segments(ctx, db, d_edges, m, row0, nq, R, nullptr, 0u, &S));
+  const uint64_t T = S.T;
   st->candidates += T;
   if (T == 0) return RTC_OK;
   TkRec* d_seg = nullptr;
@@ -224,18 +183,18 @@ int query_chunk_run(rtc_ctx* ctx, const LqArgs& A, const std::vector<uint32_t>& 
   unsigned long long fc[2] = {0ull, 0ull};
   RTC_HIP(ctx, hipMemcpyAsync(A.d_fc, fc, sizeof fc, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(lq_scatter_kernel, dim3(blocks_for(m, ctx->num_cu)), dim3(256), 0, s, (const rtc_cedge*)d_edges, m, row0, nq, q0, R, A.d_len,
-                     A.jstar, (const uint64_t*)d_off, d_cur, d_seg, d_pass, T, A.d_fc);
+                     A.jstar, (const uint64_t*)S.d_off, S.d_cur, d_seg, d_pass, T, A.d_fc);
   RTC_CHECK_LAUNCH(ctx);
   uint64_t n_long = 0;
-  for (uint32_t q = 0; q < nq; q++) n_long += h_cnt[q] > TK_LONG;
+  for (uint32_t q = 0; q < nq; q++) n_long += S.h_cnt[q] > TK_LONG;
   rtc_graph_near* d_near = nullptr;
   RTC_TRY(db.get(ctx, nq, &d_near));
   if (n_long < nq) {
-    hipLaunchKernelGGL(lq_fold_kernel<64>, dim3(nq), dim3(64), 0, s, (const TkRec*)d_seg, (const uint64_t*)d_off, nq, 0u, TK_LONG, d_near);
+    hipLaunchKernelGGL(lq_fold_kernel<64>, dim3(nq), dim3(64), 0, s, (const TkRec*)d_seg, (const uint64_t*)S.d_off, nq, 0u, TK_LONG, d_near);
     RTC_CHECK_LAUNCH(ctx);
   }
   if (n_long) {
-    hipLaunchKernelGGL(lq_fold_kernel<256>, dim3(nq), dim3(256), 0, s, (const TkRec*)d_seg, (const uint64_t*)d_off, nq, TK_LONG + 1, 0xffffffffu,
+    hipLaunchKernelGGL(lq_fold_kernel<256>, dim3(nq), dim3(256), 0, s, (const TkRec*)d_seg, (const uint64_t*)S.d_off, nq, TK_LONG + 1, 0xffffffffu,
                        d_near);
     RTC_CHECK_LAUNCH(ctx);
   }
@@ -319,26 +278,22 @@ extern "C" int rtc_graph_query(rtc_ctx* ctx, const void* d_hashes, int width, co
   RTC_TRY(db.get(ctx, 2, &A.d_fc));
   LqStats st;
   std::vector<rtc_qedge> edges;
+  LqStats before;
+  size_t had = 0;
   uint64_t chunks = 0;
-  uint32_t chunk = query_chunk ? std::min(query_chunk, n_queries) : n_queries;
-  for (uint32_t q0 = 0; q0 < n_queries;) {
-    const uint32_t q1 = std::min(n_queries, q0 + chunk);
-    const LqStats before = st;
-    const size_t had = edges.size();
-    const int rc = query_chunk_run(ctx, A, h_len, q0, q1, h_near + q0, &edges, &st);
-    if (rc == RTC_ERR_NOMEM && q1 - q0 > 1) {  // half the queries: fewer candidates, a smaller join
-      st = before;
-      edges.resize(had);
-      std::fill(h_near + q0, h_near + q1, none);
-      chunk = std::max<uint32_t>(1, (q1 - q0) / 2);
-      ctx->err.clear();
-      (void)hipGetLastError();
-      continue;
-    }
-    if (rc != RTC_OK) return rc;
-    chunks++;
-    q0 = q1;
-  }
+  RTC_TRY(for_query_chunks(
+      ctx, n_queries, query_chunk,
+      [&](uint32_t q0, uint32_t q1) {
+        before = st;
+        had = edges.size();
+        return query_chunk_run(ctx, A, h_len, q0, q1, h_near + q0, &edges, &st);
+      },
+      [&](uint32_t q0, uint32_t q1) {
+        st = before;
+        edges.resize(had);
+        std::fill(h_near + q0, h_near + q1, none);
+      },
+      &chunks));
   uint64_t lonely = 0;
   for (uint32_t q = 0; q < n_queries; q++) lonely += h_near[q].n_candidates == 0;
   *h_n_edges = edges.size();

@@ -2,6 +2,7 @@
 // the --db search (rtc_rep_topk.hip): merge the two ascending lists, stop after `sketch_size` elements of the UNION;
 // *common = shared elements among them, *denom = union elements seen (sketch_size unless both lists run out first).
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 template <typename T>

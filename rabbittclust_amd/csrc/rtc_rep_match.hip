@@ -6,19 +6,18 @@
 // nothing becomes a representative the later queries are measured against); the counts and the filters do not.  So the
 // whole set is measured at once here and the decisions are replayed on the host (append_mst_state, host/rtc_host.cpp):
 //   1. join     the representatives [0, R) and the queries [R, R + Q) as one sketch set through the inverted join of
-//               rtc_pairs_join.hip (sort of (hash, genome), a count of every column's partner lists): (row, col, common) for
-//               every row genome R + q and every col < R + q that share a hash -- old representatives and earlier queries
+//               rtc_pairs_join.hip (query_candidates, rtc_query_chunks.h): (row, col, common) for every row genome R + q and
+//               every col < R + q that share a hash -- old representatives and earlier queries
 //   2. count    a lane per candidate applies the reference's filters (size ratio for KSSD, min_common_needed, the distance
 //               against the threshold); a wave adds its survivors with one atomic
 //   3. emit     the same test again into a list of exactly that size, a place per survivor from the wave's ballot
 // The distance is taken again on the host with its libm (the device log may differ by an ulp); the device keeps a pair when
-// it is within 1e-12 of the threshold, the host decides.
+// it is within 1e-12 of the threshold, the host decides.  The queries go in chunks (for_query_chunks), halved where the join's
+// scratch does not fit.
 
-#include <algorithm>
 #include <cmath>
-#include <vector>
 
-#include "rtc_internal.h"
+#include "rtc_query_chunks.h"
 
 namespace {
 
@@ -105,18 +104,8 @@ double host_distance(int sizeQry, int sizeRef, int common, bool containment, dou
   return d;
 }
 
-struct DevBuf {  // through rtc_dev_alloc / rtc_dev_free: the context's free-memory figure stays current
-  rtc_ctx* ctx = nullptr;
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)rtc_dev_free(ctx, p); }
-  int get(rtc_ctx* c, size_t bytes) {
-    ctx = c;
-    if (p) { (void)rtc_dev_free(ctx, p); p = nullptr; }
-    return rtc_dev_alloc(ctx, std::max<size_t>(bytes, 256), &p);  // RTC_ERR_NOMEM when it does not fit
-  }
-};
-
-// queries [q0, q1): rows [R + q0, R + q1) against the columns [0, R + q1).  RTC_ERR_NOMEM: the join's scratch did not fit.
+// queries [q0, q1): rows [R + q0, R + q1) against the columns [0, R + q1); the pairs that pass are appended to out.
+// RTC_ERR_NOMEM: the join's scratch did not fit.
 int rep_match_chunk(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
                     const std::vector<uint32_t>& h_len, const RmParams& p, uint32_t q0, uint32_t q1, double threshold,
                     std::vector<rtc_rep_pair>& out) {
@@ -125,46 +114,32 @@ int rep_match_chunk(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_
   for (uint32_t g = 0; g < row1; g++) { k_all += h_len[g]; if (g >= row0) k_rows += h_len[g]; }
   if (row1 < 2 || k_all < 2 || k_rows == 0) return RTC_OK;  // nothing can share a hash (the join declines such sets)
   hipStream_t s = ctx->stream;
-  void* hpin = nullptr;
-  // ---- 1. candidates (row, col, common) from the join; the list is grown to the count when it was too short ----
-  DevBuf edges, cnt;
-  RTC_TRY(cnt.get(ctx, 16));
-  uint64_t cap = std::max<uint64_t>(1u << 16, (uint64_t)(q1 - q0) * 64), m = 0;
-  for (int attempt = 0; attempt < 3; attempt++) {
-    RTC_TRY(edges.get(ctx, cap * sizeof(rtc_cedge)));
-    RTC_HIP(ctx, hipMemsetAsync(cnt.p, 0, 16, s));
-    int handled = 0;
-    RTC_TRY(rtc_pair_edges_join(ctx, d_hashes, width, d_start, d_len, n, row0, row1, 0, row1, -1, (rtc_cedge*)edges.p, cap,
-                                (uint64_t*)cnt.p, -1.0, &handled));
-    if (!handled) return rtc_fail(ctx, RTC_ERR_NOMEM, "rtc_rep_match: the join's scratch does not fit %u queries", q1 - q0);
-    RTC_TRY(rtc_pinned(ctx, 64, &hpin));
-    RTC_HIP(ctx, hipMemcpyAsync(hpin, cnt.p, 8, hipMemcpyDeviceToHost, s));
-    RTC_HIP(ctx, hipStreamSynchronize(s));
-    m = *(const uint64_t*)hpin;
-    if (m <= cap) break;
-    cap = m + m / 8;
-    m = 0;
-    if (attempt == 2) return rtc_fail(ctx, RTC_ERR_OVERFLOW, "rtc_rep_match: candidate list kept growing");
-  }
+  // ---- 1. candidates (row, col, common) from the join: the earlier queries are columns too, and nothing bounds the list ----
+  DevBuf db;
+  rtc_cedge* d_edges = nullptr;
+  uint64_t m = 0;
+  RTC_TRY(query_candidates(ctx, db, "rtc_rep_match", d_hashes, width, d_start, d_len, n, row0, row1, row1, QC_NO_BUDGET, &d_edges, &m));
   if (m == 0) return RTC_OK;
   // ---- 2. count the survivors, 3. emit them into a list of that size ----
   const uint32_t blocks = (uint32_t)((m + 255) / 256);
-  RTC_HIP(ctx, hipMemsetAsync(cnt.p, 0, 16, s));
-  hipLaunchKernelGGL(rep_match_count_kernel, dim3(blocks), dim3(256), 0, s, (const rtc_cedge*)edges.p, m, d_len, p,
-                     (unsigned long long*)cnt.p);
+  unsigned long long* d_cnt = nullptr;  // [0] the survivors counted, [1] emitted
+  void* hpin = nullptr;
+  RTC_TRY(db.get(ctx, 2, &d_cnt));
+  RTC_HIP(ctx, hipMemsetAsync(d_cnt, 0, 16, s));
+  hipLaunchKernelGGL(rep_match_count_kernel, dim3(blocks), dim3(256), 0, s, (const rtc_cedge*)d_edges, m, d_len, p, d_cnt);
   RTC_CHECK_LAUNCH(ctx);
-  RTC_HIP(ctx, hipMemcpyAsync(hpin, cnt.p, 8, hipMemcpyDeviceToHost, s));
+  RTC_TRY(rtc_pinned(ctx, 64, &hpin));
+  RTC_HIP(ctx, hipMemcpyAsync(hpin, d_cnt, 8, hipMemcpyDeviceToHost, s));
   RTC_HIP(ctx, hipStreamSynchronize(s));
   const uint64_t keep = *(const uint64_t*)hpin;
   if (keep == 0) return RTC_OK;
-  DevBuf d_out;
-  RTC_TRY(d_out.get(ctx, keep * sizeof(rtc_rep_pair)));
-  RTC_HIP(ctx, hipMemsetAsync((char*)cnt.p + 8, 0, 8, s));
-  hipLaunchKernelGGL(rep_match_emit_kernel, dim3(blocks), dim3(256), 0, s, (const rtc_cedge*)edges.p, m, d_len, p,
-                     (rtc_rep_pair*)d_out.p, (unsigned long long)keep, (unsigned long long*)cnt.p + 1);
+  rtc_rep_pair* d_out = nullptr;
+  RTC_TRY(db.get(ctx, keep, &d_out));
+  hipLaunchKernelGGL(rep_match_emit_kernel, dim3(blocks), dim3(256), 0, s, (const rtc_cedge*)d_edges, m, d_len, p, d_out,
+                     (unsigned long long)keep, d_cnt + 1);
   RTC_CHECK_LAUNCH(ctx);
   std::vector<rtc_rep_pair> h(keep);
-  RTC_HIP(ctx, hipMemcpyAsync(h.data(), d_out.p, keep * sizeof(rtc_rep_pair), hipMemcpyDeviceToHost, s));
+  RTC_HIP(ctx, hipMemcpyAsync(h.data(), d_out, keep * sizeof(rtc_rep_pair), hipMemcpyDeviceToHost, s));
   RTC_HIP(ctx, hipStreamSynchronize(s));
   for (rtc_rep_pair& r : h) {
     bool ok = true;
@@ -204,21 +179,14 @@ extern "C" int rtc_rep_match(rtc_ctx* ctx, const void* d_hashes, int width, cons
   p.inv_k = 1.0 / (double)kmer_size;
   p.thr_dev = threshold + std::fabs(threshold) * 1e-12;
   std::vector<rtc_rep_pair> all;
-  uint32_t chunk = query_chunk ? std::min(query_chunk, n_queries) : n_queries;
-  for (uint32_t q0 = 0; q0 < n_queries;) {
-    const uint32_t q1 = std::min(n_queries, q0 + chunk);
-    std::vector<rtc_rep_pair> part;
-    const int st = rep_match_chunk(ctx, d_hashes, width, d_start, d_len, n, h_len, p, q0, q1, threshold, part);
-    if (st == RTC_ERR_NOMEM && q1 - q0 > 1) {  // half the queries: less to sort, fewer candidates
-      chunk = std::max<uint32_t>(1, (q1 - q0) / 2);
-      ctx->err.clear();
-      continue;
-    }
-    if (st != RTC_OK) return st;
-    ctx->diag[7]++;
-    all.insert(all.end(), part.begin(), part.end());
-    q0 = q1;
-  }
+  size_t had = 0;
+  RTC_TRY(for_query_chunks(
+      ctx, n_queries, query_chunk,
+      [&](uint32_t q0, uint32_t q1) {
+        had = all.size();
+        return rep_match_chunk(ctx, d_hashes, width, d_start, d_len, n, h_len, p, q0, q1, threshold, all);
+      },
+      [&](uint32_t, uint32_t) { all.resize(had); }, &ctx->diag[7]));
   std::sort(all.begin(), all.end(), [](const rtc_rep_pair& a, const rtc_rep_pair& b) {
     return a.query != b.query ? a.query < b.query : a.slot < b.slot;
   });

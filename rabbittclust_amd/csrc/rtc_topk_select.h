@@ -1,9 +1,11 @@
-// rtc_topk_select.h -- segmented top-k by an exact rational key, shared by rtc_rep_topk.hip (the best representatives of a
-// query), rtc_dbscan_sweep.hip (the k-th nearest candidate of a point) and rtc_dbscan_assign.hip (a query's candidates, folded
-// instead of selected): the record, its total order, the per-query count of the join's candidates, the one-workgroup
-// scan of the segment offsets and the running top-k selection in LDS (one wave for segments of up to TK_LONG records, 256
-// lanes for the longer ones).  DESIGN 3.4b describes the selection.
+// rtc_topk_select.h -- a query's candidates as a segment of records under an exact rational key: the record, its total order, the
+// per-query count of the join's candidates and the one-workgroup scan of the segment offsets (both run from rtc_query_chunks.h
+// for the placement entry points, the scan also by rtc_dbscan_sweep.hip for the k-th nearest candidate of a point), the running
+// top-k selection in LDS of rtc_rep_topk.hip and rtc_dbscan_sweep.hip (one wave for segments of up to TK_LONG records, 256 lanes
+// for the longer ones) and the segment fold of rtc_dbscan_assign.hip and rtc_leiden_assign.hip.
 #pragma once
+#include <type_traits>
+
 #include "rtc_internal.h"
 
 namespace {
@@ -59,6 +61,34 @@ __global__ __launch_bounds__(TK_SCAN_THREADS) void tk_scan_kernel(const uint32_t
     xa += c; xb += (k && c > k) ? k : c;
   }
   if (t == TK_SCAN_THREADS - 1) { off[nq] = sa[t]; koff[nq] = sb[t]; }
+}
+
+// A workgroup of B lanes folds the segment [s0, s1) into one F: every lane strides over the segment and takes its records
+// (f.take(record, args...)), __shfl_xor steps merge the lanes of a wave word by word (f.merge(other)), and the waves of a
+// 256-lane workgroup meet through lds_part (B / 64 entries) behind one barrier.  The result is thread 0's.  merge must not
+// depend on the order of its operands -- sums, min, max, the best record under tk_beats, which is a total order -- so the result
+// is the same for every order the scatter left the records in.  Every lane of the workgroup calls it.
+template <int B, class F, class... A>
+__device__ __forceinline__ F tk_fold_segment(const TkRec* __restrict__ seg, uint64_t s0, uint64_t s1, F f, F* lds_part, A... args) {
+  static_assert(sizeof(F) % 4 == 0 && std::is_trivially_copyable<F>::value, "the lanes exchange F as 32-bit words");
+  constexpr int W = sizeof(F) / 4;
+  for (uint64_t idx = s0 + threadIdx.x; idx < s1; idx += B) f.take(seg[idx], args...);
+  for (int d = 32; d; d >>= 1) {
+    uint32_t w[W];
+    __builtin_memcpy(w, &f, sizeof(F));
+#pragma unroll
+    for (int i = 0; i < W; i++) w[i] = __shfl_xor(w[i], d);
+    F o;
+    __builtin_memcpy(&o, w, sizeof(F));
+    f.merge(o);
+  }
+  if (B > 64) {
+    if ((threadIdx.x & 63) == 0) lds_part[threadIdx.x >> 6] = f;
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int w = 1; w < B / 64; w++) f.merge(lds_part[w]);
+  }
+  return f;
 }
 
 // a workgroup of B lanes per query whose segment length lies in [lo, hi]; k in [1, TK_KMAX]
