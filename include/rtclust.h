@@ -1061,6 +1061,67 @@ int rtc_nj_counters(const rtc_ctx* ctx, uint64_t out[10]);
 /* The paths of the last call: bit 0 the wave path, bit 1 the workgroup path, bit 2 the grid path. */
 int rtc_nj_last_path(const rtc_ctx* ctx);
 
+/* ---- clust-mst --quality: silhouette and cluster separation of a finished partition ---------------------------------- */
+/* The silhouette of every vertex of a labelled, weighted graph, and what a cluster's diameter and separation are read from, in
+ * exact integers; this is the definition (tests/refquality.py restates it).  Q1 = 2^20 is distance 1.
+ *   - Input: n vertices, m records (u, v, q): the pair u != v has distance q, 0 <= q <= Q1, in units of 2^-20.  Every pair that
+ *     is not listed has distance Q1.  h_label[x] >= 0 is x's cluster, any number below n; a negative label means x is
+ *     unclustered (noise): it is a member of nothing, it is nobody's neighbour, and its record is all zero with b_cluster =
+ *     near_cluster = UINT32_MAX.  N_d is the number of vertices labelled d.
+ *   - For a clustered x in cluster c and a cluster d: cnt(x, d) the listed neighbours of x labelled d, sum(x, d) the sum of
+ *     their q, S(x, d) = sum(x, d) + (N_d - [d == c] - cnt(x, d)) Q1: the total distance from x to d's members other than x.
+ *   - a_num = S(x, c), a_den = N_c - 1 (0 for a singleton).
+ *   - b: among the clusters d != c that hold a listed neighbour of x, the one with the least mean S(x, d) / N_d, means compared
+ *     exactly as S1 N2 against S2 N1 in 128 bits (S < 2^51, N < 2^31), equal means to the smaller d.  If that mean is strictly
+ *     below Q1: b_num = S, b_den = N_d, b_cluster = d.  Otherwise every other cluster is at mean distance exactly 1 (a cluster
+ *     without a listed neighbour always is): b_num = Q1, b_den = 1, b_cluster = UINT32_MAX.  If there is no other clustered
+ *     vertex at all: b_num = 0, b_den = 0, b_cluster = UINT32_MAX.
+ *   - far_q: the largest distance from x to a member of c: Q1 as soon as cnt(x, c) < N_c - 1, otherwise the largest listed q
+ *     into c; 0 for a singleton.  A cluster's diameter is the largest far_q of its members.
+ *   - near_q, near_cluster: the least q over the listed neighbours with a label >= 0 and != c, and that neighbour's cluster,
+ *     equal q to the smaller cluster; Q1 and UINT32_MAX without such a neighbour.  A cluster's separation is the least near_q
+ *     of its members.
+ *   - rtc_silhouette_value (host only): 0 when a_den == 0 or b_den == 0; otherwise a = (double)a_num / ((double)a_den *
+ *     1048576.0), b likewise, and the value is (b - a) / max(a, b), 0 when both are 0.  Every operation is one IEEE-754 double
+ *     operation in that order.  This is Rousseeuw's s(x) with a singleton at 0.
+ * Errors, RTC_ERR_ARG with a message naming the record: u == v, u or v >= n, q > Q1, a label >= n, a pair given twice in either
+ * orientation (whatever the labels of its ends).  n >= 2^31 - 1: RTC_ERR_ARG.
+ * Every sum is an integer (integer atomics: order-independent) and every comparison exact, so the records depend neither on the
+ * scheduling nor on the kernel path of a row: a row of up to 128 entries takes one wave with the table in LDS, one of up to
+ * 1 024 a 256-lane workgroup with a larger LDS table, a longer one a table of at least twice its entries in global memory
+ * (rabbittclust_amd/csrc/rtc_quality.h).  RTC_SIL_GLOBAL=1 sends every row through the last; results are identical.  The device
+ * holds the CSR of the 2 m directed entries and what builds it, about 124 bytes a record and 100 a vertex, and on top of that the
+ * global tables: 16 bytes a slot, 2 to 4 slots an entry of every row past 1 024 entries (of every row, 64 slots at least, under
+ * RTC_SIL_GLOBAL=1).  The call asks for the free memory twice, before the CSR and before the tables; if either does not fit:
+ * RTC_ERR_NOMEM with the bytes in the message, no fallback.  Synchronous. */
+typedef struct { uint64_t a_num, b_num; uint32_t a_den, b_den, b_cluster, far_q, near_q, near_cluster; } rtc_sil; /* 40 bytes */
+int rtc_silhouette(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, uint64_t m, const int32_t* h_label, rtc_sil* h_out /* [n] */);
+/* The last rtc_silhouette (or the score of the last rtc_cluster_quality): out[0] records, out[1] directed entries of the CSR,
+ * out[2] clustered vertices, out[3] clusters, out[4] / out[5] / out[6] rows on the wave / workgroup / global-table path (a vertex
+ * without an entry, and every unclustered one, is on none), out[7] CSR ns, out[8] row kernels ns, out[9] whole call ns. */
+int rtc_silhouette_counters(const rtc_ctx* ctx, uint64_t out[10]);
+/* the row paths of the last score: bit 0 one wave, bit 1 a 256-lane workgroup, bit 2 the table in global memory */
+int rtc_silhouette_last_path(const rtc_ctx* ctx);
+double rtc_silhouette_value(const rtc_sil* r);
+/* The same over sketches (KSSD or MinHash hash sets, width 4 or 8): the score of any labelling of them -- clust-mst's cut,
+ * rtc_dbscan's labels with -1 for noise, rtc_louvain's.  The listed pairs are all pairs that share a hash, from
+ * rtc_pair_edges_dev with radio = -1 over row chunks under RTC_EDGE_BUDGET as in rtc_dbscan: there is no size-ratio rule, a pair
+ * that the MST's filter drops has its true distance here.  Each chunk goes to the host, where every pair gets
+ *   q = min(Q1, llround(rtc_linkage_distance(common, |u| + |v| - common, kmer_size) * 1048576.0))
+ * with the host's libm on the context's host threads (rtc_ctx_set_host_threads): the set-Jaccard of the index path through the
+ * function that weighs --linkage and --nj-tree.  An empty sketch shares nothing and is at distance 1 from everything.  The
+ * records then go through rtc_silhouette's implementation.
+ * Memory: the host holds every candidate at once, 12 bytes as it arrives and 12 as a record; the device holds one chunk of the
+ * pair phase (12 bytes a candidate), and after it the score's 124 bytes a candidate and 100 a sketch, and its global tables.  RTC_ERR_NOMEM if that does
+ * not fit, no fallback.  kmer_size < 1, width not 4 or 8, NULLs, a label >= n, n >= 2^31 - 1: RTC_ERR_ARG; a sketch of 2^31 hashes
+ * or more: RTC_ERR_UNSUPPORTED.  Synchronous. */
+int rtc_cluster_quality(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                        const int32_t* h_label, int kmer_size, rtc_sil* h_out /* [n] */);
+/* The last rtc_cluster_quality: out[0] row chunks, out[1] candidates, out[2] / out[3] / out[4] rows on the wave / workgroup /
+ * global-table path, out[5] pair ns, out[6] host distance ns (copies included), out[7] score ns, out[8] clusters, out[9] whole
+ * call ns. */
+int rtc_cluster_quality_counters(const rtc_ctx* ctx, uint64_t out[10]);
+
 #ifdef __cplusplus
 }
 #endif

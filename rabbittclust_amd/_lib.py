@@ -175,6 +175,12 @@ SIGNATURES = {
     "rtc_nj_clusters": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _i, _vp, _u64, C.POINTER(_u64), _vp]),
     "rtc_nj_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_nj_last_path": (_i, [_vp]),
+    "rtc_silhouette": (_i, [_vp, _u32, _vp, _u64, _vp, _vp]),
+    "rtc_silhouette_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_silhouette_last_path": (_i, [_vp]),
+    "rtc_silhouette_value": (C.c_double, [_vp]),
+    "rtc_cluster_quality": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _i, _vp]),
+    "rtc_cluster_quality_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_hierarchy_flat": (_i, [_u32, _vp, _u64, _vp, _i, _i, _vp, _vp, C.POINTER(_u32)]),
 }
 

@@ -46,6 +46,17 @@ MCL_PATH_WAVE, MCL_PATH_WORKGROUP, MCL_PATH_GLOBAL = 1, 2, 4  # rtc_mcl_last_pat
 # wave, at most MCL_BLOCK_WORK a 256-lane workgroup, more the table in global memory
 MCL_WAVE_WORK = 256
 MCL_BLOCK_WORK = 3072
+SIL_DT = np.dtype([("a_num", "<u8"), ("b_num", "<u8"), ("a_den", "<u4"), ("b_den", "<u4"), ("b_cluster", "<u4"), ("far_q", "<u4"),
+                   ("near_q", "<u4"), ("near_cluster", "<u4")])  # rtc_sil
+SIL_ONE = 1 << 20  # distance 1 in rtc_silhouette's units
+SIL_NONE = 0xFFFFFFFF  # b_cluster / near_cluster: none
+SIL_PATH_WAVE, SIL_PATH_WORKGROUP, SIL_PATH_GLOBAL = 1, 2, 4  # rtc_silhouette_last_path
+# the row kernel's path boundaries (csrc/rtc_quality.h): a row of at most SIL_WAVE_ROW entries takes one wave and a table of
+# SIL_WAVE_SLOTS slots in LDS, one of at most SIL_BLOCK_ROW a 256-lane workgroup and SIL_BLOCK_SLOTS slots, a longer one a table of
+# 1 << max(SIL_GLOBAL_LOG2_MIN, ceil(log2(2 entries))) slots in global memory
+SIL_WAVE_ROW, SIL_WAVE_SLOTS = 128, 256
+SIL_BLOCK_ROW, SIL_BLOCK_SLOTS = 1024, 2048
+SIL_GLOBAL_LOG2_MIN = 6
 
 
 def _np_ptr(a):
@@ -979,6 +990,51 @@ class Context:
         """rtc_mcl_last_path: MCL_PATH_WAVE | MCL_PATH_WORKGROUP | MCL_PATH_GLOBAL, the column paths of the last mcl call"""
         return int(self.lib.rtc_mcl_last_path(self.h))
 
+    def silhouette(self, n, edges, labels):
+        """rtc_silhouette: the score include/rtclust.h defines over n vertices, WEDGE_DT records (u, v, q) -- q the distance of the
+        pair in units of 2^-20, unlisted pairs at SIL_ONE -- and one int32 label per vertex, negative for an unclustered one.
+        Returns SIL_DT records, one per vertex; silhouette_value turns them into the silhouette."""
+        e = np.ascontiguousarray(np.asarray(edges, dtype=WEDGE_DT))
+        lab = np.ascontiguousarray(np.asarray(labels, dtype=np.int32))
+        if lab.shape != (int(n),):
+            raise ValueError("labels must hold one label per vertex")
+        out = np.zeros(max(int(n), 1), dtype=SIL_DT)
+        self.check(self.lib.rtc_silhouette(self.h, int(n), _np_ptr(e) if e.size else None, int(e.size), _np_ptr(lab) if n else None,
+                                           _np_ptr(out) if n else None))
+        return out[:int(n)].copy()
+
+    def silhouette_counters(self):
+        """rtc_silhouette_counters as a dict (the last silhouette call, or the score of the last cluster_quality call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_silhouette_counters(self.h, a))
+        names = ("records", "entries", "clustered", "clusters", "wave_rows", "workgroup_rows", "global_rows", "csr_ns", "rows_ns", "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
+    def silhouette_last_path(self):
+        """rtc_silhouette_last_path: SIL_PATH_WAVE | SIL_PATH_WORKGROUP | SIL_PATH_GLOBAL, the row paths of the last score"""
+        return int(self.lib.rtc_silhouette_last_path(self.h))
+
+    def cluster_quality(self, sk, labels, kmer_size):
+        """rtc_cluster_quality: rtc_silhouette over sk's sketches, every pair that shares a hash at the distance
+        rtc_linkage_distance gives its exact key, every other pair at 1.  labels: one int32 per sketch from any algorithm -- the
+        MST's cut, ctx.louvain(...)'s communities, a DBSCAN run's labels with -1 for noise.  Returns SIL_DT records."""
+        n = sk.n
+        lab = np.ascontiguousarray(np.asarray(labels, dtype=np.int32))
+        if lab.shape != (n,):
+            raise ValueError("labels must hold one label per sketch")
+        out = np.zeros(max(n, 1), dtype=SIL_DT)
+        self.check(self.lib.rtc_cluster_quality(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n, _np_ptr(lab),
+                                                int(kmer_size), _np_ptr(out)))
+        return out[:n].copy()
+
+    def cluster_quality_counters(self):
+        """rtc_cluster_quality_counters as a dict (the last cluster_quality call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_cluster_quality_counters(self.h, a))
+        names = ("chunks", "candidates", "wave_rows", "workgroup_rows", "global_rows", "pair_ns", "distance_ns", "score_ns", "clusters",
+                 "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
     def linkage(self, keys, kmin=(0, 1)):
         """rtc_linkage_dev: the complete-linkage agglomeration include/rtclust.h defines over one symmetric m x m key matrix --
         an array [m, m, 2] of (common, denom), or LKEY_DT [m, m] -- uploaded for the call.  kmin: the stop bound (num, den),
@@ -1217,6 +1273,25 @@ def graph_weights_mash(edges, sketch_size, kmer_size, return_weights=False):
 def linkage_distance(common, denom, kmer_size):
     """rtc_linkage_distance: the distance the host gives a complete-linkage merge of key common / denom"""
     return float(_lib.load().rtc_linkage_distance(int(common), int(denom), int(kmer_size)))
+
+
+def silhouette_value(records):
+    """rtc_silhouette_value of every SIL_DT record, as a float64 array: (b - a) / max(a, b) with a = a_num / (a_den 2^20) and b
+    likewise, each step one double operation; 0 where a_den or b_den is 0 or both means are."""
+    r = np.atleast_1d(np.asarray(records, dtype=SIL_DT))
+    ok = (r["a_den"] != 0) & (r["b_den"] != 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a = r["a_num"].astype(np.float64) / (r["a_den"].astype(np.float64) * 1048576.0)
+        b = r["b_num"].astype(np.float64) / (r["b_den"].astype(np.float64) * 1048576.0)
+        hi = np.maximum(a, b)
+        v = (b - a) / hi
+    return np.where(ok & (hi != 0.0), v, 0.0)
+
+
+def silhouette_value_one(record):
+    """rtc_silhouette_value of one SIL_DT record through the library (no GPU needed)"""
+    r = np.ascontiguousarray(np.asarray(record, dtype=SIL_DT).reshape(1))
+    return float(_lib.load().rtc_silhouette_value(_np_ptr(r)))
 
 
 def linkage_bound(threshold, kmer_size):

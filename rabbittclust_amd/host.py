@@ -152,3 +152,30 @@ def nj_newick(labels, members, joins):
     buf = C.create_string_buffer(max(int(need), 1))
     fn(arr, mem.ctypes.data_as(C.c_void_p), len(mem), j.ctypes.data_as(C.c_void_p), len(j), buf, need)
     return buf.raw[:need].decode()
+
+
+def quality_report(names, cluster_of, records, sil):
+    """quality_report_text (rtc_host.cpp): the two reports of clust-mst --quality as (quality_tsv, silhouette_tsv).  names[g] and
+    cluster_of[g] (the cluster number <output> gives genome g) for every genome, records: api.SIL_DT, sil: their silhouettes."""
+    n = len(names)
+    lab = np.ascontiguousarray(cluster_of, dtype=np.int32)
+    rec = np.ascontiguousarray(records)
+    val = np.ascontiguousarray(sil, dtype=np.float64)
+    assert rec.dtype.itemsize == 40 and len(lab) == len(rec) == len(val) == n
+    arr = (C.c_char_p * max(n, 1))(*[s.encode() for s in names])
+    fn = load().rtch_quality_report
+    fn.restype = C.c_long
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_long]
+    if n and int(lab.min()) < 0:
+        raise ValueError("cluster_of must name a cluster for every genome: the reports are of a run's clusters, which hold them all")
+    ncl = int(lab.max()) + 1 if n else 0
+    out = []
+    for which in (0, 1):
+        args = (arr, lab.ctypes.data_as(C.c_void_p), ncl, rec.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p), n, which)
+        need = fn(*args, None, 0)
+        if need < 0:
+            raise ValueError("cluster_of outside the clusters")
+        buf = C.create_string_buffer(max(int(need), 1))
+        fn(*args, buf, need)
+        out.append(buf.raw[:need].decode())
+    return tuple(out)

@@ -300,4 +300,20 @@ long rtch_nj_newick(const char* const* labels, const uint32_t* members, uint64_t
   return (long)text.size();
 }
 
+// quality_report_text over plain arrays: names[g], cluster_of[g] in [0, n_clusters) for every genome, rec[g] (rtc_sil) and sil[g].
+// which 0: the cluster report, 1: the genome report.  Returns -1 for a cluster_of outside that range, else the text's length; the text itself when it fits cap (no terminator).
+long rtch_quality_report(const char* const* names, const int32_t* cluster_of, uint32_t n_clusters, const rtc_sil* rec, const double* sil, uint32_t n,
+                         int which, char* out, long cap) {
+  std::vector<std::vector<int>> clusters(n_clusters);
+  for (uint32_t g = 0; g < n; g++) {
+    if (cluster_of[g] < 0 || (uint32_t)cluster_of[g] >= n_clusters) return -1;  // every genome of a run is in a cluster
+    clusters[cluster_of[g]].push_back((int)g);
+  }
+  std::string q, s;
+  quality_report_text([&](uint32_t g) { return std::string(names[g]); }, clusters, rec, sil, n, &q, &s);
+  const std::string& text = which ? s : q;
+  if (out && (long)text.size() <= cap) memcpy(out, text.data(), text.size());
+  return (long)text.size();
+}
+
 }

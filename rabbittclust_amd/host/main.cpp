@@ -894,6 +894,7 @@ struct Options {
   bool hasDrlevel = false;
   string minhashOnly;        // clust-leiden: the first of -s / -c as spelled, which only --minhash gives a meaning
   bool linkageComplete = false;  // clust-mst --linkage complete: complete linkage inside every cluster (rtc_linkage_complete)
+  bool quality = false;  // clust-mst --quality: silhouette, diameter and separation of the run's clusters (rtc_cluster_quality)
   bool njTree = false, njAll = false;  // clust-mst --nj-tree / --nj-all: neighbour-joining trees of the clusters / of all genomes (rtc_nj_clusters)
 };
 
@@ -1052,6 +1053,7 @@ static Options parse(int argc, char** argv) {
     }
     else if (a == "--nj-tree") o.njTree = true;
     else if (a == "--nj-all") o.njAll = true;
+    else if (a == "--quality") o.quality = true;
 #endif
     else if (a == "-h" || a == "--help") {
 #ifdef GREEDY_CLUST
@@ -1142,6 +1144,9 @@ static Options parse(int argc, char** argv) {
            "  --nj-tree (a neighbour-joining tree of every cluster over the exact set-Jaccard distances, joined on the GPU:\n"
            "             <output>.nj.newick, one tree a line in the order of <output>; with --fast or MinHash on the index path)\n"
            "  --nj-all (one neighbour-joining tree over all genomes: <output>.nj.all.newick; genomes that share no hash are at distance 1)\n"
+           "  --quality (how good the partition is, over the exact set-Jaccard distances, scored on the GPU: <output>.quality.tsv, a\n"
+           "             line a cluster with its mean and least silhouette, mean intra-cluster distance, diameter, separation and\n"
+           "             nearest cluster, and <output>.silhouette.tsv, a line a genome; with --fast or MinHash on the index path)\n"
            "  [--fast] --db FILE --build|--query|--assign|--append LIST|--stats [--top-k N] (MST representative database)"
 #else
            "  --append LIST (with --presketched DIR)  --save-rep (cluster_state.bin beside the sketches)\n"
@@ -1352,6 +1357,46 @@ static int nj_trees_and_print(rtc_ctx* ctx, const DeviceSketches& ds, const vect
   g_metrics.num("nj_join_s", 1e-9 * (double)sum[8]);
   g_metrics.num("nj_components", (double)sum[0]);
   g_metrics.num("nj_records", (double)sum[4]);
+  return 0;
+}
+// --quality: the silhouette of every genome under the run's clusters and, per cluster, its diameter and its separation from the
+// nearest other cluster (include/rtclust.h has the definition), over the distances the host forms from the exact keys of the
+// index path; pairs that share no hash are at distance 1.  <base>.quality.tsv: a line a cluster in the order and with the numbers
+// <base> prints; <base>.silhouette.tsv: a line a genome in input order (quality_report_text, rtc_host.h).  A candidate list that does not fit the device (RTC_ERR_NOMEM, no fallback) is reported: returns 1.
+static int quality_and_print(rtc_ctx* ctx, const DeviceSketches& ds, const vector<vector<int>>& clusters, const vector<GenomeInfo>& genomes,
+                             bool sketchByFile, const string& base, int kmer_size, int threads) {
+  const uint32_t n = (uint32_t)genomes.size();
+  CHECK(ctx, rtc_ctx_set_host_threads(ctx, threads > 0 ? threads : 1));
+  vector<int32_t> label(n, -1);
+  for (size_t c = 0; c < clusters.size(); c++) for (int g : clusters[c]) label[g] = (int32_t)c;
+  vector<rtc_sil> rec(n > 0 ? n : 1);
+  const int st = rtc_cluster_quality(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, n, label.data(), kmer_size, rec.data());
+  if (st == RTC_ERR_NOMEM) { cerr << "ERROR: " << rtc_last_error(ctx) << endl; return 1; }
+  CHECK(ctx, st);
+  uint64_t cnt[10];
+  CHECK(ctx, rtc_cluster_quality_counters(ctx, cnt));
+  vector<double> sil(n);
+  for (uint32_t g = 0; g < n; g++) sil[g] = rtc_silhouette_value(&rec[g]);
+  string q_text, s_text;
+  const double all_mean = quality_report_text([&](uint32_t g) { return sketchByFile ? genomes[g].fileName : genomes[g].seq0.name; }, clusters,
+                                              rec.data(), sil.data(), n, &q_text, &s_text);
+  const string f_q = base + ".quality.tsv", f_s = base + ".silhouette.tsv";
+  for (int which = 0; which < 2; which++) {
+    const string& f = which ? f_s : f_q;
+    const string& text = which ? s_text : q_text;
+    FILE* fp = fopen(f.c_str(), "w");
+    if (!fp) { cerr << "ERROR: cannot open file: " << f << endl; join_warmup(); exit(1); }
+    fwrite(text.data(), 1, text.size(), fp);
+    fclose(fp);
+  }
+  cerr << "-----write the cluster quality into: " << f_q << endl;
+  cerr << "-----write the silhouettes into: " << f_s << endl;
+  cerr << "-----the mean silhouette of: " << base << " is: " << all_mean << endl;
+  g_metrics.num("quality_pair_s", 1e-9 * (double)cnt[5]);
+  g_metrics.num("quality_distance_s", 1e-9 * (double)cnt[6]);
+  g_metrics.num("quality_score_s", 1e-9 * (double)cnt[7]);
+  g_metrics.num("quality_candidates", (double)cnt[1]);
+  g_metrics.num("quality_silhouette_mean", all_mean);
   return 0;
 }
 #endif
@@ -2894,6 +2939,13 @@ int main(int argc, char** argv) {
                       : o.autoThreshold ? "--auto-threshold" : o.stability ? "--stability" : nullptr;
     if (bad) { cerr << "ERROR: " << (o.njTree ? "--nj-tree" : "--nj-all") << " does not go with " << bad << endl; return 1; }
   }
+  // ---- --quality: the same company again ----
+  if (o.quality) {
+    const char* bad = o.isContainment ? "-c/--containment" : !o.useIndex ? "--inverted-index=false" : o.has_append ? "--append"
+                      : o.has_premsted ? "--premsted" : !o.repdb_path.empty() ? "--db" : o.dense ? "--dense"
+                      : o.autoThreshold ? "--auto-threshold" : o.stability ? "--stability" : nullptr;
+    if (bad) { cerr << "ERROR: --quality does not go with " << bad << endl; return 1; }
+  }
 #endif
   // ---- MST RepDB mode: --db FILE (src/main.cpp:213-254, :525-600) ----
   if (o.has_topk && !o.db_query) { cerr << "ERROR: --top-k requires --query" << endl; return 1; }
@@ -3716,6 +3768,13 @@ int main(int argc, char** argv) {
   if (o.njTree || o.njAll) {
     if (is_containment) { cerr << "ERROR: " << (o.njTree ? "--nj-tree" : "--nj-all") << " does not go with containment sketches" << endl; return 1; }
     if (nj_trees_and_print(ctx, dss[0], clusters, genomes, sketchByFile, o.outputFile, kmer_size, o.threads, o.njTree, o.njAll) != 0) {
+      join_warmup();
+      return 1;
+    }
+  }
+  if (o.quality) {
+    if (is_containment) { cerr << "ERROR: --quality does not go with containment sketches" << endl; return 1; }
+    if (quality_and_print(ctx, dss[0], clusters, genomes, sketchByFile, o.outputFile, kmer_size, o.threads) != 0) {
       join_warmup();
       return 1;
     }

@@ -1304,6 +1304,55 @@ void print_nj_newick(const std::vector<GenomeInfo>& g, const std::vector<std::ve
   fclose(fp);
 }
 
+double quality_report_text(const std::function<std::string(uint32_t)>& name, const std::vector<std::vector<int>>& clusters, const rtc_sil* rec,
+                           const double* sil, uint32_t n, std::string* quality_tsv, std::string* silhouette_tsv) {
+  char buf[512];
+  std::vector<int32_t> label(n, -1);
+  std::string& Q = *quality_tsv;
+  Q = "cluster\tsize\tmean_silhouette\tmin_silhouette\tmean_intra_distance\tdiameter\tseparation\tnearest_cluster\n";
+  for (size_t c = 0; c < clusters.size(); c++) {
+    std::vector<int> mem(clusters[c]);
+    std::sort(mem.begin(), mem.end());
+    const size_t sz = mem.size();
+    double sum = 0.0, least = 0.0;
+    uint64_t a_total = 0;
+    uint32_t far = 0, near = 1u << 20, near_cluster = 0xffffffffu;
+    for (size_t i = 0; i < sz; i++) {
+      const rtc_sil& r = rec[mem[i]];
+      label[mem[i]] = (int32_t)c;
+      sum += sil[mem[i]];
+      if (i == 0 || sil[mem[i]] < least) least = sil[mem[i]];
+      a_total += r.a_num;
+      if (r.far_q > far) far = r.far_q;
+      if (i == 0 || r.near_q < near) { near = r.near_q; near_cluster = r.near_cluster; }
+    }
+    const double mean = sz ? sum / (double)sz : 0.0;
+    const double intra = sz > 1 ? (double)a_total / ((double)sz * (double)(sz - 1) * 1048576.0) : 0.0;
+    snprintf(buf, sizeof buf, "%zu\t%zu\t%.6f\t%.6f\t%.6f\t%.6f\t%.6f\t", c, sz, mean, least, intra, (double)far / 1048576.0, (double)near / 1048576.0);
+    Q += buf;
+    Q += near_cluster == 0xffffffffu ? std::string("-") : std::to_string(near_cluster);
+    Q += "\n";
+  }
+  double all = 0.0;
+  for (uint32_t g = 0; g < n; g++) all += sil[g];
+  const double all_mean = n ? all / (double)n : 0.0;
+  snprintf(buf, sizeof buf, "all\t%u\t%.6f\t-\t-\t-\t-\t-\n", n, all_mean);
+  Q += buf;
+  std::string& S = *silhouette_tsv;
+  S = "name\tcluster\tsilhouette\ta\tb\tb_cluster\n";
+  for (uint32_t g = 0; g < n; g++) {
+    const rtc_sil& r = rec[g];
+    const double a = r.a_den ? (double)r.a_num / ((double)r.a_den * 1048576.0) : 0.0;
+    const double b = r.b_den ? (double)r.b_num / ((double)r.b_den * 1048576.0) : 0.0;
+    snprintf(buf, sizeof buf, "\t%d\t%.6f\t%.6f\t%.6f\t", label[g], sil[g], a, b);
+    S += name(g);
+    S += buf;
+    S += r.b_cluster == 0xffffffffu ? std::string("-") : std::to_string(r.b_cluster);
+    S += "\n";
+  }
+  return all_mean;
+}
+
 void print_phylip_tree(const std::vector<GenomeInfo>& g, const std::vector<rtc_edge>& mst, bool sketchByFile, const std::string& output) {
   FILE* fp = open_out(output, "print_phylip_tree");
   fprintf(fp, "1\n%s\n", get_newick_tree(g, mst, sketchByFile).c_str());

@@ -179,6 +179,17 @@ std::string get_nj_newick(const std::vector<GenomeInfo>& g, const std::vector<in
 void print_nj_newick(const std::vector<GenomeInfo>& g, const std::vector<std::vector<int>>& clusters, const std::vector<rtc_njoin>& joins,
                      const std::vector<uint64_t>& first, bool sketchByFile, const std::string& output);
 
+// ---- clust-mst --quality: the two reports of rtc_cluster_quality's records (include/rtclust.h).  sil[g]: rtc_silhouette_value of
+// rec[g]; clusters: the run's, numbered as <output> numbers them, every genome in exactly one.  quality_tsv: a header, a line a
+// cluster -- cluster, size, mean silhouette, least silhouette, mean intra-cluster distance (the sum of a_num over the members /
+// (size (size - 1) 2^20), 0 for a singleton), diameter (the largest far_q / 2^20), separation (the least near_q / 2^20), nearest
+// cluster (the near_cluster of the first member in genome order that holds that least near_q, or -) -- and a last line "all"
+// with the genome count and the overall mean silhouette.  silhouette_tsv: a header and a line a genome in input order -- name,
+// cluster, silhouette, a, b, b_cluster or -.  Means are double sums over the members in ascending genome order; every value is
+// printed %.6f.  Returns the overall mean silhouette. ----
+double quality_report_text(const std::function<std::string(uint32_t)>& name, const std::vector<std::vector<int>>& clusters, const rtc_sil* rec,
+                           const double* sil, uint32_t n, std::string* quality_tsv, std::string* silhouette_tsv);
+
 // ---- clust-mst --auto-threshold / --stability: the MST edge-length analysis (src/MST.cpp:1743-2376, structs src/MST.h:77-100) ----
 struct EdgeLengthStats {
   double min_dist = 0, max_dist = 0, median_dist = 0, q1_dist = 0, q3_dist = 0, mean_dist = 0, std_dev = 0;
