@@ -1122,6 +1122,50 @@ int rtc_cluster_quality(rtc_ctx* ctx, const void* d_hashes, int width, const uin
  * call ns. */
 int rtc_cluster_quality_counters(const rtc_ctx* ctx, uint64_t out[10]);
 
+/* ---- clust-mst --upgma: average linkage (UPGMA) in exact integers ------------------------------------------------------ */
+/* Average-linkage agglomeration of one set of m clusters-to-be; this is the definition (tests/refupgma.py restates it).
+ * Q1 = 2^20 is distance 1.  All quantities are unsigned integers; no step on the device forms a floating-point value.
+ *   - Input: a symmetric m x m matrix of uint64_t sums S[i][j], the diagonal ignored, and sizes w[i] >= 1 (NULL: all 1).
+ *     S[i][j] is the sum of the quantised distances between the members of i and those of j; for single points it is the pair's
+ *     q, 0 <= q <= Q1.  W is the sum of all w; W < 2^22 keeps every S below 2^62 and every cross product below 2^106.
+ *   - Mean: D(a, b) = S(a, b) / (n_a n_b).  Two means are compared exactly, S1 (n_a2 n_b2) against S2 (n_a1 n_b1), in 128 bits.
+ *   - Every index starts as an active cluster named by its index, n_i = w[i].  A step takes the active pair a < b with the least
+ *     mean, ties to the smallest a, then the smallest b; emits rtc_umerge {a, b, size_a, size_b, sum}, sizes and sum those of the
+ *     pair before the merge; sets S(a, c) = S(a, c) + S(b, c) for every other active c; sets n_a += n_b and retires b: the
+ *     cluster keeps the name a.  Exactly m - 1 merges, in step order; there is no stop bound, the tree needs all of them.
+ *   - Height and cut are the host's.  rtc_upgma_distance(sum, size_a, size_b) = (double)sum / (((double)size_a *
+ *     (double)size_b) * 1048576.0), each operation one IEEE-754 double operation in that order.  The cut is in integers:
+ *     qcut = llround(threshold * 1048576.0), and a component's merges apply in order up to, not including, the first with
+ *     sum > qcut size_a size_b (128 bits).  Exact means never decrease from step to step -- the new D(a + b, c) is a weighted
+ *     mean of D(a, c) and D(b, c), each >= D(a, b) -- so the cut is a prefix.
+ * Three kernel paths, chosen per component: m <= 64 one wave with S and the sizes in LDS; larger ones a 256-lane workgroup with
+ * S in global memory, the whole dendrogram in one launch; from RTC_UPGMA_GRID_MIN points on (default 128; set, it holds down to 4)
+ * the whole device, two launches a merge, all of them enqueued without a read-back.  Every path scans all active pairs at every
+ * step and compares on the triple (mean, a, b), so the records are the same on every path. */
+typedef struct { uint32_t a, b, size_a, size_b; uint64_t sum; } rtc_umerge; /* 24 bytes */
+/* One matrix that is already on the device: d_sum[i * ld + j], 8-byte aligned, ld >= m; it is read and overwritten.  h_size[m]
+ * on the host, or NULL.  h_merges: room for max(m - 1, 1) records; m - 1 are written, a and b as indices.  The sums are not
+ * checked against Q1 w_i w_j: any are taken, and the records are the definition's, while every S the run forms stays below 2^62.
+ * W >= 2^22, ld < m, NULLs, a size of 0: RTC_ERR_ARG.  Synchronous. */
+int rtc_upgma_dev(rtc_ctx* ctx, uint32_t m, uint64_t* d_sum, uint64_t ld, const uint32_t* h_size /* may be NULL */, rtc_umerge* h_merges);
+/* One dendrogram per component of a labelling of n sketches: arguments, component numbering, member order, h_first and
+ * RTC_ERR_OVERFLOW (with the needed count) as rtc_nj_clusters has them; a component of m members has m - 1 records, a and b
+ * genome indices, and one of one member costs nothing.  The key blocks are rtc_linkage_complete's; each batch is copied to the
+ * host, every cell becomes q = min(Q1, llround(rtc_linkage_distance(common, denom, kmer_size) * 1048576.0)) -- Q1 for
+ * common == 0 or denom == 0, rtc_cluster_quality's formula -- on the context's host threads, the q go back as uint64_t into the
+ * same 8-byte cells and the device agglomerates.  The byte budget of a batch is RTC_UPGMA_BYTES (default half the free HBM); a
+ * component whose 8 m^2 bytes and one band exceed it: RTC_ERR_NOMEM, the message naming m and the bytes; no fallback. */
+int rtc_upgma_clusters(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                       const uint32_t* h_comp, int kmer_size, rtc_umerge* h_merges, uint64_t cap, uint64_t* h_n_merges, uint64_t* h_first);
+/* The last rtc_upgma_clusters (or rtc_upgma_dev): out[0] components of two or more, out[1] on the wave path, out[2] on the
+ * workgroup path, out[3] on the grid path, out[4] merges, out[5] row rescans (0: every step is a full scan), out[6] fill ns,
+ * out[7] host distance ns (copies included), out[8] agglomeration ns, out[9] whole call ns. */
+int rtc_upgma_counters(const rtc_ctx* ctx, uint64_t out[10]);
+/* The paths of the last call: bit 0 the wave path, bit 1 the workgroup path, bit 2 the grid path. */
+int rtc_upgma_last_path(const rtc_ctx* ctx);
+/* The height of a merge, as defined above.  Host only. */
+double rtc_upgma_distance(uint64_t sum, uint32_t size_a, uint32_t size_b);
+
 #ifdef __cplusplus
 }
 #endif

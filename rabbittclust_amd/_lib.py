@@ -181,6 +181,11 @@ SIGNATURES = {
     "rtc_silhouette_value": (C.c_double, [_vp]),
     "rtc_cluster_quality": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _i, _vp]),
     "rtc_cluster_quality_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_upgma_dev": (_i, [_vp, _u32, _vp, _u64, _vp, _vp]),
+    "rtc_upgma_clusters": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _i, _vp, _u64, C.POINTER(_u64), _vp]),
+    "rtc_upgma_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_upgma_last_path": (_i, [_vp]),
+    "rtc_upgma_distance": (C.c_double, [_u64, _u32, _u32]),
     "rtc_hierarchy_flat": (_i, [_u32, _vp, _u64, _vp, _i, _i, _vp, _vp, C.POINTER(_u32)]),
 }
 

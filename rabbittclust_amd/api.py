@@ -39,6 +39,10 @@ LMERGE_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("common", "<u4"), ("denom", "
 NJOIN_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("c", "<u4"), ("pad", "<u4"), ("len_a", "<f8"), ("len_b", "<f8"), ("len_c", "<f8")])  # rtc_njoin
 NJ_PATH_WAVE, NJ_PATH_WORKGROUP, NJ_PATH_GRID = 1, 2, 4  # rtc_nj_last_path
 NJ_GRID_MIN = 256  # the library's default RTC_NJ_GRID_MIN (rtc_nj.hip: NJ_GRID_MIN)
+UMERGE_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("size_a", "<u4"), ("size_b", "<u4"), ("sum", "<u8")])  # rtc_umerge
+UPGMA_PATH_WAVE, UPGMA_PATH_WORKGROUP, UPGMA_PATH_GRID = 1, 2, 4  # rtc_upgma_last_path
+UPGMA_GRID_MIN = 128  # the library's default RTC_UPGMA_GRID_MIN (rtc_upgma.h: UPGMA_GRID_MIN)
+UPGMA_Q1 = 1 << 20  # distance 1 in the units of rtc_upgma_dev's sums
 HEDGE_DT = np.dtype([("p", "<u4"), ("q", "<u4"), ("common", "<u4"), ("size_p", "<u4"), ("size_q", "<u4")])  # rtc_hedge
 MCL_ENTRY_DT = np.dtype([("col", "<u4"), ("row", "<u4"), ("value", "<u4"), ("pad", "<u4")])  # rtc_mcl_entry
 MCL_PATH_WAVE, MCL_PATH_WORKGROUP, MCL_PATH_GLOBAL = 1, 2, 4  # rtc_mcl_last_path
@@ -1125,6 +1129,57 @@ class Context:
         out["paths"] = int(self.lib.rtc_nj_last_path(self.h))
         return out
 
+    def upgma(self, sums, sizes=None, ld=None):
+        """rtc_upgma_dev: the average-linkage agglomeration include/rtclust.h defines over one symmetric m x m matrix of uint64
+        sums, uploaded for the call.  sizes: w[i] >= 1 per index (None: all 1).  ld: None takes the array as [m, ld]; a number
+        is passed on as it is (the refusals).  Returns the m - 1 UMERGE_DT records in step order, a and b as matrix indices."""
+        s = np.ascontiguousarray(sums, dtype=np.uint64)
+        if s.ndim != 2:
+            raise ValueError("sums must be [m, ld]")
+        m = int(s.shape[0])
+        ld = (int(s.shape[1]) if m else 0) if ld is None else int(ld)
+        w = None if sizes is None else np.ascontiguousarray(sizes, dtype=np.uint32)
+        if w is not None and w.shape != (m,):
+            raise ValueError("sizes must hold one entry per row")
+        t = torch.from_numpy(s.reshape(-1).view(np.int64).copy()).to(self.device) if s.size else torch.zeros(2, dtype=torch.int64, device=self.device)
+        out = np.zeros(max(m - 1, 1), dtype=UMERGE_DT)
+        self.check(self.lib.rtc_upgma_dev(self.h, m, _t_ptr(t), ld, None if w is None else _np_ptr(w), _np_ptr(out)))
+        return out[:max(m - 1, 0)].copy()
+
+    def upgma_clusters(self, sk, comp, kmer_size, cap=None):
+        """rtc_upgma_clusters: one average-linkage dendrogram per component of the labelling comp[g] of sk's sketches (any
+        labels; components are numbered by their smallest member) over the quantised rtc_linkage_distance of the exact keys.
+        Returns (merges, first): UMERGE_DT records with a and b as genome indices, component after component, and first[c] where
+        component c's records start.  cap: room for the records (None: n, which always suffices); too small raises
+        RTC_ERR_OVERFLOW, the needed count in self.upgma_merges_needed."""
+        n = sk.n
+        lab = np.ascontiguousarray(np.asarray(comp).astype(np.int64).astype(np.uint32))
+        if lab.shape != (n,):
+            raise ValueError("comp must hold one label per sketch")
+        room = max(n, 1) if cap is None else int(cap)
+        out = np.zeros(max(room, 1), dtype=UMERGE_DT)
+        first = np.zeros(n + 1, dtype=np.uint64)
+        nm = C.c_uint64(0)
+        st = self.lib.rtc_upgma_clusters(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n, _np_ptr(lab), int(kmer_size),
+                                         _np_ptr(out), room, C.byref(nm), _np_ptr(first))
+        self.upgma_merges_needed = int(nm.value)
+        self.check(st)
+        return out[:nm.value].copy(), first[:len(np.unique(lab)) + 1].copy()
+
+    def upgma_counters(self):
+        """rtc_upgma_counters as a dict (the last upgma or upgma_clusters call), and "paths": rtc_upgma_last_path's bits."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_upgma_counters(self.h, a))
+        names = ("components", "wave_components", "workgroup_components", "grid_components", "merges", "row_rescans", "fill_ns", "distance_ns",
+                 "agglomerate_ns", "total_ns")
+        out = {k: int(a[i]) for i, k in enumerate(names)}
+        out["paths"] = self.upgma_last_path()
+        return out
+
+    def upgma_last_path(self):
+        """rtc_upgma_last_path: UPGMA_PATH_WAVE | UPGMA_PATH_WORKGROUP | UPGMA_PATH_GRID of the last call"""
+        return int(self.lib.rtc_upgma_last_path(self.h))
+
     def graph_query(self, sk, n_db, threshold, kmer_size, knn_k=0, query_chunk=0, cap=None):
         """clust-leiden --db --assign, first call (rtc_graph_query): sk holds the n_db model genomes, then the queries.  Returns
         (edges, near): QEDGE_DT records (q, p, common) in (q, p) order -- every query's knn_k best model genomes among those
@@ -1273,6 +1328,21 @@ def graph_weights_mash(edges, sketch_size, kmer_size, return_weights=False):
 def linkage_distance(common, denom, kmer_size):
     """rtc_linkage_distance: the distance the host gives a complete-linkage merge of key common / denom"""
     return float(_lib.load().rtc_linkage_distance(int(common), int(denom), int(kmer_size)))
+
+
+def upgma_distance(sum, size_a, size_b):
+    """rtc_upgma_distance: the height of an average-linkage merge, sum / ((size_a size_b) 2^20) in double, through the library
+    (no GPU needed)"""
+    return float(_lib.load().rtc_upgma_distance(int(sum), int(size_a), int(size_b)))
+
+
+def upgma_keep(sum, size_a, size_b, threshold):
+    """clust-mst --upgma's cut rule in integers: a merge applies while sum <= qcut size_a size_b, qcut = llround(threshold 2^20)
+    (round half away from zero, as the C library's llround)"""
+    x = float(threshold) * 1048576.0
+    lo = math.floor(abs(x))
+    qcut = (int(lo) + (1 if abs(x) - lo >= 0.5 else 0)) * (1 if x >= 0 else -1)  # abs(x) - lo is exact
+    return int(sum) <= qcut * int(size_a) * int(size_b)
 
 
 def silhouette_value(records):

@@ -41,6 +41,8 @@ struct rtc_options {
   uint64_t linkage_bytes = 0;      // RTC_LINKAGE_BYTES: the byte budget of a batch of rtc_linkage_complete (0: half the free HBM)
   uint64_t nj_bytes = 0;           // RTC_NJ_BYTES: the byte budget of a batch of rtc_nj_clusters (0: half the free HBM)
   uint32_t nj_grid_min = 0;        // RTC_NJ_GRID_MIN: components of at least this many points (down to 4) take the grid path (0: default)
+  uint64_t upgma_bytes = 0;        // RTC_UPGMA_BYTES: the byte budget of a batch of rtc_upgma_clusters (0: half the free HBM)
+  uint32_t upgma_grid_min = 0;     // RTC_UPGMA_GRID_MIN: components of at least this many points (down to 4) take the grid path (0: default)
   int mcl_global = 0;              // RTC_MCL_GLOBAL: every column of rtc_mcl takes the long path (the table in global memory)
   int sil_global = 0;              // RTC_SIL_GLOBAL: every row of rtc_silhouette takes the long path (the table in global memory)
 };
@@ -106,12 +108,14 @@ struct rtc_ctx {
   uint64_t linkage[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_linkage_counters (include/rtclust.h lists them)
   uint64_t nj[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_nj_counters (include/rtclust.h lists them)
   int nj_path = 0;          // rtc_nj_last_path
+  uint64_t upgma[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_upgma_counters (include/rtclust.h lists them)
+  int upgma_path = 0;       // rtc_upgma_last_path
   uint64_t mcl[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_mcl_counters (include/rtclust.h lists them)
   int mcl_path = 0;         // rtc_mcl_last_path
   uint64_t sil[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_silhouette_counters (include/rtclust.h lists them)
   int sil_path = 0;         // rtc_silhouette_last_path
   uint64_t quality[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_cluster_quality_counters (include/rtclust.h lists them)
-  int host_threads = 1;     // rtc_ctx_set_host_threads: the host side of rtc_tree_medoids and of rtc_nj_clusters' and rtc_cluster_quality's distances
+  int host_threads = 1;     // rtc_ctx_set_host_threads: the host side of rtc_tree_medoids and of rtc_nj_clusters', rtc_upgma_clusters' and rtc_cluster_quality's distances
   // rtc_diag_counters: [0] pair tiles the join took, [1] tiled-kernel tiles, [2] merge-kernel tiles, [3] candidate lists contracted
   // to their forest, [4] greedy runs replayed from ONE global join, [5] greedy query blocks of the block loop, [6] estimates handed
   // back instead of a launch (rtc_pair_edges_dev's overflow protocol)

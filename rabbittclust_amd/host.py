@@ -179,3 +179,57 @@ def quality_report(names, cluster_of, records, sil):
         fn(*args, buf, need)
         out.append(buf.raw[:need].decode())
     return tuple(out)
+
+
+def upgma_newick(labels, members, merges):
+    """upgma_newick_text (rtc_host.cpp): the Newick text of one average-linkage tree, node height = distance / 2.  labels[g]: the
+    label of genome g; members: the genome indices of the tree; merges: its rtc_umerge records (api.UMERGE_DT), a and b as genome
+    indices."""
+    mem = np.ascontiguousarray(sorted(int(g) for g in members), dtype=np.uint32)
+    j = np.ascontiguousarray(merges)
+    assert j.dtype.itemsize == 24
+    arr = (C.c_char_p * max(len(labels), 1))(*[s.encode() for s in labels])
+    fn = load().rtch_upgma_newick
+    fn.restype = C.c_long
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_long]
+    need = fn(arr, mem.ctypes.data_as(C.c_void_p), len(mem), j.ctypes.data_as(C.c_void_p), len(j), None, 0)
+    buf = C.create_string_buffer(max(int(need), 1))
+    fn(arr, mem.ctypes.data_as(C.c_void_p), len(mem), j.ctypes.data_as(C.c_void_p), len(j), buf, need)
+    return buf.raw[:need].decode()
+
+
+def upgma_keep(sum, size_a, size_b, threshold):
+    """upgma_keep (rtc_host.cpp): the command line's integer cut rule for one merge"""
+    fn = load().rtch_upgma_keep
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_double]
+    return bool(fn(int(sum), int(size_a), int(size_b), float(threshold)))
+
+
+def upgma_report(cluster_of, merges, first, threshold):
+    """upgma_report (rtc_host.cpp): what clust-mst --upgma writes from the records of Context.upgma_clusters(sk, cluster_of, k) ->
+    (the text of <output>.upgma.linkage.txt, the refined clusters at the threshold as lists of ascending genome indices ordered
+    by smallest member, the merges kept).  cluster_of[g]: the cluster number <output> gives genome g."""
+    lab = np.ascontiguousarray(cluster_of, dtype=np.int32)
+    n = len(lab)
+    mg = np.ascontiguousarray(merges)
+    fs = np.ascontiguousarray(first, dtype=np.uint64)
+    assert mg.dtype.itemsize == 24
+    ncl = int(lab.max()) + 1 if n else 0
+    assert len(fs) >= ncl + 1
+    refined = np.full(max(n, 1), -1, dtype=np.int32)
+    kept = C.c_uint64(0)
+    fn = load().rtch_upgma_report
+    fn.restype = C.c_long
+    fn.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p, C.c_long]
+    args = (lab.ctypes.data_as(C.c_void_p), ncl, n, mg.ctypes.data_as(C.c_void_p), fs.ctypes.data_as(C.c_void_p), float(threshold),
+            refined.ctypes.data_as(C.c_void_p), C.byref(kept))
+    need = fn(*args, None, 0)
+    if need < 0:
+        raise ValueError("cluster_of must number the clusters 0 .. n_clusters - 1, none of them empty")
+    buf = C.create_string_buffer(max(int(need), 1))
+    fn(*args, buf, need)
+    out = [[] for _ in range(int(refined[:n].max()) + 1 if n else 0)]
+    for g in range(n):
+        out[int(refined[g])].append(g)
+    return buf.raw[:need].decode(), out, int(kept.value)

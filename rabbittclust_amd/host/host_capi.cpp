@@ -300,6 +300,37 @@ long rtch_nj_newick(const char* const* labels, const uint32_t* members, uint64_t
   return (long)text.size();
 }
 
+// upgma_newick_text over plain arrays, as rtch_nj_newick
+long rtch_upgma_newick(const char* const* labels, const uint32_t* members, uint64_t m, const rtc_umerge* merges, uint64_t n_merges, char* out, long cap) {
+  const std::string text = upgma_newick_text([&](uint32_t v) { return std::string(labels[v]); }, members, (size_t)m, merges, (size_t)n_merges);
+  if (out && (long)text.size() <= cap) memcpy(out, text.data(), text.size());
+  return (long)text.size();
+}
+
+int rtch_upgma_keep(uint64_t sum, uint32_t size_a, uint32_t size_b, double threshold) { return upgma_keep(sum, size_a, size_b, threshold) ? 1 : 0; }
+
+// upgma_report over plain arrays: cluster_of[g] in [0, n_clusters) for every genome, merges and first as rtc_upgma_clusters gives
+// them for that labelling.  refined_of[n]: the refined cluster of every genome, numbered in order of smallest member; *kept the
+// merges kept.  Returns -1 for a cluster_of outside that range, else the length of the linkage text; the text itself when it fits
+// cap (no terminator).
+long rtch_upgma_report(const int32_t* cluster_of, uint32_t n_clusters, uint32_t n, const rtc_umerge* merges, const uint64_t* first, double threshold,
+                       int32_t* refined_of, uint64_t* kept, char* out, long cap) {
+  std::vector<std::vector<int>> clusters(n_clusters);
+  for (uint32_t g = 0; g < n; g++) {
+    if (cluster_of[g] < 0 || (uint32_t)cluster_of[g] >= n_clusters) return -1;
+    clusters[cluster_of[g]].push_back((int)g);
+  }
+  for (const auto& c : clusters) if (c.empty()) return -1;
+  std::string text;
+  std::vector<std::vector<int>> refined;
+  const uint64_t k = upgma_report(n, clusters, merges, first, threshold, &text, &refined);
+  if (kept) *kept = k;
+  if (refined_of)
+    for (size_t c = 0; c < refined.size(); c++) for (int g : refined[c]) refined_of[g] = (int32_t)c;
+  if (out && (long)text.size() <= cap) memcpy(out, text.data(), text.size());
+  return (long)text.size();
+}
+
 // quality_report_text over plain arrays: names[g], cluster_of[g] in [0, n_clusters) for every genome, rec[g] (rtc_sil) and sil[g].
 // which 0: the cluster report, 1: the genome report.  Returns -1 for a cluster_of outside that range, else the text's length; the text itself when it fits cap (no terminator).
 long rtch_quality_report(const char* const* names, const int32_t* cluster_of, uint32_t n_clusters, const rtc_sil* rec, const double* sil, uint32_t n,

@@ -895,6 +895,7 @@ struct Options {
   string minhashOnly;        // clust-leiden: the first of -s / -c as spelled, which only --minhash gives a meaning
   bool linkageComplete = false;  // clust-mst --linkage complete: complete linkage inside every cluster (rtc_linkage_complete)
   bool quality = false;  // clust-mst --quality: silhouette, diameter and separation of the run's clusters (rtc_cluster_quality)
+  bool upgma = false;  // clust-mst --upgma: average linkage inside every cluster (rtc_upgma_clusters)
   bool njTree = false, njAll = false;  // clust-mst --nj-tree / --nj-all: neighbour-joining trees of the clusters / of all genomes (rtc_nj_clusters)
 };
 
@@ -1054,6 +1055,7 @@ static Options parse(int argc, char** argv) {
     else if (a == "--nj-tree") o.njTree = true;
     else if (a == "--nj-all") o.njAll = true;
     else if (a == "--quality") o.quality = true;
+    else if (a == "--upgma") o.upgma = true;
 #endif
     else if (a == "-h" || a == "--help") {
 #ifdef GREEDY_CLUST
@@ -1147,6 +1149,9 @@ static Options parse(int argc, char** argv) {
            "  --quality (how good the partition is, over the exact set-Jaccard distances, scored on the GPU: <output>.quality.tsv, a\n"
            "             line a cluster with its mean and least silhouette, mean intra-cluster distance, diameter, separation and\n"
            "             nearest cluster, and <output>.silhouette.tsv, a line a genome; with --fast or MinHash on the index path)\n"
+           "  --upgma (average linkage, UPGMA, inside every cluster of the run, in exact integers on the GPU: <output>.upgma, the\n"
+           "             clusters cut at -d by mean distance; <output>.upgma.linkage.txt, every merge; <output>.upgma.newick, one\n"
+           "             ultrametric tree a line in the order of <output>; with --fast or MinHash on the index path)\n"
            "  [--fast] --db FILE --build|--query|--assign|--append LIST|--stats [--top-k N] (MST representative database)"
 #else
            "  --append LIST (with --presketched DIR)  --save-rep (cluster_state.bin beside the sketches)\n"
@@ -1357,6 +1362,48 @@ static int nj_trees_and_print(rtc_ctx* ctx, const DeviceSketches& ds, const vect
   g_metrics.num("nj_join_s", 1e-9 * (double)sum[8]);
   g_metrics.num("nj_components", (double)sum[0]);
   g_metrics.num("nj_records", (double)sum[4]);
+  return 0;
+}
+// --upgma: average linkage inside every cluster of the plain run (include/rtclust.h has the definition).  The device hands back
+// every cluster's whole dendrogram on exact integer sums; upgma_report cuts it at the threshold by the integer rule.
+// <base>.upgma: the refined clusters in print_result's layout, by smallest member; <base>.upgma.linkage.txt: all merges;
+// <base>.upgma.newick: one ultrametric tree a line in the order <base> lists the clusters.  A cluster that does not fit the
+// device (RTC_ERR_NOMEM, no fallback) is reported after everything else has been written: returns 1.
+static int upgma_and_print(rtc_ctx* ctx, const DeviceSketches& ds, const vector<vector<int>>& clusters, const vector<GenomeInfo>& genomes,
+                           bool sketchByFile, const string& base, double threshold, int kmer_size, int threads) {
+  const uint32_t n = (uint32_t)genomes.size();
+  CHECK(ctx, rtc_ctx_set_host_threads(ctx, threads > 0 ? threads : 1));
+  vector<uint32_t> comp(n, 0);
+  for (size_t c = 0; c < clusters.size(); c++) for (int g : clusters[c]) comp[g] = (uint32_t)c;
+  vector<rtc_umerge> merges(n > 0 ? n : 1);
+  vector<uint64_t> first((size_t)n + 1, 0);
+  uint64_t n_merges = 0;
+  const int st = rtc_upgma_clusters(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, n, comp.data(), kmer_size, merges.data(), merges.size(), &n_merges,
+                                    first.data());
+  if (st == RTC_ERR_NOMEM) { cerr << "ERROR: " << rtc_last_error(ctx) << endl; return 1; }
+  CHECK(ctx, st);
+  uint64_t cnt[10];
+  CHECK(ctx, rtc_upgma_counters(ctx, cnt));
+  string linkage_txt;
+  vector<vector<int>> out;
+  upgma_report(n, clusters, merges.data(), first.data(), threshold, &linkage_txt, &out);
+  const string f_cl = base + ".upgma", f_lk = base + ".upgma.linkage.txt", f_nw = base + ".upgma.newick";
+  FILE* fp = fopen(f_lk.c_str(), "w");
+  if (!fp) { cerr << "ERROR: cannot open file: " << f_lk << endl; join_warmup(); exit(1); }
+  fwrite(linkage_txt.data(), 1, linkage_txt.size(), fp);
+  fclose(fp);
+  print_result(out, genomes, sketchByFile, f_cl, threshold);
+  print_upgma_newick(genomes, clusters, merges, first, sketchByFile, f_nw);
+  cerr << "-----write the average-linkage cluster result into: " << f_cl << endl;
+  cerr << "-----the cluster number of: " << f_cl << " is: " << out.size() << endl;
+  cerr << "-----write the average-linkage matrix into: " << f_lk << endl;
+  cerr << "-----write the average-linkage trees of the clusters into: " << f_nw << endl;
+  g_metrics.num("upgma_fill_s", 1e-9 * (double)cnt[6]);
+  g_metrics.num("upgma_distance_s", 1e-9 * (double)cnt[7]);
+  g_metrics.num("upgma_agglomerate_s", 1e-9 * (double)cnt[8]);
+  g_metrics.num("upgma_components", (double)cnt[0]);
+  g_metrics.num("upgma_merges", (double)cnt[4]);
+  g_metrics.num("upgma_clusters", (double)out.size());
   return 0;
 }
 // --quality: the silhouette of every genome under the run's clusters and, per cluster, its diameter and its separation from the
@@ -2946,6 +2993,13 @@ int main(int argc, char** argv) {
                       : o.autoThreshold ? "--auto-threshold" : o.stability ? "--stability" : nullptr;
     if (bad) { cerr << "ERROR: --quality does not go with " << bad << endl; return 1; }
   }
+  // ---- --upgma: and again ----
+  if (o.upgma) {
+    const char* bad = o.isContainment ? "-c/--containment" : !o.useIndex ? "--inverted-index=false" : o.has_append ? "--append"
+                      : o.has_premsted ? "--premsted" : !o.repdb_path.empty() ? "--db" : o.dense ? "--dense"
+                      : o.autoThreshold ? "--auto-threshold" : o.stability ? "--stability" : nullptr;
+    if (bad) { cerr << "ERROR: --upgma does not go with " << bad << endl; return 1; }
+  }
 #endif
   // ---- MST RepDB mode: --db FILE (src/main.cpp:213-254, :525-600) ----
   if (o.has_topk && !o.db_query) { cerr << "ERROR: --top-k requires --query" << endl; return 1; }
@@ -3775,6 +3829,13 @@ int main(int argc, char** argv) {
   if (o.quality) {
     if (is_containment) { cerr << "ERROR: --quality does not go with containment sketches" << endl; return 1; }
     if (quality_and_print(ctx, dss[0], clusters, genomes, sketchByFile, o.outputFile, kmer_size, o.threads) != 0) {
+      join_warmup();
+      return 1;
+    }
+  }
+  if (o.upgma) {
+    if (is_containment) { cerr << "ERROR: --upgma does not go with containment sketches" << endl; return 1; }
+    if (upgma_and_print(ctx, dss[0], clusters, genomes, sketchByFile, o.outputFile, o.threshold, kmer_size, o.threads) != 0) {
       join_warmup();
       return 1;
     }

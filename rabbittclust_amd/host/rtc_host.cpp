@@ -1304,6 +1304,87 @@ void print_nj_newick(const std::vector<GenomeInfo>& g, const std::vector<std::ve
   fclose(fp);
 }
 
+bool upgma_keep(uint64_t sum, uint32_t size_a, uint32_t size_b, double threshold) {
+  const long long qcut = llround(threshold * 1048576.0);
+  if (qcut < 0) return false;
+  return (unsigned __int128)sum <= (unsigned __int128)(uint64_t)qcut * ((uint64_t)size_a * (uint64_t)size_b);
+}
+
+uint64_t upgma_report(uint32_t n, const std::vector<std::vector<int>>& clusters, const rtc_umerge* merges, const uint64_t* first, double threshold,
+                      std::string* linkage_txt, std::vector<std::vector<int>>* refined) {
+  std::vector<size_t> order(clusters.size());
+  std::vector<int> smallest(clusters.size());
+  for (size_t c = 0; c < clusters.size(); c++) { order[c] = c; smallest[c] = *std::min_element(clusters[c].begin(), clusters[c].end()); }
+  std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return smallest[x] < smallest[y]; });
+  std::vector<int> cid(n), head(n);  // the linkage id of the cluster named g; the refined cluster (index into out) named g
+  for (uint32_t g = 0; g < n; g++) cid[g] = (int)g;
+  std::vector<std::vector<int>> out;
+  int next_id = (int)n;
+  uint64_t kept = 0;
+  char buf[128];
+  linkage_txt->clear();
+  for (size_t q = 0; q < order.size(); q++) {
+    const size_t out0 = out.size();
+    for (int g : clusters[order[q]]) { head[g] = (int)out.size(); out.push_back({g}); }
+    bool cut = false;
+    for (uint64_t e = first[q]; e < first[q + 1]; e++) {
+      const rtc_umerge& mg = merges[e];
+      snprintf(buf, sizeof buf, "%d\t%d\t%.6f\t%u\n", cid[mg.a], cid[mg.b], upgma_height(mg.sum, mg.size_a, mg.size_b), mg.size_a + mg.size_b);
+      *linkage_txt += buf;
+      cid[mg.a] = next_id++;
+      if (!cut && !upgma_keep(mg.sum, mg.size_a, mg.size_b, threshold)) cut = true;
+      if (cut) continue;
+      std::vector<int>& A = out[head[mg.a]];
+      std::vector<int>& B = out[head[mg.b]];
+      A.insert(A.end(), B.begin(), B.end());
+      B.clear();
+      kept++;
+    }
+    std::vector<std::vector<int>> part;
+    for (size_t i = out0; i < out.size(); i++) if (!out[i].empty()) { std::sort(out[i].begin(), out[i].end()); part.push_back(std::move(out[i])); }
+    out.resize(out0);
+    for (auto& c : part) out.push_back(std::move(c));
+  }
+  std::sort(out.begin(), out.end(), [](const std::vector<int>& x, const std::vector<int>& y) { return x[0] < y[0]; });
+  *refined = std::move(out);
+  return kept;
+}
+
+// The records become binary rtc_njoin records -- len = the new node's height minus the child's -- and nj_newick_text writes them.
+std::string upgma_newick_text(const std::function<std::string(uint32_t)>& label, const uint32_t* members, size_t m, const rtc_umerge* merges,
+                              size_t n_merges) {
+  std::unordered_map<uint32_t, double> height;  // of the cluster named g; a leaf is at 0
+  height.reserve(2 * m);
+  std::vector<rtc_njoin> joins(n_merges);
+  for (size_t e = 0; e < n_merges; e++) {
+    const rtc_umerge& mg = merges[e];
+    const double h = upgma_height(mg.sum, mg.size_a, mg.size_b) / 2.0;
+    const auto ia = height.find(mg.a), ib = height.find(mg.b);
+    const double ha = ia == height.end() ? 0.0 : ia->second, hb = ib == height.end() ? 0.0 : ib->second;
+    joins[e] = rtc_njoin{mg.a, mg.b, 0xFFFFFFFFu, 0u, h - ha, h - hb, 0.0};
+    height[mg.a] = h;
+  }
+  return nj_newick_text(label, members, m, joins.data(), n_merges);
+}
+
+void print_upgma_newick(const std::vector<GenomeInfo>& g, const std::vector<std::vector<int>>& clusters, const std::vector<rtc_umerge>& merges,
+                        const std::vector<uint64_t>& first, bool sketchByFile, const std::string& output) {
+  std::vector<size_t> order(clusters.size()), rank(clusters.size());
+  std::vector<int> smallest(clusters.size());
+  for (size_t c = 0; c < clusters.size(); c++) { order[c] = c; smallest[c] = *std::min_element(clusters[c].begin(), clusters[c].end()); }
+  std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return smallest[x] < smallest[y]; });
+  for (size_t q = 0; q < order.size(); q++) rank[order[q]] = q;
+  FILE* fp = open_out(output, "print_upgma_newick");
+  for (size_t c = 0; c < clusters.size(); c++) {
+    const size_t q = rank[c];
+    std::vector<uint32_t> mem(clusters[c].begin(), clusters[c].end());
+    std::sort(mem.begin(), mem.end());
+    fprintf(fp, "%s\n", upgma_newick_text([&](uint32_t v) { return sketchByFile ? g[v].fileName : g[v].seq0.name; }, mem.data(), mem.size(),
+                                          merges.data() + first[q], (size_t)(first[q + 1] - first[q])).c_str());
+  }
+  fclose(fp);
+}
+
 double quality_report_text(const std::function<std::string(uint32_t)>& name, const std::vector<std::vector<int>>& clusters, const rtc_sil* rec,
                            const double* sil, uint32_t n, std::string* quality_tsv, std::string* silhouette_tsv) {
   char buf[512];

@@ -179,6 +179,29 @@ std::string get_nj_newick(const std::vector<GenomeInfo>& g, const std::vector<in
 void print_nj_newick(const std::vector<GenomeInfo>& g, const std::vector<std::vector<int>>& clusters, const std::vector<rtc_njoin>& joins,
                      const std::vector<uint64_t>& first, bool sketchByFile, const std::string& output);
 
+// ---- clust-mst --upgma: the cut and the three writers over rtc_upgma_clusters' records (include/rtclust.h has the definition).
+// upgma_height is rtc_upgma_distance (the host library does not link the device library): one double operation a step.
+// upgma_keep: the integer cut rule, sum <= llround(threshold 2^20) size_a size_b in 128 bits.
+// upgma_report: clusters are the run's, every genome in exactly one; first[q] .. first[q + 1] are the merges (a, b genome indices)
+// of the cluster whose smallest member is the q-th smallest.  linkage_txt: ALL merges, cluster after cluster in that order,
+// "c1 \t c2 \t distance (%.6f) \t size" as print_linkage_matrix writes them, leaves as genome indices, new ids n, n + 1, ... in
+// file order.  refined: every cluster cut at the threshold (the prefix of its merges that upgma_keep keeps), members ascending,
+// clusters by smallest member.  Returns the merges kept.
+// upgma_newick_text: one ultrametric tree, node height = distance / 2, branch length = parent height - child height printed as
+// nj_newick_text prints lengths; labels and the one- and two-member cases as there. ----
+inline double upgma_height(uint64_t sum, uint32_t size_a, uint32_t size_b) {
+  const double pairs = (double)size_a * (double)size_b;
+  const double scale = pairs * 1048576.0;
+  return (double)sum / scale;
+}
+bool upgma_keep(uint64_t sum, uint32_t size_a, uint32_t size_b, double threshold);
+uint64_t upgma_report(uint32_t n, const std::vector<std::vector<int>>& clusters, const rtc_umerge* merges, const uint64_t* first, double threshold,
+                      std::string* linkage_txt, std::vector<std::vector<int>>* refined);
+std::string upgma_newick_text(const std::function<std::string(uint32_t)>& label, const uint32_t* members, size_t m, const rtc_umerge* merges,
+                              size_t n_merges);
+void print_upgma_newick(const std::vector<GenomeInfo>& g, const std::vector<std::vector<int>>& clusters, const std::vector<rtc_umerge>& merges,
+                        const std::vector<uint64_t>& first, bool sketchByFile, const std::string& output);
+
 // ---- clust-mst --quality: the two reports of rtc_cluster_quality's records (include/rtclust.h).  sil[g]: rtc_silhouette_value of
 // rec[g]; clusters: the run's, numbered as <output> numbers them, every genome in exactly one.  quality_tsv: a header, a line a
 // cluster -- cluster, size, mean silhouette, least silhouette, mean intra-cluster distance (the sum of a_num over the members /
