@@ -901,6 +901,39 @@ int rtc_mcl_counters(const rtc_ctx* ctx, uint64_t out[10]);
 /* the column paths of the last rtc_mcl: bit 0 one wave, bit 1 a 256-lane workgroup, bit 2 the table in global memory */
 int rtc_mcl_last_path(const rtc_ctx* ctx);
 
+/* Shared-nearest-neighbour (SNN) edge weights: clust-leiden --snn.  The weight of an edge becomes the Jaccard index of its two
+ * ends' neighbourhoods (Jarvis-Patrick; the usual preparation of a k-NN graph for Louvain and Leiden).  The quantity is an integer
+ * count per edge, so the result depends neither on the scheduling nor on the kernel path (tests/refsnn.py restates it).
+ *   - Input: n vertices and m records (u, v, q) in any order; q is not read.  G is the simple undirected graph of the records:
+ *     (u, v) and (v, u) are the same edge, equal edges collapse to one, a record with u == v is in no neighbourhood.  N(x) is the
+ *     set of neighbours of x in G, deg x = |N(x)|.
+ *   - For a record with u != v: shared = |N(u) & N(v)|, the triangles through the edge; deg_u, deg_v the two degrees; flags 0.
+ *     With the closed neighbourhoods N[x] = N(x) + {x} the weight is
+ *         w = |N[u] & N[v]| / |N[u] | N[v]| = (shared + 2) / (deg_u + deg_v - shared),
+ *     so 0 < w <= 1 and the denominator is never below 2: an isolated edge and every edge of a clique weigh 1, an edge of a star
+ *     with L leaves 2 / (L + 1), the bridge between two K40 2 / 80.  The device returns the integers; rtc_snn_weight forms the one
+ *     double division on the host.
+ *   - A record with u == v: shared 0, deg_u = deg_v = the degree of u in G, flags bit 0 set.
+ *   - h_out[m], record for record.  u or v >= n, h_edges or h_out NULL with m > 0, n >= 2^31 - 1: RTC_ERR_ARG.  m == 0 or n == 0:
+ *     RTC_OK, nothing is written.
+ * The device holds the records, two buffers of 2m 64-bit keys, the rows and the result, about 76 m + 8 n bytes and the sort's
+ * scratch; if they do not fit the free memory: RTC_ERR_NOMEM with the bytes in the message, no fallback.  A record is counted by
+ * the end with the longer row (the lower index on equal lengths), on one of three kernel paths by that row's length
+ * (rabbittclust_amd/csrc/rtc_snn.h: at most 768 entries one wave, at most 8192 a 256-lane workgroup, both with the row in LDS;
+ * beyond, the row where it lies in global memory).  RTC_SNN_GLOBAL=1 sends every record through the last; counts are identical.
+ * Synchronous. */
+typedef struct { uint32_t shared, deg_u, deg_v, flags; } rtc_snn;   /* flags bit 0: u == v (shared = 0, the degrees still those of G) */
+int rtc_graph_snn(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, uint64_t m, rtc_snn* h_out);
+/* host only: (double)(shared + 2) / (double)(deg_u + deg_v - shared) */
+double rtc_snn_weight(uint32_t shared, uint32_t deg_u, uint32_t deg_v);
+/* The last rtc_graph_snn: out[0] records, out[1] distinct edges of G, out[2] triangles of G (the sum of shared over distinct
+ * edges, divided by 3), out[3] probes (elements of the shorter rows that were looked up), out[4] / out[5] / out[6] records counted
+ * on the wave / workgroup / global path, out[7] adjacency ns (upload, sort, unique, rows), out[8] counting ns (owners, their sort
+ * and the three launches), out[9] whole call ns (host clock, each ending in a synchronise). */
+int rtc_graph_snn_counters(const rtc_ctx* ctx, uint64_t out[10]);
+/* the paths of the last rtc_graph_snn: bit 0 one wave, bit 1 a 256-lane workgroup, bit 2 the row in global memory */
+int rtc_graph_snn_last_path(const rtc_ctx* ctx);
+
 /* ---- clust-leiden --db --assign: new genomes placed into the communities of a finished run ------------------- */
 /* The move phase's choice for a vertex that was not there.  The reference has nothing of the kind: this is the definition
  * (tests/refleiden_assign.py restates it).

@@ -162,6 +162,10 @@ SIGNATURES = {
     "rtc_mcl": (_i, [_vp, _u32, _vp, _u64, _i, _u32, _u32, _vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_i), _vp, _u64, C.POINTER(_u64)]),
     "rtc_mcl_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_mcl_last_path": (_i, [_vp]),
+    "rtc_graph_snn": (_i, [_vp, _u32, _vp, _u64, _vp]),
+    "rtc_snn_weight": (C.c_double, [_u32, _u32, _u32]),
+    "rtc_graph_snn_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_graph_snn_last_path": (_i, [_vp]),
     "rtc_graph_query": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _u32, C.c_double, _i, _u32, _u32, _vp, _u64, C.POINTER(_u64), _vp]),
     "rtc_graph_query_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_leiden_place": (_i, [_vp, _u32, _vp, _u32, _vp, _u64, C.c_double, _i, _u32, _vp, _u64, _vp]),

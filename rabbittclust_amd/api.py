@@ -50,6 +50,12 @@ MCL_PATH_WAVE, MCL_PATH_WORKGROUP, MCL_PATH_GLOBAL = 1, 2, 4  # rtc_mcl_last_pat
 # wave, at most MCL_BLOCK_WORK a 256-lane workgroup, more the table in global memory
 MCL_WAVE_WORK = 256
 MCL_BLOCK_WORK = 3072
+SNN_DT = np.dtype([("shared", "<u4"), ("deg_u", "<u4"), ("deg_v", "<u4"), ("flags", "<u4")])  # rtc_snn
+SNN_PATH_WAVE, SNN_PATH_WORKGROUP, SNN_PATH_GLOBAL = 1, 2, 4  # rtc_graph_snn_last_path
+# the counting kernel's path boundaries (csrc/rtc_snn.h): a record whose longer row has at most SNN_WAVE_ROW entries takes one
+# wave, at most SNN_BLOCK_ROW a 256-lane workgroup, both with that row in LDS; a longer one is searched in global memory
+SNN_WAVE_ROW = 768
+SNN_BLOCK_ROW = 8192
 SIL_DT = np.dtype([("a_num", "<u8"), ("b_num", "<u8"), ("a_den", "<u4"), ("b_den", "<u4"), ("b_cluster", "<u4"), ("far_q", "<u4"),
                    ("near_q", "<u4"), ("near_cluster", "<u4")])  # rtc_sil
 SIL_ONE = 1 << 20  # distance 1 in rtc_silhouette's units
@@ -994,6 +1000,32 @@ class Context:
         """rtc_mcl_last_path: MCL_PATH_WAVE | MCL_PATH_WORKGROUP | MCL_PATH_GLOBAL, the column paths of the last mcl call"""
         return int(self.lib.rtc_mcl_last_path(self.h))
 
+    def graph_snn(self, n, u, v):
+        """rtc_graph_snn: the shared-neighbour counts include/rtclust.h defines over n vertices and the records (u[e], v[e]).
+        Returns (shared, deg_u, deg_v, flags), uint32 arrays with one entry per record; snn_weight turns them into weights."""
+        u = np.asarray(u, dtype=np.uint32).reshape(-1)
+        v = np.asarray(v, dtype=np.uint32).reshape(-1)
+        if u.shape != v.shape:
+            raise ValueError("u and v must hold one entry per record")
+        e = np.zeros(u.size, dtype=WEDGE_DT)
+        e["u"], e["v"] = u, v
+        out = np.zeros(max(int(e.size), 1), dtype=SNN_DT)
+        self.check(self.lib.rtc_graph_snn(self.h, int(n), _np_ptr(e) if e.size else None, int(e.size), _np_ptr(out) if e.size else None))
+        out = out[:e.size]
+        return out["shared"].copy(), out["deg_u"].copy(), out["deg_v"].copy(), out["flags"].copy()
+
+    def graph_snn_counters(self):
+        """rtc_graph_snn_counters as a dict (the last graph_snn call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_graph_snn_counters(self.h, a))
+        names = ("records", "edges", "triangles", "probes", "wave_records", "workgroup_records", "global_records", "adjacency_ns",
+                 "count_ns", "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
+    def graph_snn_last_path(self):
+        """rtc_graph_snn_last_path: SNN_PATH_WAVE | SNN_PATH_WORKGROUP | SNN_PATH_GLOBAL, the paths of the last graph_snn call"""
+        return int(self.lib.rtc_graph_snn_last_path(self.h))
+
     def silhouette(self, n, edges, labels):
         """rtc_silhouette: the score include/rtclust.h defines over n vertices, WEDGE_DT records (u, v, q) -- q the distance of the
         pair in units of 2^-20, unlisted pairs at SIL_ONE -- and one int32 label per vertex, negative for an unclustered one.
@@ -1323,6 +1355,11 @@ def graph_weights_mash(edges, sketch_size, kmer_size, return_weights=False):
                  dtype=np.float64)
     out = _weight_units(edges, w)
     return (out, w) if return_weights else out
+
+
+def snn_weight(shared, deg_u, deg_v):
+    """rtc_snn_weight: (shared + 2) / (deg_u + deg_v - shared), the library's host function"""
+    return float(_lib.load().rtc_snn_weight(int(shared), int(deg_u), int(deg_v)))
 
 
 def linkage_distance(common, denom, kmer_size):

@@ -107,6 +107,7 @@ void rtc_options_from_env(rtc_options* o) {
   if (const char* e = getenv("RTC_UPGMA_BYTES")) o->upgma_bytes = std::max<uint64_t>(strtoull(e, nullptr, 10), 1);
   if (getenv("RTC_UPGMA_GRID_MIN")) o->upgma_grid_min = (uint32_t)std::min<long long>(std::max<long long>(4, num("RTC_UPGMA_GRID_MIN", 4)), 0x7fffffff);
   o->mcl_global = flag("RTC_MCL_GLOBAL");
+  o->snn_global = flag("RTC_SNN_GLOBAL");
   o->sil_global = flag("RTC_SIL_GLOBAL");
 }
 

@@ -44,6 +44,7 @@ struct rtc_options {
   uint64_t upgma_bytes = 0;        // RTC_UPGMA_BYTES: the byte budget of a batch of rtc_upgma_clusters (0: half the free HBM)
   uint32_t upgma_grid_min = 0;     // RTC_UPGMA_GRID_MIN: components of at least this many points (down to 4) take the grid path (0: default)
   int mcl_global = 0;              // RTC_MCL_GLOBAL: every column of rtc_mcl takes the long path (the table in global memory)
+  int snn_global = 0;              // RTC_SNN_GLOBAL: every record of rtc_graph_snn takes the long path (the owner's row in global memory)
   int sil_global = 0;              // RTC_SIL_GLOBAL: every row of rtc_silhouette takes the long path (the table in global memory)
 };
 void rtc_options_from_env(rtc_options* o);
@@ -112,6 +113,8 @@ struct rtc_ctx {
   int upgma_path = 0;       // rtc_upgma_last_path
   uint64_t mcl[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_mcl_counters (include/rtclust.h lists them)
   int mcl_path = 0;         // rtc_mcl_last_path
+  uint64_t snn[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_graph_snn_counters (include/rtclust.h lists them)
+  int snn_path = 0;         // rtc_graph_snn_last_path
   uint64_t sil[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_silhouette_counters (include/rtclust.h lists them)
   int sil_path = 0;         // rtc_silhouette_last_path
   uint64_t quality[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_cluster_quality_counters (include/rtclust.h lists them)

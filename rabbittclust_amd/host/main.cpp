@@ -891,6 +891,9 @@ struct Options {
   bool mcl = false;
   string inflation = "2.0", mclSelect = "1024", mclIterations = "100";  // as spelled: the refusals name them
   const char* mclOnly = nullptr;  // the first of --inflation / --mcl-select / --mcl-iterations, which only --mcl gives a meaning
+  // clust-leiden --snn: shared-neighbour edge weights (rtc_graph_snn) in place of the pairs' own similarities
+  bool snn = false, hasSnnPrune = false;
+  string snnPrune = "0";  // as spelled
   bool hasDrlevel = false;
   string minhashOnly;        // clust-leiden: the first of -s / -c as spelled, which only --minhash gives a meaning
   bool linkageComplete = false;  // clust-mst --linkage complete: complete linkage inside every cluster (rtc_linkage_complete)
@@ -957,6 +960,8 @@ static Options parse(int argc, char** argv) {
     if (a == "--inflation") { o.inflation = need(i); if (!o.mclOnly) o.mclOnly = "--inflation"; continue; }
     if (a == "--mcl-select") { o.mclSelect = need(i); if (!o.mclOnly) o.mclOnly = "--mcl-select"; continue; }
     if (a == "--mcl-iterations") { o.mclIterations = need(i); if (!o.mclOnly) o.mclOnly = "--mcl-iterations"; continue; }
+    if (a == "--snn") { o.snn = true; continue; }
+    if (a == "--snn-prune") { o.snnPrune = need(i); o.hasSnnPrune = true; continue; }
     if (a == "--knn") { o.knn = atoi(need(i)); continue; }
     if (a == "--pregraph") { o.folder_path = need(i); o.has_pregraph = true; continue; }
     if (a == "--save-graph") { o.saveGraph = true; continue; }
@@ -1085,6 +1090,12 @@ static Options parse(int argc, char** argv) {
            "  --inflation X (with --mcl; default 2.0; a multiple of 0.5 between 1.5 and 8; higher: more clusters)\n"
            "  --mcl-select S (with --mcl; default 1024; a column of the matrix keeps its S largest entries, 1 .. 4096)\n"
            "  --mcl-iterations T (with --mcl; default 100; a run that has not converged by then warns and writes what it has)\n"
+           "  --snn (with any of the three algorithms: the weight of an edge becomes the shared-neighbour weight of include/rtclust.h,\n"
+           "         the Jaccard index of its two ends' closed neighbourhoods in the graph, (shared + 2) / (deg u + deg v - shared),\n"
+           "         counted on the GPU, in place of the pair's own 1 - distance; --save-graph still writes the similarity graph, and\n"
+           "         --pregraph DIR --snn gives the direct --snn run's result; not with --db)\n"
+           "  --snn-prune X (with --snn; default 0; 0 <= X < 1: the edges whose new weight is below X drop out, in one pass -- a\n"
+           "                 dropped edge still counted in the neighbourhoods)\n"
            "  --knn K (every genome keeps its K best edges among the higher-numbered genomes; 0 or absent: 1000 with --louvain, 500\n"
            "           with --leiden and --mcl; 1..9: 50 with a warning, as the reference defaults it, so the filter cannot be\n"
            "           switched off)\n"
@@ -2797,6 +2808,15 @@ int main(int argc, char** argv) {
     if (end == o.mclIterations.c_str() || *end || its < 0 || its > 0x7fffffffll) { cerr << "ERROR: --mcl-iterations must be 0 or more, got " << o.mclIterations << endl; return 1; }
     mcl_iterations = (uint32_t)its;
   }
+  // ---- clust-leiden --snn: a query has no neighbourhood in the model's graph, so no placement rule follows from these weights
+  double snn_prune = 0.0;
+  if (!o.snn && o.hasSnnPrune) { cerr << "ERROR: --snn-prune needs --snn" << endl; return 1; }
+  if (o.snn) {
+    if (!o.repdb_path.empty() || o.db_build || o.db_assign || o.db_stats) { cerr << "ERROR: --snn does not go with --db" << endl; return 1; }
+    char* end = nullptr;
+    snn_prune = strtod(o.snnPrune.c_str(), &end);
+    if (end == o.snnPrune.c_str() || *end || !(snn_prune >= 0.0 && snn_prune < 1.0)) { cerr << "ERROR: --snn-prune must be in [0, 1)" << endl; return 1; }
+  }
   // ---- clust-leiden --db: the model file's flows, their flag errors first ----
   LeidenModel ld_model;
   {
@@ -3426,6 +3446,27 @@ int main(int argc, char** argv) {
       cerr << "-----Graph saved to: " << graph_file << endl;
     }
   }
+  uint64_t snn_c[10] = {0}, snn_pruned = 0;
+  if (o.snn) {
+    // --snn: every record's weight becomes the shared-neighbour weight of its edge, before anything is quantised; the graph
+    // saved above stays the similarity graph.  A record of a vertex with itself (a --pregraph file may hold one) keeps its own.
+    vector<rtc_snn> sn(wedges.size());
+    CHECK(ctx, rtc_graph_snn(ctx, n_nodes, wedges.data(), wedges.size(), sn.data()));
+    rtc_graph_snn_counters(ctx, snn_c);
+    size_t kept = 0;
+    double w_lo = 0.0, w_hi = 0.0;
+    for (size_t e = 0; e < wedges.size(); e++) {
+      const double w = (sn[e].flags & 1u) ? weights[e] : rtc_snn_weight(sn[e].shared, sn[e].deg_u, sn[e].deg_v);
+      if (w < snn_prune) { snn_pruned++; continue; }  // one pass: the dropped edge counted in the neighbourhoods
+      w_lo = kept ? std::min(w_lo, w) : w;
+      w_hi = kept ? std::max(w_hi, w) : w;
+      wedges[kept] = rtc_wedge{wedges[e].u, wedges[e].v, leiden_weight_units(w)};
+      weights[kept++] = w;
+    }
+    wedges.resize(kept);
+    weights.resize(kept);
+    cerr << "-----SNN: " << snn_c[1] << " edge(s), " << snn_c[2] << " triangle(s), " << snn_pruned << " pruned, weights [" << w_lo << ", " << w_hi << "]" << endl;
+  }
   if (wedges.empty()) cerr << "-----Warning: No edges! Each sequence in its own cluster." << endl;
   vector<int32_t> labels(n_nodes);
   uint32_t ncl = 0;
@@ -3496,6 +3537,11 @@ int main(int argc, char** argv) {
   cerr << "========time of Leiden clustering is: " << get_sec() - t2 << "========" << endl;
   g_metrics.num("leiden_louvain_s", lc[9] / 1e9);  // the clustering call, whichever algorithm
   g_metrics.num("leiden_edges", (double)graph_edges);
+  if (o.snn) {
+    g_metrics.num("leiden_snn_s", snn_c[9] / 1e9);
+    g_metrics.num("leiden_snn_triangles", (double)snn_c[2]);
+    g_metrics.num("leiden_snn_pruned", (double)snn_pruned);
+  }
   if (o.mcl) {
     g_metrics.num("mcl_iterations", (double)mcl_its);
     g_metrics.num("mcl_converged", (double)mcl_converged);

@@ -26,7 +26,14 @@ With --mcl it also runs the Markov clustering (Context.mcl) on Louvain's records
 the column paths it took and the whole-call time of rtc_mcl beside rtc_louvain's (the best of --repeat calls each, after one
 call to warm up), and how many families came back whole.
 
-    python tools/run_leiden.py --mcl [--inflation 2.0] [--mcl-select 1024] [--mcl-iterations 100] [--repeat 3]"""
+    python tools/run_leiden.py --mcl [--inflation 2.0] [--mcl-select 1024] [--mcl-iterations 100] [--repeat 3]
+
+With --snn it also counts the shared neighbours of the graph's edges (Context.graph_snn, clust-leiden --snn) and prints the
+counter set of the call with the least whole-call time, the paths it took, the probes per second of its counting part, and the
+whole-call times of rtc_graph_snn (with its adjacency and counting parts), of rtc_graph_build and of rtc_louvain on the
+SNN-weighted records, all in one loop in this process: lowest and highest of --repeat calls each, after one call to warm up.
+
+    python tools/run_leiden.py --snn [--families 20 --per-family 300 --threshold 0.15] [--repeat 5]"""
 import argparse
 import json
 import os
@@ -57,8 +64,9 @@ def main():
     ap.add_argument("--inflation", type=float, default=2.0)
     ap.add_argument("--mcl-select", type=int, default=1024)
     ap.add_argument("--mcl-iterations", type=int, default=100)
+    ap.add_argument("--snn", action="store_true")
     a = ap.parse_args()
-    if a.minhash and (a.leiden or a.assign or a.mcl):
+    if a.minhash and (a.leiden or a.assign or a.mcl or a.snn):
         ap.error("--minhash prints the graph's and Louvain's counters alone")
     from rabbittclust_amd import api, host
     ctx = api.Context(0)
@@ -101,9 +109,36 @@ def main():
         out.update({"mcl": ctx.mcl_counters(), "mcl_paths": ctx.mcl_last_path(), "mcl_inflation": a.inflation, "mcl_select": a.mcl_select,
                     "mcl_clusters": ctx.mcl_clusters, "mcl_families_whole": whole, "louvain_call_ms": min(louvain_ns[1:]) / 1e6,
                     "mcl_call_ms": min(mcl_ns[1:]) / 1e6})
+    if a.snn:
+        out.update(snn(ctx, a, sk, kmer, n, edges))
     if a.assign:
         out["assign"] = assign(ctx, a, sk, kmer, n)
     print(json.dumps(out))
+
+
+def snn(ctx, a, sk, kmer, n, edges):
+    from rabbittclust_amd import api
+    build_ns, calls, louvain_ns, srec = [], [], [], None
+    for i in range(a.repeat + 1):  # the first call of each warms up
+        ctx.graph_build(sk, a.threshold, kmer, a.knn)
+        build_ns.append(ctx.graph_counters()["total_ns"])
+        shared, du, dv, _ = ctx.graph_snn(n, edges["u"], edges["v"])
+        calls.append(ctx.graph_snn_counters())
+        if srec is None:  # the command line's records: q = max(1, llround(w 2^20)) of the one double division
+            w = (shared.astype(np.float64) + 2.0) / (du.astype(np.float64) + dv.astype(np.float64) - shared.astype(np.float64))
+            srec = np.zeros(len(edges), dtype=api.WEDGE_DT)
+            srec["u"], srec["v"], srec["q"] = edges["u"], edges["v"], np.maximum(1, np.floor(w * 1048576.0 + 0.5)).astype(np.uint32)
+        labels = ctx.louvain(n, srec, a.resolution)
+        louvain_ns.append(ctx.louvain_counters()["total_ns"])
+    warm = calls[1:]
+    best = min(warm, key=lambda c: c["total_ns"])
+    span = lambda ns: [min(ns) / 1e6, max(ns) / 1e6]
+    whole = sum(1 for f in range(a.families) if len(set(labels[f * a.per_family:(f + 1) * a.per_family].tolist())) == 1)
+    return {"snn": best, "snn_paths": ctx.graph_snn_last_path(), "snn_weights": [float(w.min()), float(w.max())] if len(w) else [],
+            "snn_call_ms": span([c["total_ns"] for c in warm]), "snn_adjacency_ms": span([c["adjacency_ns"] for c in warm]),
+            "snn_count_ms": span([c["count_ns"] for c in warm]), "snn_probes_per_s": best["probes"] / max(best["count_ns"], 1) * 1e9,
+            "graph_build_call_ms": span(build_ns[1:]), "louvain_snn_call_ms": span(louvain_ns[1:]), "snn_clusters": ctx.louvain_clusters,
+            "snn_families_whole": whole}
 
 
 def minhash(ctx, a, seq, off, kmer, n):
