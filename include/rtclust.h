@@ -1094,6 +1094,50 @@ int rtc_nj_counters(const rtc_ctx* ctx, uint64_t out[10]);
 /* The paths of the last call: bit 0 the wave path, bit 1 the workgroup path, bit 2 the grid path. */
 int rtc_nj_last_path(const rtc_ctx* ctx);
 
+/* ---- clust-mst --nj-support: jackknife support values for the neighbour-joining trees --------------------------------- */
+/* How many of B delete-half jackknife replicates over the sketch hashes hold each inner branch of rtc_nj_clusters' trees.  This
+ * is the definition (tests/refnjsupport.py restates it); everything is integer but the neighbour joining itself, which is
+ * rtc_nj_dev's definition unchanged.
+ *   Mask.  mix(x): z = x + 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *     mix = z ^ (z >> 31), all modulo 2^64.  word(h, seed, w) = mix(h ^ mix(seed + w)), h the hash, zero-extended at width 4.
+ *     Replicate r in [0, B) keeps hash h iff bit r % 64 of word(h, seed, r / 64) is set: the same hash is kept or dropped in every
+ *     genome.  B lies in 1 .. 256 (a cap, not a measurement).
+ *   Keys.  size_r(a) = |{h in a : kept in r}|, common_r(a, b) = |{h in a and b : kept in r}| over the full sorted lists (the sets
+ *     rtc_pair_common_dev counts), denom_r = size_r(a) + size_r(b) - common_r, and
+ *     D_r[a][b] = rtc_linkage_distance(common_r, denom_r, kmer_size), 1 for common_r == 0 or denom_r == 0.
+ *   Trees.  rtc_nj_dev's definition on D_r, over the same components and the same member order as the main tree.
+ *   Splits.  In a tree of m >= 4 members every record with c == UINT32_MAX names a node; S is the set of leaves below it (the
+ *     leaves of the nodes it joined, and of theirs).  Its split is {S, complement}, compared as the side that does not hold the
+ *     component's smallest member.  These are the m - 3 inner branches; the closing record and trees of m <= 3 have none.
+ *   Support.  support(record) = |{r : the record's split is a split of replicate r's tree}|, splits compared exactly.
+ * The counts depend on neither the path of the joining, nor on how the replicates are grouped under the byte budget, nor on
+ * RTC_PAIR_FORCE_MERGE.
+ *
+ * h_joins, h_n_joins, h_first and the errors are rtc_nj_clusters' for the same arguments; h_support[cap] gets one count per
+ * record, 0 for the records that name no split.  The main blocks are filled as rtc_nj_clusters fills them, but a batch leaves
+ * room for one more copy of its blocks; the replicates are then taken in groups of as many as RTC_NJ_BYTES leaves room for beside
+ * the main blocks (whole words of 64 where that is more than 64).  A counting kernel walks every pair of a component once per
+ * word -- one wave, one replicate per lane -- and writes (common_r, denom_r) straight into the replicate's key block; the blocks
+ * go to the host for distances and come back, and the replicate trees are joined as further components of rtc_nj_clusters' own
+ * launches.  The host counts the splits, O(B m) nodes per tree.  A component that cannot hold its own block, one replicate block
+ * and one band: RTC_ERR_NOMEM, the message naming m and the bytes; no fallback.  replicates outside 1 .. 256: RTC_ERR_ARG.
+ * rtc_nj_counters describes the main trees as after rtc_nj_clusters.  Synchronous. */
+int rtc_nj_support(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                   const uint32_t* h_comp, int kmer_size, uint32_t replicates, uint64_t seed, rtc_njoin* h_joins, uint64_t cap,
+                   uint64_t* h_n_joins, uint64_t* h_first, uint32_t* h_support);
+/* The last rtc_nj_support: out[0] replicates, out[1] replicate trees joined, out[2] counting ns, out[3] host distance ns (copies
+ * included), out[4] joining ns, out[5] split ns, out[6] whole call ns, out[7] replicate groups, out[8] records that name a
+ * split, out[9] the sum of their counts. */
+int rtc_nj_support_counters(const rtc_ctx* ctx, uint64_t out[10]);
+/* word(hash, seed, word) above.  Host only, no context. */
+uint64_t rtc_jackknife_word(uint64_t hash, uint64_t seed, uint32_t word);
+/* The counting kernel's pair routine over an edge list: d_common[e * 64 + r] = common_r of the pair (d_edges[e].i, d_edges[e].j),
+ * e < m, both below n, for the replicates r of the given word (the edge's own count is ignored); d_size, where it is not NULL,
+ * gets d_size[g * 64 + r] = size_r(g) for every sketch.  One wave per pair: the shorter list is staged in LDS when it has at most
+ * 1024 hashes (rtc_jackknife.h: JK_LDS_ELEMS) and searched in global memory otherwise.  Context stream, asynchronous. */
+int rtc_jackknife_pairs_dev(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                            const rtc_cedge* d_edges, uint64_t m, uint64_t seed, uint32_t word, uint32_t* d_common, uint32_t* d_size);
+
 /* ---- clust-mst --quality: silhouette and cluster separation of a finished partition ---------------------------------- */
 /* The silhouette of every vertex of a labelled, weighted graph, and what a cluster's diameter and separation are read from, in
  * exact integers; this is the definition (tests/refquality.py restates it).  Q1 = 2^20 is distance 1.

@@ -39,6 +39,8 @@ LMERGE_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("common", "<u4"), ("denom", "
 NJOIN_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("c", "<u4"), ("pad", "<u4"), ("len_a", "<f8"), ("len_b", "<f8"), ("len_c", "<f8")])  # rtc_njoin
 NJ_PATH_WAVE, NJ_PATH_WORKGROUP, NJ_PATH_GRID = 1, 2, 4  # rtc_nj_last_path
 NJ_GRID_MIN = 256  # the library's default RTC_NJ_GRID_MIN (rtc_nj.hip: NJ_GRID_MIN)
+NJ_SUPPORT_MAX = 256  # rtc_nj_support's most replicates
+JK_LDS_ELEMS = 1024  # the jackknife counting kernel stages a list of up to this many hashes in LDS (csrc/rtc_jackknife.h); a longer one is searched in global memory
 UMERGE_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("size_a", "<u4"), ("size_b", "<u4"), ("sum", "<u8")])  # rtc_umerge
 UPGMA_PATH_WAVE, UPGMA_PATH_WORKGROUP, UPGMA_PATH_GRID = 1, 2, 4  # rtc_upgma_last_path
 UPGMA_GRID_MIN = 128  # the library's default RTC_UPGMA_GRID_MIN (rtc_upgma.h: UPGMA_GRID_MIN)
@@ -1161,6 +1163,52 @@ class Context:
         out["paths"] = int(self.lib.rtc_nj_last_path(self.h))
         return out
 
+    def nj_support(self, sk, comp, kmer_size, replicates, seed=0, cap=None):
+        """rtc_nj_support: nj_clusters' (joins, first) for the same arguments and, third, one uint32 per record: how many of the
+        `replicates` (1 .. NJ_SUPPORT_MAX) delete-half jackknife replicates over the sketch hashes hold the record's split; 0 for
+        the records that name none (the closing one, and trees of three members or fewer).  nj_counters describes the main trees,
+        nj_support_counters the replicates."""
+        n = sk.n
+        lab = np.ascontiguousarray(np.asarray(comp).astype(np.int64).astype(np.uint32))
+        if lab.shape != (n,):
+            raise ValueError("comp must hold one label per sketch")
+        room = max(n, 1) if cap is None else int(cap)
+        out = np.zeros(max(room, 1), dtype=NJOIN_DT)
+        support = np.zeros(max(room, 1), dtype=np.uint32)
+        first = np.zeros(n + 1, dtype=np.uint64)
+        nj = C.c_uint64(0)
+        st = self.lib.rtc_nj_support(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n, _np_ptr(lab), int(kmer_size),
+                                     int(replicates), int(seed) & 0xFFFFFFFFFFFFFFFF, _np_ptr(out), room, C.byref(nj), _np_ptr(first),
+                                     _np_ptr(support))
+        self.nj_records_needed = int(nj.value)
+        self.check(st)
+        return out[:nj.value].copy(), first[:len(np.unique(lab)) + 1].copy(), support[:nj.value].copy()
+
+    def nj_support_counters(self):
+        """rtc_nj_support_counters as a dict (the last nj_support call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_nj_support_counters(self.h, a))
+        names = ("replicates", "replicate_trees", "count_ns", "distance_ns", "join_ns", "split_ns", "total_ns", "groups", "splits", "count_sum")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
+    def jackknife_pairs(self, sk, pairs, seed=0, word=0, sizes=True):
+        """rtc_jackknife_pairs_dev: the counting kernel's pair routine over the given pairs, an (m, 2) array of indices below sk.n.
+        Returns (common, size): common[e, r] the hashes pair e shares that replicate 64 * word + r keeps, size[g, r] those of
+        sketch g it keeps (None without sizes)."""
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+        m = len(pairs)
+        if m and (pairs.min() < 0 or pairs.max() >= sk.n):
+            raise ValueError("jackknife_pairs: an index outside [0, n)")
+        edges = np.zeros(max(m, 1), dtype=CEDGE_DT)
+        edges["i"][:m], edges["j"][:m] = pairs[:, 0], pairs[:, 1]
+        d_edges = torch.from_numpy(edges.view(np.uint32).reshape(-1, 3).view(np.int32)).to(self.device)
+        common = torch.zeros((max(m, 1), 64), dtype=torch.int32, device=self.device)
+        size = torch.zeros((max(sk.n, 1), 64), dtype=torch.int32, device=self.device) if sizes else None
+        self.check(self.lib.rtc_jackknife_pairs_dev(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), sk.n, _t_ptr(d_edges), m,
+                                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(word), _t_ptr(common), _t_ptr(size) if sizes else None))
+        self.sync()
+        return common[:m].cpu().numpy().view(np.uint32), (size[:sk.n].cpu().numpy().view(np.uint32) if sizes else None)
+
     def upgma(self, sums, sizes=None, ld=None):
         """rtc_upgma_dev: the average-linkage agglomeration include/rtclust.h defines over one symmetric m x m matrix of uint64
         sums, uploaded for the call.  sizes: w[i] >= 1 per index (None: all 1).  ld: None takes the array as [m, ld]; a number
@@ -1365,6 +1413,11 @@ def snn_weight(shared, deg_u, deg_v):
 def linkage_distance(common, denom, kmer_size):
     """rtc_linkage_distance: the distance the host gives a complete-linkage merge of key common / denom"""
     return float(_lib.load().rtc_linkage_distance(int(common), int(denom), int(kmer_size)))
+
+
+def jackknife_word(hash, seed, word):
+    """rtc_jackknife_word: the 64 keep bits of a hash for the replicates 64 * word .. 64 * word + 63 (no GPU needed)"""
+    return int(_lib.load().rtc_jackknife_word(int(hash) & 0xFFFFFFFFFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF, int(word)))
 
 
 def upgma_distance(sum, size_a, size_b):

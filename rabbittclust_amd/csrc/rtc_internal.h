@@ -109,6 +109,7 @@ struct rtc_ctx {
   uint64_t linkage[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_linkage_counters (include/rtclust.h lists them)
   uint64_t nj[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_nj_counters (include/rtclust.h lists them)
   int nj_path = 0;          // rtc_nj_last_path
+  uint64_t nj_support[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_nj_support_counters (include/rtclust.h lists them)
   uint64_t upgma[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_upgma_counters (include/rtclust.h lists them)
   int upgma_path = 0;       // rtc_upgma_last_path
   uint64_t mcl[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_mcl_counters (include/rtclust.h lists them)
@@ -240,13 +241,24 @@ struct rtc_kb_batch {
   size_t c, ce;                      // the components of the batch, those of one member included
   uint64_t fill_ns;
   const std::vector<uint32_t>*csize, *cfirst, *perm;
+  uint64_t budget;                   // the byte budget the batch was formed under
 };
 // on_batch is called for every batch in component order, the stream idle and the blocks complete; it may overwrite them.
 // budget_opt 0: half the free HBM.  h_first[0 .. n_comp] is zeroed.  A component whose 8 m^2 bytes and one band exceed the budget:
-// RTC_ERR_NOMEM, the message starting with who.
+// RTC_ERR_NOMEM, the message starting with who.  spare_copies: a batch leaves room for that many further copies of its blocks
+// (rtc_nj_support's replicate blocks), and the refusal counts them.
 int rtc_key_blocks(rtc_ctx* ctx, const char* who, uint64_t budget_opt, const void* d_hashes, int width, const uint64_t* d_start,
                    const uint32_t* d_len, uint32_t n, const uint32_t* h_comp, uint64_t* h_first,
-                   const std::function<int(const rtc_kb_batch&)>& on_batch);
+                   const std::function<int(const rtc_kb_batch&)>& on_batch, uint32_t spare_copies = 0);
+
+// rtc_nj.hip, for rtc_nj_support.hip.  rtc_nj_join: the records of comps[0 .. nc) (each m >= 2) over the matrices in d_dist, laid
+// out by merge_off, which it sets; n_path[3]: the components of each path.  rtc_nj_clusters_impl is rtc_nj_clusters with a hook that sees every batch of two or more after its trees are joined: the
+// batch (blocks overwritten), the components, their records with local indices, the records before the batch.
+int rtc_nj_join(rtc_ctx* ctx, double* d_dist, std::vector<rtc_kb_comp>& comps, std::vector<rtc_njoin>& h_out, uint64_t n_path[3]);
+using rtc_nj_hook = std::function<int(const rtc_kb_batch&, const std::vector<rtc_kb_comp>&, const std::vector<rtc_njoin>&, uint64_t)>;
+int rtc_nj_clusters_impl(rtc_ctx* ctx, const char* who, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len,
+                         uint32_t n, const uint32_t* h_comp, int kmer_size, rtc_njoin* h_joins, uint64_t cap, uint64_t* h_n_joins,
+                         uint64_t* h_first, uint32_t spare_copies, const rtc_nj_hook* hook);
 
 #define RTC_HIP(ctx, call)                                                                  \
   do {                                                                                      \

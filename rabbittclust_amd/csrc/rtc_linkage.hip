@@ -376,7 +376,7 @@ extern "C" int rtc_linkage_dev(rtc_ctx* ctx, uint32_t m, rtc_lkey* d_key, uint64
 // rtc_nj_clusters joins.
 int rtc_key_blocks(rtc_ctx* ctx, const char* who, uint64_t budget_opt, const void* d_hashes, int width, const uint64_t* d_start,
                    const uint32_t* d_len, uint32_t n, const uint32_t* h_comp, uint64_t* h_first,
-                   const std::function<int(const rtc_kb_batch&)>& on_batch) {
+                   const std::function<int(const rtc_kb_batch&)>& on_batch, uint32_t spare_copies) {
   // ---- components in order of their smallest member; members in ascending genome order ----
   std::vector<uint32_t> by_label(n);
   std::iota(by_label.begin(), by_label.end(), 0u);
@@ -429,7 +429,8 @@ int rtc_key_blocks(rtc_ctx* ctx, const char* who, uint64_t budget_opt, const voi
   auto min_band = [](uint64_t m) { return 4 * m * std::min<uint64_t>(m, 64); };
   std::vector<lk_row> rows(np);
   std::vector<lk_comp> comps;
-  rtc_kb_batch batch = {nullptr, 0, &comps, 0, 0, 0, &csize, &cfirst, &perm};
+  rtc_kb_batch batch = {nullptr, 0, &comps, 0, 0, 0, &csize, &cfirst, &perm, budget};
+  const uint64_t copies = 1 + (uint64_t)spare_copies;  // block_bytes is at most 2^62 / 8 per copy below the cut, and the cut itself ends the sum
   size_t c = 0;
   while (c < n_comp) {
     comps.clear();
@@ -446,7 +447,11 @@ int rtc_key_blocks(rtc_ctx* ctx, const char* who, uint64_t budget_opt, const voi
       const uint64_t m = csize[ce];
       if (m >= 2) {
         const uint64_t nb = std::max(band, min_band(m));
-        if (kb + block_bytes(m) + nb > budget) {
+        if (block_bytes(m) > budget || copies * (kb + block_bytes(m)) + nb > budget) {
+          if (kb == 0 && spare_copies)
+            return rtc_fail(ctx, RTC_ERR_NOMEM, "%s: a component of m = %llu needs %llu bytes (8 m^2, %u replicate block(s) of 8 m^2 and one band), the budget is %llu",
+                            who, (unsigned long long)m, (unsigned long long)(block_bytes(m) > budget ? block_bytes(m) : copies * block_bytes(m) + min_band(m)),
+                            spare_copies, (unsigned long long)budget);
           if (kb == 0)
             return rtc_fail(ctx, RTC_ERR_NOMEM, "%s: a component of m = %llu needs %llu bytes (8 m^2 and one band), the budget is %llu", who,
                             (unsigned long long)m, (unsigned long long)(block_bytes(m) + min_band(m)), (unsigned long long)budget);

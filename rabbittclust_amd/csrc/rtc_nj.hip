@@ -428,14 +428,24 @@ extern "C" int rtc_nj_dev(rtc_ctx* ctx, uint32_t m, double* d_dist, uint64_t ld,
   return RTC_OK;
 }
 
+int rtc_nj_join(rtc_ctx* ctx, double* d_dist, std::vector<rtc_kb_comp>& comps, std::vector<rtc_njoin>& h_out, uint64_t n_path[3]) {
+  return nj_join(ctx, d_dist, comps, h_out, n_path);
+}
+
 extern "C" int rtc_nj_clusters(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
                                const uint32_t* h_comp, int kmer_size, rtc_njoin* h_joins, uint64_t cap, uint64_t* h_n_joins, uint64_t* h_first) {
+  return rtc_nj_clusters_impl(ctx, "rtc_nj_clusters", d_hashes, width, d_start, d_len, n, h_comp, kmer_size, h_joins, cap, h_n_joins, h_first, 0, nullptr);
+}
+
+int rtc_nj_clusters_impl(rtc_ctx* ctx, const char* who, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len,
+                         uint32_t n, const uint32_t* h_comp, int kmer_size, rtc_njoin* h_joins, uint64_t cap, uint64_t* h_n_joins,
+                         uint64_t* h_first, uint32_t spare_copies, const rtc_nj_hook* hook) {
   if (!ctx || !h_n_joins || !h_first) return RTC_ERR_ARG;
   *h_n_joins = 0;
   h_first[0] = 0;
   if (width != 4 && width != 8) return rtc_fail(ctx, RTC_ERR_ARG, "width must be 4 or 8");
-  if (kmer_size < 1) return rtc_fail(ctx, RTC_ERR_ARG, "rtc_nj_clusters: kmer_size must be at least 1");
-  if (n >= 0x7fffffffu) return rtc_fail(ctx, RTC_ERR_ARG, "rtc_nj_clusters: n must be below 2^31 - 1");
+  if (kmer_size < 1) return rtc_fail(ctx, RTC_ERR_ARG, "%s: kmer_size must be at least 1", who);
+  if (n >= 0x7fffffffu) return rtc_fail(ctx, RTC_ERR_ARG, "%s: n must be below 2^31 - 1", who);
   if (cap && !h_joins) return RTC_ERR_ARG;
   for (int i = 0; i < 10; i++) ctx->nj[i] = 0;
   ctx->nj_path = 0;
@@ -447,7 +457,7 @@ extern "C" int rtc_nj_clusters(rtc_ctx* ctx, const void* d_hashes, int width, co
   uint64_t total = 0;
   bool overflow = false;
   std::vector<uint64_t> cells;
-  RTC_TRY(rtc_key_blocks(ctx, "rtc_nj_clusters", ctx->opt.nj_bytes, d_hashes, width, d_start, d_len, n, h_comp, h_first, [&](const rtc_kb_batch& b) -> int {
+  RTC_TRY(rtc_key_blocks(ctx, who, ctx->opt.nj_bytes, d_hashes, width, d_start, d_len, n, h_comp, h_first, [&](const rtc_kb_batch& b) -> int {
     std::vector<rtc_kb_comp>& comps = *b.comps;
     std::vector<rtc_njoin> out;
     if (b.d_keys) {
@@ -467,6 +477,7 @@ extern "C" int rtc_nj_clusters(rtc_ctx* ctx, const void* d_hashes, int width, co
       RTC_TRY(nj_join(ctx, (double*)b.d_keys, comps, out, n_path));
       C[8] += nj_now_ns() - td1;
       for (int p = 0; p < 3; p++) { C[1 + p] += n_path[p]; if (n_path[p]) ctx->nj_path |= 1 << p; }
+      if (hook) RTC_TRY((*hook)(b, comps, out, total));
     }
     // the records in component order, local indices turned into genome indices
     const std::vector<uint32_t>&csize = *b.csize, &cfirst = *b.cfirst, &perm = *b.perm;
@@ -492,9 +503,9 @@ extern "C" int rtc_nj_clusters(rtc_ctx* ctx, const void* d_hashes, int width, co
       h_first[q + 1] = total;
     }
     return RTC_OK;
-  }));
+  }, spare_copies));
   *h_n_joins = total;
   C[9] = nj_now_ns() - t0;
-  if (overflow) return rtc_fail(ctx, RTC_ERR_OVERFLOW, "rtc_nj_clusters: %llu records, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+  if (overflow) return rtc_fail(ctx, RTC_ERR_OVERFLOW, "%s: %llu records, room for %llu", who, (unsigned long long)total, (unsigned long long)cap);
   return RTC_OK;
 }

@@ -154,6 +154,26 @@ def nj_newick(labels, members, joins):
     return buf.raw[:need].decode()
 
 
+def nj_support_newick(labels, members, joins, support, replicates):
+    """nj_support_newick_text (rtc_host.cpp): nj_newick's text with the support of every node that names a split, in percent (half
+    up), between its ")" and its ":".  support: one count per record (Context.nj_support's), of `replicates`."""
+    mem = np.ascontiguousarray(sorted(int(g) for g in members), dtype=np.uint32)
+    j = np.ascontiguousarray(joins)
+    sup = np.ascontiguousarray(support, dtype=np.uint32)
+    assert j.dtype.itemsize == 40 and len(sup) == len(j)
+    if int(replicates) < 1:
+        raise ValueError("replicates must be at least 1")
+    arr = (C.c_char_p * max(len(labels), 1))(*[s.encode() for s in labels])
+    fn = load().rtch_nj_support_newick
+    fn.restype = C.c_long
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_long]
+    args = (arr, mem.ctypes.data_as(C.c_void_p), len(mem), j.ctypes.data_as(C.c_void_p), len(j), sup.ctypes.data_as(C.c_void_p), int(replicates))
+    need = fn(*args, None, 0)
+    buf = C.create_string_buffer(max(int(need), 1))
+    fn(*args, buf, need)
+    return buf.raw[:need].decode()
+
+
 def quality_report(names, cluster_of, records, sil):
     """quality_report_text (rtc_host.cpp): the two reports of clust-mst --quality as (quality_tsv, silhouette_tsv).  names[g] and
     cluster_of[g] (the cluster number <output> gives genome g) for every genome, records: api.SIL_DT, sil: their silhouettes."""

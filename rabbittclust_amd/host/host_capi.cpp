@@ -300,6 +300,15 @@ long rtch_nj_newick(const char* const* labels, const uint32_t* members, uint64_t
   return (long)text.size();
 }
 
+// nj_support_newick_text over plain arrays, as rtch_nj_newick; support[n_joins]
+long rtch_nj_support_newick(const char* const* labels, const uint32_t* members, uint64_t m, const rtc_njoin* joins, uint64_t n_joins,
+                            const uint32_t* support, uint32_t replicates, char* out, long cap) {
+  if (!support || replicates == 0) return -1;
+  const std::string text = nj_support_newick_text([&](uint32_t v) { return std::string(labels[v]); }, members, (size_t)m, joins, (size_t)n_joins, support, replicates);
+  if (out && (long)text.size() <= cap) memcpy(out, text.data(), text.size());
+  return (long)text.size();
+}
+
 // upgma_newick_text over plain arrays, as rtch_nj_newick
 long rtch_upgma_newick(const char* const* labels, const uint32_t* members, uint64_t m, const rtc_umerge* merges, uint64_t n_merges, char* out, long cap) {
   const std::string text = upgma_newick_text([&](uint32_t v) { return std::string(labels[v]); }, members, (size_t)m, merges, (size_t)n_merges);

@@ -900,6 +900,9 @@ struct Options {
   bool quality = false;  // clust-mst --quality: silhouette, diameter and separation of the run's clusters (rtc_cluster_quality)
   bool upgma = false;  // clust-mst --upgma: average linkage inside every cluster (rtc_upgma_clusters)
   bool njTree = false, njAll = false;  // clust-mst --nj-tree / --nj-all: neighbour-joining trees of the clusters / of all genomes (rtc_nj_clusters)
+  bool has_njSupport = false, has_njSeed = false;  // clust-mst --nj-support B [--nj-seed S]: jackknife support values for those trees (rtc_nj_support)
+  long long njSupport = 0;
+  uint64_t njSeed = 0;
 };
 
 #ifdef LEIDEN_CLUST
@@ -1059,6 +1062,8 @@ static Options parse(int argc, char** argv) {
     }
     else if (a == "--nj-tree") o.njTree = true;
     else if (a == "--nj-all") o.njAll = true;
+    else if (a == "--nj-support") { o.njSupport = atoll(need(i)); o.has_njSupport = true; }
+    else if (a == "--nj-seed") { o.njSeed = strtoull(need(i), nullptr, 10); o.has_njSeed = true; }
     else if (a == "--quality") o.quality = true;
     else if (a == "--upgma") o.upgma = true;
 #endif
@@ -1157,6 +1162,9 @@ static Options parse(int argc, char** argv) {
            "  --nj-tree (a neighbour-joining tree of every cluster over the exact set-Jaccard distances, joined on the GPU:\n"
            "             <output>.nj.newick, one tree a line in the order of <output>; with --fast or MinHash on the index path)\n"
            "  --nj-all (one neighbour-joining tree over all genomes: <output>.nj.all.newick; genomes that share no hash are at distance 1)\n"
+           "  --nj-support B [--nj-seed S] (with --nj-tree / --nj-all: B = 1 .. 256 delete-half jackknife replicates over the sketch\n"
+           "             hashes, counted on the GPU; <output>.nj.support.newick / .nj.all.support.newick carry every inner branch's\n"
+           "             support in percent, <output>.nj.support.tsv / .nj.all.support.tsv the counts; S: the mask seed, default 0)\n"
            "  --quality (how good the partition is, over the exact set-Jaccard distances, scored on the GPU: <output>.quality.tsv, a\n"
            "             line a cluster with its mean and least silhouette, mean intra-cluster distance, diameter, separation and\n"
            "             nearest cluster, and <output>.silhouette.tsv, a line a genome; with --fast or MinHash on the index path)\n"
@@ -1344,10 +1352,11 @@ static void linkage_complete_and_print(rtc_ctx* ctx, const DeviceSketches& ds, c
 // the order <base> lists the clusters; --nj-all: all genomes are one component, <base>.nj.all.newick.  A tree that does not fit
 // the device (RTC_ERR_NOMEM, no fallback) is reported after everything else has been written: returns 1.
 static int nj_trees_and_print(rtc_ctx* ctx, const DeviceSketches& ds, const vector<vector<int>>& clusters, const vector<GenomeInfo>& genomes,
-                              bool sketchByFile, const string& base, int kmer_size, int threads, bool per_cluster, bool all) {
+                              bool sketchByFile, const string& base, int kmer_size, int threads, bool per_cluster, bool all, uint32_t replicates,
+                              uint64_t seed) {
   const uint32_t n = (uint32_t)genomes.size();
   CHECK(ctx, rtc_ctx_set_host_threads(ctx, threads > 0 ? threads : 1));
-  uint64_t sum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t sum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ssum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int pass = 0; pass < 2; pass++) {
     if (!(pass == 0 ? per_cluster : all)) continue;
     vector<uint32_t> comp(n, 0);
@@ -1357,8 +1366,11 @@ static int nj_trees_and_print(rtc_ctx* ctx, const DeviceSketches& ds, const vect
     vector<rtc_njoin> joins(n > 0 ? n : 1);
     vector<uint64_t> first((size_t)n + 1, 0);
     uint64_t n_joins = 0;
-    const int st = rtc_nj_clusters(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, n, comp.data(), kmer_size, joins.data(), joins.size(), &n_joins,
-                                   first.data());
+    vector<uint32_t> support(replicates ? joins.size() : 0);
+    const int st = replicates ? rtc_nj_support(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, n, comp.data(), kmer_size, replicates, seed, joins.data(),
+                                               joins.size(), &n_joins, first.data(), support.data())
+                              : rtc_nj_clusters(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, n, comp.data(), kmer_size, joins.data(), joins.size(),
+                                                &n_joins, first.data());
     if (st == RTC_ERR_NOMEM) { cerr << "ERROR: " << rtc_last_error(ctx) << endl; return 1; }
     CHECK(ctx, st);
     uint64_t cnt[10];
@@ -1367,6 +1379,26 @@ static int nj_trees_and_print(rtc_ctx* ctx, const DeviceSketches& ds, const vect
     const string f = base + (pass == 0 ? ".nj.newick" : ".nj.all.newick");
     print_nj_newick(genomes, pass == 0 ? clusters : whole, joins, first, sketchByFile, f);
     cerr << "-----write the neighbour-joining " << (pass == 0 ? "trees of the clusters" : "tree of all genomes") << " into: " << f << endl;
+    if (replicates) {
+      // the same trees with the support of every inner branch, and the counts as a table
+      uint64_t scnt[10];
+      CHECK(ctx, rtc_nj_support_counters(ctx, scnt));
+      for (int i = 0; i < 10; i++) ssum[i] += scnt[i];
+      const string stem = base + (pass == 0 ? ".nj" : ".nj.all");
+      print_nj_support(genomes, pass == 0 ? clusters : whole, joins, first, support, replicates, sketchByFile, stem + ".support.newick", stem + ".support.tsv");
+      cerr << "-----write the jackknife support of the neighbour-joining " << (pass == 0 ? "trees of the clusters" : "tree of all genomes")
+           << " into: " << stem << ".support.newick and " << stem << ".support.tsv" << endl;
+    }
+  }
+  if (replicates) {
+    const double mean = ssum[8] ? (double)ssum[9] / (double)ssum[8] : 0.0;
+    cerr << "-----jackknife support: " << sum[0] << " trees, " << ssum[8] << " splits, " << replicates << " replicates, mean count " << mean << endl;
+    g_metrics.num("nj_support_count_s", 1e-9 * (double)ssum[2]);
+    g_metrics.num("nj_support_distance_s", 1e-9 * (double)ssum[3]);
+    g_metrics.num("nj_support_join_s", 1e-9 * (double)ssum[4]);
+    g_metrics.num("nj_support_split_s", 1e-9 * (double)ssum[5]);
+    g_metrics.num("nj_support_replicates", (double)replicates);
+    g_metrics.num("nj_support_mean", mean);
   }
   g_metrics.num("nj_fill_s", 1e-9 * (double)sum[6]);
   g_metrics.num("nj_distance_s", 1e-9 * (double)sum[7]);
@@ -3006,6 +3038,10 @@ int main(int argc, char** argv) {
                       : o.autoThreshold ? "--auto-threshold" : o.stability ? "--stability" : nullptr;
     if (bad) { cerr << "ERROR: " << (o.njTree ? "--nj-tree" : "--nj-all") << " does not go with " << bad << endl; return 1; }
   }
+  // ---- --nj-support / --nj-seed: what they need, before any GPU is asked for ----
+  if (o.has_njSupport && !(o.njTree || o.njAll)) { cerr << "ERROR: --nj-support needs --nj-tree or --nj-all" << endl; return 1; }
+  if (o.has_njSupport && (o.njSupport < 1 || o.njSupport > 256)) { cerr << "ERROR: --nj-support must lie in 1 .. 256, not " << o.njSupport << endl; return 1; }
+  if (o.has_njSeed && !o.has_njSupport) { cerr << "ERROR: --nj-seed needs --nj-support" << endl; return 1; }
   // ---- --quality: the same company again ----
   if (o.quality) {
     const char* bad = o.isContainment ? "-c/--containment" : !o.useIndex ? "--inverted-index=false" : o.has_append ? "--append"
@@ -3867,7 +3903,8 @@ int main(int argc, char** argv) {
   }
   if (o.njTree || o.njAll) {
     if (is_containment) { cerr << "ERROR: " << (o.njTree ? "--nj-tree" : "--nj-all") << " does not go with containment sketches" << endl; return 1; }
-    if (nj_trees_and_print(ctx, dss[0], clusters, genomes, sketchByFile, o.outputFile, kmer_size, o.threads, o.njTree, o.njAll) != 0) {
+    if (nj_trees_and_print(ctx, dss[0], clusters, genomes, sketchByFile, o.outputFile, kmer_size, o.threads, o.njTree, o.njAll,
+                           o.has_njSupport ? (uint32_t)o.njSupport : 0, o.njSeed) != 0) {
       join_warmup();
       return 1;
     }

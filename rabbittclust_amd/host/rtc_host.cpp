@@ -1223,8 +1223,12 @@ std::string get_newick_tree(const std::vector<GenomeInfo>& g, const std::vector<
 // text(x) is the subtree currently named x: a leaf at first, after a join {a, b} the node "(text(a):len_a,text(b):len_b)" under
 // the name a; the last record of three or more members has three children and closes the tree.  One member: "label;", two:
 // "(a:x,b:y);".  The nodes live in one flat array and the text is written by an explicit stack, as get_newick_tree's.
-std::string nj_newick_text(const std::function<std::string(uint32_t)>& label, const uint32_t* members, size_t m, const rtc_njoin* joins,
-                           size_t n_joins) {
+//
+// With support (rtc_nj_support's counts, one per record, of `replicates`): in a tree of four or more members every node of a
+// record with c == UINT32_MAX names a split and carries nj_support_percent between its ")" and its ":"; the closing node and
+// smaller trees carry nothing.  Without it the text is the plain one, and the labelled text with the labels taken out is too.
+std::string nj_support_newick_text(const std::function<std::string(uint32_t)>& label, const uint32_t* members, size_t m, const rtc_njoin* joins,
+                                   size_t n_joins, const uint32_t* support, uint32_t replicates) {
   if (m == 0) return ";";
   if (m == 1 || n_joins == 0) return label(members[0]) + ";";
   struct Node { int kid[3]; double len[3]; int nk; };
@@ -1258,6 +1262,7 @@ std::string nj_newick_text(const std::function<std::string(uint32_t)>& label, co
       continue;
     } else {
       text += ")";
+      if (support && m >= 4 && nodes[v.node - leaves].nk == 2) text += std::to_string(nj_support_percent(support[v.node - leaves], replicates));
     }
     path.pop_back();
     if (!path.empty()) {  // the subtree just closed hangs on branch done-1 of the node now on top
@@ -1266,6 +1271,29 @@ std::string nj_newick_text(const std::function<std::string(uint32_t)>& label, co
     }
   }
   return text + ";";
+}
+
+std::string nj_newick_text(const std::function<std::string(uint32_t)>& label, const uint32_t* members, size_t m, const rtc_njoin* joins,
+                           size_t n_joins) {
+  return nj_support_newick_text(label, members, m, joins, n_joins, nullptr, 0);
+}
+
+// The table of one tree's labelled nodes, a line a record that names a split, in record order:
+// cluster \t record \t leaves below the node \t count \t replicates
+std::string nj_support_tsv_lines(size_t cluster, size_t m, const rtc_njoin* joins, size_t n_joins, const uint32_t* support, uint32_t replicates) {
+  std::string text;
+  if (m < 4) return text;
+  std::unordered_map<uint32_t, uint64_t> below;  // the leaves under the node a name stands for (a name not seen yet: one leaf)
+  for (size_t e = 0; e < n_joins; e++) {
+    const rtc_njoin& r = joins[e];
+    if (r.c != 0xFFFFFFFFu) continue;
+    auto leaves = [&](uint32_t x) { auto it = below.find(x); return it == below.end() ? (uint64_t)1 : it->second; };
+    const uint64_t s = leaves(r.a) + leaves(r.b);
+    below[r.a] = s;
+    text += std::to_string(cluster) + "\t" + std::to_string(e) + "\t" + std::to_string(s) + "\t" + std::to_string(support[e]) + "\t" +
+            std::to_string(replicates) + "\n";
+  }
+  return text;
 }
 
 std::string get_nj_newick(const std::vector<GenomeInfo>& g, const std::vector<int>& members, const rtc_njoin* joins, size_t n_joins,
@@ -1302,6 +1330,32 @@ void print_nj_newick(const std::vector<GenomeInfo>& g, const std::vector<std::ve
     fprintf(fp, "%s\n", get_nj_newick(g, clusters[c], joins.data() + first[q], (size_t)(first[q + 1] - first[q]), sketchByFile).c_str());
   }
   fclose(fp);
+}
+
+// print_nj_newick's trees with their support (newick), and the counts (tsv): a header, then the lines of nj_support_tsv_lines tree
+// after tree in the order of `clusters`, the cluster numbered as `clusters` lists it.
+void print_nj_support(const std::vector<GenomeInfo>& g, const std::vector<std::vector<int>>& clusters, const std::vector<rtc_njoin>& joins,
+                      const std::vector<uint64_t>& first, const std::vector<uint32_t>& support, uint32_t replicates, bool sketchByFile,
+                      const std::string& newick, const std::string& tsv) {
+  std::vector<size_t> order(clusters.size()), rank(clusters.size());
+  std::vector<int> smallest(clusters.size());
+  for (size_t c = 0; c < clusters.size(); c++) { order[c] = c; smallest[c] = *std::min_element(clusters[c].begin(), clusters[c].end()); }
+  std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return smallest[x] < smallest[y]; });
+  for (size_t q = 0; q < order.size(); q++) rank[order[q]] = q;
+  FILE* fn = open_out(newick, "print_nj_support");
+  FILE* ft = open_out(tsv, "print_nj_support");
+  fprintf(ft, "cluster\trecord\tleaves\tcount\treplicates\n");
+  for (size_t c = 0; c < clusters.size(); c++) {
+    const size_t q = rank[c];
+    const size_t nr = (size_t)(first[q + 1] - first[q]);
+    std::vector<uint32_t> mem(clusters[c].begin(), clusters[c].end());
+    std::sort(mem.begin(), mem.end());
+    fprintf(fn, "%s\n", nj_support_newick_text([&](uint32_t v) { return sketchByFile ? g[v].fileName : g[v].seq0.name; }, mem.data(), mem.size(),
+                                               joins.data() + first[q], nr, support.data() + first[q], replicates).c_str());
+    fputs(nj_support_tsv_lines(c, mem.size(), joins.data() + first[q], nr, support.data() + first[q], replicates).c_str(), ft);
+  }
+  fclose(fn);
+  fclose(ft);
 }
 
 bool upgma_keep(uint64_t sum, uint32_t size_a, uint32_t size_b, double threshold) {

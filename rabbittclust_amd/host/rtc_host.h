@@ -179,6 +179,17 @@ std::string get_nj_newick(const std::vector<GenomeInfo>& g, const std::vector<in
 void print_nj_newick(const std::vector<GenomeInfo>& g, const std::vector<std::vector<int>>& clusters, const std::vector<rtc_njoin>& joins,
                      const std::vector<uint64_t>& first, bool sketchByFile, const std::string& output);
 
+// ---- clust-mst --nj-support: the same trees with rtc_nj_support's counts.  A node that names a split (a record with
+// c == UINT32_MAX in a tree of four or more) carries nj_support_percent between ")" and ":"; the tsv has a header and a line a
+// labelled node: cluster as `clusters` lists it, record index in its tree, leaves below the node, count, replicates. ----
+inline uint32_t nj_support_percent(uint32_t count, uint32_t replicates) { return (200u * count + replicates) / (2u * replicates); }  // percent, half up
+std::string nj_support_newick_text(const std::function<std::string(uint32_t)>& label, const uint32_t* members, size_t m, const rtc_njoin* joins,
+                                   size_t n_joins, const uint32_t* support, uint32_t replicates);
+std::string nj_support_tsv_lines(size_t cluster, size_t m, const rtc_njoin* joins, size_t n_joins, const uint32_t* support, uint32_t replicates);
+void print_nj_support(const std::vector<GenomeInfo>& g, const std::vector<std::vector<int>>& clusters, const std::vector<rtc_njoin>& joins,
+                      const std::vector<uint64_t>& first, const std::vector<uint32_t>& support, uint32_t replicates, bool sketchByFile,
+                      const std::string& newick, const std::string& tsv);
+
 // ---- clust-mst --upgma: the cut and the three writers over rtc_upgma_clusters' records (include/rtclust.h has the definition).
 // upgma_height is rtc_upgma_distance (the host library does not link the device library): one double operation a step.
 // upgma_keep: the integer cut rule, sum <= llround(threshold 2^20) size_a size_b in 128 bits.

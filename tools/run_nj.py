@@ -9,7 +9,12 @@ phase times (fill, host distances, joining).
 with integer branch lengths, so every value is exact -- through the workgroup path and through the grid path at every m of
 --sizes; one JSON line per m with both joining times (the best of --repeat calls, upload excluded) and whether the records agree.
 
-    python tools/run_nj.py [--sizes 10,30,64,65,100,300,1000,3000] [--copies 1] [--sketch-size 1000] [--repeat 3] [--threads 16]
+--support B: clust-mst --nj-support on the same set: Context.nj_support with B replicates, the best
+whole-call time of --repeat warm calls with its four phase times (counting, host distances, joining, splits), and beside it B
+times Context.nj_clusters' best whole-call time on the same set in the same session -- what B separate runs over filtered sets
+could not beat.
+
+    python tools/run_nj.py [--sizes 10,30,64,65,100,300,1000,3000] [--copies 1] [--sketch-size 1000] [--repeat 3] [--threads 16] [--support B [--seed S]]
     python tools/run_nj.py --crossover [--sizes 256,512,1024,2048,4096,8192] [--repeat 2] [--wg-max 8192]"""
 import argparse
 import json
@@ -83,6 +88,8 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--threads", type=int, default=16, help="host threads of the distances")
     ap.add_argument("--crossover", action="store_true")
+    ap.add_argument("--support", type=int, default=0, help="jackknife replicates (1 .. 256): time Context.nj_support as well")
+    ap.add_argument("--seed", type=int, default=0, help="--support: the mask seed")
     ap.add_argument("--wg-max", type=int, default=8192, help="--crossover: the largest m the workgroup path is timed at")
     a = ap.parse_args()
     if a.crossover:
@@ -102,7 +109,19 @@ def main():
             best = c
     print(json.dumps({"sketches": sk.n, "sketch_size": a.sketch_size, "families": sorted(sizes), "records": len(joins), "counters": best,
                       "fill_s": best["fill_ns"] * 1e-9, "distance_s": best["distance_ns"] * 1e-9, "join_s": best["join_ns"] * 1e-9,
-                      "total_s": best["total_ns"] * 1e-9}))
+                      "total_s": best["total_ns"] * 1e-9}), flush=True)
+    if a.support:
+        sbest, main = None, None
+        for r in range(a.repeat + 1):
+            sjoins, _, support = ctx.nj_support(sk, comp, 21, a.support, seed=a.seed)
+            c = ctx.nj_support_counters()
+            if r and (sbest is None or c["total_ns"] < sbest["total_ns"]):
+                sbest, main = c, ctx.nj_counters()
+        assert sjoins.tobytes() == joins.tobytes()
+        print(json.dumps({"replicates": a.support, "seed": a.seed, "counters": sbest, "main_counters": main,
+                          "mean_count": sbest["count_sum"] / max(sbest["splits"], 1), "count_s": sbest["count_ns"] * 1e-9,
+                          "distance_s": sbest["distance_ns"] * 1e-9, "join_s": sbest["join_ns"] * 1e-9, "split_s": sbest["split_ns"] * 1e-9,
+                          "total_s": sbest["total_ns"] * 1e-9, "replicates_times_nj_clusters_s": a.support * best["total_ns"] * 1e-9}), flush=True)
 
 
 if __name__ == "__main__":
