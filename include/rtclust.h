@@ -1138,6 +1138,67 @@ uint64_t rtc_jackknife_word(uint64_t hash, uint64_t seed, uint32_t word);
 int rtc_jackknife_pairs_dev(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
                             const rtc_cedge* d_edges, uint64_t m, uint64_t seed, uint32_t word, uint32_t* d_common, uint32_t* d_size);
 
+/* ---- clust-mst --cluster-support: jackknife support of the clusters themselves ---------------------------------------- */
+/* Which clusters of a partition survive resampling of the sketches' hashes: for every cluster, in how many of B delete-half
+ * jackknife replicates it comes back whole and alone.  This is the definition (tests/refsupport.py restates it); everything is
+ * integer, and the one double function is evaluated on the host, when the keep table is built.
+ *   Input.  Sketches as everywhere (width 4 or 8, ascending, distinct), n, a labelling h_comp[n] (any labelling), kmer_size,
+ *     threshold, replicates B in 1 .. 256 and seed.  Clusters are numbered by their smallest member, a cluster's members are taken
+ *     ascending; f_c is cluster c's smallest member and m_c its size.
+ *   Mask, size_r, common_r, denom_r.  rtc_nj_support's, through rtc_jackknife_word.
+ *   Candidates.  The pairs rtc_pair_edges_dev lists for radio = floor(2 e^(threshold (kmer_size - 1)) - 1), saturated at INT32_MAX:
+ *     they share a hash and pass the size-ratio rule on the full sketches -- the MST's own candidates.  Replicates do not re-apply
+ *     the size rule.
+ *   Replicate graph G_r.  Candidate (i, j) is an edge of G_r iff common_r > 0 and
+ *     rtc_linkage_distance(common_r, denom_r, kmer_size) <= threshold: the function that weighs the MST's edges, cut as the forest
+ *     is cut.
+ *   Keep table.  need[d], d in 0 .. D, is the least c in 1 .. d with rtc_linkage_distance(c, d, kmer_size) <= threshold, or d + 1
+ *     if there is none; the device keeps an edge iff common_r >= need[denom_r].  D is the largest |a| + |b| over the sketches; a
+ *     table of more than 2^25 entries is RTC_ERR_UNSUPPORTED (a cap, not a measurement).  The rule is monotone in c: checked on
+ *     the host for (k, d) = (21, 0.05), (21, 0.001), (16, 0.2), (31, 0.9), (21, 0) and every denom up to 3 000
+ *     (tests/test_cpu_support.py).
+ *   Inner and crossing edges.  An edge of G_r is inner if both ends carry the same label and crossing otherwise.  P_r(g) is the
+ *     smallest member of g's component in the graph of the inner edges of G_r; it always lies in g's cluster.  piece_r(g) is the
+ *     number of genomes x with P_r(x) = P_r(g).
+ *   Per cluster and replicate.  whole iff P_r(g) = f_c for every member; pure iff no crossing edge of G_r has an end in c (that is:
+ *     every component of G_r that meets c lies inside c); pieces_r(c) = |{g in c : P_r(g) = g}|.
+ *   Records.  One rtc_csupport per cluster, in cluster order: size = m_c; recovered = |{r : whole and pure}|, split = pure only,
+ *     merged = whole only, mixed = neither -- the four always sum to B; max_pieces = max_r pieces_r(c).
+ *     h_together[g] = sum_r (piece_r(g) - 1).
+ *   Consequences.  A singleton cluster is recovered unless a crossing edge reaches it; an empty sketch has no candidate.
+ * threshold below 0 or NaN, replicates outside 1 .. 256, width not 4 or 8, NULLs, kmer_size < 1, n >= 2^31 - 1: RTC_ERR_ARG.
+ * threshold >= 1: RTC_ERR_UNSUPPORTED (pairs without a common hash are at distance 1 and no list holds them); a sketch of 2^31
+ * hashes or more likewise.  Memory that does not fit: RTC_ERR_NOMEM with the bytes in the message, no fallback.
+ *
+ * The call: the pair phase in row chunks under RTC_EDGE_BUDGET as in rtc_cluster_quality; a chunk's candidates are taken in
+ * pieces of 2^20 and, per piece and word of 64 replicates, rtc_jackknife_pairs_dev counts common_r, a mask kernel (one wave a
+ * candidate, a replicate a lane) forms the 64-bit keep mask of every candidate -- inner edges with a non-zero mask go to a
+ * compacted list, a crossing edge ORs its mask into a word per cluster end -- and rtc_components64_dev hooks the list into the
+ * word's labels; at the end one wave per cluster tallies the word.  A word's state is 512 bytes a sketch; as many words as
+ * RTC_SUPPORT_BYTES allows (default: half the free HBM, at least one word) are held at once, and the pair phase runs once per
+ * group of words held.  The records depend on none of: the row chunks, the words held at once, the pair routine's LDS or global
+ * path, RTC_PAIR_FORCE_MERGE.  h_out[number of distinct labels], h_together[n].  Synchronous. */
+typedef struct { uint32_t size, recovered, split, merged, mixed, max_pieces; } rtc_csupport; /* 24 bytes */
+int rtc_cluster_support(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                        const uint32_t* h_comp, int kmer_size, double threshold, uint32_t replicates, uint64_t seed, rtc_csupport* h_out,
+                        uint64_t* h_together);
+/* The last rtc_cluster_support: out[0] row chunks (over every run of the pair phase), out[1] candidates, out[2] inner edges kept
+ * (a candidate counts once per word in which some replicate keeps it), out[3] crossing edges kept (likewise), out[4] hooking
+ * passes, out[5] pair ns, out[6] count ns (the pair routine and the mask kernel), out[7] components ns, out[8] tally ns, out[9]
+ * whole call ns. */
+int rtc_cluster_support_counters(const rtc_ctx* ctx, uint64_t out[10]);
+/* need[0 .. max_denom] above into out.  Host only, no context.  kmer_size < 1, threshold below 0 or NaN, out NULL: RTC_ERR_ARG;
+ * more than 2^25 entries: RTC_ERR_UNSUPPORTED. */
+int rtc_support_keep_table(int kmer_size, double threshold, uint32_t max_denom, uint32_t* out);
+/* The connected components of 64 graphs over the same n vertices at once: graph r has the edges e < m whose d_mask[e] has bit r
+ * set (d_edges[e].i and .j, both below n, in either order; the edge's count is ignored; duplicates and loops are allowed).
+ * d_label[g * 64 + r] is state: on entry the smallest vertex of g's component under the edges given so far -- g itself for a
+ * fresh start -- and on return the smallest vertex of g's component with these edges added, so chunks of edges may arrive one
+ * after another, and a call on converged labels changes nothing.  One wave per edge, lane r graph r: every access to a vertex's
+ * 64 labels is one 256-byte row.  Min-hooking on roots with pointer jumping, repeated until a device flag reports a pass
+ * without change; the flag is read back once per pass.  Context stream, synchronous. */
+int rtc_components64_dev(rtc_ctx* ctx, uint32_t n, const rtc_cedge* d_edges, const uint64_t* d_mask, uint64_t m, uint32_t* d_label);
+
 /* ---- clust-mst --quality: silhouette and cluster separation of a finished partition ---------------------------------- */
 /* The silhouette of every vertex of a labelled, weighted graph, and what a cluster's diameter and separation are read from, in
  * exact integers; this is the definition (tests/refquality.py restates it).  Q1 = 2^20 is distance 1.

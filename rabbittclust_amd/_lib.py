@@ -183,6 +183,10 @@ SIGNATURES = {
     "rtc_nj_support_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_jackknife_word": (_u64, [_u64, _u64, _u32]),
     "rtc_jackknife_pairs_dev": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _u64, _u64, _u32, _vp, _vp]),
+    "rtc_cluster_support": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _i, C.c_double, _u32, _u64, _vp, _vp]),
+    "rtc_cluster_support_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_support_keep_table": (_i, [_i, C.c_double, _u32, _vp]),
+    "rtc_components64_dev": (_i, [_vp, _u32, _vp, _vp, _u64, _vp]),
     "rtc_silhouette": (_i, [_vp, _u32, _vp, _u64, _vp, _vp]),
     "rtc_silhouette_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_silhouette_last_path": (_i, [_vp]),

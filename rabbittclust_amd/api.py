@@ -41,6 +41,9 @@ NJ_PATH_WAVE, NJ_PATH_WORKGROUP, NJ_PATH_GRID = 1, 2, 4  # rtc_nj_last_path
 NJ_GRID_MIN = 256  # the library's default RTC_NJ_GRID_MIN (rtc_nj.hip: NJ_GRID_MIN)
 NJ_SUPPORT_MAX = 256  # rtc_nj_support's most replicates
 JK_LDS_ELEMS = 1024  # the jackknife counting kernel stages a list of up to this many hashes in LDS (csrc/rtc_jackknife.h); a longer one is searched in global memory
+CSUPPORT_DT = np.dtype([("size", "<u4"), ("recovered", "<u4"), ("split", "<u4"), ("merged", "<u4"), ("mixed", "<u4"), ("max_pieces", "<u4")])  # rtc_csupport
+CSUPPORT_MAX = 256  # rtc_cluster_support's most replicates (csrc/rtc_support.h: CSUP_MAX_REPLICATES)
+CSUPPORT_TABLE_MAX = 1 << 25  # the keep table's most entries (csrc/rtc_support.h: CSUP_TABLE_MAX)
 UMERGE_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("size_a", "<u4"), ("size_b", "<u4"), ("sum", "<u8")])  # rtc_umerge
 UPGMA_PATH_WAVE, UPGMA_PATH_WORKGROUP, UPGMA_PATH_GRID = 1, 2, 4  # rtc_upgma_last_path
 UPGMA_GRID_MIN = 128  # the library's default RTC_UPGMA_GRID_MIN (rtc_upgma.h: UPGMA_GRID_MIN)
@@ -1209,6 +1212,58 @@ class Context:
         self.sync()
         return common[:m].cpu().numpy().view(np.uint32), (size[:sk.n].cpu().numpy().view(np.uint32) if sizes else None)
 
+    def cluster_support(self, sk, comp, kmer_size, threshold, replicates, seed=0):
+        """rtc_cluster_support: (records, together).  records: one CSUPPORT_DT per cluster of the labelling `comp` (any labelling),
+        the clusters in order of their smallest member -- in how many of the `replicates` (1 .. CSUPPORT_MAX) delete-half jackknife
+        replicates over the sketch hashes the cluster comes back whole and alone (recovered), in pieces (split), whole but joined
+        to others (merged) or neither (mixed), and its most pieces.  together: one uint64 per sketch, the sum over the replicates
+        of the genomes that stay with it, itself not counted."""
+        n = sk.n
+        lab = np.ascontiguousarray(np.asarray(comp).astype(np.int64).astype(np.uint32))
+        if lab.shape != (n,):
+            raise ValueError("comp must hold one label per sketch")
+        n_cl = len(np.unique(lab))
+        out = np.zeros(max(n_cl, 1), dtype=CSUPPORT_DT)
+        together = np.zeros(max(n, 1), dtype=np.uint64)
+        self.check(self.lib.rtc_cluster_support(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n, _np_ptr(lab), int(kmer_size),
+                                                float(threshold), int(replicates), int(seed) & 0xFFFFFFFFFFFFFFFF, _np_ptr(out), _np_ptr(together)))
+        return out[:n_cl].copy(), together[:n].copy()
+
+    def cluster_support_counters(self):
+        """rtc_cluster_support_counters as a dict (the last cluster_support call)."""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_cluster_support_counters(self.h, a))
+        names = ("chunks", "candidates", "inner_kept", "crossing_kept", "hook_passes", "pair_ns", "count_ns", "components_ns", "tally_ns", "total_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
+    def components64(self, n, edges, masks, labels=None):
+        """rtc_components64_dev: the connected components of 64 graphs over n vertices at once.  edges: an (m, 2) array of vertices
+        below n, masks: m uint64 -- edge e belongs to graph r iff bit r of masks[e] is set.  labels: None for a fresh start, or
+        the [n, 64] array an earlier call returned, to add these edges to those.  Returns labels[g, r], the smallest vertex of g's
+        component in graph r, as uint32."""
+        n = int(n)
+        edges = np.ascontiguousarray(np.asarray(edges, dtype=np.int64).reshape(-1, 2))
+        mk = np.ascontiguousarray(np.asarray(masks, dtype=np.uint64).reshape(-1))
+        m = len(edges)
+        if len(mk) != m:
+            raise ValueError("components64: one mask per edge")
+        if m and (edges.min() < 0 or edges.max() >= n):
+            raise ValueError("components64: a vertex outside [0, n)")
+        if labels is None:
+            lab = np.repeat(np.arange(n, dtype=np.uint32), 64).reshape(n, 64)
+        else:
+            lab = np.ascontiguousarray(np.asarray(labels, dtype=np.uint32))
+            if lab.shape != (n, 64) or (n and (lab > np.arange(n, dtype=np.uint32)[:, None]).any()):
+                raise ValueError("components64: labels must be [n, 64] and no label above its vertex")
+        rec = np.zeros(max(m, 1), dtype=CEDGE_DT)
+        rec["i"][:m], rec["j"][:m] = edges[:, 0], edges[:, 1]
+        d_edges = torch.from_numpy(rec.view(np.uint32).reshape(-1, 3).view(np.int32)).to(self.device)
+        d_mask = torch.from_numpy(np.concatenate([mk, np.zeros(1, dtype=np.uint64)]).view(np.int64)).to(self.device)
+        d_lab = torch.from_numpy(np.concatenate([lab.reshape(-1), np.zeros(64, dtype=np.uint32)]).view(np.int32)).to(self.device)
+        self.check(self.lib.rtc_components64_dev(self.h, n, _t_ptr(d_edges), _t_ptr(d_mask), m, _t_ptr(d_lab)))
+        self.sync()
+        return d_lab[:n * 64].cpu().numpy().view(np.uint32).reshape(n, 64)
+
     def upgma(self, sums, sizes=None, ld=None):
         """rtc_upgma_dev: the average-linkage agglomeration include/rtclust.h defines over one symmetric m x m matrix of uint64
         sums, uploaded for the call.  sizes: w[i] >= 1 per index (None: all 1).  ld: None takes the array as [m, ld]; a number
@@ -1418,6 +1473,16 @@ def linkage_distance(common, denom, kmer_size):
 def jackknife_word(hash, seed, word):
     """rtc_jackknife_word: the 64 keep bits of a hash for the replicates 64 * word .. 64 * word + 63 (no GPU needed)"""
     return int(_lib.load().rtc_jackknife_word(int(hash) & 0xFFFFFFFFFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF, int(word)))
+
+
+def support_keep_table(kmer_size, threshold, max_denom):
+    """rtc_support_keep_table: need[0 .. max_denom] as uint32 -- need[d] the least common count in 1 .. d whose distance at
+    denominator d is at most the threshold, d + 1 where there is none (no GPU needed)"""
+    out = np.zeros(int(max_denom) + 1, dtype=np.uint32)
+    st = _lib.load().rtc_support_keep_table(int(kmer_size), float(threshold), int(max_denom), _np_ptr(out))
+    if st != 0:
+        raise _lib.RtcError(st, "rtc_support_keep_table(%r, %r, %r)" % (kmer_size, threshold, max_denom))
+    return out
 
 
 def upgma_distance(sum, size_a, size_b):

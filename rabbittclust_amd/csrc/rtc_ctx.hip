@@ -109,6 +109,7 @@ void rtc_options_from_env(rtc_options* o) {
   o->mcl_global = flag("RTC_MCL_GLOBAL");
   o->snn_global = flag("RTC_SNN_GLOBAL");
   o->sil_global = flag("RTC_SIL_GLOBAL");
+  if (const char* e = getenv("RTC_SUPPORT_BYTES")) o->support_bytes = std::max<uint64_t>(strtoull(e, nullptr, 10), 1);
 }
 
 extern "C" {

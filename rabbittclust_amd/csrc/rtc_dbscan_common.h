@@ -274,11 +274,12 @@ struct PlanHold {
 // The pair phase of a DBSCAN call: every pair sharing a hash (rtc_pair_edges_dev, radio < 0) over row chunks, the overflow
 // protocol of rtc_candidate_edges_device.  on_chunk(d_cand, count) sees every chunk once, before the next one is produced;
 // the candidate list is released on the way out.  budget: the candidate edges of one chunk.  first_row: the rows below it are
-// columns only (1: every pair of the set; rtc_dbscan_update joins its row ranges alone).
+// columns only (1: every pair of the set; rtc_dbscan_update joins its row ranges alone).  radio: rtc_pair_edges_dev's size-ratio
+// bound, below 0 for none (rtc_cluster_support passes the MST's).
 struct PairPhase { uint64_t chunks = 0, cand_total = 0, pair_ns = 0; };
 template <class F>
 int dbscan_pair_chunks(rtc_ctx* ctx, DevBuf& db, const void* ph, int width, const uint64_t* pstart, const uint32_t* plen, uint32_t n,
-                       uint32_t first_row, unsigned long long* d_cnt, PairPhase* pp, F&& on_chunk) {
+                       uint32_t first_row, unsigned long long* d_cnt, PairPhase* pp, F&& on_chunk, int radio = -1) {
   hipStream_t s = ctx->stream;
   uint64_t budget = (uint64_t)256 << 20;  // candidate edges of one chunk (3 GiB)
   if (ctx->opt.edge_budget) budget = ctx->opt.edge_budget;
@@ -295,7 +296,7 @@ int dbscan_pair_chunks(rtc_ctx* ctx, DevBuf& db, const void* ph, int width, cons
     const uint64_t tp = now_ns();
     unsigned long long cnt = 0;
     RTC_HIP(ctx, hipMemsetAsync(d_cnt, 0, 8, s));
-    const int st = rtc_pair_edges_dev(ctx, ph, width, pstart, plen, n, r0, r1, 0, r1 - 1, -1, d_cand, cand_cap, (uint64_t*)d_cnt);
+    const int st = rtc_pair_edges_dev(ctx, ph, width, pstart, plen, n, r0, r1, 0, r1 - 1, radio, d_cand, cand_cap, (uint64_t*)d_cnt);
     if (st != RTC_OK) { (void)hipStreamSynchronize(s); return st; }
     RTC_HIP(ctx, hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, s));
     RTC_HIP(ctx, hipStreamSynchronize(s));

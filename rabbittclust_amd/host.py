@@ -253,3 +253,33 @@ def upgma_report(cluster_of, merges, first, threshold):
     for g in range(n):
         out[int(refined[g])].append(g)
     return buf.raw[:need].decode(), out, int(kept.value)
+
+
+def support_report(names, cluster_of, records, together, replicates):
+    """support_report_text (rtc_host.cpp): the two reports of clust-mst --cluster-support as (support_tsv, genomes_tsv).  names[g]
+    and cluster_of[g] (the cluster number <output> gives genome g) for every genome; records: api.CSUPPORT_DT, one per cluster in
+    the library's order (that of the clusters' smallest members); together: Context.cluster_support's, one per genome."""
+    n = len(names)
+    lab = np.ascontiguousarray(cluster_of, dtype=np.int32)
+    rec = np.ascontiguousarray(records)
+    tog = np.ascontiguousarray(together, dtype=np.uint64)
+    if n and int(lab.min()) < 0:
+        raise ValueError("cluster_of must name a cluster for every genome")
+    ncl = int(lab.max()) + 1 if n else 0
+    assert rec.dtype.itemsize == 24 and len(lab) == len(tog) == n and len(rec) == ncl
+    if int(replicates) < 1:
+        raise ValueError("replicates must be at least 1")
+    arr = (C.c_char_p * max(n, 1))(*[s.encode() for s in names])
+    fn = load().rtch_support_report
+    fn.restype = C.c_long
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_long]
+    out = []
+    for which in (0, 1):
+        args = (arr, lab.ctypes.data_as(C.c_void_p), ncl, rec.ctypes.data_as(C.c_void_p), tog.ctypes.data_as(C.c_void_p), n, int(replicates), which)
+        need = fn(*args, None, 0)
+        if need < 0:
+            raise ValueError("cluster_of outside the clusters, or a cluster without a member")
+        buf = C.create_string_buffer(max(int(need), 1))
+        fn(*args, buf, need)
+        out.append(buf.raw[:need].decode())
+    return tuple(out)

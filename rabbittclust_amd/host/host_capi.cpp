@@ -356,4 +356,23 @@ long rtch_quality_report(const char* const* names, const int32_t* cluster_of, ui
   return (long)text.size();
 }
 
+// support_report_text over plain arrays: names[g], cluster_of[g] in [0, n_clusters) for every genome, rec[n_clusters] (rtc_csupport, in
+// the order of the clusters' smallest members) and together[g].  which 0: the cluster report, 1: the genome report.  Returns -1
+// for a cluster_of outside that range, a cluster without members or replicates == 0, else the text's length; the text itself when it fits cap.
+long rtch_support_report(const char* const* names, const int32_t* cluster_of, uint32_t n_clusters, const rtc_csupport* rec, const uint64_t* together,
+                         uint32_t n, uint32_t replicates, int which, char* out, long cap) {
+  if (replicates == 0) return -1;
+  std::vector<std::vector<int>> clusters(n_clusters);
+  for (uint32_t g = 0; g < n; g++) {
+    if (cluster_of[g] < 0 || (uint32_t)cluster_of[g] >= n_clusters) return -1;
+    clusters[cluster_of[g]].push_back((int)g);
+  }
+  for (const std::vector<int>& c : clusters) if (c.empty()) return -1;
+  std::string a, b;
+  support_report_text([&](uint32_t g) { return std::string(names[g]); }, clusters, rec, together, n, replicates, &a, &b);
+  const std::string& text = which ? b : a;
+  if (out && (long)text.size() <= cap) memcpy(out, text.data(), text.size());
+  return (long)text.size();
+}
+
 }

@@ -903,6 +903,9 @@ struct Options {
   bool has_njSupport = false, has_njSeed = false;  // clust-mst --nj-support B [--nj-seed S]: jackknife support values for those trees (rtc_nj_support)
   long long njSupport = 0;
   uint64_t njSeed = 0;
+  bool has_clusterSupport = false, has_supportSeed = false;  // clust-mst --cluster-support B [--support-seed S]: jackknife support of the clusters themselves (rtc_cluster_support)
+  long long clusterSupport = 0;
+  uint64_t supportSeed = 0;
 };
 
 #ifdef LEIDEN_CLUST
@@ -1065,6 +1068,8 @@ static Options parse(int argc, char** argv) {
     else if (a == "--nj-support") { o.njSupport = atoll(need(i)); o.has_njSupport = true; }
     else if (a == "--nj-seed") { o.njSeed = strtoull(need(i), nullptr, 10); o.has_njSeed = true; }
     else if (a == "--quality") o.quality = true;
+    else if (a == "--cluster-support") { o.clusterSupport = atoll(need(i)); o.has_clusterSupport = true; }
+    else if (a == "--support-seed") { o.supportSeed = strtoull(need(i), nullptr, 10); o.has_supportSeed = true; }
     else if (a == "--upgma") o.upgma = true;
 #endif
     else if (a == "-h" || a == "--help") {
@@ -1168,6 +1173,10 @@ static Options parse(int argc, char** argv) {
            "  --quality (how good the partition is, over the exact set-Jaccard distances, scored on the GPU: <output>.quality.tsv, a\n"
            "             line a cluster with its mean and least silhouette, mean intra-cluster distance, diameter, separation and\n"
            "             nearest cluster, and <output>.silhouette.tsv, a line a genome; with --fast or MinHash on the index path)\n"
+           "  --cluster-support B [--support-seed S] (which clusters survive resampling: B = 1 .. 256 delete-half jackknife replicates\n"
+           "             over the sketch hashes, each with its own single-linkage components at -d, formed on the GPU;\n"
+           "             <output>.support.tsv, a line a cluster with the replicates that recover, split, merge and mix it, and\n"
+           "             <output>.support.genomes.tsv, a line a genome; S: the mask seed, default 0)\n"
            "  --upgma (average linkage, UPGMA, inside every cluster of the run, in exact integers on the GPU: <output>.upgma, the\n"
            "             clusters cut at -d by mean distance; <output>.upgma.linkage.txt, every merge; <output>.upgma.newick, one\n"
            "             ultrametric tree a line in the order of <output>; with --fast or MinHash on the index path)\n"
@@ -1487,6 +1496,47 @@ static int quality_and_print(rtc_ctx* ctx, const DeviceSketches& ds, const vecto
   g_metrics.num("quality_score_s", 1e-9 * (double)cnt[7]);
   g_metrics.num("quality_candidates", (double)cnt[1]);
   g_metrics.num("quality_silhouette_mean", all_mean);
+  return 0;
+}
+// --cluster-support B: which of the run's clusters survive a delete-half jackknife over the sketch hashes (include/rtclust.h has
+// the definition): B replicates, each with its own single-linkage components over the MST's candidates at the run's threshold,
+// tallied against the run's clusters.  <base>.support.tsv: a line a cluster in the order and with the numbers <base> prints;
+// <base>.support.genomes.tsv: a line a genome in input order (support_report_text, rtc_host.h).  State that does not fit the
+// device (RTC_ERR_NOMEM, no fallback) is reported: returns 1.
+static int cluster_support_and_print(rtc_ctx* ctx, const DeviceSketches& ds, const vector<vector<int>>& clusters, const vector<GenomeInfo>& genomes,
+                                     bool sketchByFile, const string& base, double threshold, int kmer_size, uint32_t replicates, uint64_t seed) {
+  const uint32_t n = (uint32_t)genomes.size();
+  vector<uint32_t> comp(n, 0);
+  for (size_t c = 0; c < clusters.size(); c++) for (int g : clusters[c]) comp[g] = (uint32_t)c;
+  vector<rtc_csupport> rec(clusters.size() > 0 ? clusters.size() : 1);
+  vector<uint64_t> together(n > 0 ? n : 1, 0);
+  const int st = rtc_cluster_support(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, n, comp.data(), kmer_size, threshold, replicates, seed, rec.data(),
+                                     together.data());
+  if (st == RTC_ERR_NOMEM || st == RTC_ERR_UNSUPPORTED) { cerr << "ERROR: " << rtc_last_error(ctx) << endl; return 1; }
+  CHECK(ctx, st);
+  uint64_t cnt[10];
+  CHECK(ctx, rtc_cluster_support_counters(ctx, cnt));
+  string c_text, g_text;
+  const double mean = support_report_text([&](uint32_t g) { return sketchByFile ? genomes[g].fileName : genomes[g].seq0.name; }, clusters, rec.data(),
+                                          together.data(), n, replicates, &c_text, &g_text);
+  const string f_c = base + ".support.tsv", f_g = base + ".support.genomes.tsv";
+  for (int which = 0; which < 2; which++) {
+    const string& f = which ? f_g : f_c;
+    const string& text = which ? g_text : c_text;
+    FILE* fp = fopen(f.c_str(), "w");
+    if (!fp) { cerr << "ERROR: cannot open file: " << f << endl; join_warmup(); exit(1); }
+    fwrite(text.data(), 1, text.size(), fp);
+    fclose(fp);
+  }
+  cerr << "-----write the jackknife support of the clusters into: " << f_c << " and " << f_g << endl;
+  cerr << "-----cluster support: " << clusters.size() << " clusters, " << replicates << " replicates, " << cnt[1] << " candidates, " << cnt[4]
+       << " hooking passes, mean recovered " << mean << endl;
+  g_metrics.num("support_pair_s", 1e-9 * (double)cnt[5]);
+  g_metrics.num("support_count_s", 1e-9 * (double)cnt[6]);
+  g_metrics.num("support_components_s", 1e-9 * (double)cnt[7]);
+  g_metrics.num("support_tally_s", 1e-9 * (double)cnt[8]);
+  g_metrics.num("support_replicates", (double)replicates);
+  g_metrics.num("support_recovered_mean", mean);
   return 0;
 }
 #endif
@@ -3049,6 +3099,15 @@ int main(int argc, char** argv) {
                       : o.autoThreshold ? "--auto-threshold" : o.stability ? "--stability" : nullptr;
     if (bad) { cerr << "ERROR: --quality does not go with " << bad << endl; return 1; }
   }
+  // ---- --cluster-support / --support-seed: the same company, and what they need ----
+  if (o.has_clusterSupport) {
+    const char* bad = o.isContainment ? "-c/--containment" : !o.useIndex ? "--inverted-index=false" : o.has_append ? "--append"
+                      : o.has_premsted ? "--premsted" : !o.repdb_path.empty() ? "--db" : o.dense ? "--dense"
+                      : o.autoThreshold ? "--auto-threshold" : o.stability ? "--stability" : nullptr;
+    if (bad) { cerr << "ERROR: --cluster-support does not go with " << bad << endl; return 1; }
+    if (o.clusterSupport < 1 || o.clusterSupport > 256) { cerr << "ERROR: --cluster-support must lie in 1 .. 256, not " << o.clusterSupport << endl; return 1; }
+  }
+  if (o.has_supportSeed && !o.has_clusterSupport) { cerr << "ERROR: --support-seed needs --cluster-support" << endl; return 1; }
   // ---- --upgma: and again ----
   if (o.upgma) {
     const char* bad = o.isContainment ? "-c/--containment" : !o.useIndex ? "--inverted-index=false" : o.has_append ? "--append"
@@ -3912,6 +3971,14 @@ int main(int argc, char** argv) {
   if (o.quality) {
     if (is_containment) { cerr << "ERROR: --quality does not go with containment sketches" << endl; return 1; }
     if (quality_and_print(ctx, dss[0], clusters, genomes, sketchByFile, o.outputFile, kmer_size, o.threads) != 0) {
+      join_warmup();
+      return 1;
+    }
+  }
+  if (o.has_clusterSupport) {
+    if (is_containment) { cerr << "ERROR: --cluster-support does not go with containment sketches" << endl; return 1; }
+    if (cluster_support_and_print(ctx, dss[0], clusters, genomes, sketchByFile, o.outputFile, o.threshold, kmer_size, (uint32_t)o.clusterSupport,
+                                  o.supportSeed) != 0) {
       join_warmup();
       return 1;
     }

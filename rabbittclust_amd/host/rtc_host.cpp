@@ -1488,6 +1488,46 @@ double quality_report_text(const std::function<std::string(uint32_t)>& name, con
   return all_mean;
 }
 
+double support_report_text(const std::function<std::string(uint32_t)>& name, const std::vector<std::vector<int>>& clusters, const rtc_csupport* rec,
+                           const uint64_t* together, uint32_t n, uint32_t replicates, std::string* support_tsv, std::string* genomes_tsv) {
+  char buf[512];
+  const size_t nc = clusters.size();
+  // the library numbers the clusters by their smallest member
+  std::vector<size_t> order(nc), rank(nc);
+  std::vector<int> smallest(nc, 0);
+  for (size_t c = 0; c < nc; c++) { order[c] = c; if (!clusters[c].empty()) smallest[c] = *std::min_element(clusters[c].begin(), clusters[c].end()); }
+  std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return smallest[x] < smallest[y]; });
+  for (size_t q = 0; q < nc; q++) rank[order[q]] = q;
+  std::vector<int32_t> label(n, -1);
+  std::string& S = *support_tsv;
+  S = "cluster\tsize\treplicates\trecovered\tsplit\tmerged\tmixed\tmax_pieces\tsupport\n";
+  uint64_t recovered = 0;
+  for (size_t c = 0; c < nc; c++) {
+    const rtc_csupport& r = rec[rank[c]];
+    for (int g : clusters[c]) label[g] = (int32_t)c;
+    recovered += r.recovered;
+    snprintf(buf, sizeof buf, "%zu\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", c, r.size, replicates, r.recovered, r.split, r.merged, r.mixed, r.max_pieces,
+             nj_support_percent(r.recovered, replicates));
+    S += buf;
+  }
+  std::string& G = *genomes_tsv;
+  G = "name\tcluster\ttogether\tfraction\n";
+  for (uint32_t g = 0; g < n; g++) {
+    const size_t size = label[g] >= 0 ? clusters[label[g]].size() : 0;
+    snprintf(buf, sizeof buf, "\t%d\t%llu\t", label[g], (unsigned long long)together[g]);
+    G += name(g);
+    G += buf;
+    if (size > 1) {
+      snprintf(buf, sizeof buf, "%.6f", (double)together[g] / ((double)replicates * (double)(size - 1)));
+      G += buf;
+    } else {
+      G += "-";
+    }
+    G += "\n";
+  }
+  return nc ? (double)recovered / (double)nc : 0.0;
+}
+
 void print_phylip_tree(const std::vector<GenomeInfo>& g, const std::vector<rtc_edge>& mst, bool sketchByFile, const std::string& output) {
   FILE* fp = open_out(output, "print_phylip_tree");
   fprintf(fp, "1\n%s\n", get_newick_tree(g, mst, sketchByFile).c_str());

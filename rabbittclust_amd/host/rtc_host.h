@@ -224,6 +224,16 @@ void print_upgma_newick(const std::vector<GenomeInfo>& g, const std::vector<std:
 double quality_report_text(const std::function<std::string(uint32_t)>& name, const std::vector<std::vector<int>>& clusters, const rtc_sil* rec,
                            const double* sil, uint32_t n, std::string* quality_tsv, std::string* silhouette_tsv);
 
+// ---- clust-mst --cluster-support: the two reports of rtc_cluster_support's records (include/rtclust.h).  clusters: the run's,
+// numbered as <output> numbers them, every genome in exactly one; rec: one record per cluster in the library's order, that of the
+// clusters' smallest members; together[g] per genome.  support_tsv: a header, then a line a cluster in the order of `clusters` --
+// cluster, size, replicates, recovered, split, merged, mixed, max_pieces, support = (200 recovered + B) / (2 B) in integer
+// division: percent, half up, the rule of --nj-support's labels.  genomes_tsv: a header, then a line a genome in input order --
+// name, cluster, together, fraction = together / (B (size - 1)) as %.6f, or - for a singleton.  Returns the mean of recovered over
+// the clusters. ----
+double support_report_text(const std::function<std::string(uint32_t)>& name, const std::vector<std::vector<int>>& clusters, const rtc_csupport* rec,
+                           const uint64_t* together, uint32_t n, uint32_t replicates, std::string* support_tsv, std::string* genomes_tsv);
+
 // ---- clust-mst --auto-threshold / --stability: the MST edge-length analysis (src/MST.cpp:1743-2376, structs src/MST.h:77-100) ----
 struct EdgeLengthStats {
   double min_dist = 0, max_dist = 0, median_dist = 0, q1_dist = 0, q3_dist = 0, mean_dist = 0, std_dev = 0;
