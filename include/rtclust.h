@@ -1073,7 +1073,9 @@ double rtc_linkage_distance(uint32_t common, uint32_t denom, int kmer_size);
  *
  * Three kernel paths, chosen per component: m <= 64 one wave with D and R in LDS; larger ones a 256-lane workgroup with D in
  * global memory, the whole tree in one launch; from RTC_NJ_GRID_MIN points on (default 256; set, it holds down to 4) the whole
- * device, two launches a join, all of them enqueued without a read-back.  The records are the same on every path. */
+ * device, two launches a join, all of them enqueued without a read-back.  The records are the same on every path.  A grid-path
+ * scan launch has one workgroup per four rows of the active list, at most RTC_NJ_SCAN_BLOCKS of them (1 .. 1024, default and
+ * ceiling 1024); past that a workgroup takes further rows.  The switch is for tests: it brings that at any m. */
 typedef struct { uint32_t a, b, c, pad; double len_a, len_b, len_c; } rtc_njoin;
 /* One matrix that is already on the device: d_dist[i * ld + j], ld >= m; it is read and overwritten.  h_joins: room for
  * max(m - 2, 1) records, *h_n_joins their number.  ld < m, m >= 2^31 - 1, NULLs: RTC_ERR_ARG.  Synchronous. */
@@ -1093,6 +1095,8 @@ int rtc_nj_clusters(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_
 int rtc_nj_counters(const rtc_ctx* ctx, uint64_t out[10]);
 /* The paths of the last call: bit 0 the wave path, bit 1 the workgroup path, bit 2 the grid path. */
 int rtc_nj_last_path(const rtc_ctx* ctx);
+/* RTC_NJ_SCAN_BLOCKS as this context holds it: the most workgroups of a grid-path scan launch, 1 .. 1024 (unset: 1024). */
+int rtc_nj_scan_blocks(const rtc_ctx* ctx);
 
 /* ---- clust-mst --nj-support: jackknife support values for the neighbour-joining trees --------------------------------- */
 /* How many of B delete-half jackknife replicates over the sketch hashes hold each inner branch of rtc_nj_clusters' trees.  This
@@ -1279,7 +1283,9 @@ int rtc_cluster_quality_counters(const rtc_ctx* ctx, uint64_t out[10]);
  * Three kernel paths, chosen per component: m <= 64 one wave with S and the sizes in LDS; larger ones a 256-lane workgroup with
  * S in global memory, the whole dendrogram in one launch; from RTC_UPGMA_GRID_MIN points on (default 128; set, it holds down to 4)
  * the whole device, two launches a merge, all of them enqueued without a read-back.  Every path scans all active pairs at every
- * step and compares on the triple (mean, a, b), so the records are the same on every path. */
+ * step and compares on the triple (mean, a, b), so the records are the same on every path.  A grid-path scan launch has one
+ * workgroup per four rows of the active list, at most RTC_UPGMA_SCAN_BLOCKS of them (1 .. 1024, default and ceiling 1024); past
+ * that a workgroup takes further rows.  The switch is for tests: it brings that at any m. */
 typedef struct { uint32_t a, b, size_a, size_b; uint64_t sum; } rtc_umerge; /* 24 bytes */
 /* One matrix that is already on the device: d_sum[i * ld + j], 8-byte aligned, ld >= m; it is read and overwritten.  h_size[m]
  * on the host, or NULL.  h_merges: room for max(m - 1, 1) records; m - 1 are written, a and b as indices.  The sums are not
@@ -1301,6 +1307,8 @@ int rtc_upgma_clusters(rtc_ctx* ctx, const void* d_hashes, int width, const uint
 int rtc_upgma_counters(const rtc_ctx* ctx, uint64_t out[10]);
 /* The paths of the last call: bit 0 the wave path, bit 1 the workgroup path, bit 2 the grid path. */
 int rtc_upgma_last_path(const rtc_ctx* ctx);
+/* RTC_UPGMA_SCAN_BLOCKS as this context holds it: the most workgroups of a grid-path scan launch, 1 .. 1024 (unset: 1024). */
+int rtc_upgma_scan_blocks(const rtc_ctx* ctx);
 /* The height of a merge, as defined above.  Host only. */
 double rtc_upgma_distance(uint64_t sum, uint32_t size_a, uint32_t size_b);
 

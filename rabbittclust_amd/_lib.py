@@ -179,6 +179,7 @@ SIGNATURES = {
     "rtc_nj_clusters": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _i, _vp, _u64, C.POINTER(_u64), _vp]),
     "rtc_nj_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_nj_last_path": (_i, [_vp]),
+    "rtc_nj_scan_blocks": (_i, [_vp]),
     "rtc_nj_support": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _i, _u32, _u64, _vp, _u64, C.POINTER(_u64), _vp, _vp]),
     "rtc_nj_support_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_jackknife_word": (_u64, [_u64, _u64, _u32]),
@@ -197,6 +198,7 @@ SIGNATURES = {
     "rtc_upgma_clusters": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _i, _vp, _u64, C.POINTER(_u64), _vp]),
     "rtc_upgma_counters": (_i, [_vp, C.POINTER(_u64)]),
     "rtc_upgma_last_path": (_i, [_vp]),
+    "rtc_upgma_scan_blocks": (_i, [_vp]),
     "rtc_upgma_distance": (C.c_double, [_u64, _u32, _u32]),
     "rtc_hierarchy_flat": (_i, [_u32, _vp, _u64, _vp, _i, _i, _vp, _vp, C.POINTER(_u32)]),
 }

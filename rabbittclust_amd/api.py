@@ -39,6 +39,7 @@ LMERGE_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("common", "<u4"), ("denom", "
 NJOIN_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("c", "<u4"), ("pad", "<u4"), ("len_a", "<f8"), ("len_b", "<f8"), ("len_c", "<f8")])  # rtc_njoin
 NJ_PATH_WAVE, NJ_PATH_WORKGROUP, NJ_PATH_GRID = 1, 2, 4  # rtc_nj_last_path
 NJ_GRID_MIN = 256  # the library's default RTC_NJ_GRID_MIN (rtc_nj.hip: NJ_GRID_MIN)
+NJ_SCAN_BLOCKS = 1024  # the default and ceiling of RTC_NJ_SCAN_BLOCKS (rtc_nj.hip: NJ_SCAN_BLOCKS)
 NJ_SUPPORT_MAX = 256  # rtc_nj_support's most replicates
 JK_LDS_ELEMS = 1024  # the jackknife counting kernel stages a list of up to this many hashes in LDS (csrc/rtc_jackknife.h); a longer one is searched in global memory
 CSUPPORT_DT = np.dtype([("size", "<u4"), ("recovered", "<u4"), ("split", "<u4"), ("merged", "<u4"), ("mixed", "<u4"), ("max_pieces", "<u4")])  # rtc_csupport
@@ -47,6 +48,7 @@ CSUPPORT_TABLE_MAX = 1 << 25  # the keep table's most entries (csrc/rtc_support.
 UMERGE_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("size_a", "<u4"), ("size_b", "<u4"), ("sum", "<u8")])  # rtc_umerge
 UPGMA_PATH_WAVE, UPGMA_PATH_WORKGROUP, UPGMA_PATH_GRID = 1, 2, 4  # rtc_upgma_last_path
 UPGMA_GRID_MIN = 128  # the library's default RTC_UPGMA_GRID_MIN (rtc_upgma.h: UPGMA_GRID_MIN)
+UPGMA_SCAN_BLOCKS = 1024  # the default and ceiling of RTC_UPGMA_SCAN_BLOCKS (rtc_upgma.h: UPGMA_SCAN_BLOCKS)
 UPGMA_Q1 = 1 << 20  # distance 1 in the units of rtc_upgma_dev's sums
 HEDGE_DT = np.dtype([("p", "<u4"), ("q", "<u4"), ("common", "<u4"), ("size_p", "<u4"), ("size_q", "<u4")])  # rtc_hedge
 MCL_ENTRY_DT = np.dtype([("col", "<u4"), ("row", "<u4"), ("value", "<u4"), ("pad", "<u4")])  # rtc_mcl_entry
@@ -1166,6 +1168,10 @@ class Context:
         out["paths"] = int(self.lib.rtc_nj_last_path(self.h))
         return out
 
+    def nj_scan_blocks(self):
+        """rtc_nj_scan_blocks: RTC_NJ_SCAN_BLOCKS as the context holds it, 1 .. NJ_SCAN_BLOCKS (unset: NJ_SCAN_BLOCKS)"""
+        return int(self.lib.rtc_nj_scan_blocks(self.h))
+
     def nj_support(self, sk, comp, kmer_size, replicates, seed=0, cap=None):
         """rtc_nj_support: nj_clusters' (joins, first) for the same arguments and, third, one uint32 per record: how many of the
         `replicates` (1 .. NJ_SUPPORT_MAX) delete-half jackknife replicates over the sketch hashes hold the record's split; 0 for
@@ -1314,6 +1320,10 @@ class Context:
     def upgma_last_path(self):
         """rtc_upgma_last_path: UPGMA_PATH_WAVE | UPGMA_PATH_WORKGROUP | UPGMA_PATH_GRID of the last call"""
         return int(self.lib.rtc_upgma_last_path(self.h))
+
+    def upgma_scan_blocks(self):
+        """rtc_upgma_scan_blocks: RTC_UPGMA_SCAN_BLOCKS as the context holds it, 1 .. UPGMA_SCAN_BLOCKS (unset: UPGMA_SCAN_BLOCKS)"""
+        return int(self.lib.rtc_upgma_scan_blocks(self.h))
 
     def graph_query(self, sk, n_db, threshold, kmer_size, knn_k=0, query_chunk=0, cap=None):
         """clust-leiden --db --assign, first call (rtc_graph_query): sk holds the n_db model genomes, then the queries.  Returns

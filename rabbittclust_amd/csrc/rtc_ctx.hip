@@ -104,8 +104,10 @@ void rtc_options_from_env(rtc_options* o) {
   if (const char* e = getenv("RTC_LINKAGE_BYTES")) o->linkage_bytes = std::max<uint64_t>(strtoull(e, nullptr, 10), 1);
   if (const char* e = getenv("RTC_NJ_BYTES")) o->nj_bytes = std::max<uint64_t>(strtoull(e, nullptr, 10), 1);
   if (getenv("RTC_NJ_GRID_MIN")) o->nj_grid_min = (uint32_t)std::min<long long>(std::max<long long>(4, num("RTC_NJ_GRID_MIN", 4)), 0x7fffffff);
+  if (getenv("RTC_NJ_SCAN_BLOCKS")) o->nj_scan_blocks = (uint32_t)std::min<long long>(std::max<long long>(1, num("RTC_NJ_SCAN_BLOCKS", 1)), 1024);
   if (const char* e = getenv("RTC_UPGMA_BYTES")) o->upgma_bytes = std::max<uint64_t>(strtoull(e, nullptr, 10), 1);
   if (getenv("RTC_UPGMA_GRID_MIN")) o->upgma_grid_min = (uint32_t)std::min<long long>(std::max<long long>(4, num("RTC_UPGMA_GRID_MIN", 4)), 0x7fffffff);
+  if (getenv("RTC_UPGMA_SCAN_BLOCKS")) o->upgma_scan_blocks = (uint32_t)std::min<long long>(std::max<long long>(1, num("RTC_UPGMA_SCAN_BLOCKS", 1)), 1024);
   o->mcl_global = flag("RTC_MCL_GLOBAL");
   o->snn_global = flag("RTC_SNN_GLOBAL");
   o->sil_global = flag("RTC_SIL_GLOBAL");

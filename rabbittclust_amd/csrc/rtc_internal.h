@@ -41,8 +41,10 @@ struct rtc_options {
   uint64_t linkage_bytes = 0;      // RTC_LINKAGE_BYTES: the byte budget of a batch of rtc_linkage_complete (0: half the free HBM)
   uint64_t nj_bytes = 0;           // RTC_NJ_BYTES: the byte budget of a batch of rtc_nj_clusters (0: half the free HBM)
   uint32_t nj_grid_min = 0;        // RTC_NJ_GRID_MIN: components of at least this many points (down to 4) take the grid path (0: default)
+  uint32_t nj_scan_blocks = 0;     // RTC_NJ_SCAN_BLOCKS: the most workgroups of a grid-path scan launch, 1 .. 1024 (0: 1024)
   uint64_t upgma_bytes = 0;        // RTC_UPGMA_BYTES: the byte budget of a batch of rtc_upgma_clusters (0: half the free HBM)
   uint32_t upgma_grid_min = 0;     // RTC_UPGMA_GRID_MIN: components of at least this many points (down to 4) take the grid path (0: default)
+  uint32_t upgma_scan_blocks = 0;  // RTC_UPGMA_SCAN_BLOCKS: the most workgroups of a grid-path scan launch, 1 .. 1024 (0: 1024)
   int mcl_global = 0;              // RTC_MCL_GLOBAL: every column of rtc_mcl takes the long path (the table in global memory)
   int snn_global = 0;              // RTC_SNN_GLOBAL: every record of rtc_graph_snn takes the long path (the owner's row in global memory)
   int sil_global = 0;              // RTC_SIL_GLOBAL: every row of rtc_silhouette takes the long path (the table in global memory)

@@ -287,6 +287,8 @@ struct nj_bufs {
 
 inline uint64_t nj_records_of(uint32_t m) { return m >= 3 ? m - 2 : m == 2 ? 1 : 0; }
 inline uint32_t nj_grid_min(const rtc_ctx* ctx) { return ctx->opt.nj_grid_min ? std::max<uint32_t>(ctx->opt.nj_grid_min, 4) : NJ_GRID_MIN; }
+// the most workgroups of a scan launch: RTC_NJ_SCAN_BLOCKS below the ceiling the scratch reserves (tests reach a second row per workgroup with it)
+inline uint32_t nj_scan_blocks(const rtc_ctx* ctx) { return ctx->opt.nj_scan_blocks ? std::min<uint32_t>(ctx->opt.nj_scan_blocks, NJ_SCAN_BLOCKS) : NJ_SCAN_BLOCKS; }
 // 0 wave, 1 workgroup, 2 grid
 inline int nj_path_of(const rtc_ctx* ctx, uint32_t m) { return m >= nj_grid_min(ctx) ? 2 : m <= NJ_WAVE_MAX ? 0 : 1; }
 
@@ -347,8 +349,9 @@ int nj_join(rtc_ctx* ctx, double* d_dist, std::vector<rtc_kb_comp>& comps, std::
     hipLaunchKernelGGL(nj_grid_init_kernel, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, (const double*)D, c.ld, m, R, act[0]);
     RTC_CHECK_LAUNCH(ctx);
     int w = 0;
+    const uint32_t cap = nj_scan_blocks(ctx);
     for (uint32_t r = m; r > 3; r--, w ^= 1) {
-      const uint32_t nb = std::min<uint32_t>((r - 1 + 3) / 4, NJ_SCAN_BLOCKS);
+      const uint32_t nb = std::min<uint32_t>((r - 1 + 3) / 4, cap);
       hipLaunchKernelGGL(nj_grid_scan_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const double*)D, c.ld, (const uint32_t*)act[w], (const double*)R, r, minima);
       RTC_CHECK_LAUNCH(ctx);
       hipLaunchKernelGGL(nj_grid_join_kernel, dim3((r + 255) / 256), dim3(256), 0, ctx->stream, D, c.ld, (const uint32_t*)act[w], act[w ^ 1], R, r,
@@ -401,6 +404,8 @@ extern "C" int rtc_nj_counters(const rtc_ctx* ctx, uint64_t out[10]) {
 }
 
 extern "C" int rtc_nj_last_path(const rtc_ctx* ctx) { return ctx ? ctx->nj_path : 0; }
+
+extern "C" int rtc_nj_scan_blocks(const rtc_ctx* ctx) { return ctx ? (int)nj_scan_blocks(ctx) : 0; }
 
 extern "C" int rtc_nj_dev(rtc_ctx* ctx, uint32_t m, double* d_dist, uint64_t ld, rtc_njoin* h_joins, uint32_t* h_n_joins) {
   if (!ctx || !h_n_joins) return RTC_ERR_ARG;

@@ -229,6 +229,8 @@ struct up_bufs {
 };
 
 inline uint32_t up_grid_min(const rtc_ctx* ctx) { return ctx->opt.upgma_grid_min ? std::max<uint32_t>(ctx->opt.upgma_grid_min, 4) : UPGMA_GRID_MIN; }
+// the most workgroups of a scan launch: RTC_UPGMA_SCAN_BLOCKS below the ceiling the scratch reserves (tests reach a second row per workgroup with it)
+inline uint32_t up_scan_blocks(const rtc_ctx* ctx) { return ctx->opt.upgma_scan_blocks ? std::min<uint32_t>(ctx->opt.upgma_scan_blocks, UPGMA_SCAN_BLOCKS) : UPGMA_SCAN_BLOCKS; }
 // 0 wave, 1 workgroup, 2 grid
 inline int up_path_of(const rtc_ctx* ctx, uint32_t m) { return m >= up_grid_min(ctx) ? 2 : m <= UPGMA_WAVE_MAX ? 0 : 1; }
 
@@ -291,8 +293,9 @@ int up_agglomerate(rtc_ctx* ctx, uint64_t* d_sum, std::vector<rtc_kb_comp>& comp
     hipLaunchKernelGGL(upgma_grid_init_kernel, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, m, d_w, N, act[0]);
     RTC_CHECK_LAUNCH(ctx);
     int t = 0;
+    const uint32_t cap = up_scan_blocks(ctx);
     for (uint32_t r = m; r > 1; r--, t ^= 1) {
-      const uint32_t nb = std::min<uint32_t>((r - 1 + 3) / 4, UPGMA_SCAN_BLOCKS);
+      const uint32_t nb = std::min<uint32_t>((r - 1 + 3) / 4, cap);
       hipLaunchKernelGGL(upgma_grid_scan_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const uint64_t*)S, c.ld, (const uint32_t*)act[t], (const uint32_t*)N, r,
                          minima);
       RTC_CHECK_LAUNCH(ctx);
@@ -348,6 +351,8 @@ extern "C" int rtc_upgma_counters(const rtc_ctx* ctx, uint64_t out[10]) {
 }
 
 extern "C" int rtc_upgma_last_path(const rtc_ctx* ctx) { return ctx ? ctx->upgma_path : 0; }
+
+extern "C" int rtc_upgma_scan_blocks(const rtc_ctx* ctx) { return ctx ? (int)up_scan_blocks(ctx) : 0; }
 
 extern "C" double rtc_upgma_distance(uint64_t sum, uint32_t size_a, uint32_t size_b) {
   const double pairs = (double)size_a * (double)size_b;

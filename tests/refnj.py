@@ -7,8 +7,10 @@ import numpy as np
 NONE = 0xFFFFFFFF
 
 
-def nj(dist):
-    """[(a, b, c, len_a, len_b, len_c)] in step order; c is NONE but in the last record of m >= 3"""
+def nj(dist, steps=None, exact_sums=False):
+    """[(a, b, c, len_a, len_b, len_c)] in step order; c is NONE but in the last record of m >= 3.  steps: stop after that many
+    joins (the records are the first `steps` of the whole run's).  exact_sums: the caller vouches that every sum of a row's
+    entries is exact in any order (entries on a coarse binary grid), so the initial R may be numpy's row sums."""
     D = np.array(dist, dtype=np.float64, copy=True)
     m = int(D.shape[0])
     assert D.ndim == 2 and D.shape[1] == m
@@ -19,18 +21,25 @@ def nj(dist):
         la = np.float64(0.5) * d
         return [(0, 1, NONE, float(la), float(d - la), 0.0)]
     R = np.zeros(m, dtype=np.float64)
-    for i in range(m):
-        s = np.float64(0.0)
-        row = D[i]
-        for j in range(m):
-            if j != i:
-                s = s + row[j]
-        R[i] = s
+    if exact_sums:
+        off = D.copy()
+        np.fill_diagonal(off, 0.0)
+        R[:] = off.sum(axis=1)
+    else:
+        for i in range(m):
+            s = np.float64(0.0)
+            row = D[i]
+            for j in range(m):
+                if j != i:
+                    s = s + row[j]
+            R[i] = s
     act = np.arange(m)
     r = m
     out = []
     half = np.float64(0.5)
     while r > 3:
+        if steps is not None and len(out) >= steps:
+            return out
         sub = D[np.ix_(act, act)]
         ra = R[act]
         Q = (np.float64(r - 2) * sub - ra[:, None]) - ra[None, :]  # Q[p, q], p < q: ((r - 2) D[i][j] - R[i]) - R[j]
@@ -51,6 +60,8 @@ def nj(dist):
         out.append((i, j, NONE, float(len_i), float(len_j), 0.0))
         act = np.delete(act, q)
         r -= 1
+    if steps is not None and len(out) >= steps:
+        return out
     i, j, k = (int(v) for v in act)
     out.append((i, j, k, float(half * ((D[i, j] + D[i, k]) - D[j, k])), float(half * ((D[i, j] + D[j, k]) - D[i, k])),
                 float(half * ((D[i, k] + D[j, k]) - D[i, j]))))
