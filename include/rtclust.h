@@ -416,6 +416,51 @@ int rtc_greedy_mash(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_
                     uint32_t n, int kmer_size, int is_containment, uint32_t sketch_size, double threshold,
                     int32_t* h_rep_of, uint32_t* h_n_clusters);
 
+/* ---- clust-greedy --order degree: representatives that do not depend on the order of the genomes ----------------- */
+/* rtc_greedy's clusters are a function of the order the genomes are walked in.  Here the order is a function of the
+ * neighbour graph, so the clusters are a function of the set alone.  The reference has no counterpart: this is the definition.
+ *
+ * Neighbours.  N is symmetric, p != q.
+ *   KSSD (is_minhash = 0): rtc_dbscan's predicate at eps = threshold with max_posting = 0 -- both orientations in double with the
+ *     1e-12 term and the size bounds, on the count that predicate sees (u32 sketches: saturated at 65 535).  A pair whose
+ *     orientations disagree fails the call with RTC_ERR_UNSUPPORTED and is named in the message; so do a threshold whose
+ *     jaccard_min t is <= 1e-12 and, for u32 sketches, a size bound ceil(max |sketch| / t) past INT_MAX.
+ *   MinHash (is_minhash = 1): rtc_mash_distance(common, denom, sketch_size, kmer_size) <= threshold on the union-truncated
+ *     counts, decided through the table rtc_dbscan_mash_table gives -- the device forms no distance.  threshold < 0 or NaN:
+ *     RTC_ERR_ARG; threshold >= 1 (pairs without a common hash would be neighbours): RTC_ERR_UNSUPPORTED.  sketch_size: 1 .. 2^28 - 1.
+ *   An empty sketch has no neighbours at either width and is a cluster of its own.  This is the one place where N is not
+ *   rtc_dbscan's relation: the u64 brute force there makes the empty sketches neighbours of each other.
+ * Order.  degree(v) = |N(v)|.  v precedes w iff degree(v) > degree(w), or the degrees are equal and v < w (clust-greedy puts
+ *   the larger genome at the lower index, so ties go to the larger genome).
+ * Representatives.  Walking the order, v is a representative iff no earlier representative is in N(v): R is the
+ *   lexicographically first maximal independent set of the graph under the order.
+ * Members.  Every other v joins the representative r in N(v) & R with the largest j(v, r) -- KSSD: common / (|v| + |r| -
+ *   common), MinHash: the truncated common / denom -- compared exactly by cross-multiplication in 64 bits; equal j goes to the
+ *   r that comes earlier in the order.
+ * h_out[v]: rep (v itself for a representative), degree, and the common and denom of the pair (v, rep), both 0 for a
+ *   representative.  *h_n_clusters = |R|.  n = 0 is fine (h_out may be NULL).
+ *
+ * The pair phase is rtc_dbscan's: RTC_EDGE_BUDGET chunks the rows.  The kept pairs (16 bytes each) stay on the device;
+ * RTC_ERR_NOMEM when they do not fit, no fallback.  The selection runs in rounds (mark, promote, demote: DESIGN 3.4s) until no
+ * vertex is open, with no round cap -- a path of n genomes takes n / 2 rounds.  From RTC_DEGREE_TAIL open vertices down (0:
+ * never; default 4 096, measured on one MI355X: DESIGN 3.4s), with at most four times as many edges between them, one workgroup
+ * runs the remaining rounds in one launch.  A member's candidate
+ * representatives are folded by one wave, by 256 lanes from 4 097 of them on; RTC_DEGREE_BLOCK=1 sends every row through the
+ * latter.  Neither switch changes a result.  Synchronous. */
+typedef struct { uint32_t rep, degree, common, denom; } rtc_degree_place;
+int rtc_greedy_degree(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                      int is_minhash, uint32_t sketch_size, double threshold, int kmer_size, rtc_degree_place* h_out,
+                      uint32_t* h_n_clusters);
+/* The last rtc_greedy_degree: out[0] row chunks, out[1] candidate edges, out[2] MinHash candidates merged, out[3] pairs kept,
+ * out[4] representatives, out[5] selection rounds in the low 32 bits and, of those, the rounds run inside the tail kernel in
+ * the high 32, out[6] rows of the assignment on the wave path in the low 32 bits and on the 256-lane path in the high 32,
+ * out[7] pair phase ns, out[8] predicate ns, out[9] selection ns (degrees included), out[10] assignment ns, out[11] whole call
+ * ns (host clock, each ending in a synchronise). */
+int rtc_greedy_degree_counters(const rtc_ctx* ctx, uint64_t out[12]);
+/* the paths of the last rtc_greedy_degree: bit 0 the one-wave row path of the assignment, bit 1 the 256-lane path, bit 2 the
+ * tail kernel ran */
+int rtc_greedy_degree_last_path(const rtc_ctx* ctx);
+
 /* ---- clust-mst post-processing ----------------------------------------------------------- */
 /* The --dedup-dist representatives: build_dedup_candidates_per_cluster_core (src/cluster_postprocess.cpp:60-156).  The forest
  * edges with dist <= dedup_dist (h_edges[0..m), EdgeInfo records; those edges must form a forest over n nodes) are joined into

@@ -117,6 +117,9 @@ SIGNATURES = {
     "rtc_mst_mash": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _u32, _i, _i, _u32, _vp, C.POINTER(_u64), _i, _vp, _vp]),
     "rtc_greedy": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _i, _i, _i, C.c_double, _vp,
                         C.POINTER(_u32)]),
+    "rtc_greedy_degree": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _i, _u32, C.c_double, _i, _vp, C.POINTER(_u32)]),
+    "rtc_greedy_degree_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_greedy_degree_last_path": (_i, [_vp]),
     "rtc_tree_medoids": (_i, [_vp, _u32, _vp, _u64, C.c_double, _vp, _vp]),
     "rtc_dedup_last_path": (_i, [_vp]),
     "rtc_ctx_set_host_threads": (_i, [_vp, _i]),

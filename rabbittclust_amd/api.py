@@ -63,6 +63,9 @@ SNN_PATH_WAVE, SNN_PATH_WORKGROUP, SNN_PATH_GLOBAL = 1, 2, 4  # rtc_graph_snn_la
 # wave, at most SNN_BLOCK_ROW a 256-lane workgroup, both with that row in LDS; a longer one is searched in global memory
 SNN_WAVE_ROW = 768
 SNN_BLOCK_ROW = 8192
+DEGREE_PLACE_DT = np.dtype([("rep", "<u4"), ("degree", "<u4"), ("common", "<u4"), ("denom", "<u4")])  # rtc_degree_place
+DEGREE_PATH_WAVE, DEGREE_PATH_WORKGROUP, DEGREE_PATH_TAIL = 1, 2, 4  # rtc_greedy_degree_last_path
+DEGREE_WAVE_ROW = 4096  # a member with more candidate representatives takes the 256-lane path (csrc/rtc_topk_select.h: TK_LONG)
 SIL_DT = np.dtype([("a_num", "<u8"), ("b_num", "<u8"), ("a_den", "<u4"), ("b_den", "<u4"), ("b_cluster", "<u4"), ("far_q", "<u4"),
                    ("near_q", "<u4"), ("near_cluster", "<u4")])  # rtc_sil
 SIL_ONE = 1 << 20  # distance 1 in rtc_silhouette's units
@@ -596,6 +599,35 @@ class Context:
                                        int(is_containment), int(sk.kind == "kssd"), float(threshold),
                                        _np_ptr(rep), C.byref(nc)))
         return int(nc.value), rep[:n].copy()
+
+    def greedy_degree(self, sk, threshold, kmer_size, sketch_size=None):
+        """clust-greedy --order degree (rtc_greedy_degree): the clusters include/rtclust.h defines over the neighbour graph at
+        `threshold` -- KSSD sketches with sketch_size None (rtc_dbscan's predicate), MinHash sketches of at most sketch_size
+        hashes otherwise (rtc_mash_distance <= threshold).  Returns (rep, degree, common, denom, n_clusters): uint32 arrays
+        with one entry per genome, rep[v] == v for a representative, common / denom those of the pair (v, rep[v])."""
+        n = sk.n
+        out = np.zeros(max(n, 1), dtype=DEGREE_PLACE_DT)
+        nc = C.c_uint32()
+        self.check(self.lib.rtc_greedy_degree(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n,
+                                              int(sketch_size is not None), int(sketch_size or 0), float(threshold), int(kmer_size),
+                                              _np_ptr(out), C.byref(nc)))
+        out = out[:n]
+        return out["rep"].copy(), out["degree"].copy(), out["common"].copy(), out["denom"].copy(), int(nc.value)
+
+    def greedy_degree_counters(self):
+        """rtc_greedy_degree_counters as a dict (the last greedy_degree call), the two packed words taken apart."""
+        a = (C.c_uint64 * 12)()
+        self.check(self.lib.rtc_greedy_degree_counters(self.h, a))
+        names = ("chunks", "candidate_edges", "merged", "kept_edges", "representatives", None, None, "pair_ns", "predicate_ns",
+                 "select_ns", "assign_ns", "total_ns")
+        out = {k: int(a[i]) for i, k in enumerate(names) if k}
+        out["rounds"], out["tail_rounds"] = int(a[5]) & 0xFFFFFFFF, int(a[5]) >> 32
+        out["wave_rows"], out["workgroup_rows"] = int(a[6]) & 0xFFFFFFFF, int(a[6]) >> 32
+        return out
+
+    def greedy_degree_last_path(self):
+        """rtc_greedy_degree_last_path: DEGREE_PATH_WAVE | DEGREE_PATH_WORKGROUP | DEGREE_PATH_TAIL of the last greedy_degree call"""
+        return int(self.lib.rtc_greedy_degree_last_path(self.h))
 
     def tree_medoids(self, n, edges, dedup_dist, seq_len=None, threads=None):
         """--dedup-dist representatives (build_dedup_candidates_per_cluster_core): node_to_rep[n] (int32) from forest edges

@@ -49,6 +49,9 @@ struct rtc_options {
   int snn_global = 0;              // RTC_SNN_GLOBAL: every record of rtc_graph_snn takes the long path (the owner's row in global memory)
   int sil_global = 0;              // RTC_SIL_GLOBAL: every row of rtc_silhouette takes the long path (the table in global memory)
   uint64_t support_bytes = 0;      // RTC_SUPPORT_BYTES: the bytes rtc_cluster_support's words of 64 replicates may take at once (0: half the free HBM)
+  bool has_degree_tail = false;
+  uint32_t degree_tail = 0;        // RTC_DEGREE_TAIL: rtc_greedy_degree's selection goes to the one-workgroup kernel from this many open vertices down (0: never)
+  int degree_block = 0;            // RTC_DEGREE_BLOCK: every row of rtc_greedy_degree's assignment takes the 256-lane path
 };
 void rtc_options_from_env(rtc_options* o);
 
@@ -123,6 +126,8 @@ struct rtc_ctx {
   int sil_path = 0;         // rtc_silhouette_last_path
   uint64_t quality[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_cluster_quality_counters (include/rtclust.h lists them)
   uint64_t csupport[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_cluster_support_counters (include/rtclust.h lists them)
+  uint64_t greedy_degree[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_greedy_degree_counters (include/rtclust.h lists them)
+  int greedy_degree_path = 0;  // rtc_greedy_degree_last_path
   int host_threads = 1;     // rtc_ctx_set_host_threads: the host side of rtc_tree_medoids and of rtc_nj_clusters', rtc_upgma_clusters' and rtc_cluster_quality's distances
   // rtc_diag_counters: [0] pair tiles the join took, [1] tiled-kernel tiles, [2] merge-kernel tiles, [3] candidate lists contracted
   // to their forest, [4] greedy runs replayed from ONE global join, [5] greedy query blocks of the block loop, [6] estimates handed

@@ -898,6 +898,7 @@ struct Options {
   string minhashOnly;        // clust-leiden: the first of -s / -c as spelled, which only --minhash gives a meaning
   bool linkageComplete = false;  // clust-mst --linkage complete: complete linkage inside every cluster (rtc_linkage_complete)
   bool quality = false;  // clust-mst --quality: silhouette, diameter and separation of the run's clusters (rtc_cluster_quality)
+  bool orderDegree = false;  // clust-greedy --order degree: representatives by how many genomes they cover (rtc_greedy_degree)
   bool upgma = false;  // clust-mst --upgma: average linkage inside every cluster (rtc_upgma_clusters)
   bool njTree = false, njAll = false;  // clust-mst --nj-tree / --nj-all: neighbour-joining trees of the clusters / of all genomes (rtc_nj_clusters)
   bool has_njSupport = false, has_njSeed = false;  // clust-mst --nj-support B [--nj-seed S]: jackknife support values for those trees (rtc_nj_support)
@@ -1029,6 +1030,10 @@ static Options parse(int argc, char** argv) {
     else if (a == "--fast") o.is_fast = true;
 #ifdef GREEDY_CLUST
     else if (a == "--save-rep") o.saveRep = true;
+    else if (a == "--order") {
+      if (strcmp(need(i), "degree") != 0) { fprintf(stderr, "ERROR: --order must be degree\n"); exit(1); }
+      o.orderDegree = true;
+    }
 #endif
     else if (a == "--db") o.repdb_path = need(i);
     else if (a == "--build") o.db_build = true;
@@ -1183,6 +1188,13 @@ static Options parse(int argc, char** argv) {
            "  [--fast] --db FILE --build|--query|--assign|--append LIST|--stats [--top-k N] (MST representative database)"
 #else
            "  --append LIST (with --presketched DIR)  --save-rep (cluster_state.bin beside the sketches)\n"
+           "  --order degree (clusters that do not depend on the order of the genomes: two genomes are neighbours when they are\n"
+           "             within -d, the genomes are walked by their number of neighbours, most first, the larger genome first among\n"
+           "             equals, one becomes a representative when no earlier representative is its neighbour, and every other\n"
+           "             genome joins its most similar neighbouring representative -- all on the GPU; <output>.order.tsv lists the\n"
+           "             genomes in that order with degree, role, representative and distance; with --fast or MinHash sketches\n"
+           "             (0 <= d < 1), lists, a single FASTA and --presketched; not with -c, --inverted-index=false, --append,\n"
+           "             --db or --save-rep)\n"
            "  [--fast] --db FILE --build|--query|--assign|--append LIST|--stats [--top-k N] (representative database)"
 #endif
       );
@@ -2836,6 +2848,16 @@ int main(int argc, char** argv) {
   if (!o.has_threshold) { o.threshold = 0.05; cerr << "-----use default threshold: " << o.threshold << endl; }
 
 #ifdef GREEDY_CLUST
+  // ---- --order degree: what it does not go with, before any GPU is asked for ----
+  if (o.orderDegree) {
+    const char* bad = o.isContainment ? "-c/--containment" : !o.useIndex ? "--inverted-index=false" : o.has_append ? "--append"
+                      : !o.repdb_path.empty() ? "--db" : o.saveRep ? "--save-rep" : nullptr;
+    if (bad) { cerr << "ERROR: --order does not go with " << bad << endl; return 1; }
+    if (!o.is_fast && !(o.threshold >= 0.0 && o.threshold < 1.0)) {
+      cerr << "ERROR: --order degree on MinHash sketches needs 0 <= -d/--threshold < 1, got " << o.threshold << endl;
+      return 1;
+    }
+  }
   // ---- RepDB mode (src/main.cpp:160-170, :300-370) ----
   const bool db_action = o.db_build || o.db_query || o.db_assign || o.db_stats;
   if (db_action && o.repdb_path.empty()) { cerr << "ERROR: --build / --query / --assign / --stats require --db" << endl; return 1; }
@@ -3447,7 +3469,42 @@ int main(int argc, char** argv) {
   else upload_sketches(ctx, &mh.hashes, nullptr, ds);
   vector<int32_t> rep_of(genomes.size());
   uint32_t ncl = 0;
-  if (!o.is_fast && !o.useIndex)  // greedyCluster: every representative, MinHash::distance() (src/sub_command.cpp:2683,2914)
+  if (o.orderDegree) {
+    // --order degree: the genomes keep the numbering of the size sort above, the clustering is include/rtclust.h's
+    // (rtc_greedy_degree); <output>.order.tsv lists them in the order the definition walks them
+    const uint32_t s_mh = o.is_fast ? 0u : size_cfg[0];
+    vector<rtc_degree_place> place(genomes.size());
+    CHECK(ctx, rtc_greedy_degree(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, o.is_fast ? 0 : 1, s_mh, o.threshold, kmer_size,
+                                 place.data(), &ncl));
+    for (size_t v = 0; v < place.size(); v++) rep_of[v] = (int32_t)place[v].rep;
+    const string tsv = o.outputFile + ".order.tsv";
+    FILE* fp = fopen(tsv.c_str(), "w");
+    if (!fp) { cerr << "ERROR: cannot open file: " << tsv << endl; return 1; }
+    vector<uint32_t> order(place.size());
+    iota(order.begin(), order.end(), 0u);
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return place[a].degree != place[b].degree ? place[a].degree > place[b].degree : a < b; });
+    auto name_of = [&](uint32_t v) -> const string& { return sketchByFile ? genomes[v].fileName : genomes[v].seq0.name; };
+    fprintf(fp, "name\tdegree\trole\trepresentative\tdistance\n");
+    for (uint32_t v : order) {
+      const rtc_degree_place& p = place[v];
+      double dist = 0.0;
+      if (p.rep != v) {
+        if (!o.is_fast) dist = rtc_mash_distance(p.common, p.denom, s_mh, kmer_size);
+        else if (p.denom != p.common) { const double j = (double)p.common / (double)p.denom; dist = -log(2.0 * j / (1.0 + j)) / kmer_size; }
+      }
+      fprintf(fp, "%s\t%u\t%s\t%s\t%.6f\n", name_of(v).c_str(), p.degree, p.rep == v ? "rep" : "member", name_of(p.rep).c_str(), dist);
+    }
+    fclose(fp);
+    cerr << "-----write the processing order into: " << tsv << endl;
+    uint64_t dc[12];
+    if (rtc_greedy_degree_counters(ctx, dc) == RTC_OK) {
+      g_metrics.num("greedy_degree_pair_s", 1e-9 * (double)(dc[7] + dc[8]));
+      g_metrics.num("greedy_degree_select_s", 1e-9 * (double)dc[9]);
+      g_metrics.num("greedy_degree_assign_s", 1e-9 * (double)dc[10]);
+      g_metrics.num("greedy_degree_rounds", (double)(dc[5] & 0xffffffffull));
+      g_metrics.num("greedy_degree_edges", (double)dc[3]);
+    }
+  } else if (!o.is_fast && !o.useIndex)  // greedyCluster: every representative, MinHash::distance() (src/sub_command.cpp:2683,2914)
     CHECK(ctx, rtc_greedy_mash(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, ds.n, kmer_size, (int)mh.isContainment, size_cfg[0], o.threshold,
                                rep_of.data(), &ncl));
   else
