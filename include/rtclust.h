@@ -519,6 +519,51 @@ int rtc_rep_topk_last_path(const rtc_ctx* ctx);
  * scatter), out[8] selection ns (with the read-back), out[9] reserved. */
 int rtc_rep_topk_counters(const rtc_ctx* ctx, uint64_t out[10]);
 
+/* ---- clust-mst --db --screen: which representatives a sample contains --------------------------- */
+typedef struct { uint32_t query, slot, common, size, unique, rank; } rtc_screen_hit;
+typedef struct { uint32_t n_hashes, n_matched, n_explained, n_hits, n_picks, pad; } rtc_screen_sum;
+/* Containment of every representative in every sample, and a winner-takes-all decomposition of the sample (what mash screen -w
+ * and sourmash gather give), for KSSD sketches: a fixed subsample of k-mer space, so |X n P| / |P| is an unbiased containment
+ * whatever the two sizes.  The set is laid out as for rtc_rep_topk: n_reps representatives, then n_queries samples, ascending
+ * lists of distinct hashes, width 4 or 8, empty lists allowed.  For a sample X and a slot p with hash set P:
+ *   eligible  h_live == NULL or h_live[p] != 0; |P| > 0; common = |X n P| >= max(1, min_common); and
+ *             common * 2^20 >= min_cont_q20 * |P| in 64-bit integers (min_cont_q20 = llround(min_containment * 2^20), formed by
+ *             the caller; 0: no containment test).  The device forms no quotient and no floating-point number.
+ *   matched   the hashes of X that lie in at least one eligible slot.
+ *   gather    R = matched.  In round t = 1, 2, ... every eligible slot not yet picked has u_p = |R n P|; the pick is the slot
+ *             with the largest u_p, equal counts to the lower slot.  The rounds end when that u_p < min_unique (>= 1), when no
+ *             unpicked slot is left, or when max_picks > 0 picks have been made; otherwise the pick gets rank = t and
+ *             unique = u_p, and R <- R \ P.  A sample takes at most as many rounds as it has eligible slots.
+ *   hits      every eligible slot, (query, slot, common, size = |P|, unique, rank): for a pick unique is its count when picked;
+ *             for the others rank = 0 and unique is what was left of them when the rounds ended.  A query's picks come first,
+ *             by rank; the rest follow by common / size, larger first, compared exactly by 64-bit cross-multiplication, equal
+ *             ratios to the lower slot.
+ *   summary   n_hashes = |X|, n_matched, n_explained = n_matched - |R| at the end (the sum of unique over the picks), n_hits,
+ *             n_picks.
+ * Queries never see each other and the database is not changed.  Everything is an integer: the result depends on no kernel
+ * path, chunking or scheduling.  h_hits[0 .. min(*n_hits, cap)) is sorted by query, then in the order above; *n_hits beyond
+ * cap: call again with a buffer that large (h_sum[n_queries] is complete either way).  query_chunk > 0 screens that many
+ * samples at a time (0: all at once).  A chunk's match records and views are charged against RTC_SCREEN_BYTES (default: half
+ * the free HBM; csrc/rtc_screen.h has the rates); a chunk that does not fit is halved and screened again, a single sample that
+ * does not fit is RTC_ERR_NOMEM, as is one with 2^32 - 1 match records or more.  RTC_ERR_ARG: min_unique == 0, min_cont_q20 >
+ * 2^20, h_sum == NULL with n_queries > 0, a width other than 4 or 8, n_reps + n_queries >= 2^31 - 1.  RTC_ERR_UNSUPPORTED: a
+ * sketch of 2^31 hashes or more.  One workgroup runs all rounds of one sample, by its number of eligible slots on one of three
+ * paths; RTC_SCREEN_GLOBAL=1 sends every sample through the last one.  Synchronous. */
+int rtc_rep_screen(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len,
+                   uint32_t n_reps, uint32_t n_queries, const uint8_t* h_live, uint32_t min_common, uint32_t min_cont_q20,
+                   uint32_t min_unique, uint32_t max_picks, uint32_t query_chunk, rtc_screen_hit* h_hits, uint64_t cap,
+                   uint64_t* n_hits, rtc_screen_sum* h_sum);
+/* What the last rtc_rep_screen call did: out[0] query chunks screened, out[1] match records, out[2] candidates (pairs that share
+ * a hash), out[3] eligible candidates, out[4] picks, out[5] the most rounds any sample took, out[6] / out[7] / out[8] samples
+ * gathered by the wave / workgroup / global path, out[9] expansion ns (index, join, candidates, views), out[10] gather ns (with
+ * the read-back), out[11] the whole call's ns. */
+int rtc_rep_screen_counters(const rtc_ctx* ctx, uint64_t out[12]);
+/* Which gather paths the last rtc_rep_screen call took: bit 0 one wave (u in LDS), bit 1 a 256-lane workgroup (u in LDS),
+ * bit 2 a 256-lane workgroup with u in global memory. */
+int rtc_rep_screen_last_path(const rtc_ctx* ctx);
+/* Mash's containment identity, host only: 1 if common == size, 0 if common == 0, else pow(common / size, 1 / kmer_size). */
+double rtc_screen_identity(uint32_t common, uint32_t size, int kmer_size);
+
 /* ---- clust-dbscan --fast: KSSD DBSCAN on one GPU ----------------------------------------------------- */
 /* KssdDBSCAN (src/dbscan.cpp:725-985) without --knn.  Neighbours are findNeighborsKSSDWithIndex's (:366-612): p != q, both
  * non-empty, floor(t |p|) <= |q| <= ceil(|p| / t) and !(common (1 + t) + 1e-12 < t |p| + t |q|) in double, t = x / (2 - x),

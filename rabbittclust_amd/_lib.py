@@ -127,6 +127,10 @@ SIGNATURES = {
     "rtc_rep_topk": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _u32, _vp, _i, _u32, _u32, _vp, _u64, C.POINTER(_u64), _vp]),
     "rtc_rep_topk_last_path": (_i, [_vp]),
     "rtc_rep_topk_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_rep_screen": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u64, C.POINTER(_u64), _vp]),
+    "rtc_rep_screen_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_rep_screen_last_path": (_i, [_vp]),
+    "rtc_screen_identity": (C.c_double, [_u32, _u32, _i]),
     "rtc_dbscan": (_i, [_vp, _vp, _i, _vp, _vp, _u32, C.c_double, _i, _i, _i, _vp, _vp, C.POINTER(_u32),
                        C.POINTER(_u32)]),
     "rtc_dbscan_counters": (_i, [_vp, C.POINTER(_u64)]),

@@ -77,6 +77,18 @@ SIL_PATH_WAVE, SIL_PATH_WORKGROUP, SIL_PATH_GLOBAL = 1, 2, 4  # rtc_silhouette_l
 SIL_WAVE_ROW, SIL_WAVE_SLOTS = 128, 256
 SIL_BLOCK_ROW, SIL_BLOCK_SLOTS = 1024, 2048
 SIL_GLOBAL_LOG2_MIN = 6
+SCREEN_HIT_DT = np.dtype([("query", "<u4"), ("slot", "<u4"), ("common", "<u4"), ("size", "<u4"), ("unique", "<u4"), ("rank", "<u4")])  # rtc_screen_hit
+SCREEN_SUM_DT = np.dtype([("n_hashes", "<u4"), ("n_matched", "<u4"), ("n_explained", "<u4"), ("n_hits", "<u4"), ("n_picks", "<u4"),
+                          ("pad", "<u4")])  # rtc_screen_sum
+SCREEN_PATH_WAVE, SCREEN_PATH_BLOCK, SCREEN_PATH_GLOBAL = 1, 2, 4  # rtc_rep_screen_last_path
+# the gather kernel's path boundaries (csrc/rtc_screen.h): a sample with at most SCREEN_WAVE_CANDS eligible candidates takes one
+# wave, one with at most SCREEN_BLOCK_CANDS a 256-lane workgroup, both with the remaining counts in LDS; more: the counts in global
+# memory.  SCREEN_POS_BYTES a sample hash and SCREEN_MATCH_BYTES a match record are what a chunk is charged against RTC_SCREEN_BYTES.
+SCREEN_WAVE_CANDS = 512
+SCREEN_BLOCK_CANDS = 4096
+SCREEN_POS_BYTES = 40
+SCREEN_MATCH_BYTES = 72
+SCREEN_Q20 = 1 << 20  # containment 1 in rtc_rep_screen's min_cont_q20
 
 
 def _np_ptr(a):
@@ -700,6 +712,43 @@ class Context:
         self.check(self.lib.rtc_rep_topk_counters(self.h, a))
         names = ("chunks", "wave_queries", "workgroup_queries", "sort_queries", "candidates", "bytes_read", "join_ns",
                  "bucket_ns", "select_ns")
+        return {k: int(a[i]) for i, k in enumerate(names)}
+
+    def rep_screen(self, sk, n_reps, min_common=1, min_containment_q20=0, min_unique=1, max_picks=0, live=None, query_chunk=0):
+        """clust-mst --db --screen: sk holds the n_reps representatives, then the samples (KSSD sketches).  Containment of every
+        representative in every sample and the winner-takes-all decomposition of include/rtclust.h (rtc_rep_screen).
+        min_containment_q20: round(min_containment * SCREEN_Q20), 0 for no containment test.  live: n_reps flags (None: all live).
+        Returns (SCREEN_HIT_DT records sorted by query, picks first by rank, the rest by containment; SCREEN_SUM_DT, one per sample)."""
+        nq = sk.n - int(n_reps)
+        if nq < 0:
+            raise ValueError("n_reps exceeds the sketch set")
+        lv = None
+        if live is not None:
+            lv = np.ascontiguousarray(np.asarray(live, dtype=np.uint8))
+            if lv.shape != (int(n_reps),):
+                raise ValueError("live needs one flag per representative")
+        sums = np.zeros(max(nq, 1), dtype=SCREEN_SUM_DT)
+        cap = max(1024, 64 * max(nq, 1))
+        while True:
+            out = np.zeros(cap, dtype=SCREEN_HIT_DT)
+            n = C.c_uint64()
+            self.check(self.lib.rtc_rep_screen(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), int(n_reps), nq,
+                                               _np_ptr(lv) if lv is not None else None, int(min_common), int(min_containment_q20),
+                                               int(min_unique), int(max_picks), int(query_chunk), _np_ptr(out), cap, C.byref(n), _np_ptr(sums)))
+            if n.value <= cap:
+                return out[:n.value].copy(), sums[:nq].copy()
+            cap = int(n.value)
+
+    def rep_screen_last_path(self):
+        """rtc_rep_screen_last_path: SCREEN_PATH_WAVE | SCREEN_PATH_BLOCK | SCREEN_PATH_GLOBAL, the gather paths of the last rep_screen call"""
+        return int(self.lib.rtc_rep_screen_last_path(self.h))
+
+    def rep_screen_counters(self):
+        """rtc_rep_screen_counters as a dict (the last rep_screen call)."""
+        a = (C.c_uint64 * 12)()
+        self.check(self.lib.rtc_rep_screen_counters(self.h, a))
+        names = ("chunks", "matches", "candidates", "eligible", "picks", "rounds_max", "wave_queries", "workgroup_queries", "global_queries",
+                 "expand_ns", "gather_ns", "call_ns")
         return {k: int(a[i]) for i, k in enumerate(names)}
 
     def dbscan(self, sk, eps, min_pts, kmer_size, max_posting=0, return_core=False):
@@ -1505,6 +1554,11 @@ def graph_weights_mash(edges, sketch_size, kmer_size, return_weights=False):
 def snn_weight(shared, deg_u, deg_v):
     """rtc_snn_weight: (shared + 2) / (deg_u + deg_v - shared), the library's host function"""
     return float(_lib.load().rtc_snn_weight(int(shared), int(deg_u), int(deg_v)))
+
+
+def screen_identity(common, size, kmer_size):
+    """rtc_screen_identity: Mash's containment identity (common / size) ** (1 / kmer_size), the library's host function"""
+    return float(_lib.load().rtc_screen_identity(int(common), int(size), int(kmer_size)))
 
 
 def linkage_distance(common, denom, kmer_size):

@@ -114,6 +114,8 @@ void rtc_options_from_env(rtc_options* o) {
   if (const char* e = getenv("RTC_SUPPORT_BYTES")) o->support_bytes = std::max<uint64_t>(strtoull(e, nullptr, 10), 1);
   if (getenv("RTC_DEGREE_TAIL")) { o->has_degree_tail = true; o->degree_tail = (uint32_t)std::min<long long>(std::max<long long>(0, num("RTC_DEGREE_TAIL", 0)), 0x7fffffff); }
   o->degree_block = flag("RTC_DEGREE_BLOCK");
+  if (const char* e = getenv("RTC_SCREEN_BYTES")) o->screen_bytes = std::max<uint64_t>(strtoull(e, nullptr, 10), 1);
+  o->screen_global = flag("RTC_SCREEN_GLOBAL");
 }
 
 extern "C" {

@@ -52,6 +52,8 @@ struct rtc_options {
   bool has_degree_tail = false;
   uint32_t degree_tail = 0;        // RTC_DEGREE_TAIL: rtc_greedy_degree's selection goes to the one-workgroup kernel from this many open vertices down (0: never)
   int degree_block = 0;            // RTC_DEGREE_BLOCK: every row of rtc_greedy_degree's assignment takes the 256-lane path
+  uint64_t screen_bytes = 0;       // RTC_SCREEN_BYTES: the bytes a chunk of rtc_rep_screen's match records and views may take (0: half the free HBM)
+  int screen_global = 0;           // RTC_SCREEN_GLOBAL: every sample of rtc_rep_screen takes the long path (the counts in global memory)
 };
 void rtc_options_from_env(rtc_options* o);
 
@@ -128,6 +130,8 @@ struct rtc_ctx {
   uint64_t csupport[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_cluster_support_counters (include/rtclust.h lists them)
   uint64_t greedy_degree[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_greedy_degree_counters (include/rtclust.h lists them)
   int greedy_degree_path = 0;  // rtc_greedy_degree_last_path
+  uint64_t rep_screen[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_rep_screen_counters (include/rtclust.h lists them)
+  int rep_screen_path = 0;  // rtc_rep_screen_last_path
   int host_threads = 1;     // rtc_ctx_set_host_threads: the host side of rtc_tree_medoids and of rtc_nj_clusters', rtc_upgma_clusters' and rtc_cluster_quality's distances
   // rtc_diag_counters: [0] pair tiles the join took, [1] tiled-kernel tiles, [2] merge-kernel tiles, [3] candidate lists contracted
   // to their forest, [4] greedy runs replayed from ONE global join, [5] greedy query blocks of the block loop, [6] estimates handed
@@ -223,6 +227,7 @@ int rtc_msf_device(rtc_ctx* ctx, const rtc_cedge* d_edges, uint64_t m, const uin
                    uint64_t* n_sel_out, int* rounds_out, bool sorted = true, uint32_t max_len = 0);
 int rtc_sort_forest_device(rtc_ctx* ctx, rtc_cedge* d_sel, uint64_t ns, const uint32_t* d_len, int wmode);
 int rtc_sort_u32_pairs(rtc_ctx* ctx, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t n);
+int rtc_sort_u64_pairs(rtc_ctx* ctx, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t n);
 // rtc_graph.hip: the least Jaccard quotient whose distance through the host function is below threshold (rtc_graph_build's J*)
 double rtc_graph_jstar(double threshold, int kmer_size);
 uint32_t rtc_fixed_size_of(const uint32_t* h_len, uint32_t n);

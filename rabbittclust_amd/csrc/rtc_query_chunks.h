@@ -6,6 +6,7 @@
 //   query_segments    the candidates bucketed by query: tk_count_kernel, tk_scan_kernel and the sizes read back
 //   for_query_chunks  the loop over the chunks, which halves a chunk that came back with RTC_ERR_NOMEM
 // What is done with a candidate -- the scatter, and the fold, selection or sort behind it -- stays with each entry point.
+// rtc_rep_screen takes for_query_chunks alone: its join keeps the shared hashes, which these candidates have folded away.
 #pragma once
 #include "rtc_dbscan_common.h"
 #include "rtc_topk_select.h"

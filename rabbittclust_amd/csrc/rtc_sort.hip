@@ -91,3 +91,15 @@ int rtc_sort_u32_pairs(rtc_ctx* ctx, const uint32_t* keys_in, uint32_t* keys_out
   RTC_HIP(ctx, rocprim::radix_sort_pairs(tmp, tb, keys_in, keys_out, vals_in, vals_out, n, 0u, 32u, ctx->stream));
   return RTC_OK;
 }
+
+// The same for u64 keys, sorted on all 64 bits whatever the keys' range.  (rtc_rep_screen: the model index by hash, the match
+// records by (sample, slot).)
+int rtc_sort_u64_pairs(rtc_ctx* ctx, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t n) {
+  if (!n) return RTC_OK;
+  size_t tb = 0;
+  RTC_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tb, keys_in, keys_out, vals_in, vals_out, n, 0u, 64u, ctx->stream));
+  void* tmp = nullptr;
+  RTC_TRY(rtc_ws(ctx, 5, tb + 256, &tmp));
+  RTC_HIP(ctx, rocprim::radix_sort_pairs(tmp, tb, keys_in, keys_out, vals_in, vals_out, n, 0u, 64u, ctx->stream));
+  return RTC_OK;
+}

@@ -283,3 +283,34 @@ def support_report(names, cluster_of, records, together, replicates):
         fn(*args, buf, need)
         out.append(buf.raw[:need].decode())
     return tuple(out)
+
+
+def screen_report(names, rep_names, cluster_id, cluster_size, hits, sums, kmer_size):
+    """screen_report_text (rtc_host.cpp): the two reports of clust-mst --db --screen as (screen_tsv, summary_tsv).  names[q]: the
+    samples (an empty name prints as query_<q>); rep_names, cluster_id and cluster_size by slot; hits: api.SCREEN_HIT_DT sorted by
+    sample, in Context.rep_screen's order; sums: api.SCREEN_SUM_DT, one per sample."""
+    nq, nr = len(names), len(rep_names)
+    hit = np.ascontiguousarray(hits)
+    sm = np.ascontiguousarray(sums)
+    cid = np.ascontiguousarray(cluster_id, dtype=np.int32)
+    csz = np.ascontiguousarray(cluster_size, dtype=np.int32)
+    assert hit.dtype.itemsize == 24 and sm.dtype.itemsize == 24 and len(sm) == nq and len(cid) == len(csz) == nr
+    arr = (C.c_char_p * max(nq, 1))(*[s.encode() for s in names])
+    rarr = (C.c_char_p * max(nr, 1))(*[s.encode() for s in rep_names])
+    from . import _lib
+    idf = C.cast(_lib.load().rtc_screen_identity, C.c_void_p)
+    fn = load().rtch_screen_report
+    fn.restype = C.c_long
+    fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p,
+                   C.c_int, C.c_void_p, C.c_long]
+    out = []
+    for which in (0, 1):
+        args = (arr, nq, rarr, cid.ctypes.data_as(C.c_void_p), csz.ctypes.data_as(C.c_void_p), nr, hit.ctypes.data_as(C.c_void_p), len(hit),
+                sm.ctypes.data_as(C.c_void_p), int(kmer_size), idf, which)
+        need = fn(*args, None, 0)
+        if need < 0:
+            raise ValueError("a hit names a sample or a slot out of range, or the hits are not sorted by sample")
+        buf = C.create_string_buffer(max(int(need), 1))
+        fn(*args, buf, need)
+        out.append(buf.raw[:need].decode())
+    return tuple(out)

@@ -375,4 +375,21 @@ long rtch_support_report(const char* const* names, const int32_t* cluster_of, ui
   return (long)text.size();
 }
 
+// screen_report_text with the caller's identity function (rtc_screen_identity) over plain arrays: names[n_queries] (an empty name: query_<q>), rep_names / cluster_id / cluster_size by slot
+// (n_reps of each), hits sorted by sample, sums[n_queries].  which 0: the hit report, 1: the summary.  Returns -1 for a hit whose
+// sample or slot is out of range or out of order, else the text's length; the text itself when it fits cap (no terminator).
+long rtch_screen_report(const char* const* names, uint32_t n_queries, const char* const* rep_names, const int32_t* cluster_id,
+                        const int32_t* cluster_size, uint32_t n_reps, const rtc_screen_hit* hits, uint64_t n_hits, const rtc_screen_sum* sums,
+                        int kmer_size, double (*identity_fn)(uint32_t, uint32_t, int), int which, char* out, long cap) {
+  for (uint64_t h = 0; h < n_hits; h++)
+    if (hits[h].query >= n_queries || hits[h].slot >= n_reps || (h && hits[h].query < hits[h - 1].query)) return -1;
+  std::vector<std::string> nm(names, names + n_queries), rn(rep_names, rep_names + n_reps);
+  const std::vector<int> id(cluster_id, cluster_id + n_reps), sz(cluster_size, cluster_size + n_reps);
+  std::string a, b;
+  screen_report_text(nm, rn, id, sz, hits, (size_t)n_hits, sums, kmer_size, identity_fn, &a, &b);
+  const std::string& text = which ? b : a;
+  if (out && (long)text.size() <= cap) memcpy(out, text.data(), text.size());
+  return (long)text.size();
+}
+
 }

@@ -907,6 +907,10 @@ struct Options {
   bool has_clusterSupport = false, has_supportSeed = false;  // clust-mst --cluster-support B [--support-seed S]: jackknife support of the clusters themselves (rtc_cluster_support)
   long long clusterSupport = 0;
   uint64_t supportSeed = 0;
+  // clust-mst --fast --db FILE --screen: which clusters a sample contains (rtc_rep_screen)
+  bool db_screen = false;
+  string minContainment = "0.05", minShared = "2", minUnique = "2", screenPicks = "0";  // as spelled: the refusals read them
+  const char* screenOnly = nullptr;  // the first of --min-containment / --min-shared / --min-unique / --screen-picks, which only --screen gives a meaning
 };
 
 #ifdef LEIDEN_CLUST
@@ -1076,6 +1080,11 @@ static Options parse(int argc, char** argv) {
     else if (a == "--cluster-support") { o.clusterSupport = atoll(need(i)); o.has_clusterSupport = true; }
     else if (a == "--support-seed") { o.supportSeed = strtoull(need(i), nullptr, 10); o.has_supportSeed = true; }
     else if (a == "--upgma") o.upgma = true;
+    else if (a == "--screen") o.db_screen = true;
+    else if (a == "--min-containment") { o.minContainment = need(i); if (!o.screenOnly) o.screenOnly = "--min-containment"; }
+    else if (a == "--min-shared") { o.minShared = need(i); if (!o.screenOnly) o.screenOnly = "--min-shared"; }
+    else if (a == "--min-unique") { o.minUnique = need(i); if (!o.screenOnly) o.screenOnly = "--min-unique"; }
+    else if (a == "--screen-picks") { o.screenPicks = need(i); if (!o.screenOnly) o.screenOnly = "--screen-picks"; }
 #endif
     else if (a == "-h" || a == "--help") {
 #ifdef GREEDY_CLUST
@@ -1185,7 +1194,11 @@ static Options parse(int argc, char** argv) {
            "  --upgma (average linkage, UPGMA, inside every cluster of the run, in exact integers on the GPU: <output>.upgma, the\n"
            "             clusters cut at -d by mean distance; <output>.upgma.linkage.txt, every merge; <output>.upgma.newick, one\n"
            "             ultrametric tree a line in the order of <output>; with --fast or MinHash on the index path)\n"
-           "  [--fast] --db FILE --build|--query|--assign|--append LIST|--stats [--top-k N] (MST representative database)"
+           "  [--fast] --db FILE --build|--query|--assign|--append LIST|--stats [--top-k N] (MST representative database)\n"
+           "  --fast --db FILE --screen -i SAMPLES [--min-containment C] [--min-shared N] [--min-unique N] [--screen-picks N] (which\n"
+           "             clusters a mixture holds: the containment of every representative in every sample and a winner-takes-all\n"
+           "             decomposition of the sample, on the GPU; <output>, a line a hit, and <output>.summary.tsv, a line a sample;\n"
+           "             defaults 0.05, 2, 2 and 0 = no limit; KSSD databases only)"
 #else
            "  --append LIST (with --presketched DIR)  --save-rep (cluster_state.bin beside the sketches)\n"
            "  --order degree (clusters that do not depend on the order of the genomes: two genomes are neighbours when they are\n"
@@ -1797,6 +1810,84 @@ static int mst_db_search(const Options& o, vector<Gpu>& gpus) {
     if (!write_mst_query_tsv(o.outputFile, st, names, hits, per)) return 1;
     cerr << "===== Query Results =====" << endl << "  Output: " << o.outputFile << endl << "=========================" << endl;
   }
+  return 0;
+}
+
+// clust-mst --fast --db FILE --screen: the samples (-l LIST, or the records of one FASTA file, named query_<i>) sketched with the
+// database's parameters as --query sketches them, rtc_rep_screen on the first GPU with one retry at the reported size, the two
+// reports.  The checks of main() have been through the flags: min_containment in [0, 1], the counts at least 1.
+static int mst_db_screen(const Options& o, vector<Gpu>& gpus) {
+  rtc_ctx* ctx = gpus[0].ctx;
+  MstState st;
+  if (!load_mst_state(o.repdb_path, true, st)) { cerr << "ERROR: failed to load MST RepDB from: " << o.repdb_path << endl; return 1; }
+  SketchJob job;
+  job.kssd = true; job.minLen = o.minLen; job.threads = o.threads;
+  job.kmerSize = st.kmer_size > 0 ? st.kmer_size : st.half_k * 2; job.drlevel = st.drlevel;
+  const double t0 = get_sec();
+  vector<GenomeInfo> q; MinHashSketchFile mh; KssdSketchFile ks; Resident rs;
+  if (o.sketchByFile) sketch_files(gpus, o.inputFile, job, q, &mh, &ks, rs, true);
+  else {
+    vector<FastaRecord> recs; SeqModeSizes sz;
+    if (!read_sequences(o.inputFile, o.minLen, recs, sz)) return 1;
+    sketch_sequences(gpus, recs, job, q, &mh, &ks);
+  }
+  const double t1 = get_sec();
+  g_metrics.num("sketch_queries_s", t1 - t0);
+  if (!q.empty() && ks.use64 != st.use64) {
+    cerr << "ERROR: the query sketches have use64=" << ks.use64 << " but the MST RepDB has use64=" << st.use64 << " (different hash width)" << endl;
+    return 1;
+  }
+  vector<string> names;
+  for (size_t i = 0; i < q.size(); i++) names.push_back(o.sketchByFile ? q[i].fileName : string());  // single FASTA: fileName is empty
+  const uint32_t R = (uint32_t)st.reps(), Q = (uint32_t)q.size();
+  const double min_cont = atof(o.minContainment.c_str());
+  const uint32_t min_cont_q20 = (uint32_t)llround(min_cont * 1048576.0);
+  const uint32_t min_shared = (uint32_t)std::min<long long>(atoll(o.minShared.c_str()), 0x7fffffff);
+  const uint32_t min_unique = (uint32_t)std::min<long long>(atoll(o.minUnique.c_str()), 0x7fffffff);
+  const uint32_t picks = (uint32_t)std::min<long long>(std::max<long long>(atoll(o.screenPicks.c_str()), 0), 0x7fffffff);
+  cerr << "===== MST RepDB Screen (KSSD) =====" << endl << "  Samples:          " << Q << endl << "  DB reps:          " << R << endl
+       << "  Min containment:  " << min_cont << endl << "  Min shared:       " << min_shared << endl << "  Min unique:       " << min_unique << endl;
+  vector<rtc_screen_hit> hits;
+  vector<rtc_screen_sum> sums(Q);
+  for (uint32_t i = 0; i < Q; i++) sums[i] = rtc_screen_sum{(uint32_t)(st.use64 ? ks.h64[i].size() : ks.h32[i].size()), 0, 0, 0, 0, 0};
+  uint64_t cnt[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (Q && R) {
+    vector<uint8_t> live(R);
+    for (uint32_t r = 0; r < R; r++) live[r] = st.clusters[r].empty() ? 0 : 1;
+    DeviceSketches ds;
+    if (st.use64) {
+      vector<vector<uint64_t>> all(st.h64);
+      all.insert(all.end(), ks.h64.begin(), ks.h64.end());
+      upload_sketches(ctx, &all, nullptr, ds);
+    } else {
+      vector<vector<uint32_t>> all(st.h32);
+      all.insert(all.end(), ks.h32.begin(), ks.h32.end());
+      upload_sketches(ctx, nullptr, &all, ds);
+    }
+    uint64_t nh = 0;
+    hits.resize((size_t)Q * 64);
+    CHECK(ctx, rtc_rep_screen(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, R, Q, live.data(), min_shared, min_cont_q20, min_unique, picks, 0,
+                              hits.data(), hits.size(), &nh, sums.data()));
+    if (nh > hits.size()) {
+      hits.resize(nh);
+      CHECK(ctx, rtc_rep_screen(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, R, Q, live.data(), min_shared, min_cont_q20, min_unique, picks, 0,
+                                hits.data(), hits.size(), &nh, sums.data()));
+    }
+    hits.resize(nh);
+    CHECK(ctx, rtc_rep_screen_counters(ctx, cnt));
+    (void)rtc_dev_free(ctx, ds.d_hashes); (void)rtc_dev_free(ctx, ds.d_start); (void)rtc_dev_free(ctx, ds.d_len);
+  }
+  const double t2 = get_sec();
+  g_metrics.num("rep_screen_s", t2 - t1);
+  g_metrics.num("screen_hits", (double)hits.size());
+  g_metrics.num("screen_picks", (double)cnt[4]);
+  g_metrics.num("screen_rounds_max", (double)cnt[5]);
+  cerr << "========time of rep screen (GPU) is: " << t2 - t1 << "========" << endl;
+  const string f_sum = o.outputFile + ".summary.tsv";
+  if (!write_mst_screen_tsv(o.outputFile, st, names, hits, sums, rtc_screen_identity)) return 1;
+  if (!write_mst_screen_summary_tsv(f_sum, st, names, hits, sums)) return 1;
+  cerr << "===== Screen Results =====" << endl << "  Hits:    " << hits.size() << endl << "  Picks:   " << cnt[4] << endl << "  Output:  " << o.outputFile << endl
+       << "  Summary: " << f_sum << endl << "==========================" << endl;
   return 0;
 }
 
@@ -3143,6 +3234,19 @@ int main(int argc, char** argv) {
   const bool db_action = o.db_build || o.db_query || o.db_assign || o.db_stats;
   if (db_action && o.repdb_path.empty()) { cerr << "ERROR: --build / --query / --assign / --stats require --db" << endl; return 1; }
   if ((int)o.db_build + (int)o.db_query + (int)o.db_assign + (int)o.db_stats > 1) { cerr << "ERROR: --build, --query, --assign and --stats exclude each other" << endl; return 1; }
+  // ---- --screen: what it needs and does not go with, before any GPU is asked for and before --stats prints ----
+  if (o.db_screen) {
+    if (o.repdb_path.empty()) { cerr << "ERROR: --screen requires --db" << endl; return 1; }
+    if (!o.is_fast) { cerr << "ERROR: --screen needs --fast (a KSSD database)" << endl; return 1; }
+    const char* bad = o.db_build ? "--build" : o.db_query ? "--query" : o.db_assign ? "--assign" : o.db_stats ? "--stats" : o.has_append ? "--append" : nullptr;
+    if (bad) { cerr << "ERROR: --screen does not go with " << bad << endl; return 1; }
+    if (!o.has_input) { cerr << "ERROR: --screen requires -i <input_file>" << endl; return 1; }
+    char* end = nullptr;
+    const double c = strtod(o.minContainment.c_str(), &end);
+    if (o.minContainment.empty() || *end != 0 || !(c >= 0.0 && c <= 1.0)) { cerr << "ERROR: --min-containment must be in [0, 1]" << endl; return 1; }
+    if (atoll(o.minShared.c_str()) < 1) { cerr << "ERROR: --min-shared must be at least 1" << endl; return 1; }
+    if (atoll(o.minUnique.c_str()) < 1) { cerr << "ERROR: --min-unique must be at least 1" << endl; return 1; }
+  } else if (o.screenOnly) { cerr << "ERROR: " << o.screenOnly << " needs --screen" << endl; return 1; }
   if (!o.repdb_path.empty()) {
     if (o.db_stats) {  // mst_repdb_stats[_fast]: before any GPU context
       MstState st;
@@ -3154,7 +3258,7 @@ int main(int argc, char** argv) {
     if (o.db_build && !o.has_presketched && !o.has_input) { cerr << "ERROR: --build requires --presketched <folder> or -i <genome_list> -l" << endl; return 1; }
     if (o.db_query && !o.has_input) { cerr << "ERROR: --query requires -i <input_file>" << endl; return 1; }
     if (o.db_assign && !o.has_input) { cerr << "ERROR: --assign requires -i <input_file>" << endl; return 1; }
-    if (!db_action && !o.has_append) { cerr << "ERROR: --db requires one of: --build, --query, --assign, --append, --stats" << endl; return 1; }
+    if (!db_action && !o.has_append && !o.db_screen) { cerr << "ERROR: --db requires one of: --build, --query, --assign, --append, --stats" << endl; return 1; }
     if (o.db_build && !o.has_presketched && !o.sketchByFile) unsupported("single-FASTA input (run with -l and a genome list)");
     // the tree writers, --dense and the post-processing flags have no effect here; the build keeps no sketch folder
     // (isSave = false) and takes -k or 21, -s or 1000, without the tuner
@@ -3293,7 +3397,7 @@ int main(int argc, char** argv) {
   Resident rs;
 #if !defined(GREEDY_CLUST) && !defined(DBSCAN_CLUST)
   if (!o.repdb_path.empty() && !o.db_build) {  // --build goes on through the MST flow below
-    const int rc = (o.db_query || o.db_assign) ? mst_db_search(o, gpus) : mst_db_append(o, gpus);
+    const int rc = o.db_screen ? mst_db_screen(o, gpus) : (o.db_query || o.db_assign) ? mst_db_search(o, gpus) : mst_db_append(o, gpus);
     g_metrics.str("command", "clust-mst");
     g_metrics.str("sketch", o.is_fast ? "kssd" : "minhash");
     g_metrics.write();

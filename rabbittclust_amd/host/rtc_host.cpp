@@ -2940,6 +2940,62 @@ bool write_mst_assign_tsv(const std::string& path, const MstState& st, const std
   return true;
 }
 
+void screen_report_text(const std::vector<std::string>& names, const std::vector<std::string>& rep_names, const std::vector<int>& cluster_id,
+                        const std::vector<int>& cluster_size, const rtc_screen_hit* hits, size_t n_hits, const rtc_screen_sum* sums, int kmer_size,
+                        double (*identity_fn)(uint32_t, uint32_t, int), std::string* tsv, std::string* summary) {
+  char buf[256];
+  if (tsv) *tsv = "#sample\trank\tcluster_id\trep_name\tcluster_size\tshared\trep_hashes\tcontainment\tidentity\tunique\tunique_share\n";
+  if (summary) *summary = "#sample\thashes\tmatched\texplained\thits\tpicks\tunexplained_share\n";
+  size_t h = 0;
+  for (size_t q = 0; q < names.size(); q++) {
+    const std::string name = mst_query_name(names, q);
+    const rtc_screen_sum& s = sums[q];
+    const size_t h0 = h;
+    for (; h < n_hits && hits[h].query == q; h++) {
+      if (!tsv) continue;
+      const rtc_screen_hit& x = hits[h];
+      *tsv += name + "\t" + (x.rank ? std::to_string(x.rank) : std::string("-")) + "\t" + std::to_string(cluster_id[x.slot]) + "\t" +
+              rep_names[x.slot];
+      snprintf(buf, sizeof buf, "\t%d\t%u\t%u\t%.6f\t%.6f\t%u\t%.6f\n", cluster_size[x.slot], x.common, x.size,
+               x.size ? (double)x.common / (double)x.size : 0.0, identity_fn(x.common, x.size, kmer_size), x.unique,
+               s.n_hashes ? (double)x.unique / (double)s.n_hashes : 0.0);
+      *tsv += buf;
+    }
+    if (tsv && h == h0) *tsv += name + "\t0\t-1\tno_match\t0\t0\t0\t0.000000\t0.000000\t0\t0.000000\n";
+    if (summary) {
+      snprintf(buf, sizeof buf, "\t%u\t%u\t%u\t%u\t%u\t", s.n_hashes, s.n_matched, s.n_explained, s.n_hits, s.n_picks);
+      *summary += name + buf;
+      if (s.n_hashes) { snprintf(buf, sizeof buf, "%.6f\n", (double)(s.n_hashes - s.n_explained) / (double)s.n_hashes); *summary += buf; }
+      else *summary += "-\n";
+    }
+  }
+}
+
+static bool write_mst_screen_file(const std::string& path, const MstState& st, const std::vector<std::string>& names,
+                                  const std::vector<rtc_screen_hit>& hits, const std::vector<rtc_screen_sum>& sums,
+                                  double (*identity_fn)(uint32_t, uint32_t, int), bool summary) {
+  const std::vector<int> live = mst_live_index(st);
+  std::vector<int> size(st.clusters.size());
+  for (size_t r = 0; r < st.clusters.size(); r++) size[r] = (int)st.clusters[r].size();
+  std::string text;
+  screen_report_text(names, st.rep_names, live, size, hits.data(), hits.size(), sums.data(), st.kmer_size, identity_fn, summary ? nullptr : &text,
+                     summary ? &text : nullptr);
+  FILE* fp = fopen(path.c_str(), "w");
+  if (!fp) { std::cerr << "ERROR: cannot open output file: " << path << std::endl; return false; }
+  fwrite(text.data(), 1, text.size(), fp);
+  fclose(fp);
+  return true;
+}
+bool write_mst_screen_tsv(const std::string& path, const MstState& st, const std::vector<std::string>& names,
+                          const std::vector<rtc_screen_hit>& hits, const std::vector<rtc_screen_sum>& sums,
+                          double (*identity_fn)(uint32_t, uint32_t, int)) {
+  return write_mst_screen_file(path, st, names, hits, sums, identity_fn, false);
+}
+bool write_mst_screen_summary_tsv(const std::string& path, const MstState& st, const std::vector<std::string>& names,
+                                  const std::vector<rtc_screen_hit>& hits, const std::vector<rtc_screen_sum>& sums) {
+  return write_mst_screen_file(path, st, names, hits, sums, nullptr, true);
+}
+
 void print_mst_state_clusters(const std::vector<std::vector<int>>& clusters, const std::vector<std::string>& member_names,
                               const std::vector<uint64_t>& member_lens, bool sketch_by_file, const std::string& output_file,
                               double threshold) {

@@ -337,6 +337,21 @@ bool write_mst_query_tsv(const std::string& path, const MstState& st, const std:
                          const std::vector<rtc_rep_hit>& hits, const std::vector<uint32_t>& per_query);
 bool write_mst_assign_tsv(const std::string& path, const MstState& st, const std::vector<std::string>& qnames,
                           const std::vector<rtc_rep_hit>& hits, const std::vector<uint32_t>& per_query, int* n_assigned);
+// clust-mst --db --screen: the two reports from rtc_rep_screen's hits (sorted by sample, then in the library's order) and sums.
+// names[q]: the sample (empty: query_<q>, as the --query TSV names it); rep_names / cluster_id / cluster_size by slot, what
+// write_mst_query_tsv prints (cluster_id: mst_live_index).  *tsv: #sample rank cluster_id rep_name cluster_size shared rep_hashes
+// containment identity unique unique_share, a line a hit, rank "-" for a hit that was not picked, one no_match line for a sample
+// without a hit; *summary: #sample hashes matched explained hits picks unexplained_share ("-" for a sample without a hash).
+// identity_fn is rtc_screen_identity; this library does not link the GPU library.
+void screen_report_text(const std::vector<std::string>& names, const std::vector<std::string>& rep_names, const std::vector<int>& cluster_id,
+                        const std::vector<int>& cluster_size, const rtc_screen_hit* hits, size_t n_hits, const rtc_screen_sum* sums, int kmer_size,
+                        double (*identity_fn)(uint32_t, uint32_t, int), std::string* tsv, std::string* summary);
+// the two files, <path> and <path>.summary.tsv; false if one does not open
+bool write_mst_screen_tsv(const std::string& path, const MstState& st, const std::vector<std::string>& names,
+                          const std::vector<rtc_screen_hit>& hits, const std::vector<rtc_screen_sum>& sums,
+                          double (*identity_fn)(uint32_t, uint32_t, int));
+bool write_mst_screen_summary_tsv(const std::string& path, const MstState& st, const std::vector<std::string>& names,
+                                  const std::vector<rtc_screen_hit>& hits, const std::vector<rtc_screen_sum>& sums);
 
 // clust-dbscan --db FILE: a clustered sketch set that new genomes can be placed into (rtc_dbscan_assign).  One binary file,
 // little-endian, INTEGRATION.md section 6 lists it byte by byte.  Written to FILE.tmp and renamed.
