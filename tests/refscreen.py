@@ -13,7 +13,9 @@ def screen(reps, queries, min_common=1, min_cont_q20=0, min_unique=1, max_picks=
              first, compared by cross-multiplication, equal ratios to the lower slot
     sums[q]  (n_hashes, n_matched, n_explained, n_hits, n_picks)
     info[q]  dict: rounds (picks made), ties (the picks decided between equal counts by the lower slot), expansion (the most
-             live representatives one hash of the sample lies in), matches (its match records)"""
+             live representatives one hash of the sample lies in), matches (its match records), widest_pick (the largest
+             common of a pick), holders_max (the most eligible candidates that hold one matched hash), last_index_picks (the
+             ranks won by the highest eligible slot)"""
     assert min_unique >= 1 and 0 <= min_cont_q20 <= Q20
     sizes = [len(r) for r in reps]
     index = {}
@@ -46,6 +48,9 @@ def screen(reps, queries, min_common=1, min_cont_q20=0, min_unique=1, max_picks=
         rank = [0] * len(elig)
         unique = [0] * len(elig)
         ties = []
+        last_index_picks = []
+        widest_pick = 0
+        holders_max = max((len(c) for c in holders.values()), default=0)
         t = 0
         limit = min(max_picks, len(elig)) if max_picks else len(elig)
         while t < limit:
@@ -58,6 +63,9 @@ def screen(reps, queries, min_common=1, min_cont_q20=0, min_unique=1, max_picks=
             if len(tied) > 1:
                 ties.append(t)
             rank[w], unique[w] = t, best
+            widest_pick = max(widest_pick, len(shared[elig[w]]))
+            if w == len(elig) - 1:
+                last_index_picks.append(t)
             for h in shared[elig[w]]:
                 if h in alive:
                     alive.discard(h)
@@ -72,7 +80,8 @@ def screen(reps, queries, min_common=1, min_cont_q20=0, min_unique=1, max_picks=
         rest = sorted((r for r in recs if not r[4]), key=_ratio_key)
         hits.append(picks + rest)
         sums.append((len(xs), n_matched, n_matched - len(alive), len(recs), len(picks)))
-        info.append({"rounds": t, "ties": ties, "expansion": expansion, "matches": matches})
+        info.append({"rounds": t, "ties": ties, "expansion": expansion, "matches": matches, "widest_pick": widest_pick,
+                     "holders_max": holders_max, "last_index_picks": last_index_picks})
     return hits, sums, info
 
 
