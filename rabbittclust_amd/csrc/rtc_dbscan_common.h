@@ -1,7 +1,7 @@
 // rtc_dbscan_common.h -- the parts of the one DBSCAN implementation (rtc_dbscan_sweep.hip, with rtc_dbscan_hier.h) that do not
 // depend on what a call asks for: the neighbour predicate and its refusals, the filter kernels' predicate block and wave
-// append, the growing device list a filter appends to, the --max-posting pruning, the scratch holder and the row-chunk loop of
-// the pair phase.  Every unit that evaluates eps_pred is built with -ffp-contract=off.
+// append, the growing device list a filter appends to, the --max-posting pruning and the row-chunk loop of the pair
+// phase (the scratch holder, DevBuf, is rtc_internal.h's).  Every unit that evaluates eps_pred is built with -ffp-contract=off.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -126,29 +126,6 @@ __global__ __launch_bounds__(256) void posting_rows_kernel(const uint64_t* __res
     nlen[g] = (uint32_t)(b - a);
   }
 }
-
-struct DevBuf {  // hipMalloc'd scratch released on every way out; the context's free-memory figure stays current, as with rtc_dev_alloc / rtc_dev_free
-  rtc_ctx* ctx = nullptr;
-  std::vector<void*> p;
-  ~DevBuf() {
-    for (void* q : p) (void)hipFree(q);
-    if (ctx) ctx->free_hbm_at = -1.0;
-  }
-  template <class T> int get(rtc_ctx* c, size_t count, T** out) {
-    void* q = nullptr;
-    const hipError_t e = hipMalloc(&q, std::max<size_t>(count * sizeof(T), 256));
-    if (e != hipSuccess) return rtc_fail(c, RTC_ERR_NOMEM, "device scratch: %zu bytes: %s", count * sizeof(T), hipGetErrorString(e));
-    p.push_back(q);
-    ctx = c;
-    ctx->free_hbm_at = -1.0;
-    *out = (T*)q;
-    return RTC_OK;
-  }
-  void release(void* q) {
-    for (auto& x : p) if (x == q) { (void)hipFree(x); x = nullptr; }
-    if (ctx) ctx->free_hbm_at = -1.0;
-  }
-};
 
 // A device list of pairs that a filter kernel appends to chunk by chunk, and what the filter has found so far.  R: the record
 // (rtc_cedge everywhere but in rtc_graph_build_mash, whose 16-byte record carries the truncated denom beside the common).

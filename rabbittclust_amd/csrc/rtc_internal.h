@@ -6,7 +6,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 
+#include <algorithm>
 #include <functional>
 #include <string>
 #include <vector>
@@ -191,6 +193,36 @@ int rtc_check_runs_async(rtc_ctx* ctx, const uint64_t* d_runs, uint64_t n_runs, 
 int rtc_sticky_error(rtc_ctx* ctx);
 uint64_t rtc_free_hbm(rtc_ctx* ctx);
 
+// the host's monotonic clock, for the phase times of the counters
+static inline uint64_t rtc_now_ns() {
+  timespec ts;
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
+}
+
+struct DevBuf {  // hipMalloc'd scratch released on every way out; the context's free-memory figure stays current, as with rtc_dev_alloc / rtc_dev_free
+  rtc_ctx* ctx = nullptr;
+  std::vector<void*> p;
+  ~DevBuf() {
+    for (void* q : p) (void)hipFree(q);
+    if (ctx) ctx->free_hbm_at = -1.0;
+  }
+  template <class T> int get(rtc_ctx* c, size_t count, T** out) {
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, std::max<size_t>(count * sizeof(T), 256));
+    if (e != hipSuccess) { (void)hipGetLastError(); return rtc_fail(c, RTC_ERR_NOMEM, "device scratch: %zu bytes: %s", count * sizeof(T), hipGetErrorString(e)); }
+    p.push_back(q);
+    ctx = c;
+    ctx->free_hbm_at = -1.0;
+    *out = (T*)q;
+    return RTC_OK;
+  }
+  void release(void* q) {
+    for (auto& x : p) if (x == q) { (void)hipFree(x); x = nullptr; }
+    if (ctx) ctx->free_hbm_at = -1.0;
+  }
+};
+
 // ---- internal C++ interfaces shared by the translation units ----------------------------------
 // all-reduce of a per-round key array across the ranks of a multi-GPU run (rtc_comm.hip);
 // dtype 0 = int64, 1 = uint32, 2 = uint64; op 0 = MIN, 1 = MAX
@@ -264,7 +296,37 @@ struct rtc_kb_batch {
 int rtc_key_blocks(rtc_ctx* ctx, const char* who, uint64_t budget_opt, const void* d_hashes, int width, const uint64_t* d_start,
                    const uint32_t* d_len, uint32_t n, const uint32_t* h_comp, uint64_t* h_first,
                    const std::function<int(const rtc_kb_batch&)>& on_batch, uint32_t spare_copies = 0);
+// How an on_batch hands its records over: those of the batch's components in component order behind *total, local indices
+// turned into genome indices, h_first kept.  n_of(i, comp): the records comps[i] has at recs[comp.merge_off ..), and where the
+// caller counts the component.  Once a component does not fit under cap, *overflow is up, nothing more is written and *total
+// goes on counting.
+template <class Rec> inline void rtc_kb_to_genomes(Rec& r, const uint32_t* g) { r.a = g[r.a]; r.b = g[r.b]; }
+inline void rtc_kb_to_genomes(rtc_njoin& r, const uint32_t* g) { r.a = g[r.a]; r.b = g[r.b]; if (r.c != 0xFFFFFFFFu) r.c = g[r.c]; }
+template <class Rec, class NOf>
+void rtc_kb_remap(const rtc_kb_batch& b, const std::vector<Rec>& recs, NOf n_of, Rec* h_out, uint64_t cap, uint64_t* h_first, uint64_t* total,
+                  bool* overflow) {
+  const std::vector<uint32_t>&csize = *b.csize, &cfirst = *b.cfirst, &perm = *b.perm;
+  size_t i = 0;
+  for (size_t q = b.c; q < b.ce; q++) {
+    if (csize[q] >= 2) {
+      const rtc_kb_comp& cp = (*b.comps)[i];
+      const uint64_t nr = n_of(i, cp);
+      if (*total + nr > cap) *overflow = true;
+      if (!*overflow)
+        for (uint64_t e = 0; e < nr; e++) {
+          Rec r = recs[cp.merge_off + e];
+          rtc_kb_to_genomes(r, perm.data() + cfirst[q]);
+          h_out[*total + e] = r;
+        }
+      *total += nr;
+      i++;
+    }
+    h_first[q + 1] = *total;
+  }
+}
 
+// the records of a neighbour-joining tree of m points
+static inline uint64_t rtc_nj_records_of(uint32_t m) { return m >= 3 ? m - 2 : m == 2 ? 1 : 0; }
 // rtc_nj.hip, for rtc_nj_support.hip.  rtc_nj_join: the records of comps[0 .. nc) (each m >= 2) over the matrices in d_dist, laid
 // out by merge_off, which it sets; n_path[3]: the components of each path.  rtc_nj_clusters_impl is rtc_nj_clusters with a hook that sees every batch of two or more after its trees are joined: the
 // batch (blocks overwritten), the components, their records with local indices, the records before the batch.

@@ -10,8 +10,6 @@
 // Both run a component's whole dendrogram in one launch.  A retired cluster's entries are overwritten with the key 0 / 0, whose
 // kappa is 0 and which no row-best ever takes, so a scan needs no list of the live clusters; the workgroup path keeps the member
 // count of cluster x in the diagonal entry (x, x) as {size, 0} -- kappa 0 as well.
-#include <time.h>
-
 #include <algorithm>
 #include <numeric>
 #include <vector>
@@ -250,28 +248,6 @@ __global__ __launch_bounds__(256) void lk_gather_kernel(const uint64_t* __restri
   p_len[i] = len[g];
 }
 
-uint64_t lk_now_ns() {
-  timespec ts;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
-}
-
-// device buffers of one call, released on every way out
-struct lk_bufs {
-  std::vector<void*> p;
-  ~lk_bufs() { for (void* q : p) (void)hipFree(q); }
-  int get(rtc_ctx* ctx, size_t bytes, void** out) {
-    ctx->free_hbm_at = -1.0;
-    hipError_t e = hipMalloc(out, bytes ? bytes : 16);
-    if (e != hipSuccess) { (void)hipGetLastError(); return rtc_fail(ctx, RTC_ERR_NOMEM, "rtc_linkage: hipMalloc(%zu): %s", bytes, hipGetErrorString(e)); }
-    p.push_back(*out);
-    return RTC_OK;
-  }
-  void drop(void* q) {
-    for (size_t i = 0; i < p.size(); i++) if (p[i] == q) { (void)hipFree(q); p.erase(p.begin() + i); return; }
-  }
-};
-
 // Agglomerates comps[0 .. nc) over the blocks in d_keys: one launch per path, then the merge lists and counts come back.
 // h_merges_out: sum(m - 1) records, laid out by merge_off; h_nm / h_nres: per component.
 int lk_agglomerate(rtc_ctx* ctx, rtc_lkey* d_keys, std::vector<lk_comp>& comps, uint32_t knum, uint32_t kden, std::vector<rtc_lmerge>& h_merges_out,
@@ -296,14 +272,14 @@ int lk_agglomerate(rtc_ctx* ctx, rtc_lkey* d_keys, std::vector<lk_comp>& comps, 
     else { c.scratch_off = n_scratch; n_scratch += (uint64_t)3 * c.m + (c.m & 1); }
     sorted[s] = c;
   }
-  lk_bufs B;
+  DevBuf B;
   lk_comp* d_comps = nullptr;
   rtc_lmerge* d_merges = nullptr;
   uint32_t *d_cnt = nullptr, *d_scratch = nullptr;
-  RTC_TRY(B.get(ctx, nc * sizeof(lk_comp), (void**)&d_comps));
-  RTC_TRY(B.get(ctx, n_rec * sizeof(rtc_lmerge), (void**)&d_merges));
-  RTC_TRY(B.get(ctx, nc * 8, (void**)&d_cnt));
-  RTC_TRY(B.get(ctx, n_scratch * 4, (void**)&d_scratch));
+  RTC_TRY(B.get(ctx, nc, &d_comps));
+  RTC_TRY(B.get(ctx, n_rec, &d_merges));
+  RTC_TRY(B.get(ctx, 2 * nc, &d_cnt));
+  RTC_TRY(B.get(ctx, n_scratch, &d_scratch));
   RTC_HIP(ctx, hipMemcpyAsync(d_comps, sorted.data(), nc * sizeof(lk_comp), hipMemcpyHostToDevice, ctx->stream));
   RTC_HIP(ctx, hipMemsetAsync(d_cnt, 0, nc * 8, ctx->stream));
   uint32_t* d_nm = d_cnt;
@@ -358,7 +334,7 @@ extern "C" int rtc_linkage_dev(rtc_ctx* ctx, uint32_t m, rtc_lkey* d_key, uint64
   if (((uintptr_t)d_key & 7) != 0) return rtc_fail(ctx, RTC_ERR_ARG, "rtc_linkage_dev: d_key must be 8-byte aligned");
   if (ld < m) return rtc_fail(ctx, RTC_ERR_ARG, "rtc_linkage_dev: ld smaller than m");
   RTC_HIP(ctx, hipSetDevice(ctx->device));
-  const uint64_t t0 = lk_now_ns();
+  const uint64_t t0 = rtc_now_ns();
   std::vector<lk_comp> comps(1);
   comps[0] = lk_comp{0, ld, 0, 0, m, 0};
   std::vector<rtc_lmerge> mg;
@@ -366,7 +342,7 @@ extern "C" int rtc_linkage_dev(rtc_ctx* ctx, uint32_t m, rtc_lkey* d_key, uint64
   RTC_TRY(lk_agglomerate(ctx, d_key, comps, kmin_num, kmin_den, mg, nm, nres));
   if (nm[0]) memcpy(h_merges, mg.data(), (size_t)nm[0] * sizeof(rtc_lmerge));
   *h_n_merges = nm[0];
-  const uint64_t t1 = lk_now_ns();
+  const uint64_t t1 = rtc_now_ns();
   uint64_t* C = ctx->linkage;
   C[0] = 1; C[1] = m <= LK_WAVE_MAX; C[2] = m > LK_WAVE_MAX; C[3] = nm[0]; C[4] = nres[0]; C[5] = 1; C[7] = t1 - t0; C[8] = m; C[9] = t1 - t0;
   return RTC_OK;
@@ -410,14 +386,14 @@ int rtc_key_blocks(rtc_ctx* ctx, const char* who, uint64_t budget_opt, const voi
   if (np == 0) return RTC_OK;
   if (!d_hashes) return RTC_ERR_ARG;
 
-  lk_bufs B;
+  DevBuf B;
   uint32_t *d_perm = nullptr, *p_len = nullptr;
   uint64_t* p_start = nullptr;
   lk_row* d_rows = nullptr;
-  RTC_TRY(B.get(ctx, (size_t)np * 4, (void**)&d_perm));
-  RTC_TRY(B.get(ctx, (size_t)np * 8, (void**)&p_start));
-  RTC_TRY(B.get(ctx, (size_t)np * 4, (void**)&p_len));
-  RTC_TRY(B.get(ctx, (size_t)np * sizeof(lk_row), (void**)&d_rows));
+  RTC_TRY(B.get(ctx, np, &d_perm));
+  RTC_TRY(B.get(ctx, np, &p_start));
+  RTC_TRY(B.get(ctx, np, &p_len));
+  RTC_TRY(B.get(ctx, np, &d_rows));
   RTC_HIP(ctx, hipMemcpyAsync(d_perm, perm.data(), (size_t)np * 4, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(lk_gather_kernel, dim3((np + 255) / 256), dim3(256), 0, ctx->stream, d_start, d_len, (const uint32_t*)d_perm, np, p_start, p_len);
   RTC_CHECK_LAUNCH(ctx);
@@ -463,10 +439,10 @@ int rtc_key_blocks(rtc_ctx* ctx, const char* who, uint64_t budget_opt, const voi
       ce++;
     }
     const uint64_t temp_cap = std::max(band, std::min<uint64_t>(LK_BAND_BYTES, budget - kb));
-    const uint64_t tf0 = lk_now_ns();
+    const uint64_t tf0 = rtc_now_ns();
     rtc_lkey* d_keys = nullptr;
     uint32_t* d_tmp = nullptr;
-    RTC_TRY(B.get(ctx, kb, (void**)&d_keys));
+    RTC_TRY(B.get(ctx, kb / sizeof(rtc_lkey), &d_keys));
     std::vector<size_t> comp_of;  // comps[i] is component comp_of[i]
     {
       uint64_t off = 0;
@@ -502,7 +478,7 @@ int rtc_key_blocks(rtc_ctx* ctx, const char* who, uint64_t budget_opt, const voi
       }
     }
     for (const band_t& b : bands) tmp_bytes = std::max<uint64_t>(tmp_bytes, 4ull * (b.r1 - b.r0) * (b.r1 - b.c0));
-    RTC_TRY(B.get(ctx, tmp_bytes, (void**)&d_tmp));
+    RTC_TRY(B.get(ctx, tmp_bytes / 4, &d_tmp));
     for (const band_t& b : bands) {
       const uint32_t ldc = b.r1 - b.c0;
       // the band is handed over as a set of its own, so the tiled kernel's plan covers its sketches only; RTC_PAIR_FORCE_MERGE:
@@ -514,10 +490,10 @@ int rtc_key_blocks(rtc_ctx* ctx, const char* who, uint64_t budget_opt, const voi
       RTC_CHECK_LAUNCH(ctx);
     }
     RTC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    batch.d_keys = d_keys; batch.n_keys = kb / 8; batch.c = c; batch.ce = ce; batch.fill_ns = lk_now_ns() - tf0;
+    batch.d_keys = d_keys; batch.n_keys = kb / 8; batch.c = c; batch.ce = ce; batch.fill_ns = rtc_now_ns() - tf0;
     RTC_TRY(on_batch(batch));
-    B.drop(d_tmp);
-    B.drop(d_keys);
+    B.release(d_tmp);
+    B.release(d_keys);
     c = ce;
   }
   return RTC_OK;
@@ -537,7 +513,7 @@ extern "C" int rtc_linkage_complete(rtc_ctx* ctx, const void* d_hashes, int widt
   if (n == 0) return RTC_OK;
   if (!d_start || !d_len || !h_comp) return RTC_ERR_ARG;
   RTC_HIP(ctx, hipSetDevice(ctx->device));
-  const uint64_t t0 = lk_now_ns();
+  const uint64_t t0 = rtc_now_ns();
   uint64_t* C = ctx->linkage;
   uint64_t total = 0;
   bool overflow = false;
@@ -548,34 +524,19 @@ extern "C" int rtc_linkage_complete(rtc_ctx* ctx, const void* d_hashes, int widt
     if (b.d_keys) {
       C[5]++;
       C[6] += b.fill_ns;
-      const uint64_t tf1 = lk_now_ns();
+      const uint64_t tf1 = rtc_now_ns();
       RTC_TRY(lk_agglomerate(ctx, b.d_keys, comps, kmin_num, kmin_den, mg, nm, nres));
-      C[7] += lk_now_ns() - tf1;
+      C[7] += rtc_now_ns() - tf1;
     }
     // the merge lists in component order, local indices turned into genome indices
-    const std::vector<uint32_t>&csize = *b.csize, &cfirst = *b.cfirst, &perm = *b.perm;
-    size_t i = 0;
-    for (size_t q = b.c; q < b.ce; q++) {
-      if (csize[q] >= 2) {
-        const lk_comp& cp = comps[i];
-        C[0]++; C[cp.m <= LK_WAVE_MAX ? 1 : 2]++; C[3] += nm[i]; C[4] += nres[i]; C[8] = std::max<uint64_t>(C[8], cp.m);
-        if (total + nm[i] > cap) overflow = true;
-        if (!overflow)
-          for (uint32_t e = 0; e < nm[i]; e++) {
-            rtc_lmerge r = mg[cp.merge_off + e];
-            r.a = perm[cfirst[q] + r.a];
-            r.b = perm[cfirst[q] + r.b];
-            h_merges[total + e] = r;
-          }
-        total += nm[i];
-        i++;
-      }
-      h_first[q + 1] = total;
-    }
+    rtc_kb_remap(b, mg, [&](size_t i, const lk_comp& cp) -> uint64_t {
+      C[0]++; C[cp.m <= LK_WAVE_MAX ? 1 : 2]++; C[3] += nm[i]; C[4] += nres[i]; C[8] = std::max<uint64_t>(C[8], cp.m);
+      return nm[i];
+    }, h_merges, cap, h_first, &total, &overflow);
     return RTC_OK;
   }));
   *h_n_merges = total;
-  C[9] = lk_now_ns() - t0;
+  C[9] = rtc_now_ns() - t0;
   if (overflow) return rtc_fail(ctx, RTC_ERR_OVERFLOW, "rtc_linkage_complete: %llu merges, room for %llu", (unsigned long long)total, (unsigned long long)cap);
   return RTC_OK;
 }

@@ -12,8 +12,6 @@
 // counts, for every inner branch of the main tree, the replicate trees that hold its split -- Day's algorithm: the main tree's
 // leaves numbered in depth-first order from the component's smallest member, every cluster an interval of that numbering, and a
 // replicate's cluster is one of them iff its least and greatest number span exactly its size and the interval is in the table.
-#include <time.h>
-
 #include <algorithm>
 #include <atomic>
 #include <memory>
@@ -85,26 +83,6 @@ __global__ __launch_bounds__(64) void jk_edges_kernel(const T* __restrict__ hash
     common[e * 64 + lane] = jk_pair_wave(s, ns, sb, staged, hashes + start[j], len[j], key, lane);
   }
 }
-
-uint64_t njs_now_ns() {
-  timespec ts;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
-}
-
-struct njs_bufs {
-  std::vector<void*> p;
-  ~njs_bufs() { for (void* q : p) (void)hipFree(q); }
-  int get(rtc_ctx* ctx, size_t bytes, void** out) {
-    ctx->free_hbm_at = -1.0;
-    hipError_t e = hipMalloc(out, bytes ? bytes : 16);
-    if (e != hipSuccess) { (void)hipGetLastError(); return rtc_fail(ctx, RTC_ERR_NOMEM, "rtc_nj_support: hipMalloc(%zu): %s", bytes, hipGetErrorString(e)); }
-    p.push_back(*out);
-    return RTC_OK;
-  }
-};
-
-inline uint64_t njs_records_of(uint32_t m) { return m >= 3 ? m - 2 : m == 2 ? 1 : 0; }
 
 // ---- distances ----------------------------------------------------------------------------------------------------------------
 // rtc_linkage_distance per (common, denom), kept in a triangle over denom <= D where that is at most NJS_MEMO_DENOM: the same
@@ -314,7 +292,7 @@ extern "C" int rtc_nj_support(rtc_ctx* ctx, const void* d_hashes, int width, con
     return rtc_fail(ctx, RTC_ERR_ARG, "rtc_nj_support: replicates must lie in 1 .. %u", NJS_MAX_REPLICATES);
   if (cap && !h_support) return RTC_ERR_ARG;
   for (uint64_t i = 0; i < cap; i++) h_support[i] = 0;
-  const uint64_t t0 = njs_now_ns();
+  const uint64_t t0 = rtc_now_ns();
   uint64_t* S = ctx->nj_support;
   S[0] = replicates;
   const uint32_t B = replicates;
@@ -358,16 +336,16 @@ extern "C" int rtc_nj_support(rtc_ctx* ctx, const void* d_hashes, int width, con
     uint64_t G = std::max<uint64_t>(1, (b.budget > kb ? b.budget - kb : 0) / kb);
     G = std::min<uint64_t>(G, B);
     if (G >= 64 && G < B) G -= G % 64;
-    njs_bufs bufs;
+    DevBuf bufs;
     jk_row* d_rows = nullptr;
     uint32_t* d_size = nullptr;
     uint64_t* d_rep = nullptr;
-    RTC_TRY(bufs.get(ctx, (size_t)n_rows * sizeof(jk_row), (void**)&d_rows));
-    RTC_TRY(bufs.get(ctx, (size_t)n_rows * 64 * 4, (void**)&d_size));
-    RTC_TRY(bufs.get(ctx, (size_t)(G * kb), (void**)&d_rep));
+    RTC_TRY(bufs.get(ctx, n_rows, &d_rows));
+    RTC_TRY(bufs.get(ctx, (size_t)n_rows * 64, &d_size));
+    RTC_TRY(bufs.get(ctx, (size_t)(G * b.n_keys), &d_rep));
     RTC_HIP(ctx, hipMemcpyAsync(d_rows, rows.data(), (size_t)n_rows * sizeof(jk_row), hipMemcpyHostToDevice, s));
     // ---- the main trees' tables ----
-    const uint64_t ts0 = njs_now_ns();
+    const uint64_t ts0 = rtc_now_ns();
     std::vector<njs_table> tables(nc);
     std::vector<uint64_t> rec_at(nc);  // where component i's records start in the call's output
     {
@@ -375,13 +353,13 @@ extern "C" int rtc_nj_support(rtc_ctx* ctx, const void* d_hashes, int width, con
       uint64_t at = total;
       for (size_t i = 0; i < nc; i++) {
         rec_at[i] = at;
-        at += njs_records_of(comps[i].m);
+        at += rtc_nj_records_of(comps[i].m);
         if (comps[i].m < 4) continue;
         t.build(main_rec.data() + comps[i].merge_off, comps[i].m);
         njs_main_table(t, &tables[i]);
       }
     }
-    S[5] += njs_now_ns() - ts0;
+    S[5] += rtc_now_ns() - ts0;
     // partner slices: enough waves for the device where the rows alone are few
     const uint32_t want = (uint32_t)ctx->num_cu * 8;
     const uint32_t gy = std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(m_max - 1, 1024), (want + n_rows - 1) / n_rows));
@@ -392,7 +370,7 @@ extern "C" int rtc_nj_support(rtc_ctx* ctx, const void* d_hashes, int width, con
       const uint32_t r1 = (uint32_t)std::min<uint64_t>(B, r0 + G), ng = r1 - r0;
       S[7]++;
       // ---- counting: the keys of replicates [r0, r1), word after word ----
-      const uint64_t tc0 = njs_now_ns();
+      const uint64_t tc0 = rtc_now_ns();
       for (uint32_t w = r0 / 64; w <= (r1 - 1) / 64; w++) {
         const uint64_t key = rtc_jk_mix(seed + w);
         if (width == 8) {
@@ -409,7 +387,7 @@ extern "C" int rtc_nj_support(rtc_ctx* ctx, const void* d_hashes, int width, con
         RTC_CHECK_LAUNCH(ctx);
       }
       RTC_HIP(ctx, hipStreamSynchronize(s));
-      const uint64_t tc1 = njs_now_ns();
+      const uint64_t tc1 = rtc_now_ns();
       S[2] += tc1 - tc0;
       // ---- distances on the host, as the main blocks get them ----
       rcomps.clear();
@@ -432,12 +410,12 @@ extern "C" int rtc_nj_support(rtc_ctx* ctx, const void* d_hashes, int width, con
       njs_distances(cells.data(), rcomps, memo, ctx->host_threads);
       RTC_HIP(ctx, hipMemcpyAsync(d_rep, cells.data(), (size_t)ng * kb, hipMemcpyHostToDevice, s));
       RTC_HIP(ctx, hipStreamSynchronize(s));
-      const uint64_t td1 = njs_now_ns();
+      const uint64_t td1 = rtc_now_ns();
       S[3] += td1 - tc1;
       // ---- the replicate trees: further components of rtc_nj's launches ----
       uint64_t n_path[3];
       RTC_TRY(rtc_nj_join(ctx, (double*)d_rep, rcomps, rrec, n_path));
-      const uint64_t tj1 = njs_now_ns();
+      const uint64_t tj1 = rtc_now_ns();
       S[4] += tj1 - td1;
       S[1] += rcomps.size();
       // ---- splits ----
@@ -448,7 +426,7 @@ extern "C" int rtc_nj_support(rtc_ctx* ctx, const void* d_hashes, int width, con
         njs_tree rt;
         for (const rtc_kb_comp& c : rcomps) {
           const size_t i = c.pad;
-          if (i % T != t || rec_at[i] + njs_records_of(c.m) > cap) continue;  // past cap: the call ends in RTC_ERR_OVERFLOW
+          if (i % T != t || rec_at[i] + rtc_nj_records_of(c.m) > cap) continue;  // past cap: the call ends in RTC_ERR_OVERFLOW
           rt.build(rrec.data() + c.merge_off, c.m);
           njs_count(tables[i], rt, h_support + rec_at[i], &found[t]);
         }
@@ -460,12 +438,12 @@ extern "C" int rtc_nj_support(rtc_ctx* ctx, const void* d_hashes, int width, con
         for (std::thread& th : pool) th.join();
       }
       for (uint64_t f : found) S[9] += f;
-      S[5] += njs_now_ns() - tj1;
+      S[5] += rtc_now_ns() - tj1;
     }
     for (size_t i = 0; i < nc; i++) if (comps[i].m >= 4) S[8] += comps[i].m - 3;
     return RTC_OK;
   };
   const int st = rtc_nj_clusters_impl(ctx, "rtc_nj_support", d_hashes, width, d_start, d_len, n, h_comp, kmer_size, h_joins, cap, h_n_joins, h_first, 1, &hook);
-  S[6] = njs_now_ns() - t0;
+  S[6] = rtc_now_ns() - t0;
   return st;
 }

@@ -2,10 +2,12 @@
 later turns of four loops that every matrix of test_gpu_linkage.py, test_gpu_nj.py and test_gpu_upgma.py (m <= 300) leaves at
 their first.
 
-  a. a scan workgroup's rows past the first (nj_scan / up_scan on the grid path): RTC_*_SCAN_BLOCKS of 1, 2 and 3 at small m
+  a. a scan workgroup's rows past the first (agg_scan on the grid path, under either rule): RTC_*_SCAN_BLOCKS of 1, 2 and 3 at small m
   b. the join / merge kernels' reduce of the scan's minima past the first 256: m = 1 030 and 1 300, no switch
   c. lk_wg_kernel's steps 1 and 2 past 1 024 rows and past 1 280
   d. the shipped cap of 1 024 scan workgroups, once per kernel: m = 4 104 and 4 102, no switch
+  e. neighbour joining, UPGMA and neighbour joining again on one context, once per path: the two share their kernels' source
+     and their host side, and each keeps its own records, counters and path bits
 
 Every comparison is exact, against the restatements or a closed form (tests/dendrogram_sets.py; tests/test_cpu_dendrogram_sets.py
 holds the inputs to what is assumed of them here).
@@ -249,3 +251,54 @@ def test_nj_scan_past_the_shipped_cap(ctx, switch):
     a, b, cc, *_ = got[-1]
     assert a < b < cc and alive == {a, b, cc}
     _defaults_hold(ctx)
+
+
+# ---- e. the two methods in turn on one context -----------------------------------------------------------------------------------
+# Neighbour joining and UPGMA run one skeleton (rtc_agglom.h) under two rules.  m = 3: NJ's closing record alone; 5, 64: the wave
+# path; 65: the workgroup path; 9 with the switches at 4 and 1: the grid path, one scan workgroup walking every row.
+WAVE, WORKGROUP = 1, 2
+IN_TURN = ((3, False, WAVE), (5, False, WAVE), (64, False, WAVE), (65, False, WORKGROUP), (9, True, GRID))
+
+
+@functools.lru_cache(maxsize=None)
+def _in_turn_inputs(m):
+    D = N.case("random_ties", m) if m >= 5 else N.additive(m)[0]
+    Sm = DS.top_chain(m)
+    want_up = RU.rowcache(Sm.tolist())[0]
+    assert want_up == DS.top_chain_records(m)  # the restatement and the closed form agree before the device is asked
+    return D, RN.nj(D), Sm, want_up
+
+
+def _without_times(c):
+    return {k: v for k, v in c.items() if not k.endswith("_ns")}
+
+
+@pytest.mark.parametrize("m,on_grid,path", IN_TURN, ids=["m%d_path%d" % (m, p) for m, _, p in IN_TURN])
+def test_nj_and_upgma_in_turn_on_one_context(ctx, switch, m, on_grid, path):
+    D, want_nj, Sm, want_up = _in_turn_inputs(m)
+    if on_grid:
+        for name in ("RTC_NJ_GRID_MIN", "RTC_UPGMA_GRID_MIN"):
+            switch(name, 4)
+        for name in ("RTC_NJ_SCAN_BLOCKS", "RTC_UPGMA_SCAN_BLOCKS"):
+            switch(name, 1)
+        assert (ctx.nj_scan_blocks(), ctx.upgma_scan_blocks()) == (1, 1)
+    components = {"wave_components": int(path == WAVE), "workgroup_components": int(path == WORKGROUP), "grid_components": int(path == GRID)}
+    nj_own = dict(components, components=1, records=max(m - 2, 1), batches=1, paths=path)
+    up_own = dict(components, components=1, merges=m - 1, row_rescans=0, paths=path)
+
+    first = ctx.nj(D)
+    c_first = ctx.nj_counters()
+    assert RN.bits(_nj_tuples(first)) == RN.bits(want_nj), _first_difference(_nj_tuples(first), want_nj)
+    assert _without_times(c_first) == nj_own
+
+    got_up = RU.as_tuples(ctx.upgma(Sm))
+    c_up = ctx.upgma_counters()
+    assert got_up == want_up, _first_difference(got_up, want_up)
+    assert _without_times(c_up) == up_own
+    assert ctx.nj_counters() == c_first  # the UPGMA call left neighbour joining's counters alone, times included
+
+    second = ctx.nj(D)
+    assert second.tobytes() == first.tobytes()  # every field of every record, the padding too
+    assert RN.bits(_nj_tuples(second)) == RN.bits(want_nj)
+    assert _without_times(ctx.nj_counters()) == nj_own
+    assert ctx.upgma_counters() == c_up  # and the other way round
