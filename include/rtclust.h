@@ -1402,6 +1402,69 @@ int rtc_upgma_scan_blocks(const rtc_ctx* ctx);
 /* The height of a merge, as defined above.  Host only. */
 double rtc_upgma_distance(uint64_t sum, uint32_t size_a, uint32_t size_b);
 
+/* ---- clust-mst --pangenome: core and accessory hashes of the clusters ---------------------------------------------------- */
+/* What the members of a cluster hold in common and what only a few of them hold: for every cluster the number of members that
+ * hold each hash.  A KSSD sketch is a fixed subsample of k-mer space, so the answer for the sketches estimates the answer for
+ * the k-mers.  This is the definition (tests/refpangenome.py restates it); everything on the device is an integer.
+ *   Input.  Sketches as everywhere (width 4 or 8, ascending, distinct), n, h_label[n] as rtc_cluster_quality takes it (any number
+ *     in [0, n); negative: unclustered), soft_pct and cloud_pct with 1 <= cloud_pct <= soft_pct <= 100.  Clusters are numbered by
+ *     their smallest member; m_c is the size of cluster c.
+ *   Occurrence.  occ_c(h) is the number of members of c whose sketch holds h; occ(g, h) = occ_c(h) for c = g's cluster.
+ *   Classes of a hash in c, every compare in 64-bit integers.  Core: occ == m_c.  Soft: not core and 100 occ >= soft_pct m_c.
+ *     Cloud: not core and 100 occ < cloud_pct m_c.  Shell: the rest.
+ *   Per cluster, one rtc_pan in cluster order: size = m_c; total = the sum of the members' sketch lengths; pan = the number of
+ *     distinct hashes; core, soft, shell, cloud (they sum to pan); single = the hashes with occ == 1.
+ *   Histogram.  Cluster c owns h_hist[o_c .. o_c + m_c), o_c the sum of the sizes of the clusters before it; entry f - 1 is the
+ *     number of distinct hashes with occ == f.  The caller gives n entries; those past the clustered genomes are zeroed.
+ *   Per genome, rtc_pan_genome[n]: unique = its hashes with occ == 1; core, soft, shell, cloud = its hashes by class; occ_sum =
+ *     the sum of occ over its hashes.  An unclustered genome gets an all-zero record and belongs to no cluster.  An empty sketch
+ *     contributes nothing (and still counts in m_c).
+ *   Consequences.  A singleton cluster has pan = core = single = len.  sum_f f hist[f] = total.  hist[m] = core.  The members'
+ *     unique values sum to hist[1].  The members' occ_sum values sum to sum_f f^2 hist[f].
+ * Percentages out of order, a label >= n, width not 4 or 8, NULLs, n >= 2^31 - 1: RTC_ERR_ARG.  A sketch of 2^31 hashes or more:
+ * RTC_ERR_UNSUPPORTED.  Memory that does not fit: RTC_ERR_NOMEM with the bytes in the message, no fallback.
+ *
+ * The call.  One open-addressing table of (hash, count) slots per cluster, never more than half full; three steps over it: count
+ * (insert with a 64-bit compare-and-swap, add 1), sweep (every slot into the histogram) and look-up (every member's hashes again,
+ * for the genomes' records).  The members are reached through the clustered genomes ordered by cluster, a permutation and segment
+ * offsets built once on the host.  A cluster of up to 512 records (the sum of its members' lengths) takes one wave with table
+ * and histogram in LDS, one of up to 2 048 a 256-lane workgroup likewise, everything larger a table of 1 << ceil(log2(2 K)) slots
+ * in one arena in global memory, where count, sweep and look-up are device-wide kernels over all arena clusters at once: a member
+ * a wave, 256 slots a tile (rabbittclust_amd/csrc/rtc_pan.h).  RTC_PAN_GLOBAL=1 sends every cluster through the arena; results are
+ * identical.  The all-ones 64-bit value marks an empty slot; a hash of that value is counted in a word of its own per cluster, and
+ * 0 is a key like any other.  A cluster's class counts are sums over its histogram, formed on the host.  Clusters are taken in
+ * groups, in cluster order, whose arena (12 bytes a slot) and views (56 bytes a member, 48 a cluster) fit RTC_PAN_BYTES (default:
+ * half the free HBM); a cluster that does not fit alone: RTC_ERR_NOMEM.  The records depend on neither the grouping nor the path:
+ * every sum is an integer and every compare exact.  h_clusters[number of distinct labels >= 0, at least 1], h_hist[n],
+ * h_genomes[n].  Returns the number of clusters in *h_n_clusters.  Synchronous. */
+typedef struct { uint64_t total, pan, core, soft, shell, cloud, single; uint32_t size, pad; } rtc_pan; /* 64 bytes */
+typedef struct { uint64_t occ_sum; uint32_t unique, core, soft, shell, cloud, pad; } rtc_pan_genome; /* 32 bytes */
+int rtc_pangenome(rtc_ctx* ctx, const void* d_hashes, int width, const uint64_t* d_start, const uint32_t* d_len, uint32_t n,
+                  const int32_t* h_label, uint32_t soft_pct, uint32_t cloud_pct, rtc_pan* h_clusters, uint64_t* h_hist,
+                  rtc_pan_genome* h_genomes, uint32_t* h_n_clusters);
+/* The last rtc_pangenome: out[0] clusters, out[1] clustered genomes, out[2] records (the clustered genomes' hashes), out[3]
+ * distinct hashes (the sum of pan), out[4] / out[5] / out[6] clusters on the wave / workgroup / arena path, out[7] groups, out[8]
+ * kernel ns, out[9] whole call ns. */
+int rtc_pangenome_counters(const rtc_ctx* ctx, uint64_t out[10]);
+/* The kernel ns of the last rtc_pangenome by step: out[0] count (the LDS kernels do all three steps in one launch and are counted
+ * here), out[1] the arena's sweep, out[2] the arena's look-up. */
+int rtc_pangenome_phases(const rtc_ctx* ctx, uint64_t out[3]);
+/* the cluster paths of the last call: bit 0 one wave, bit 1 a 256-lane workgroup, bit 2 the arena in global memory */
+int rtc_pangenome_last_path(const rtc_ctx* ctx);
+/* The expected pangenome and core size after j of a cluster's m members, over all orders of the members, from the cluster's
+ * histogram h_hist[0 .. m) (entry f - 1: the hashes held by f members).  The closed form; nothing is sampled.  Host only, no
+ * context.
+ *   Points: j = 1 .. m when m <= 256, else the 256 values 1 + floor(i (m - 1) / 255), i = 0 .. 255.
+ *   For every f with hist[f] > 0 start u = v = 1.0 and for i = 0, 1, ..: u = u * (double)(m - f - i) / (double)(m - i), and 0 from
+ *     the first zero factor on; v = v * (double)(f - i) / (double)(m - i), f - i a signed integer.  u_f(j), v_f(j) are the
+ *     values after the factors i = 0 .. j - 1: the chance that none, and that every one, of j members holds a hash held by f.
+ *   pan(j) is the sum over ascending f of (double)hist[f] * (1.0 - u_f(j)), core(j) that of (double)hist[f] * v_f(j), both
+ *     starting from 0.0.  Every step is one IEEE-754 double operation in that order; nothing is contracted into an fma.
+ *   It follows exactly that pan(m) = pan and core(m) = hist[m].
+ * The f are spread over `threads` host threads (each u_f, v_f is independent; the final sums keep their order).  h_j, h_pan,
+ * h_core: room for min(m, 256) entries each; *h_points gets the number of points, 0 for m == 0.  NULLs: RTC_ERR_ARG. */
+int rtc_pan_growth(const uint64_t* h_hist, uint32_t m, int threads, uint32_t* h_j, double* h_pan, double* h_core, uint32_t* h_points);
+
 #ifdef __cplusplus
 }
 #endif

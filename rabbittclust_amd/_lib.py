@@ -208,6 +208,11 @@ SIGNATURES = {
     "rtc_upgma_scan_blocks": (_i, [_vp]),
     "rtc_upgma_distance": (C.c_double, [_u64, _u32, _u32]),
     "rtc_hierarchy_flat": (_i, [_u32, _vp, _u64, _vp, _i, _i, _vp, _vp, C.POINTER(_u32)]),
+    "rtc_pangenome": (_i, [_vp, _vp, _i, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "rtc_pangenome_counters": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_pangenome_phases": (_i, [_vp, C.POINTER(_u64)]),
+    "rtc_pangenome_last_path": (_i, [_vp]),
+    "rtc_pan_growth": (_i, [_vp, _u32, _i, _vp, _vp, _vp, C.POINTER(_u32)]),
 }
 
 _lib = None

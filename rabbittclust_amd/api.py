@@ -89,6 +89,63 @@ SCREEN_BLOCK_CANDS = 4096
 SCREEN_POS_BYTES = 40
 SCREEN_MATCH_BYTES = 72
 SCREEN_Q20 = 1 << 20  # containment 1 in rtc_rep_screen's min_cont_q20
+PAN_DT = np.dtype([("total", "<u8"), ("pan", "<u8"), ("core", "<u8"), ("soft", "<u8"), ("shell", "<u8"), ("cloud", "<u8"), ("single", "<u8"),
+                   ("size", "<u4"), ("pad", "<u4")])  # rtc_pan
+PAN_GENOME_DT = np.dtype([("occ_sum", "<u8"), ("unique", "<u4"), ("core", "<u4"), ("soft", "<u4"), ("shell", "<u4"), ("cloud", "<u4"),
+                          ("pad", "<u4")])  # rtc_pan_genome
+PAN_PATH_WAVE, PAN_PATH_BLOCK, PAN_PATH_GLOBAL = 1, 2, 4  # rtc_pangenome_last_path
+# the cluster paths' boundaries (csrc/rtc_pan.h): a cluster of at most PAN_WAVE_RECORDS records (the sum of its members' sketch
+# lengths) takes one wave with a table of PAN_WAVE_SLOTS slots and a histogram of PAN_WAVE_HIST entries in LDS, one of at most
+# PAN_BLOCK_RECORDS a 256-lane workgroup likewise, a larger one a table of 1 << max(PAN_GLOBAL_LOG2_MIN, ceil(log2(2 records)))
+# slots in the arena in global memory.  PAN_SLOT_BYTES a slot, PAN_MEMBER_BYTES a member and PAN_CLUSTER_BYTES a cluster are what
+# a group of clusters is charged against RTC_PAN_BYTES.
+PAN_WAVE_RECORDS, PAN_WAVE_SLOTS, PAN_WAVE_HIST = 512, 1024, 512
+PAN_BLOCK_RECORDS, PAN_BLOCK_SLOTS, PAN_BLOCK_HIST = 2048, 4096, 1024
+PAN_GLOBAL_LOG2_MIN = 8
+PAN_GLOBAL_WGS_PER_CU = 16  # the arena's count and look-up kernels take a member a wave: 4 * PAN_GLOBAL_WGS_PER_CU waves a CU a turn
+PAN_SLOT_BYTES, PAN_MEMBER_BYTES, PAN_CLUSTER_BYTES = 12, 56, 48
+PAN_EMPTY = 0xFFFFFFFFFFFFFFFF  # the empty slot's key; a hash of this value is counted beside the table
+PAN_MULT = 0x9E3779B97F4A7C15
+PAN_GROWTH_POINTS = 256
+
+
+def pan_slot(hash_value, log2_slots):
+    """The slot a hash's probe starts from in a table of 1 << log2_slots slots (csrc/rtc_pangenome.hip: pan_slot); the probe
+    goes on to the next slot, wrapping."""
+    return ((int(hash_value) * PAN_MULT) & 0xFFFFFFFFFFFFFFFF) >> (64 - int(log2_slots))
+
+
+def pan_table_log2(records, all_global=False):
+    """log2 of the slots of the arena table of a cluster of `records` records, or None for a cluster on an LDS path."""
+    if not all_global and records <= PAN_BLOCK_RECORDS:
+        return None
+    lg = PAN_GLOBAL_LOG2_MIN
+    while (1 << lg) < 2 * records:
+        lg += 1
+    return lg
+
+
+def pan_cluster_bytes(records, members, all_global=False):
+    """What rtc_pangenome charges a cluster of `members` members and `records` records against RTC_PAN_BYTES."""
+    lg = pan_table_log2(records, all_global)
+    return PAN_SLOT_BYTES * ((1 << lg) if lg is not None else 0) + PAN_MEMBER_BYTES * members + PAN_CLUSTER_BYTES
+
+
+def pan_growth(hist, threads=1):
+    """rtc_pan_growth: (j, pan, core) -- the expected pangenome and core size after j of the m = len(hist) members of a cluster
+    whose histogram is hist (entry f - 1: the hashes held by f members), over all orders of the members, at j = 1 .. m or, past
+    256 members, at 256 values of j from 1 to m."""
+    h = np.ascontiguousarray(np.asarray(hist, dtype=np.uint64).reshape(-1))
+    m = len(h)
+    P = min(m, PAN_GROWTH_POINTS)
+    j = np.zeros(max(P, 1), dtype=np.uint32)
+    pan = np.zeros(max(P, 1), dtype=np.float64)
+    core = np.zeros(max(P, 1), dtype=np.float64)
+    got = C.c_uint32(0)
+    st = _lib.load().rtc_pan_growth(_np_ptr(h), m, int(threads), _np_ptr(j), _np_ptr(pan), _np_ptr(core), C.byref(got))
+    if st != _lib.RTC_OK:
+        raise RtcError(st, "rtc_pan_growth")
+    return j[:got.value].copy(), pan[:got.value].copy(), core[:got.value].copy()
 
 
 def _np_ptr(a):
@@ -1322,6 +1379,41 @@ class Context:
         self.check(self.lib.rtc_cluster_support_counters(self.h, a))
         names = ("chunks", "candidates", "inner_kept", "crossing_kept", "hook_passes", "pair_ns", "count_ns", "components_ns", "tally_ns", "total_ns")
         return {k: int(a[i]) for i, k in enumerate(names)}
+
+    def pangenome(self, sk, labels, soft_pct=95, cloud_pct=15):
+        """rtc_pangenome: (clusters, hist, genomes).  labels[g] >= 0 is g's cluster (any number below n), negative: unclustered.
+        clusters: one PAN_DT per cluster, the clusters in order of their smallest member -- size, total (the members' hashes), pan
+        (distinct hashes), and those by class: core (held by every member), soft (by at least soft_pct % of them), cloud (by less
+        than cloud_pct %), shell (the rest), and single (held by one).  hist: n uint64; cluster c owns the size_c entries behind
+        those of the clusters before it, entry f - 1 the hashes held by f members.  genomes: one PAN_GENOME_DT per sketch -- its
+        hashes nobody else in its cluster holds (unique), its hashes by class, and occ_sum, the sum over its hashes of the members
+        that hold them."""
+        n = sk.n
+        lab = np.ascontiguousarray(np.asarray(labels).astype(np.int64).astype(np.int32))
+        if lab.shape != (n,):
+            raise ValueError("labels must hold one label per sketch")
+        clusters = np.zeros(max(n, 1), dtype=PAN_DT)
+        hist = np.zeros(max(n, 1), dtype=np.uint64)
+        genomes = np.zeros(max(n, 1), dtype=PAN_GENOME_DT)
+        n_cl = C.c_uint32(0)
+        self.check(self.lib.rtc_pangenome(self.h, _t_ptr(sk.hashes), sk.width, _t_ptr(sk.start), _t_ptr(sk.len), n, _np_ptr(lab), int(soft_pct),
+                                          int(cloud_pct), _np_ptr(clusters), _np_ptr(hist), _np_ptr(genomes), C.byref(n_cl)))
+        return clusters[:n_cl.value].copy(), hist[:n].copy(), genomes[:n].copy()
+
+    def pangenome_counters(self):
+        """rtc_pangenome_counters as a dict (the last pangenome call), with rtc_pangenome_phases' three times"""
+        a = (C.c_uint64 * 10)()
+        self.check(self.lib.rtc_pangenome_counters(self.h, a))
+        names = ("clusters", "clustered", "records", "distinct", "wave_clusters", "block_clusters", "global_clusters", "groups", "kernel_ns", "total_ns")
+        out = {k: int(a[i]) for i, k in enumerate(names)}
+        p = (C.c_uint64 * 3)()
+        self.check(self.lib.rtc_pangenome_phases(self.h, p))
+        out.update(count_ns=int(p[0]), sweep_ns=int(p[1]), genome_ns=int(p[2]))
+        return out
+
+    def pangenome_last_path(self):
+        """the cluster paths of the last pangenome call: PAN_PATH_WAVE | PAN_PATH_BLOCK | PAN_PATH_GLOBAL"""
+        return int(self.lib.rtc_pangenome_last_path(self.h))
 
     def components64(self, n, edges, masks, labels=None):
         """rtc_components64_dev: the connected components of 64 graphs over n vertices at once.  edges: an (m, 2) array of vertices

@@ -116,6 +116,8 @@ void rtc_options_from_env(rtc_options* o) {
   o->degree_block = flag("RTC_DEGREE_BLOCK");
   if (const char* e = getenv("RTC_SCREEN_BYTES")) o->screen_bytes = std::max<uint64_t>(strtoull(e, nullptr, 10), 1);
   o->screen_global = flag("RTC_SCREEN_GLOBAL");
+  if (const char* e = getenv("RTC_PAN_BYTES")) o->pan_bytes = std::max<uint64_t>(strtoull(e, nullptr, 10), 1);
+  o->pan_global = flag("RTC_PAN_GLOBAL");
 }
 
 extern "C" {

@@ -56,6 +56,8 @@ struct rtc_options {
   int degree_block = 0;            // RTC_DEGREE_BLOCK: every row of rtc_greedy_degree's assignment takes the 256-lane path
   uint64_t screen_bytes = 0;       // RTC_SCREEN_BYTES: the bytes a chunk of rtc_rep_screen's match records and views may take (0: half the free HBM)
   int screen_global = 0;           // RTC_SCREEN_GLOBAL: every sample of rtc_rep_screen takes the long path (the counts in global memory)
+  uint64_t pan_bytes = 0;          // RTC_PAN_BYTES: the bytes a group of rtc_pangenome's clusters (arena and views) may take (0: half the free HBM)
+  int pan_global = 0;              // RTC_PAN_GLOBAL: every cluster of rtc_pangenome takes the arena in global memory
 };
 void rtc_options_from_env(rtc_options* o);
 
@@ -134,6 +136,9 @@ struct rtc_ctx {
   int greedy_degree_path = 0;  // rtc_greedy_degree_last_path
   uint64_t rep_screen[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_rep_screen_counters (include/rtclust.h lists them)
   int rep_screen_path = 0;  // rtc_rep_screen_last_path
+  uint64_t pan[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // rtc_pangenome_counters (include/rtclust.h lists them)
+  uint64_t pan_phase[3] = {0, 0, 0};  // rtc_pangenome_phases
+  int pan_path = 0;         // rtc_pangenome_last_path
   int host_threads = 1;     // rtc_ctx_set_host_threads: the host side of rtc_tree_medoids and of rtc_nj_clusters', rtc_upgma_clusters' and rtc_cluster_quality's distances
   // rtc_diag_counters: [0] pair tiles the join took, [1] tiled-kernel tiles, [2] merge-kernel tiles, [3] candidate lists contracted
   // to their forest, [4] greedy runs replayed from ONE global join, [5] greedy query blocks of the block loop, [6] estimates handed

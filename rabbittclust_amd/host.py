@@ -285,6 +285,39 @@ def support_report(names, cluster_of, records, together, replicates):
     return tuple(out)
 
 
+def pangenome_report(names, cluster_of, clusters, hist, genomes):
+    """pangenome_report_text (rtc_host.cpp): the four reports of clust-mst --pangenome as (pangenome_tsv, genomes_tsv, hist_tsv,
+    curve_tsv).  names[g] and cluster_of[g] (the cluster number <output> gives genome g) for every genome; clusters (api.PAN_DT),
+    hist and genomes (api.PAN_GENOME_DT): Context.pangenome's, the clusters in the library's order (that of their smallest
+    members)."""
+    n = len(names)
+    lab = np.ascontiguousarray(cluster_of, dtype=np.int32)
+    rec = np.ascontiguousarray(clusters)
+    hs = np.ascontiguousarray(hist, dtype=np.uint64)
+    gen = np.ascontiguousarray(genomes)
+    if n and int(lab.min()) < 0:
+        raise ValueError("cluster_of must name a cluster for every genome")
+    ncl = int(lab.max()) + 1 if n else 0
+    assert rec.dtype.itemsize == 64 and gen.dtype.itemsize == 32 and len(lab) == len(gen) == n and len(hs) >= n and len(rec) == ncl
+    arr = (C.c_char_p * max(n, 1))(*[s.encode() for s in names])
+    from . import _lib
+    growth = C.cast(_lib.load().rtc_pan_growth, C.c_void_p)
+    fn = load().rtch_pangenome_report
+    fn.restype = C.c_long
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_long]
+    out = []
+    for which in range(4):
+        args = (arr, lab.ctypes.data_as(C.c_void_p), ncl, rec.ctypes.data_as(C.c_void_p), hs.ctypes.data_as(C.c_void_p),
+                gen.ctypes.data_as(C.c_void_p), n, growth, which)
+        need = fn(*args, None, 0)
+        if need < 0:
+            raise ValueError("cluster_of outside the clusters, a cluster without a member, or records that are not these clusters'")
+        buf = C.create_string_buffer(max(int(need), 1))
+        fn(*args, buf, need)
+        out.append(buf.raw[:need].decode())
+    return tuple(out)
+
+
 def screen_report(names, rep_names, cluster_id, cluster_size, hits, sums, kmer_size):
     """screen_report_text (rtc_host.cpp): the two reports of clust-mst --db --screen as (screen_tsv, summary_tsv).  names[q]: the
     samples (an empty name prints as query_<q>); rep_names, cluster_id and cluster_size by slot; hits: api.SCREEN_HIT_DT sorted by

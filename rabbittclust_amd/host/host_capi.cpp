@@ -375,6 +375,31 @@ long rtch_support_report(const char* const* names, const int32_t* cluster_of, ui
   return (long)text.size();
 }
 
+// pangenome_report_text over plain arrays: names[g], cluster_of[g] in [0, n_clusters) for every genome, rec[n_clusters] (rtc_pan) and
+// hist[n] in the order of the clusters' smallest members, gen[g] (rtc_pan_genome), growth_fn rtc_pan_growth.  which 0: the cluster
+// report, 1: the genome report, 2: the histogram, 3: the curves.  Returns -1 for a cluster_of outside that range, a cluster
+// without members or a record whose size is not its cluster's, else the text's length; the text itself when it fits cap.
+long rtch_pangenome_report(const char* const* names, const int32_t* cluster_of, uint32_t n_clusters, const rtc_pan* rec, const uint64_t* hist,
+                           const rtc_pan_genome* gen, uint32_t n, pan_growth_fn growth_fn, int which, char* out, long cap) {
+  std::vector<std::vector<int>> clusters(n_clusters);
+  for (uint32_t g = 0; g < n; g++) {
+    if (cluster_of[g] < 0 || (uint32_t)cluster_of[g] >= n_clusters) return -1;
+    clusters[cluster_of[g]].push_back((int)g);
+  }
+  std::vector<std::pair<int, size_t>> by_first;
+  for (const std::vector<int>& c : clusters) {
+    if (c.empty()) return -1;
+    by_first.push_back({c[0], c.size()});
+  }
+  std::sort(by_first.begin(), by_first.end());
+  for (uint32_t q = 0; q < n_clusters; q++) if (rec[q].size != by_first[q].second) return -1;
+  std::string t[4];
+  pangenome_report_text([&](uint32_t g) { return std::string(names[g]); }, clusters, rec, hist, gen, n, 1, growth_fn, &t[0], &t[1], &t[2], &t[3]);
+  const std::string& text = t[which & 3];
+  if (out && (long)text.size() <= cap) memcpy(out, text.data(), text.size());
+  return (long)text.size();
+}
+
 // screen_report_text with the caller's identity function (rtc_screen_identity) over plain arrays: names[n_queries] (an empty name: query_<q>), rep_names / cluster_id / cluster_size by slot
 // (n_reps of each), hits sorted by sample, sums[n_queries].  which 0: the hit report, 1: the summary.  Returns -1 for a hit whose
 // sample or slot is out of range or out of order, else the text's length; the text itself when it fits cap (no terminator).

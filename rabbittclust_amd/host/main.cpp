@@ -907,6 +907,8 @@ struct Options {
   bool has_clusterSupport = false, has_supportSeed = false;  // clust-mst --cluster-support B [--support-seed S]: jackknife support of the clusters themselves (rtc_cluster_support)
   long long clusterSupport = 0;
   uint64_t supportSeed = 0;
+  bool pangenome = false, has_panSoft = false, has_panCloud = false;  // clust-mst --fast --pangenome [--pan-soft P] [--pan-cloud P]: core and accessory hashes of the clusters (rtc_pangenome)
+  long long panSoft = 95, panCloud = 15;
   // clust-mst --fast --db FILE --screen: which clusters a sample contains (rtc_rep_screen)
   bool db_screen = false;
   string minContainment = "0.05", minShared = "2", minUnique = "2", screenPicks = "0";  // as spelled: the refusals read them
@@ -1080,6 +1082,9 @@ static Options parse(int argc, char** argv) {
     else if (a == "--cluster-support") { o.clusterSupport = atoll(need(i)); o.has_clusterSupport = true; }
     else if (a == "--support-seed") { o.supportSeed = strtoull(need(i), nullptr, 10); o.has_supportSeed = true; }
     else if (a == "--upgma") o.upgma = true;
+    else if (a == "--pangenome") o.pangenome = true;
+    else if (a == "--pan-soft") { o.panSoft = atoll(need(i)); o.has_panSoft = true; }
+    else if (a == "--pan-cloud") { o.panCloud = atoll(need(i)); o.has_panCloud = true; }
     else if (a == "--screen") o.db_screen = true;
     else if (a == "--min-containment") { o.minContainment = need(i); if (!o.screenOnly) o.screenOnly = "--min-containment"; }
     else if (a == "--min-shared") { o.minShared = need(i); if (!o.screenOnly) o.screenOnly = "--min-shared"; }
@@ -1194,6 +1199,12 @@ static Options parse(int argc, char** argv) {
            "  --upgma (average linkage, UPGMA, inside every cluster of the run, in exact integers on the GPU: <output>.upgma, the\n"
            "             clusters cut at -d by mean distance; <output>.upgma.linkage.txt, every merge; <output>.upgma.newick, one\n"
            "             ultrametric tree a line in the order of <output>; with --fast or MinHash on the index path)\n"
+           "  --fast --pangenome [--pan-soft P] [--pan-cloud P] (what the members of every cluster hold in common: how many members\n"
+           "             hold each sketch hash, counted on the GPU; <output>.pangenome.tsv, a line a cluster with its pan, core,\n"
+           "             soft-core (held by at least P %, default 95), shell and cloud (by less than P %, default 15) hashes and its\n"
+           "             most typical member; <output>.pangenome.genomes.tsv, a line a genome; <output>.pangenome.hist.tsv, hashes by\n"
+           "             the number of members that hold them; <output>.pangenome.curve.tsv, the expected pan and core size after j\n"
+           "             members; KSSD sketches only)\n"
            "  [--fast] --db FILE --build|--query|--assign|--append LIST|--stats [--top-k N] (MST representative database)\n"
            "  --fast --db FILE --screen -i SAMPLES [--min-containment C] [--min-shared N] [--min-unique N] [--screen-picks N] (which\n"
            "             clusters a mixture holds: the containment of every representative in every sample and a winner-takes-all\n"
@@ -1562,6 +1573,48 @@ static int cluster_support_and_print(rtc_ctx* ctx, const DeviceSketches& ds, con
   g_metrics.num("support_tally_s", 1e-9 * (double)cnt[8]);
   g_metrics.num("support_replicates", (double)replicates);
   g_metrics.num("support_recovered_mean", mean);
+  return 0;
+}
+// --pangenome: how many members of its cluster hold each hash of every genome (include/rtclust.h has the definition), counted on
+// the GPU over the run's clusters.  <base>.pangenome.tsv: a line a cluster in the order and with the numbers <base> prints;
+// <base>.pangenome.genomes.tsv: a line a genome in input order; <base>.pangenome.hist.tsv and <base>.pangenome.curve.tsv: the
+// clusters' histograms and growth curves (pangenome_report_text, rtc_host.h).  Tables that do not fit the device (RTC_ERR_NOMEM, no
+// fallback) are reported: returns 1.
+static int pangenome_and_print(rtc_ctx* ctx, const DeviceSketches& ds, const vector<vector<int>>& clusters, const vector<GenomeInfo>& genomes,
+                               bool sketchByFile, const string& base, uint32_t soft_pct, uint32_t cloud_pct, int threads) {
+  const uint32_t n = (uint32_t)genomes.size();
+  vector<int32_t> label(n, -1);
+  for (size_t c = 0; c < clusters.size(); c++) for (int g : clusters[c]) label[g] = (int32_t)c;
+  vector<rtc_pan> rec(n > 0 ? n : 1);
+  vector<uint64_t> hist(n > 0 ? n : 1, 0);
+  vector<rtc_pan_genome> gen(n > 0 ? n : 1);
+  uint32_t n_cl = 0;
+  const int st = rtc_pangenome(ctx, ds.d_hashes, ds.width, ds.d_start, ds.d_len, n, label.data(), soft_pct, cloud_pct, rec.data(), hist.data(), gen.data(),
+                               &n_cl);
+  if (st == RTC_ERR_NOMEM || st == RTC_ERR_UNSUPPORTED) { cerr << "ERROR: " << rtc_last_error(ctx) << endl; return 1; }
+  CHECK(ctx, st);
+  uint64_t cnt[10], phase[3];
+  CHECK(ctx, rtc_pangenome_counters(ctx, cnt));
+  CHECK(ctx, rtc_pangenome_phases(ctx, phase));
+  string text[4];
+  const double share = pangenome_report_text([&](uint32_t g) { return sketchByFile ? genomes[g].fileName : genomes[g].seq0.name; }, clusters, rec.data(),
+                                             hist.data(), gen.data(), n, threads > 0 ? threads : 1, rtc_pan_growth, &text[0], &text[1], &text[2], &text[3]);
+  const string files[4] = {base + ".pangenome.tsv", base + ".pangenome.genomes.tsv", base + ".pangenome.hist.tsv", base + ".pangenome.curve.tsv"};
+  for (int which = 0; which < 4; which++) {
+    FILE* fp = fopen(files[which].c_str(), "w");
+    if (!fp) { cerr << "ERROR: cannot open file: " << files[which] << endl; join_warmup(); exit(1); }
+    fwrite(text[which].data(), 1, text[which].size(), fp);
+    fclose(fp);
+  }
+  cerr << "-----write the pangenome of the clusters into: " << files[0] << ", " << files[1] << ", " << files[2] << " and " << files[3] << endl;
+  cerr << "-----pangenome: " << cnt[0] << " clusters, " << cnt[2] << " hashes of " << cnt[1] << " genomes, " << cnt[3] << " distinct, " << cnt[4] << " / "
+       << cnt[5] << " / " << cnt[6] << " clusters on the wave / workgroup / arena path, " << cnt[7] << " group(s), mean core share " << share << endl;
+  g_metrics.num("pangenome_count_s", 1e-9 * (double)phase[0]);
+  g_metrics.num("pangenome_sweep_s", 1e-9 * (double)phase[1]);
+  g_metrics.num("pangenome_genome_s", 1e-9 * (double)phase[2]);
+  g_metrics.num("pangenome_clusters", (double)cnt[0]);
+  g_metrics.num("pangenome_hashes", (double)cnt[3]);
+  g_metrics.num("pangenome_core_share_mean", share);
   return 0;
 }
 #endif
@@ -3228,6 +3281,22 @@ int main(int argc, char** argv) {
                       : o.autoThreshold ? "--auto-threshold" : o.stability ? "--stability" : nullptr;
     if (bad) { cerr << "ERROR: --upgma does not go with " << bad << endl; return 1; }
   }
+  // ---- --pangenome / --pan-soft / --pan-cloud: the same company, and what they need ----
+  if (o.pangenome) {
+    const char* bad = o.isContainment ? "-c/--containment" : !o.useIndex ? "--inverted-index=false" : o.has_append ? "--append"
+                      : o.has_premsted ? "--premsted" : !o.repdb_path.empty() ? "--db" : o.dense ? "--dense"
+                      : o.autoThreshold ? "--auto-threshold" : o.stability ? "--stability" : nullptr;
+    if (bad) { cerr << "ERROR: --pangenome does not go with " << bad << endl; return 1; }
+    // a bottom-s MinHash sketch says nothing about the hashes above its own cut
+    if (!o.is_fast) { cerr << "ERROR: --pangenome needs --fast (KSSD sketches)" << endl; return 1; }
+    if (!(1 <= o.panCloud && o.panCloud <= o.panSoft && o.panSoft <= 100)) {
+      cerr << "ERROR: --pan-soft and --pan-cloud must satisfy 1 <= cloud <= soft <= 100, not soft " << o.panSoft << " and cloud " << o.panCloud << endl;
+      return 1;
+    }
+  } else if (o.has_panSoft || o.has_panCloud) {
+    cerr << "ERROR: " << (o.has_panSoft ? "--pan-soft" : "--pan-cloud") << " needs --pangenome" << endl;
+    return 1;
+  }
 #endif
   // ---- MST RepDB mode: --db FILE (src/main.cpp:213-254, :525-600) ----
   if (o.has_topk && !o.db_query) { cerr << "ERROR: --top-k requires --query" << endl; return 1; }
@@ -4147,6 +4216,13 @@ int main(int argc, char** argv) {
   if (o.upgma) {
     if (is_containment) { cerr << "ERROR: --upgma does not go with containment sketches" << endl; return 1; }
     if (upgma_and_print(ctx, dss[0], clusters, genomes, sketchByFile, o.outputFile, o.threshold, kmer_size, o.threads) != 0) {
+      join_warmup();
+      return 1;
+    }
+  }
+  if (o.pangenome) {
+    if (is_containment) { cerr << "ERROR: --pangenome does not go with containment sketches" << endl; return 1; }
+    if (pangenome_and_print(ctx, dss[0], clusters, genomes, sketchByFile, o.outputFile, (uint32_t)o.panSoft, (uint32_t)o.panCloud, o.threads) != 0) {
       join_warmup();
       return 1;
     }

@@ -1528,6 +1528,89 @@ double support_report_text(const std::function<std::string(uint32_t)>& name, con
   return nc ? (double)recovered / (double)nc : 0.0;
 }
 
+double pangenome_report_text(const std::function<std::string(uint32_t)>& name, const std::vector<std::vector<int>>& clusters, const rtc_pan* rec,
+                             const uint64_t* hist, const rtc_pan_genome* gen, uint32_t n, int threads, pan_growth_fn growth_fn, std::string* pan_tsv,
+                             std::string* genomes_tsv, std::string* hist_tsv, std::string* curve_tsv) {
+  char buf[512];
+  const size_t nc = clusters.size();
+  // the library numbers the clusters by their smallest member; a cluster's histogram starts behind those of the clusters before it
+  std::vector<size_t> order(nc), rank(nc);
+  std::vector<int> smallest(nc, 0);
+  for (size_t c = 0; c < nc; c++) { order[c] = c; if (!clusters[c].empty()) smallest[c] = *std::min_element(clusters[c].begin(), clusters[c].end()); }
+  std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return smallest[x] < smallest[y]; });
+  for (size_t q = 0; q < nc; q++) rank[order[q]] = q;
+  std::vector<uint64_t> first(nc + 1, 0);
+  for (size_t q = 0; q < nc; q++) first[q + 1] = first[q] + rec[q].size;
+  std::vector<int32_t> label(n, -1);
+  std::string &P = *pan_tsv, &H = *hist_tsv, &V = *curve_tsv;
+  P = "cluster\tsize\thashes\tpan\tcore\tsoft_core\tshell\tcloud\tsingletons\tcore_share\tnew_per_genome\tcentre\n";
+  H = "cluster\tf\tcount\n";
+  V = "cluster\tj\tpan\tcore\n";
+  double share_sum = 0.0;
+  size_t share_n = 0;
+  std::vector<uint32_t> js;
+  std::vector<double> gp, gc;
+  for (size_t c = 0; c < nc; c++) {
+    const rtc_pan& r = rec[rank[c]];
+    const uint64_t* h = hist + first[rank[c]];
+    int centre = -1;
+    for (int g : clusters[c]) {
+      label[g] = (int32_t)c;
+      if (centre < 0 || gen[g].occ_sum > gen[centre].occ_sum || (gen[g].occ_sum == gen[centre].occ_sum && g < centre)) centre = g;
+    }
+    snprintf(buf, sizeof buf, "%zu\t%u\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t", c, r.size, (unsigned long long)r.total, (unsigned long long)r.pan,
+             (unsigned long long)r.core, (unsigned long long)r.soft, (unsigned long long)r.shell, (unsigned long long)r.cloud,
+             (unsigned long long)r.single);
+    P += buf;
+    if (r.pan) {
+      const double share = (double)r.core / (double)r.pan;
+      share_sum += share;
+      share_n++;
+      snprintf(buf, sizeof buf, "%.6f", share);
+      P += buf;
+    } else {
+      P += "-";
+    }
+    snprintf(buf, sizeof buf, "\t%.6f\t", r.size ? (double)h[0] / (double)r.size : 0.0);
+    P += buf;
+    P += centre >= 0 ? name((uint32_t)centre) : std::string("-");
+    P += "\n";
+    for (uint32_t f = 1; f <= r.size; f++)
+      if (h[f - 1]) {
+        snprintf(buf, sizeof buf, "%zu\t%u\t%llu\n", c, f, (unsigned long long)h[f - 1]);
+        H += buf;
+      }
+    if (r.size >= 2 && growth_fn) {
+      const uint32_t cap = r.size < 256 ? r.size : 256;
+      js.assign(cap, 0); gp.assign(cap, 0.0); gc.assign(cap, 0.0);
+      uint32_t points = 0;
+      if (growth_fn(h, r.size, threads, js.data(), gp.data(), gc.data(), &points) == 0)
+        for (uint32_t p = 0; p < points && p < cap; p++) {
+          snprintf(buf, sizeof buf, "%zu\t%u\t%.6f\t%.6f\n", c, js[p], gp[p], gc[p]);
+          V += buf;
+        }
+    }
+  }
+  std::string& G = *genomes_tsv;
+  G = "name\tcluster\thashes\tunique\tcore\tsoft_core\tshell\tcloud\ttypicality\n";
+  for (uint32_t g = 0; g < n; g++) {
+    const rtc_pan_genome& r = gen[g];
+    const uint64_t hashes = (uint64_t)r.core + r.soft + r.shell + r.cloud;  // every hash of a clustered genome has a class
+    const size_t size = label[g] >= 0 ? clusters[label[g]].size() : 0;
+    snprintf(buf, sizeof buf, "\t%d\t%llu\t%u\t%u\t%u\t%u\t%u\t", label[g], (unsigned long long)hashes, r.unique, r.core, r.soft, r.shell, r.cloud);
+    G += name(g);
+    G += buf;
+    if (hashes && size) {
+      snprintf(buf, sizeof buf, "%.6f", (double)r.occ_sum / ((double)hashes * (double)size));
+      G += buf;
+    } else {
+      G += "-";
+    }
+    G += "\n";
+  }
+  return share_n ? share_sum / (double)share_n : 0.0;
+}
+
 void print_phylip_tree(const std::vector<GenomeInfo>& g, const std::vector<rtc_edge>& mst, bool sketchByFile, const std::string& output) {
   FILE* fp = open_out(output, "print_phylip_tree");
   fprintf(fp, "1\n%s\n", get_newick_tree(g, mst, sketchByFile).c_str());

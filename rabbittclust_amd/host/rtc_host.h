@@ -234,6 +234,23 @@ double quality_report_text(const std::function<std::string(uint32_t)>& name, con
 double support_report_text(const std::function<std::string(uint32_t)>& name, const std::vector<std::vector<int>>& clusters, const rtc_csupport* rec,
                            const uint64_t* together, uint32_t n, uint32_t replicates, std::string* support_tsv, std::string* genomes_tsv);
 
+// ---- clust-mst --pangenome: the four reports of rtc_pangenome's records (include/rtclust.h).  clusters: the run's, numbered as
+// <output> numbers them, every genome in exactly one; rec and hist in the library's order, that of the clusters' smallest members;
+// gen[g] per genome.  Every real number is %.6f.
+//   pan_tsv: a header, then a line a cluster in the order of `clusters` -- cluster, size, hashes (total), pan, core, soft_core,
+//     shell, cloud, singletons, core_share = core / pan (- without a hash), new_per_genome = hist[1] / size (what the closed form
+//     gives for pan(m) - pan(m - 1)), centre = the name of the member with the largest occ_sum, equal sums to the smaller index.
+//   genomes_tsv: a header, then a line a genome in input order -- name, cluster, hashes, unique, core, soft_core, shell, cloud,
+//     typicality = occ_sum / (hashes size), or - for an empty sketch.
+//   hist_tsv: cluster, f, count for every count > 0.   curve_tsv: cluster, j, pan(j), core(j) at rtc_pan_growth's points, for the
+//     clusters of two or more.
+// growth_fn is rtc_pan_growth (this library does not link the GPU library), run on `threads` host threads.  Returns the mean of
+// core_share over the clusters that have a hash. ----
+typedef int (*pan_growth_fn)(const uint64_t*, uint32_t, int, uint32_t*, double*, double*, uint32_t*);
+double pangenome_report_text(const std::function<std::string(uint32_t)>& name, const std::vector<std::vector<int>>& clusters, const rtc_pan* rec,
+                             const uint64_t* hist, const rtc_pan_genome* gen, uint32_t n, int threads, pan_growth_fn growth_fn, std::string* pan_tsv,
+                             std::string* genomes_tsv, std::string* hist_tsv, std::string* curve_tsv);
+
 // ---- clust-mst --auto-threshold / --stability: the MST edge-length analysis (src/MST.cpp:1743-2376, structs src/MST.h:77-100) ----
 struct EdgeLengthStats {
   double min_dist = 0, max_dist = 0, median_dist = 0, q1_dist = 0, q3_dist = 0, mean_dist = 0, std_dev = 0;
