@@ -1,15 +1,25 @@
 // rtc_community.h -- what rtc_louvain (rtc_louvain.hip) and rtc_leiden (rtc_leiden.hip) share: a level's graph as a CSR built
-// by one sort and one reduce_by_key, the row kernel that scores the communities next to a vertex, and the rows sorted by kernel
-// path.  The comment at the head of rtc_louvain.hip describes the three paths.
+// by one sort and one reduce_by_key, and the rules of the row kernel (rtc_rowtable.h) that score the communities next to a
+// vertex: move_rule for both, place_rule for rtc_leiden_place.  The comment at the head of rtc_louvain.hip describes the three
+// paths.
 #ifndef RTC_COMMUNITY_H
 #define RTC_COMMUNITY_H
 #include "rtc_dbscan_common.h"
+#include "rtc_rowtable.h"
 
 namespace {
 
 typedef __int128 i128;
 constexpr uint32_t LV_WAVE_ROW = 128, LV_WAVE_SLOTS = 256, LV_BLOCK_ROW = 2048, LV_BLOCK_SLOTS = 4096;
-constexpr uint32_t LV_NONE = 0xffffffffu;
+constexpr uint32_t LV_NONE = RT_NONE;
+constexpr uint32_t LV_WAVE_WGS_PER_CU = 32, LV_BLOCK_WGS_PER_CU = 3, LV_GLOBAL_WGS_PER_CU = 8;
+// 12-byte slots (the community, the weight into it); a global table has 1 << 13 slots or more: above 2 * LV_BLOCK_ROW
+struct lv_shape {
+  static constexpr uint32_t WAVE_ROW = LV_WAVE_ROW, WAVE_SLOTS = LV_WAVE_SLOTS, BLOCK_ROW = LV_BLOCK_ROW, BLOCK_SLOTS = LV_BLOCK_SLOTS;
+  static constexpr uint32_t GLOBAL_LOG2_MIN = 13;
+  static constexpr uint32_t WGS_PER_CU[3] = {LV_WAVE_WGS_PER_CU, LV_BLOCK_WGS_PER_CU, LV_GLOBAL_WGS_PER_CU};
+  static constexpr bool CNT = false;
+};
 constexpr uint32_t LV_MAX_ROUNDS = 64, LV_MAX_LEVELS = 32;
 
 struct LevelView {
@@ -26,127 +36,97 @@ struct LevelView {
   const uint32_t* target;   // the refined community is an eligible target in this round
 };
 
-// Row list[it] decides.  SLOTS > 0: the table lies in LDS; SLOTS == 0: in global memory, 1 << tab_log2[it] slots from
-// tab_off[it] on.  The score of community d is e_d A - gB nu_x (tot_d - [d == c] nu_x) (include/rtclust.h: rtc_leiden's table
-// of A and B; rtc_louvain is its modularity row).  A < 2^62 and gB < 2^52.
-// PROPOSE false, a move round: comm_new holds comm on entry; moves counts the rows that change community.
+// the order of (score, community): larger score, then smaller community
+__device__ __forceinline__ bool lv_better(i128 sc, uint32_t d, i128 best, uint32_t best_d) { return sc > best || (sc == best && d < best_d); }
+
+// row_kernel's rule for a move or a refinement round; the table holds the weight into each neighbouring community.  The score
+// of community d is e_d A - gB nu_x (tot_d - [d == c] nu_x) (include/rtclust.h: rtc_leiden's table of A and B; rtc_louvain is
+// its modularity row).  A < 2^62 and gB < 2^52.
+// PROPOSE false, a move round: out holds comm on entry; count counts the rows that change community.
 // PROPOSE true, a refinement round: only an eligible vertex alone in its refined community decides, over the eligible targets
-// that hold a neighbour of its coarse community, and a score of 0 or more is enough; comm_new (all LV_NONE on entry) receives
-// the proposal, moves counts the proposals.
-template <int BLOCK, uint32_t SLOTS, bool PROPOSE>
-__global__ __launch_bounds__(BLOCK) void louvain_move_kernel(const uint32_t* __restrict__ list, uint32_t n_list, LevelView G, uint64_t A, uint64_t gB,
-                                                             int odd, const uint64_t* __restrict__ tab_off, const uint32_t* __restrict__ tab_log2,
-                                                             uint32_t* gkeys, unsigned long long* gvals, uint32_t* __restrict__ comm_new,
-                                                             unsigned long long* __restrict__ moves) {
-  __shared__ uint32_t s_keys[SLOTS ? SLOTS : 1];
-  __shared__ unsigned long long s_vals[SLOTS ? SLOTS : 1];
-  __shared__ unsigned long long s_hi[4], s_lo[4];
-  __shared__ uint32_t s_d[4];
-  const i128 m2s = (i128)A;
-  for (uint32_t it = blockIdx.x; it < n_list; it += gridDim.x) {  // uniform over the workgroup: the barriers below are reached by all
-    const uint32_t x = list[it];
-    uint32_t cx = 0;
+// that hold a neighbour of its coarse community, and a score of 0 or more is enough; out (all LV_NONE on entry) receives the
+// proposal, count counts the proposals.
+struct MoveArgs : LevelView { uint64_t A, gB; int odd; uint32_t* out; unsigned long long* count; };
+// (score, community) under lv_better.  LV_NONE stands for staying, at S(c): a candidate needs a score strictly above it, so
+// none ever ties with it.
+struct __attribute__((packed, aligned(4))) LvBest { i128 s; uint32_t d; };
+template <bool PROPOSE>
+struct move_rule {
+  typedef lv_shape shape;
+  typedef RowTable<lv_shape::CNT, /* AGENT_READS */ false> Table;
+  typedef MoveArgs Args;
+  typedef LvBest Best;
+  struct Lds { Best best[4]; };
+  uint32_t cx, c;
+  i128 gk, stay;
+
+  __device__ __forceinline__ bool enter(const Args& G, uint32_t x) {
+    cx = 0;
     if (PROPOSE) {
-      if (!G.elig[x] || G.members[x] != 1) continue;  // uniform too: x is
+      if (!G.elig[x] || G.members[x] != 1) return false;
       cx = G.coarse[x];
     }
-    uint32_t* keys = s_keys;
-    unsigned long long* vals = s_vals;
-    uint32_t log2_slots = 31 - __builtin_clz(SLOTS ? SLOTS : 1u);
-    if (!SLOTS) {
-      keys = gkeys + tab_off[it];
-      vals = gvals + tab_off[it];
-      log2_slots = tab_log2[it];
-    }
-    const uint32_t slots = 1u << log2_slots, mask = slots - 1, shift = 32 - log2_slots;
-    for (uint32_t s = threadIdx.x; s < slots; s += BLOCK) { keys[s] = LV_NONE; vals[s] = 0ull; }
-    __syncthreads();
-    const uint64_t r0 = G.row_off[x], r1 = G.row_off[x + 1];
-    for (uint64_t e = r0 + threadIdx.x; e < r1; e += BLOCK) {
-      const uint32_t y = (uint32_t)G.key[e];
-      if (y == x) continue;  // the self entry is no neighbour
-      if (PROPOSE && G.coarse[y] != cx) continue;
-      const uint32_t d = G.comm[y];
-      uint32_t h = (d * 2654435761u) >> shift;
-      for (;;) {
-        const uint32_t old = atomicCAS(&keys[h], LV_NONE, d);
-        if (old == LV_NONE || old == d) break;
-        h = (h + 1) & mask;
-      }
-      atomicAdd(&vals[h], (unsigned long long)G.w[e]);
-    }
-    __syncthreads();
-    const uint32_t c = G.comm[x];
+    return true;
+  }
+  __device__ __forceinline__ void gather(const Args& G, const Table& tab, uint32_t x, uint64_t e) {
+    const uint32_t y = (uint32_t)G.key[e];
+    if (y == x) return;  // the self entry is no neighbour
+    if (PROPOSE && G.coarse[y] != cx) return;
+    const uint32_t h = tab.claim(G.comm[y]);
+    atomicAdd(&tab.sum[h], (unsigned long long)G.w[e]);
+  }
+  template <int BLOCK>
+  __device__ __forceinline__ void gathered(Lds&) {}
+  template <int BLOCK>
+  __device__ __forceinline__ Best begin(const Args& G, const Table& tab, uint32_t x, const Lds&) {
+    c = G.comm[x];
     const uint64_t kx = G.nu[x];
     uint64_t e_c = 0;
-    if (!PROPOSE)
-      for (uint32_t h = (c * 2654435761u) >> shift;; h = (h + 1) & mask) {
-        const uint32_t key = keys[h];
-        if (key == c) e_c = vals[h];
-        if (key == c || key == LV_NONE) break;
-      }
-    const i128 gk = (i128)gB * (i128)kx;
+    if (!PROPOSE) {
+      const uint32_t h = tab.find(c);
+      if (h != RT_NONE) e_c = tab.read(&tab.sum[h]);
+    }
+    gk = (i128)G.gB * (i128)kx;
     // a lone vertex of the refinement stays at score 0 and takes a candidate at 0 or more: above -1
-    const i128 stay = PROPOSE ? (i128)-1 : (i128)e_c * m2s - gk * (i128)(G.tot[c] - kx);
-    // (score, community) in the order: larger score, then smaller community.  LV_NONE stands for staying, at S(c): a
-    // candidate needs a score strictly above it, so none ever ties with it.
-    i128 best = stay;
-    uint32_t best_d = LV_NONE;
-    for (uint32_t s = threadIdx.x; s < slots; s += BLOCK) {
-      const uint32_t d = keys[s];
-      if (d == LV_NONE || d == c || (odd ? d < c : d > c)) continue;
-      if (PROPOSE && !G.target[d]) continue;
-      const i128 sc = (i128)vals[s] * m2s - gk * (i128)G.tot[d];
-      if (!(sc > stay)) continue;
-      if (sc > best || (sc == best && d < best_d)) { best = sc; best_d = d; }
-    }
-    for (int off = 32; off; off >>= 1) {
-      const unsigned long long ohi = __shfl_xor((unsigned long long)((unsigned __int128)best >> 64), off);
-      const unsigned long long olo = __shfl_xor((unsigned long long)best, off);
-      const uint32_t od = __shfl_xor(best_d, off);
-      const i128 o = (i128)(((unsigned __int128)ohi << 64) | olo);
-      if (o > best || (o == best && od < best_d)) { best = o; best_d = od; }
-    }
-    if (BLOCK > 64) {
-      const uint32_t wave = threadIdx.x / 64;
-      if ((threadIdx.x & 63) == 0) {
-        s_hi[wave] = (unsigned long long)((unsigned __int128)best >> 64);
-        s_lo[wave] = (unsigned long long)best;
-        s_d[wave] = best_d;
-      }
-      __syncthreads();
-      if (threadIdx.x == 0)
-        for (uint32_t wv = 1; wv < BLOCK / 64; wv++) {
-          const i128 o = (i128)(((unsigned __int128)s_hi[wv] << 64) | s_lo[wv]);
-          if (o > best || (o == best && s_d[wv] < best_d)) { best = o; best_d = s_d[wv]; }
-        }
-    }
-    if (threadIdx.x == 0 && best_d != LV_NONE) {
-      comm_new[x] = best_d;
-      atomicAdd(moves, 1ull);
-    }
-    __syncthreads();  // the table and the wave slots are written again in the next turn
+    stay = PROPOSE ? (i128)-1 : (i128)e_c * (i128)G.A - gk * (i128)(G.tot[c] - kx);
+    return Best{stay, LV_NONE};
   }
-}
+  __device__ __forceinline__ void sweep(const Args& G, const Table& tab, uint32_t s, Best& best) {
+    const uint32_t d = tab.read(&tab.keys[s]);
+    if (d == LV_NONE || d == c || (G.odd ? d < c : d > c)) return;
+    if (PROPOSE && !G.target[d]) return;
+    const i128 sc = (i128)tab.read(&tab.sum[s]) * (i128)G.A - gk * (i128)G.tot[d];
+    if (!(sc > stay)) return;
+    if (lv_better(sc, d, best.s, best.d)) best = Best{sc, d};
+  }
+  static __device__ __forceinline__ void fold(Best& best, const Best& o) {
+    if (lv_better(o.s, o.d, best.s, best.d)) best = o;
+  }
+  __device__ __forceinline__ void finish(const Args& G, const Table&, uint32_t x, uint64_t, const Best& best) {
+    if (best.d == LV_NONE) return;
+    G.out[x] = best.d;
+    atomicAdd(G.count, 1ull);
+  }
+};
 
-// ---- placement (rtc_leiden_place, rtc_leiden_assign.hip): the move kernel's sibling for a vertex that is not in the graph ----
-// The move kernel's table and order, as functions: open addressing over 1 << (32 - shift) slots with its hash, keys all LV_NONE
-// on entry.  Returns community d's slot, claimed if it had none; the caller adds the weight to vals[slot].  (louvain_move_kernel
-// keeps its own lines: written through these functions its instruction stream comes out differently.)
-__device__ __forceinline__ uint32_t lv_table_slot(uint32_t* keys, uint32_t d, uint32_t shift, uint32_t mask) {
-  uint32_t h = (d * 2654435761u) >> shift;
-  for (;;) {
-    const uint32_t old = atomicCAS(&keys[h], LV_NONE, d);
-    if (old == LV_NONE || old == d) break;
-    h = (h + 1) & mask;
-  }
-  return h;
-}
-// the move kernel's order of (score, community): larger score, then smaller community
-__device__ __forceinline__ bool lv_better(i128 sc, uint32_t d, i128 best, uint32_t best_d) { return sc > best || (sc == best && d < best_d); }
-// The two best communities of a row under lv_better, with the weight into each.  d == LV_NONE at score 0: none -- a candidate
-// needs a score above 0, so it beats every such entry and no such entry beats anything.
-struct LvTop2 { i128 s[2]; uint64_t e[2]; uint32_t d[2]; };
+// ---- placement (rtc_leiden_place, rtc_leiden_assign.hip): a vertex that is not in the graph ----
+// Query x's row holds its records (key: query << 32 | model genome, equal keys summed).  The table is the move rule's, keyed by
+// the model genome's community; tot[d] is N_d (CPM) or tot_d (modularity).  The score is the one of a vertex alone in a
+// community of its own in the model's graph with the query added (include/rtclust.h: rtc_leiden_place):
+//   CPM         S(d) = e_d 65536 - g 2^20 N_d
+//   modularity  S(d) = e_d (M2 + 2 k_x) 65536 - g k_x (tot_d + e_d),   M2 + 2 k_x < 2^46 (the host refuses more)
+// Lane 0 writes the query's record; nothing else touches it.
+struct PlaceArgs {
+  const uint64_t *row_off, *key, *w, *tot;
+  const int32_t* labels;
+  int modularity;
+  uint64_t g, m2;
+  rtc_leiden_placement* out;
+};
+// The two best communities of a row under lv_better, with the weight into each, and how many communities the lane saw.
+// d == LV_NONE at score 0: none -- a candidate needs a score above 0, so it beats every such entry and no such entry beats
+// anything.
+struct __attribute__((packed, aligned(4))) LvTop2 { i128 s[2]; uint64_t e[2]; uint32_t d[2]; uint32_t nc; };
 __device__ __forceinline__ void lv_top2_insert(LvTop2& t, i128 sc, uint32_t d, uint64_t e) {
   if (lv_better(sc, d, t.s[0], t.d[0])) {
     t.s[1] = t.s[0]; t.d[1] = t.d[0]; t.e[1] = t.e[0];
@@ -155,109 +135,57 @@ __device__ __forceinline__ void lv_top2_insert(LvTop2& t, i128 sc, uint32_t d, u
     t.s[1] = sc; t.d[1] = d; t.e[1] = e;
   }
 }
-__device__ __forceinline__ i128 lv_shfl_xor(i128 v, int off) {
-  const unsigned long long hi = __shfl_xor((unsigned long long)((unsigned __int128)v >> 64), off);
-  const unsigned long long lo = __shfl_xor((unsigned long long)v, off);
-  return (i128)(((unsigned __int128)hi << 64) | lo);
-}
+struct place_rule {
+  typedef lv_shape shape;
+  typedef RowTable<lv_shape::CNT, /* AGENT_READS */ false> Table;
+  typedef PlaceArgs Args;
+  typedef LvTop2 Best;
+  struct Lds { Best best[4]; unsigned long long k[4]; };
+  unsigned long long kx;
+  i128 A, gB;
 
-// Query list[it]'s row holds its records (key: query << 32 | model genome, equal keys summed).  The table is the move kernel's,
-// keyed by the model genome's community; tot[d] is N_d (CPM) or tot_d (modularity).  The score is the one of a vertex alone in
-// a community of its own in the model's graph with the query added (include/rtclust.h: rtc_leiden_place):
-//   CPM         S(d) = e_d 65536 - g 2^20 N_d
-//   modularity  S(d) = e_d (M2 + 2 k_x) 65536 - g k_x (tot_d + e_d),   M2 + 2 k_x < 2^46 (the host refuses more)
-// Lane 0 writes the query's record; nothing else touches it.
-template <int BLOCK, uint32_t SLOTS>
-__global__ __launch_bounds__(BLOCK) void leiden_place_kernel(const uint32_t* __restrict__ list, uint32_t n_list, const uint64_t* __restrict__ row_off,
-                                                             const uint64_t* __restrict__ key, const uint64_t* __restrict__ w,
-                                                             const int32_t* __restrict__ labels, const uint64_t* __restrict__ tot, int modularity,
-                                                             uint64_t g, uint64_t m2, const uint64_t* __restrict__ tab_off,
-                                                             const uint32_t* __restrict__ tab_log2, uint32_t* gkeys, unsigned long long* gvals,
-                                                             rtc_leiden_placement* __restrict__ out) {
-  __shared__ uint32_t s_keys[SLOTS ? SLOTS : 1];
-  __shared__ unsigned long long s_vals[SLOTS ? SLOTS : 1];
-  __shared__ unsigned long long s_k[4];
-  __shared__ uint32_t s_n[4];
-  __shared__ LvTop2 s_top[4];
-  for (uint32_t it = blockIdx.x; it < n_list; it += gridDim.x) {  // uniform over the workgroup
-    const uint32_t x = list[it];
-    uint32_t* keys = s_keys;
-    unsigned long long* vals = s_vals;
-    uint32_t log2_slots = 31 - __builtin_clz(SLOTS ? SLOTS : 1u);
-    if (!SLOTS) {
-      keys = gkeys + tab_off[it];
-      vals = gvals + tab_off[it];
-      log2_slots = tab_log2[it];
-    }
-    const uint32_t slots = 1u << log2_slots, mask = slots - 1, shift = 32 - log2_slots;
-    for (uint32_t s = threadIdx.x; s < slots; s += BLOCK) { keys[s] = LV_NONE; vals[s] = 0ull; }
-    __syncthreads();
-    const uint64_t r0 = row_off[x], r1 = row_off[x + 1];
-    unsigned long long kx = 0;
-    for (uint64_t e = r0 + threadIdx.x; e < r1; e += BLOCK) {
-      const uint64_t we = w[e];
-      const uint32_t h = lv_table_slot(keys, (uint32_t)labels[(uint32_t)key[e]], shift, mask);
-      atomicAdd(&vals[h], (unsigned long long)we);
-      kx += we;
-    }
-    for (int off = 32; off; off >>= 1) kx += __shfl_xor(kx, off);
-    if (BLOCK > 64) {
-      if ((threadIdx.x & 63) == 0) s_k[threadIdx.x / 64] = kx;
-    }
-    __syncthreads();  // the table is complete, and so are the waves' sums
-    if (BLOCK > 64) {
-      kx = 0;
-      for (uint32_t wv = 0; wv < BLOCK / 64; wv++) kx += s_k[wv];
-    }
-    const i128 A = modularity ? (i128)(m2 + 2 * kx) * 65536 : (i128)65536;
-    const i128 gB = modularity ? (i128)g * (i128)kx : (i128)g * 1048576;
-    LvTop2 t;
-    t.s[0] = t.s[1] = 0; t.d[0] = t.d[1] = LV_NONE; t.e[0] = t.e[1] = 0;
-    uint32_t nc = 0;
-    for (uint32_t s = threadIdx.x; s < slots; s += BLOCK) {
-      const uint32_t d = keys[s];
-      if (d == LV_NONE) continue;
-      nc++;
-      const uint64_t ed = vals[s];
-      const i128 sc = (i128)ed * A - gB * (i128)(tot[d] + (modularity ? ed : 0ull));
-      if (sc > 0) lv_top2_insert(t, sc, d, ed);
-    }
-    for (int off = 32; off; off >>= 1) {
-      nc += __shfl_xor(nc, off);
-      LvTop2 o;
-      for (int j = 0; j < 2; j++) {
-        o.s[j] = lv_shfl_xor(t.s[j], off);
-        o.d[j] = __shfl_xor(t.d[j], off);
-        o.e[j] = __shfl_xor((unsigned long long)t.e[j], off);
-      }
-      lv_top2_insert(t, o.s[0], o.d[0], o.e[0]);
-      lv_top2_insert(t, o.s[1], o.d[1], o.e[1]);
-    }
-    if (BLOCK > 64) {
-      if ((threadIdx.x & 63) == 0) { s_top[threadIdx.x / 64] = t; s_n[threadIdx.x / 64] = nc; }
-      __syncthreads();
-      if (threadIdx.x == 0)
-        for (uint32_t wv = 1; wv < BLOCK / 64; wv++) {
-          const LvTop2 o = s_top[wv];
-          lv_top2_insert(t, o.s[0], o.d[0], o.e[0]);
-          lv_top2_insert(t, o.s[1], o.d[1], o.e[1]);
-          nc += s_n[wv];
-        }
-    }
-    if (threadIdx.x == 0) {
-      rtc_leiden_placement r;
-      r.label = t.d[0] == LV_NONE ? -1 : (int32_t)t.d[0];
-      r.runner_up = t.d[1] == LV_NONE ? -1 : (int32_t)t.d[1];
-      r.n_edges = (uint32_t)(r1 - r0);
-      r.n_comms = nc;
-      r.k_x = kx;
-      r.e_label = t.e[0];
-      r.e_runner = t.e[1];
-      out[x] = r;
-    }
-    __syncthreads();  // the table and the wave slots are written again in the next turn
+  static __device__ __forceinline__ void add(unsigned long long& k, unsigned long long o) { k += o; }
+  __device__ __forceinline__ bool enter(const Args&, uint32_t) { kx = 0; return true; }
+  __device__ __forceinline__ void gather(const Args& P, const Table& tab, uint32_t, uint64_t e) {
+    const uint64_t we = P.w[e];
+    const uint32_t h = tab.claim((uint32_t)P.labels[(uint32_t)P.key[e]]);
+    atomicAdd(&tab.sum[h], (unsigned long long)we);
+    kx += we;
   }
-}
+  template <int BLOCK>
+  __device__ __forceinline__ void gathered(Lds& lds) { kx = row_reduce_wave<BLOCK>(kx, add, lds.k); }
+  template <int BLOCK>
+  __device__ __forceinline__ Best begin(const Args& P, const Table&, uint32_t, const Lds& lds) {
+    kx = row_reduce_all<BLOCK>(kx, add, lds.k);
+    A = P.modularity ? (i128)(P.m2 + 2 * kx) * 65536 : (i128)65536;
+    gB = P.modularity ? (i128)P.g * (i128)kx : (i128)P.g * 1048576;
+    return Best{{0, 0}, {0, 0}, {LV_NONE, LV_NONE}, 0};
+  }
+  __device__ __forceinline__ void sweep(const Args& P, const Table& tab, uint32_t s, Best& t) {
+    const uint32_t d = tab.read(&tab.keys[s]);
+    if (d == LV_NONE) return;
+    t.nc++;
+    const uint64_t ed = tab.read(&tab.sum[s]);
+    const i128 sc = (i128)ed * A - gB * (i128)(P.tot[d] + (P.modularity ? ed : 0ull));
+    if (sc > 0) lv_top2_insert(t, sc, d, ed);
+  }
+  static __device__ __forceinline__ void fold(Best& t, const Best& o) {
+    lv_top2_insert(t, o.s[0], o.d[0], o.e[0]);
+    lv_top2_insert(t, o.s[1], o.d[1], o.e[1]);
+    t.nc += o.nc;
+  }
+  __device__ __forceinline__ void finish(const Args& P, const Table&, uint32_t x, uint64_t len, const Best& t) {
+    rtc_leiden_placement r;
+    r.label = t.d[0] == LV_NONE ? -1 : (int32_t)t.d[0];
+    r.runner_up = t.d[1] == LV_NONE ? -1 : (int32_t)t.d[1];
+    r.n_edges = (uint32_t)len;
+    r.n_comms = t.nc;
+    r.k_x = kx;
+    r.e_label = t.e[0];
+    r.e_runner = t.e[1];
+    P.out[x] = r;
+  }
+};
 
 // level 0: record e as two directed entries (u == v: twice the self entry, 2q in all)
 __global__ __launch_bounds__(256) void louvain_entries_kernel(const rtc_wedge* __restrict__ edges, uint64_t m, uint64_t* __restrict__ key,
@@ -368,92 +296,6 @@ struct Louvain {
                        (uint64_t)cnt, (unsigned long long*)k);
     RTC_CHECK_LAUNCH(ctx);
     return RTC_OK;
-  }
-};
-
-
-// The rows of a level by kernel path (which one a row takes depends on its length alone) and the tables of the long ones.
-struct RowPaths {
-  std::vector<uint64_t> h_row, h_off;
-  std::vector<uint32_t> lists[3], h_log2;
-  uint32_t* d_list[3] = {nullptr, nullptr, nullptr};
-  uint32_t *d_log2 = nullptr, *d_gkeys = nullptr;
-  uint64_t* d_off = nullptr;
-  unsigned long long* d_gvals = nullptr;
-
-  // synchronises the stream: the host lists are rewritten at the next level
-  int prepare(Louvain& L, uint32_t nl, const char* who) {
-    rtc_ctx* ctx = L.ctx;
-    hipStream_t s = ctx->stream;
-    h_row.resize((size_t)nl + 1);
-    RTC_HIP(ctx, hipMemcpyAsync(h_row.data(), L.row_off, ((size_t)nl + 1) * 8, hipMemcpyDeviceToHost, s));
-    RTC_HIP(ctx, hipStreamSynchronize(s));
-    for (auto& l : lists) l.clear();
-    h_log2.clear();
-    h_off.clear();
-    uint64_t table_slots = 0;
-    for (uint32_t x = 0; x < nl; x++) {
-      const uint64_t len = h_row[x + 1] - h_row[x];
-      if (len == 0) continue;  // no neighbour: it stays
-      if (len <= LV_WAVE_ROW) lists[0].push_back(x);
-      else if (len <= LV_BLOCK_ROW) lists[1].push_back(x);
-      else {
-        uint32_t lg = 13;  // above 2 * LV_BLOCK_ROW
-        while ((1ull << lg) < 2 * len) lg++;
-        if (lg > 31) return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "%s: a row of %llu entries", who, (unsigned long long)len);
-        lists[2].push_back(x);
-        h_log2.push_back(lg);
-        h_off.push_back(table_slots);
-        table_slots += 1ull << lg;
-      }
-    }
-    for (int p = 0; p < 3; p++)
-      if (!lists[p].empty()) {
-        RTC_TRY(L.db.get(ctx, lists[p].size(), &d_list[p]));
-        RTC_HIP(ctx, hipMemcpyAsync(d_list[p], lists[p].data(), lists[p].size() * 4, hipMemcpyHostToDevice, s));
-      }
-    if (!lists[2].empty()) {
-      RTC_TRY(L.db.get(ctx, h_log2.size(), &d_log2));
-      RTC_TRY(L.db.get(ctx, h_off.size(), &d_off));
-      RTC_TRY(L.db.get(ctx, table_slots, &d_gkeys));
-      RTC_TRY(L.db.get(ctx, table_slots, &d_gvals));
-      RTC_HIP(ctx, hipMemcpyAsync(d_log2, h_log2.data(), h_log2.size() * 4, hipMemcpyHostToDevice, s));
-      RTC_HIP(ctx, hipMemcpyAsync(d_off, h_off.data(), h_off.size() * 8, hipMemcpyHostToDevice, s));
-    }
-    RTC_HIP(ctx, hipStreamSynchronize(s));
-    return RTC_OK;
-  }
-
-  // one round over every row: the three launches
-  template <bool PROPOSE>
-  int launch(rtc_ctx* ctx, const LevelView& G, uint64_t A, uint64_t gB, int odd, uint32_t* out, unsigned long long* count) {
-    hipStream_t s = ctx->stream;
-    if (!lists[0].empty()) {
-      const uint32_t nb = (uint32_t)std::min<uint64_t>(lists[0].size(), (uint64_t)ctx->num_cu * 32);
-      hipLaunchKernelGGL((louvain_move_kernel<64, LV_WAVE_SLOTS, PROPOSE>), dim3(nb), dim3(64), 0, s, (const uint32_t*)d_list[0],
-                         (uint32_t)lists[0].size(), G, A, gB, odd, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                         (unsigned long long*)nullptr, out, count);
-      RTC_CHECK_LAUNCH(ctx);
-    }
-    if (!lists[1].empty()) {
-      const uint32_t nb = (uint32_t)std::min<uint64_t>(lists[1].size(), (uint64_t)ctx->num_cu * 3);
-      hipLaunchKernelGGL((louvain_move_kernel<256, LV_BLOCK_SLOTS, PROPOSE>), dim3(nb), dim3(256), 0, s, (const uint32_t*)d_list[1],
-                         (uint32_t)lists[1].size(), G, A, gB, odd, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                         (unsigned long long*)nullptr, out, count);
-      RTC_CHECK_LAUNCH(ctx);
-    }
-    if (!lists[2].empty()) {
-      const uint32_t nb = (uint32_t)std::min<uint64_t>(lists[2].size(), (uint64_t)ctx->num_cu * 8);
-      hipLaunchKernelGGL((louvain_move_kernel<256, 0, PROPOSE>), dim3(nb), dim3(256), 0, s, (const uint32_t*)d_list[2], (uint32_t)lists[2].size(),
-                         G, A, gB, odd, (const uint64_t*)d_off, (const uint32_t*)d_log2, d_gkeys, d_gvals, out, count);
-      RTC_CHECK_LAUNCH(ctx);
-    }
-    return RTC_OK;
-  }
-
-  void release(Louvain& L) {
-    for (void** q : {(void**)&d_list[0], (void**)&d_list[1], (void**)&d_list[2], (void**)&d_log2, (void**)&d_off, (void**)&d_gkeys, (void**)&d_gvals})
-      if (*q) { L.db.release(*q); *q = nullptr; }
   }
 };
 

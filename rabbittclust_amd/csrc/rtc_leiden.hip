@@ -161,7 +161,7 @@ extern "C" int rtc_leiden(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, ui
   LD_LAUNCH(louvain_iota_kernel, n, n, start);
 
   std::vector<int32_t> h_new(n);
-  RowPaths P;
+  RowPaths<lv_shape> P;
   uint32_t ncl = n;
   for (uint32_t iteration = 0; iteration < LD_MAX_ITERATIONS; iteration++) {
     uint32_t nl = n;
@@ -179,7 +179,7 @@ extern "C" int rtc_leiden(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, ui
 
     uint32_t levels = 0;
     for (;;) {
-      RTC_TRY(P.prepare(L, nl, who));
+      RTC_TRY(P.prepare(ctx, L.db, L.row_off, nl, who));
       // ---- (a) the move phase, from the partition in L.comm ----
       uint64_t t0 = now_ns();
       RTC_HIP(ctx, hipMemsetAsync(L.tot, 0, (size_t)nl * 8, s));
@@ -189,7 +189,7 @@ extern "C" int rtc_leiden(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, ui
         const LevelView G{L.row_off, L.key, L.w, nu, L.tot, L.comm, nullptr, nullptr, nullptr, nullptr};
         RTC_HIP(ctx, hipMemsetAsync(d_cnt, 0, 8, s));
         RTC_HIP(ctx, hipMemcpyAsync(L.comm_new, L.comm, (size_t)nl * 4, hipMemcpyDeviceToDevice, s));
-        RTC_TRY(P.launch<false>(ctx, G, A, gB, (int)(rounds & 1), L.comm_new, d_cnt));
+        RTC_TRY(P.launch<move_rule<false>>(ctx, MoveArgs{G, A, gB, (int)(rounds & 1), L.comm_new, d_cnt}));
         std::swap(L.comm, L.comm_new);
         RTC_HIP(ctx, hipMemsetAsync(L.tot, 0, (size_t)nl * 8, s));
         LD_LAUNCH(louvain_totals_kernel, nl, (const uint32_t*)L.comm, (const uint64_t*)nu, nl, (unsigned long long*)L.tot);
@@ -223,7 +223,7 @@ extern "C" int rtc_leiden(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, ui
         RTC_HIP(ctx, hipMemsetAsync(prop, 0xff, (size_t)nl * 4, s));
         RTC_HIP(ctx, hipMemsetAsync(d_cnt, 0, 3 * 8, s));
         const LevelView G{L.row_off, L.key, L.w, nu, tot_refined, R, coarse, elig, members, target};
-        RTC_TRY(P.launch<true>(ctx, G, A, gB, (int)(rounds & 1), prop, d_cnt));
+        RTC_TRY(P.launch<move_rule<true>>(ctx, MoveArgs{G, A, gB, (int)(rounds & 1), prop, d_cnt}));
         LD_LAUNCH(leiden_accept_kernel, nl, (const uint32_t*)prop, nl, R, d_cnt + 1);
         unsigned long long cnt[3] = {0, 0, 0};
         RTC_HIP(ctx, hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
@@ -236,7 +236,7 @@ extern "C" int rtc_leiden(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, ui
       C[4] += rounds;
       C[5] += merges;
       C[8] += now_ns() - t0;
-      P.release(L);
+      P.release(L.db);
       levels++;
       C[1]++;
       if (!merges || levels == LV_MAX_LEVELS) break;

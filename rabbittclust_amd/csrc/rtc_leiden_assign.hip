@@ -20,7 +20,8 @@
 // A chunk whose candidates exceed the edge budget or whose join scratch does not fit is halved; RTC_ERR_NOMEM past one query.
 //
 // rtc_leiden_place: the records (query, model genome, q) become a CSR by one radix sort and one reduce_by_key (equal pairs
-// summed), the rows are split by length as a level's rows are (RowPaths) and leiden_place_kernel (rtc_community.h) scores them.
+// summed), the rows are split by length as a level's rows are (RowPaths) and row_kernel under place_rule (rtc_community.h)
+// scores them.
 #include "rtc_community.h"
 #include "rtc_query_chunks.h"
 
@@ -409,31 +410,9 @@ extern "C" int rtc_leiden_place(rtc_ctx* ctx, uint32_t n_db, const int32_t* h_la
   hipLaunchKernelGGL(louvain_rows_kernel, dim3(blocks_for((uint64_t)n_queries + 1, ctx->num_cu)), dim3(256), 0, s, (const uint64_t*)key, (uint64_t)E,
                      n_queries, L.row_off);
   RTC_CHECK_LAUNCH(ctx);
-  RowPaths P;
-  RTC_TRY(P.prepare(L, n_queries, who));
-  const int mod = modularity ? 1 : 0;
-  if (!P.lists[0].empty()) {
-    const uint32_t nb = (uint32_t)std::min<uint64_t>(P.lists[0].size(), (uint64_t)ctx->num_cu * 32);
-    hipLaunchKernelGGL((leiden_place_kernel<64, LV_WAVE_SLOTS>), dim3(nb), dim3(64), 0, s, (const uint32_t*)P.d_list[0], (uint32_t)P.lists[0].size(),
-                       (const uint64_t*)L.row_off, (const uint64_t*)key, (const uint64_t*)w, (const int32_t*)d_labels, (const uint64_t*)d_tot, mod, g,
-                       m2, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (unsigned long long*)nullptr, d_out);
-    RTC_CHECK_LAUNCH(ctx);
-  }
-  if (!P.lists[1].empty()) {
-    const uint32_t nb = (uint32_t)std::min<uint64_t>(P.lists[1].size(), (uint64_t)ctx->num_cu * 3);
-    hipLaunchKernelGGL((leiden_place_kernel<256, LV_BLOCK_SLOTS>), dim3(nb), dim3(256), 0, s, (const uint32_t*)P.d_list[1],
-                       (uint32_t)P.lists[1].size(), (const uint64_t*)L.row_off, (const uint64_t*)key, (const uint64_t*)w, (const int32_t*)d_labels,
-                       (const uint64_t*)d_tot, mod, g, m2, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                       (unsigned long long*)nullptr, d_out);
-    RTC_CHECK_LAUNCH(ctx);
-  }
-  if (!P.lists[2].empty()) {
-    const uint32_t nb = (uint32_t)std::min<uint64_t>(P.lists[2].size(), (uint64_t)ctx->num_cu * 8);
-    hipLaunchKernelGGL((leiden_place_kernel<256, 0>), dim3(nb), dim3(256), 0, s, (const uint32_t*)P.d_list[2], (uint32_t)P.lists[2].size(),
-                       (const uint64_t*)L.row_off, (const uint64_t*)key, (const uint64_t*)w, (const int32_t*)d_labels, (const uint64_t*)d_tot, mod, g,
-                       m2, (const uint64_t*)P.d_off, (const uint32_t*)P.d_log2, P.d_gkeys, P.d_gvals, d_out);
-    RTC_CHECK_LAUNCH(ctx);
-  }
+  RowPaths<lv_shape> P;
+  RTC_TRY(P.prepare(ctx, L.db, L.row_off, n_queries, who));
+  RTC_TRY(P.launch<place_rule>(ctx, PlaceArgs{L.row_off, key, w, d_tot, d_labels, modularity ? 1 : 0, g, m2, d_out}));
   RTC_HIP(ctx, hipMemcpyAsync(h_out, d_out, (size_t)n_queries * sizeof(rtc_leiden_placement), hipMemcpyDeviceToHost, s));
   RTC_HIP(ctx, hipStreamSynchronize(s));
   uint64_t placed = 0, with = 0;
@@ -441,7 +420,7 @@ extern "C" int rtc_leiden_place(rtc_ctx* ctx, uint32_t n_db, const int32_t* h_la
   const uint64_t t1 = now_ns();
   const uint64_t c[10] = {m, E, with, placed, n_queries - placed, P.lists[0].size(), P.lists[1].size(), P.lists[2].size(), t1 - t0, t1 - t_begin};
   std::copy(c, c + 10, ctx->leiden_place);
-  ctx->leiden_place_path = (P.lists[0].empty() ? 0 : 1) | (P.lists[1].empty() ? 0 : 2) | (P.lists[2].empty() ? 0 : 4);
+  ctx->leiden_place_path = P.path_mask();
   return RTC_OK;
 }
 

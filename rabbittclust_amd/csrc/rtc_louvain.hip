@@ -2,8 +2,8 @@
 // the definition, tests/reflouvain.py restates it).
 //   * A level's graph is a CSR of (row << 32 | column) keys in ascending order with u64 weights, built by one rocPRIM radix sort
 //     and one reduce_by_key over the directed entries: the input's at level 0, the relabelled entries of the level below after.
-//   * louvain_move_kernel (rtc_community.h, shared with rtc_leiden.hip) is the hot path: one row per workgroup, the weights to the neighbouring communities summed in a hash
-//     table over community ids (integer atomics: the sums do not depend on the order), every occupied slot scored in 128-bit
+//   * row_kernel (rtc_rowtable.h) under move_rule (rtc_community.h, shared with rtc_leiden.hip) is the hot path: one row per
+//     workgroup, the weights to the neighbouring communities summed in a hash table over community ids (integer atomics: the sums do not depend on the order), every occupied slot scored in 128-bit
 //     integers, the best (score, then smaller id) reduced over the workgroup.  Three launches share the code:
 //       - rows of up to LV_WAVE_ROW entries: a workgroup of ONE wave, its table of LV_WAVE_SLOTS slots in LDS (3 KiB);
 //       - rows of up to LV_BLOCK_ROW entries: 256 lanes, LV_BLOCK_SLOTS slots in LDS (48 KiB, three workgroups on a CU's 160 KiB);
@@ -60,10 +60,10 @@ extern "C" int rtc_louvain(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, u
   RTC_CHECK_LAUNCH(ctx);
   C[7] += now_ns() - t0;
 
-  RowPaths P;
+  RowPaths<lv_shape> P;
   uint32_t levels = 0;
   while (levels < LV_MAX_LEVELS) {
-    RTC_TRY(P.prepare(L, nl, who));
+    RTC_TRY(P.prepare(ctx, L.db, L.row_off, nl, who));
     hipLaunchKernelGGL(louvain_iota_kernel, dim3(blocks_for(nl, ctx->num_cu)), dim3(256), 0, s, nl, L.comm);
     RTC_CHECK_LAUNCH(ctx);
     RTC_HIP(ctx, hipMemcpyAsync(L.tot, L.k, (size_t)nl * 8, hipMemcpyDeviceToDevice, s));
@@ -77,7 +77,7 @@ extern "C" int rtc_louvain(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, u
       const int odd = (int)(rounds & 1);
       RTC_HIP(ctx, hipMemsetAsync(L.d_cnt + 1, 0, 8, s));
       RTC_HIP(ctx, hipMemcpyAsync(L.comm_new, L.comm, (size_t)nl * 4, hipMemcpyDeviceToDevice, s));
-      RTC_TRY(P.launch<false>(ctx, G, M2 << 16, g, odd, L.comm_new, L.d_cnt + 1));
+      RTC_TRY(P.launch<move_rule<false>>(ctx, MoveArgs{G, M2 << 16, g, odd, L.comm_new, L.d_cnt + 1}));
       std::swap(L.comm, L.comm_new);
       RTC_HIP(ctx, hipMemsetAsync(L.tot, 0, (size_t)nl * 8, s));
       hipLaunchKernelGGL(louvain_totals_kernel, dim3(blocks_for(nl, ctx->num_cu)), dim3(256), 0, s, (const uint32_t*)L.comm, (const uint64_t*)L.k, nl,
@@ -93,7 +93,7 @@ extern "C" int rtc_louvain(rtc_ctx* ctx, uint32_t n, const rtc_wedge* h_edges, u
       C[8] += P.lists[2].size();
     }
     C[6] += now_ns() - t0;
-    P.release(L);
+    P.release(L.db);
     levels++;
     C[0] = levels; C[1] += rounds; C[2] += level_moves; C[3] = nl; C[4] = E;
     if (!level_moves) break;

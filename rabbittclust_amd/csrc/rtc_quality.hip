@@ -3,11 +3,11 @@
 //   - The records become a CSR as rtc_louvain's level 0 does (rtc_community.h: one sort, one reduce_by_key); a pair given twice
 //     leaves fewer than 2 m entries, which is how it is found.
 //   - sil_fill_kernel writes every vertex's record as if it had no listed neighbour: all its distances are Q1.
-//   - sil_row_kernel, one row a workgroup, rewrites the record of a clustered vertex with a row: an open-addressing table keyed by
-//     the neighbours' cluster holds the count and the sum of q (integer atomics: order-free), far_q and near_q / near_cluster are
-//     register reductions beside the gather, then every occupied slot is scored and the workgroup reduces the total order
-//     (mean ascending, cluster ascending) with the means compared as 128-bit cross products.  Three paths by row length
-//     (rtc_quality.h), as louvain_move_kernel's; RTC_SIL_GLOBAL=1 sends every row through the global table.
+//   - row_kernel (rtc_rowtable.h) under sil_rule, one row a workgroup, rewrites the record of a clustered vertex with a row: an
+//     open-addressing table keyed by the neighbours' cluster holds the count and the sum of q (integer atomics: order-free), far_q
+//     and near_q / near_cluster are register reductions beside the gather, then every occupied slot is scored and the workgroup
+//     reduces the total order (mean ascending, cluster ascending) with the means compared as 128-bit cross products.  Three paths
+//     by row length (rtc_quality.h), as Louvain's rows; RTC_SIL_GLOBAL=1 sends every row through the global table.
 //   - rtc_cluster_quality: every pair sharing a hash from the pair phase's row chunks (rtc_dbscan_common.h), copied to the host
 //     chunk by chunk, each one's distance through rtc_linkage_distance on the context's host threads, then the above.
 #include <thread>
@@ -26,13 +26,6 @@ __device__ __forceinline__ bool sil_before(uint64_t S1, uint32_t N1, uint32_t d1
   if (d2 == LV_NONE) return true;
   const u128 l = (u128)S1 * N2, r = (u128)S2 * N1;  // S < 2^51, N < 2^31: past 64 bits
   return l < r || (l == r && d1 < d2);
-}
-
-// A slot read after the gather.  The global table was written by this workgroup's atomics, which act in L2: the read goes there
-// too (device scope) and never takes a line the CU's vector cache kept from the fill.
-template <bool GLOBAL, class T>
-__device__ __forceinline__ T sil_slot(const T* p) {
-  return GLOBAL ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
 }
 
 // the record of a vertex none of whose listed neighbours is clustered
@@ -56,108 +49,85 @@ __global__ __launch_bounds__(256) void sil_fill_kernel(const int32_t* __restrict
   for (uint32_t x = blockIdx.x * blockDim.x + threadIdx.x; x < n; x += gridDim.x * blockDim.x) out[x] = sil_bare(label[x], csize, n_clustered);
 }
 
-// Row list[it], a clustered vertex with at least one entry.  SLOTS > 0: the table lies in LDS; SLOTS == 0: in global memory,
-// 1 << tab_log2[it] slots from tab_off[it] on.  Lane 0 writes the vertex's record; nothing else touches it.
-template <int BLOCK, uint32_t SLOTS>
-__global__ __launch_bounds__(BLOCK) void sil_row_kernel(const uint32_t* __restrict__ list, uint32_t n_list, const uint64_t* __restrict__ row_off,
-                                                        const uint64_t* __restrict__ key, const uint64_t* __restrict__ w,
-                                                        const int32_t* __restrict__ label, const uint32_t* __restrict__ csize, uint32_t n_clustered,
-                                                        const uint64_t* __restrict__ tab_off, const uint32_t* __restrict__ tab_log2, uint32_t* gkeys,
-                                                        uint32_t* gcnt, unsigned long long* gsum, rtc_sil* __restrict__ out) {
-  __shared__ uint32_t s_keys[SLOTS ? SLOTS : 1];
-  __shared__ uint32_t s_cnt[SLOTS ? SLOTS : 1];
-  __shared__ unsigned long long s_sum[SLOTS ? SLOTS : 1];
-  __shared__ unsigned long long s_near[4], s_S[4];
-  __shared__ uint32_t s_far[4], s_N[4], s_d[4];
-  for (uint32_t it = blockIdx.x; it < n_list; it += gridDim.x) {  // uniform over the workgroup: the barriers below are reached by all
-    const uint32_t x = list[it];
-    uint32_t* keys = s_keys;
-    uint32_t* cnts = s_cnt;
-    unsigned long long* sums = s_sum;
-    uint32_t log2_slots = 31 - __builtin_clz(SLOTS ? SLOTS : 1u);
-    if (!SLOTS) {
-      keys = gkeys + tab_off[it];
-      cnts = gcnt + tab_off[it];
-      sums = gsum + tab_off[it];
-      log2_slots = tab_log2[it];
-    }
-    const uint32_t slots = 1u << log2_slots, mask = slots - 1, shift = 32 - log2_slots;
-    for (uint32_t s = threadIdx.x; s < slots; s += BLOCK) { keys[s] = LV_NONE; cnts[s] = 0u; sums[s] = 0ull; }
-    __syncthreads();
-    const uint32_t c = (uint32_t)label[x];
-    const uint64_t r0 = row_off[x], r1 = row_off[x + 1];
-    uint32_t far = 0;
-    unsigned long long near = ((unsigned long long)SIL_Q1 << 32) | LV_NONE;  // (q, cluster): the least, q first
-    for (uint64_t e = r0 + threadIdx.x; e < r1; e += BLOCK) {
-      const int32_t dl = label[(uint32_t)key[e]];
-      if (dl < 0) continue;  // an unclustered neighbour is no member of anything
-      const uint32_t d = (uint32_t)dl, q = (uint32_t)w[e];
-      const uint32_t h = lv_table_slot(keys, d, shift, mask);
-      atomicAdd(&sums[h], (unsigned long long)q);
-      atomicAdd(&cnts[h], 1u);
-      if (d == c) far = q > far ? q : far;
-      else {
-        const unsigned long long cand = ((unsigned long long)q << 32) | d;
-        near = cand < near ? cand : near;
-      }
-    }
-    for (int off = 32; off; off >>= 1) {
-      const uint32_t of = __shfl_xor(far, off);
-      const unsigned long long on = __shfl_xor(near, off);
-      far = of > far ? of : far;
-      near = on < near ? on : near;
-    }
-    if (BLOCK > 64) {
-      if ((threadIdx.x & 63) == 0) { s_far[threadIdx.x / 64] = far; s_near[threadIdx.x / 64] = near; }
-    }
-    __syncthreads();  // the table is complete, and so are the waves' far and near
-    if (BLOCK > 64)
-      for (uint32_t wv = 0; wv < BLOCK / 64; wv++) {
-        far = s_far[wv] > far ? s_far[wv] : far;
-        near = s_near[wv] < near ? s_near[wv] : near;
-      }
-    // (mean, cluster) of the best other cluster that holds a listed neighbour
-    uint64_t bS = 0;
-    uint32_t bN = 0, bd = LV_NONE;
-    for (uint32_t s = threadIdx.x; s < slots; s += BLOCK) {
-      const uint32_t d = sil_slot<SLOTS == 0>(&keys[s]);
-      if (d == LV_NONE || d == c) continue;
-      const uint32_t N = csize[d];
-      const uint64_t S = sil_slot<SLOTS == 0>(&sums[s]) + (uint64_t)(N - sil_slot<SLOTS == 0>(&cnts[s])) * SIL_Q1;
-      if (sil_before(S, N, d, bS, bN, bd)) { bS = S; bN = N; bd = d; }
-    }
-    for (int off = 32; off; off >>= 1) {
-      const uint64_t oS = __shfl_xor((unsigned long long)bS, off);
-      const uint32_t oN = __shfl_xor(bN, off), od = __shfl_xor(bd, off);
-      if (sil_before(oS, oN, od, bS, bN, bd)) { bS = oS; bN = oN; bd = od; }
-    }
-    if (BLOCK > 64) {
-      if ((threadIdx.x & 63) == 0) { s_S[threadIdx.x / 64] = bS; s_N[threadIdx.x / 64] = bN; s_d[threadIdx.x / 64] = bd; }
-      __syncthreads();
-      if (threadIdx.x == 0)
-        for (uint32_t wv = 1; wv < BLOCK / 64; wv++)
-          if (sil_before(s_S[wv], s_N[wv], s_d[wv], bS, bN, bd)) { bS = s_S[wv]; bN = s_N[wv]; bd = s_d[wv]; }
-    }
-    if (threadIdx.x == 0) {
-      uint32_t cnt_c = 0;
-      uint64_t sum_c = 0;
-      for (uint32_t h = (c * 2654435761u) >> shift;; h = (h + 1) & mask) {
-        const uint32_t k = sil_slot<SLOTS == 0>(&keys[h]);
-        if (k == c) { cnt_c = sil_slot<SLOTS == 0>(&cnts[h]); sum_c = sil_slot<SLOTS == 0>(&sums[h]); }
-        if (k == c || k == LV_NONE) break;
-      }
-      rtc_sil r = sil_bare((int32_t)c, csize, n_clustered);
-      const uint32_t nc = csize[c];
-      r.a_num = sum_c + (uint64_t)(nc - 1 - cnt_c) * SIL_Q1;
-      r.far_q = cnt_c < nc - 1 ? SIL_Q1 : far;
-      if (bd != LV_NONE && bS < (uint64_t)bN * SIL_Q1) { r.b_num = bS; r.b_den = bN; r.b_cluster = bd; }
-      r.near_q = (uint32_t)(near >> 32);
-      r.near_cluster = (uint32_t)near;
-      out[x] = r;
-    }
-    __syncthreads();  // the table and the wave slots are written again in the next turn
+// 16-byte slots (rtc_quality.h): the cluster, the listed neighbours in it, the sum of their q
+struct sil_shape {
+  static constexpr uint32_t WAVE_ROW = SIL_WAVE_ROW, WAVE_SLOTS = SIL_WAVE_SLOTS, BLOCK_ROW = SIL_BLOCK_ROW, BLOCK_SLOTS = SIL_BLOCK_SLOTS;
+  static constexpr uint32_t GLOBAL_LOG2_MIN = SIL_GLOBAL_LOG2_MIN;
+  static constexpr uint32_t WGS_PER_CU[3] = {SIL_WAVE_WGS_PER_CU, SIL_BLOCK_WGS_PER_CU, SIL_GLOBAL_WGS_PER_CU};
+  static constexpr bool CNT = true;
+};
+struct SilArgs { const uint64_t *row_off, *key, *w; const int32_t* label; const uint32_t* csize; uint32_t n_clustered; rtc_sil* out; };
+struct SilBest { uint64_t S; uint32_t N, d; };  // (mean S / N, cluster) under sil_before
+struct __attribute__((packed, aligned(4))) SilEnds {
+  unsigned long long near;  // (q, cluster) of the nearest listed neighbour in another cluster: the least, q first
+  uint32_t far;             // the largest q of a listed neighbour in the vertex's own cluster
+};
+// row_kernel's rule (rtc_rowtable.h) for row x, a clustered vertex with at least one entry.  Lane 0 writes the vertex's
+// record; nothing else touches it.  A slot of a global table is read at device scope (RowTable: AGENT_READS).
+struct sil_rule {
+  typedef sil_shape shape;
+  typedef RowTable<sil_shape::CNT, /* AGENT_READS */ true> Table;
+  typedef SilArgs Args;
+  typedef SilBest Best;
+  struct Lds { Best best[4]; SilEnds ends[4]; };
+  uint32_t c;
+  SilEnds ends;
+
+  static __device__ __forceinline__ void widen(SilEnds& m, const SilEnds& o) {
+    m.far = o.far > m.far ? o.far : m.far;
+    m.near = o.near < m.near ? o.near : m.near;
   }
-}
+  __device__ __forceinline__ bool enter(const Args& a, uint32_t x) {
+    c = (uint32_t)a.label[x];
+    ends = SilEnds{((unsigned long long)SIL_Q1 << 32) | LV_NONE, 0};
+    return true;
+  }
+  __device__ __forceinline__ void gather(const Args& a, const Table& tab, uint32_t, uint64_t e) {
+    const int32_t dl = a.label[(uint32_t)a.key[e]];
+    if (dl < 0) return;  // an unclustered neighbour is no member of anything
+    const uint32_t d = (uint32_t)dl, q = (uint32_t)a.w[e];
+    const uint32_t h = tab.claim(d);
+    atomicAdd(&tab.sum[h], (unsigned long long)q);
+    atomicAdd(&tab.cnt[h], 1u);
+    if (d == c) ends.far = q > ends.far ? q : ends.far;
+    else {
+      const unsigned long long cand = ((unsigned long long)q << 32) | d;
+      ends.near = cand < ends.near ? cand : ends.near;
+    }
+  }
+  template <int BLOCK>
+  __device__ __forceinline__ void gathered(Lds& lds) { ends = row_reduce_wave<BLOCK>(ends, widen, lds.ends); }
+  // (mean, cluster) of the best other cluster that holds a listed neighbour: none yet
+  template <int BLOCK>
+  __device__ __forceinline__ Best begin(const Args&, const Table&, uint32_t, const Lds& lds) {
+    ends = row_reduce_all<BLOCK>(ends, widen, lds.ends);
+    return Best{0, 0, LV_NONE};
+  }
+  __device__ __forceinline__ void sweep(const Args& a, const Table& tab, uint32_t s, Best& b) {
+    const uint32_t d = tab.read(&tab.keys[s]);
+    if (d == LV_NONE || d == c) return;
+    const uint32_t N = a.csize[d];
+    const uint64_t S = tab.read(&tab.sum[s]) + (uint64_t)(N - tab.read(&tab.cnt[s])) * SIL_Q1;
+    if (sil_before(S, N, d, b.S, b.N, b.d)) b = Best{S, N, d};
+  }
+  static __device__ __forceinline__ void fold(Best& b, const Best& o) {
+    if (sil_before(o.S, o.N, o.d, b.S, b.N, b.d)) b = o;
+  }
+  __device__ __forceinline__ void finish(const Args& a, const Table& tab, uint32_t x, uint64_t, const Best& b) {
+    uint32_t cnt_c = 0;
+    uint64_t sum_c = 0;
+    const uint32_t h = tab.find(c);
+    if (h != RT_NONE) { cnt_c = tab.read(&tab.cnt[h]); sum_c = tab.read(&tab.sum[h]); }
+    rtc_sil r = sil_bare((int32_t)c, a.csize, a.n_clustered);
+    const uint32_t nc = a.csize[c];
+    r.a_num = sum_c + (uint64_t)(nc - 1 - cnt_c) * SIL_Q1;
+    r.far_q = cnt_c < nc - 1 ? SIL_Q1 : ends.far;
+    if (b.d != LV_NONE && b.S < (uint64_t)b.N * SIL_Q1) { r.b_num = b.S; r.b_den = b.N; r.b_cluster = b.d; }
+    r.near_q = (uint32_t)(ends.near >> 32);
+    r.near_cluster = (uint32_t)ends.near;
+    a.out[x] = r;
+  }
+};
 
 // The score of n vertices under h_label from m records that are already known to be in range.  C[0 .. 9]: rtc_silhouette's
 // counters, C[9] left to the caller.  A label out of range and a pair given twice are found here.
@@ -218,69 +188,22 @@ int sil_score(rtc_ctx* ctx, const char* who, uint32_t n, const rtc_wedge* rec, u
       (void)hipStreamSynchronize(s);
       return rtc_fail(ctx, RTC_ERR_ARG, "%s: record %llu gives the pair (%u, %u) a second time", who, (unsigned long long)at, rec[at].u, rec[at].v);
     }
-    // the rows by kernel path, and the tables of the long ones
-    std::vector<uint64_t> h_row((size_t)n + 1), h_off;
-    RTC_HIP(ctx, hipMemcpyAsync(h_row.data(), L.row_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
-    RTC_HIP(ctx, hipStreamSynchronize(s));
+    // the rows by kernel path, and the tables of the long ones: the fill kernel's record of an unclustered vertex stands
+    RowPaths<sil_shape> P;
+    RTC_TRY(P.fetch(ctx, L.row_off, n));
     C[7] = now_ns() - t_csr;
     const uint64_t t_rows = now_ns();
-    std::vector<uint32_t> lists[3], h_log2;
-    uint64_t table_slots = 0;
-    const int all_global = ctx->opt.sil_global;
-    for (uint32_t x = 0; x < n; x++) {
-      const uint64_t len = h_row[x + 1] - h_row[x];
-      if (len == 0 || h_label[x] < 0) continue;  // the fill kernel's record stands
-      if (!all_global && len <= SIL_WAVE_ROW) lists[0].push_back(x);
-      else if (!all_global && len <= SIL_BLOCK_ROW) lists[1].push_back(x);
-      else {
-        uint32_t lg = SIL_GLOBAL_LOG2_MIN;
-        while ((1ull << lg) < 2 * len) lg++;
-        if (lg > 31) return rtc_fail(ctx, RTC_ERR_UNSUPPORTED, "%s: a row of %llu entries", who, (unsigned long long)len);
-        lists[2].push_back(x);
-        h_log2.push_back(lg);
-        h_off.push_back(table_slots);
-        table_slots += 1ull << lg;
-      }
-    }
-    // the lists (4 bytes a row), and 16 bytes a slot and 12 a row for the tables
-    const uint64_t need_tab = 4ull * (lists[0].size() + lists[1].size() + lists[2].size()) + 16 * table_slots + 12ull * lists[2].size() + 4096;
+    RTC_TRY(P.plan(ctx, who, ctx->opt.sil_global != 0, [&](uint32_t x) { return h_label[x] >= 0; }));
+    const uint64_t need_tab = P.bytes() + 4096;
     const uint64_t free_tab = rtc_free_hbm(ctx);
     if (need_tab > free_tab)
       return rtc_fail(ctx, RTC_ERR_NOMEM, "%s: %llu bytes for the row lists and %llu slots of global tables (%llu rows), %llu free", who,
-                      (unsigned long long)need_tab, (unsigned long long)table_slots, (unsigned long long)lists[2].size(),
+                      (unsigned long long)need_tab, (unsigned long long)P.table_slots, (unsigned long long)P.lists[2].size(),
                       (unsigned long long)free_tab);
-    uint32_t *d_list[3] = {nullptr, nullptr, nullptr}, *d_log2 = nullptr, *d_gkeys = nullptr, *d_gcnt = nullptr;
-    uint64_t* d_off = nullptr;
-    unsigned long long* d_gsum = nullptr;
-    for (int p = 0; p < 3; p++)
-      if (!lists[p].empty()) {
-        RTC_TRY(L.db.get(ctx, lists[p].size(), &d_list[p]));
-        RTC_HIP(ctx, hipMemcpyAsync(d_list[p], lists[p].data(), lists[p].size() * 4, hipMemcpyHostToDevice, s));
-        C[4 + p] = lists[p].size();
-        *path |= 1 << p;
-      }
-    if (!lists[2].empty()) {
-      RTC_TRY(L.db.get(ctx, h_log2.size(), &d_log2));
-      RTC_TRY(L.db.get(ctx, h_off.size(), &d_off));
-      RTC_TRY(L.db.get(ctx, table_slots, &d_gkeys));
-      RTC_TRY(L.db.get(ctx, table_slots, &d_gcnt));
-      RTC_TRY(L.db.get(ctx, table_slots, &d_gsum));
-      RTC_HIP(ctx, hipMemcpyAsync(d_log2, h_log2.data(), h_log2.size() * 4, hipMemcpyHostToDevice, s));
-      RTC_HIP(ctx, hipMemcpyAsync(d_off, h_off.data(), h_off.size() * 8, hipMemcpyHostToDevice, s));
-    }
-    // one launch a path; the table arguments are NULL unless a row takes the global path
-    auto launch = [&](auto kernel, uint32_t block, int p, uint32_t wgs_per_cu) -> int {
-      if (lists[p].empty()) return RTC_OK;
-      const uint32_t nb = (uint32_t)std::min<uint64_t>(lists[p].size(), (uint64_t)ctx->num_cu * wgs_per_cu);
-      hipLaunchKernelGGL(kernel, dim3(nb), dim3(block), 0, s, (const uint32_t*)d_list[p], (uint32_t)lists[p].size(), (const uint64_t*)L.row_off,
-                         (const uint64_t*)L.key, (const uint64_t*)L.w, (const int32_t*)d_label, (const uint32_t*)d_csize, n_clustered,
-                         (const uint64_t*)d_off, (const uint32_t*)d_log2, d_gkeys, d_gcnt, d_gsum, d_out);
-      RTC_CHECK_LAUNCH(ctx);
-      return RTC_OK;
-    };
-    RTC_TRY(launch(sil_row_kernel<64, SIL_WAVE_SLOTS>, 64, 0, SIL_WAVE_WGS_PER_CU));
-    RTC_TRY(launch(sil_row_kernel<256, SIL_BLOCK_SLOTS>, 256, 1, SIL_BLOCK_WGS_PER_CU));
-    RTC_TRY(launch(sil_row_kernel<256, 0>, 256, 2, SIL_GLOBAL_WGS_PER_CU));
+    for (int p = 0; p < 3; p++) C[4 + p] = P.lists[p].size();
+    *path |= P.path_mask();
+    RTC_TRY(P.alloc(ctx, L.db));
+    RTC_TRY(P.launch<sil_rule>(ctx, SilArgs{L.row_off, L.key, L.w, d_label, d_csize, n_clustered, d_out}));
     RTC_HIP(ctx, hipStreamSynchronize(s));
     C[8] = now_ns() - t_rows;
   }
