@@ -103,6 +103,8 @@ PAN_WAVE_RECORDS, PAN_WAVE_SLOTS, PAN_WAVE_HIST = 512, 1024, 512
 PAN_BLOCK_RECORDS, PAN_BLOCK_SLOTS, PAN_BLOCK_HIST = 2048, 4096, 1024
 PAN_GLOBAL_LOG2_MIN = 8
 PAN_GLOBAL_WGS_PER_CU = 16  # the arena's count and look-up kernels take a member a wave: 4 * PAN_GLOBAL_WGS_PER_CU waves a CU a turn
+PAN_WAVE_WGS_PER_CU, PAN_BLOCK_WGS_PER_CU = 11, 3  # the LDS paths' grids: at most so many workgroups a CU, a cluster a workgroup and turn
+PAN_SWEEP_BINS = 1024  # the arena's sweep keeps the counts 2 .. PAN_SWEEP_BINS + 1 in bins in LDS; larger ones go to the histogram one by one
 PAN_SLOT_BYTES, PAN_MEMBER_BYTES, PAN_CLUSTER_BYTES = 12, 56, 48
 PAN_EMPTY = 0xFFFFFFFFFFFFFFFF  # the empty slot's key; a hash of this value is counted beside the table
 PAN_MULT = 0x9E3779B97F4A7C15

@@ -1,6 +1,8 @@
 """The sketch sets of tests/test_gpu_pangenome.py and tests/test_cpu_pangenome.py: every set is (sketches, labels), the sketches
 ascending arrays of distinct 32-bit values held as uint64.  materialise() turns them into the hashes of a width: themselves at
-width 4, spread over all 64 bits at width 8, with the largest 32-bit value becoming the largest 64-bit one."""
+width 4, spread over all 64 bits at width 8, with the largest 32-bit value becoming the largest 64-bit one.  The sets at the end
+take the device's CU count and have more clusters than a launch has workgroups (tests/test_cpu_pangenome_turns.py shows what they
+reach, tests/test_gpu_pangenome_turns.py runs them)."""
 import numpy as np
 
 from rabbittclust_amd import api
@@ -166,3 +168,122 @@ def small_identity_sets():
     """what the restatement's own identities are checked on without a GPU"""
     return {"edges": path_edges(), "wide": wide(), "markers": markers(), "labels": mixed_labels(), "arena": several_arena(3),
             "m7": thresholds(7), "m20": thresholds(20)}
+
+
+# ---- sets sized from the device: a workgroup's second turn, the sweep across tables, counts past the sweep's bins ----------------
+# The clusters of these sets stand in input order, so cluster c is the c-th of its path's list and, with a grid of G workgroups,
+# workgroup c % G meets it in turn c // G.  All clusters of a set draw from one small pool: successive clusters of a workgroup
+# hold the same keys, so a slot that was not cleared changes a count.
+SMALL_POOL, SMALL_BIG_EVERY, SMALL_BIG_MEMBERS, SMALL_BIG_RECORDS, SMALL_TALL_MEMBERS, SMALL_TALL_HOLDERS = 24, 50, 20, 300, 600, 150
+BLOCK_POOL, BLOCK_TALL_MEMBERS, BLOCK_TALL_HOLDERS = 700, 1100, 100
+
+
+def _pool(seed, size):
+    """`size` distinct values below 2^31, ascending, 0 among them"""
+    vals = np.random.default_rng(seed).choice(1 << 31, size=size - 1, replace=False).astype(np.uint64)
+    return np.unique(np.concatenate([vals, np.zeros(1, dtype=np.uint64)]))
+
+
+def many_small_layout(num_cu):
+    """where the special clusters of many_small stand: `tall` (of SMALL_TALL_MEMBERS members) once in a workgroup's second turn,
+    between two small clusters of the same workgroup, and once in the first turn; `big` (of SMALL_BIG_RECORDS records) about every
+    SMALL_BIG_EVERY-th of the others"""
+    grid = api.PAN_WAVE_WGS_PER_CU * num_cu
+    n = 2 * api.PAN_GLOBAL_WGS_PER_CU * num_cu + 531
+    p, q = grid // 3 + 7, grid // 6 + 3
+    assert q + grid < p + grid < p + 2 * grid < n and p != q
+    small = {p, p + 2 * grid, q + grid}  # the clusters the two tall ones' workgroups meet before and after them
+    tall = (p + grid, q)
+    big = [c for c in range(SMALL_BIG_EVERY // 2, n, SMALL_BIG_EVERY) if c not in small and c not in tall]
+    return {"clusters": n, "grid": grid, "tall": tall, "big": big, "around": sorted(small)}
+
+
+def many_small(num_cu):
+    """2 * PAN_GLOBAL_WGS_PER_CU * num_cu + 531 clusters over a pool of SMALL_POOL values, all on the wave path by their records:
+    small ones of 2 to 5 members with 0 to 5 hashes each -- one member of every cluster holds the pool's first value, and the
+    all-ones value is in every fifth (cluster + member) -- big ones of 20 members and 300 records (1 024 slots, four tiles, where
+    every cluster is in the arena), and two of 600 members of whom 150 hold 3 hashes: 450 records, and more members than the
+    wave path's LDS histogram has entries."""
+    lay = many_small_layout(num_cu)
+    rng = np.random.default_rng(61)
+    pool = _pool(60, SMALL_POOL)
+    big = set(lay["big"])
+    sketches, labels = [], []
+    for c in range(lay["clusters"]):
+        first = len(sketches)
+        if c in lay["tall"]:
+            for j in range(SMALL_TALL_MEMBERS):
+                k = j // 4
+                sketches.append(_sk([pool[0], pool[1 + k % 5], pool[6 + k % 7]] if j % 4 == 0 else []))
+        elif c in big:
+            for j in range(SMALL_BIG_MEMBERS):
+                per = SMALL_BIG_RECORDS // SMALL_BIG_MEMBERS
+                ones = [ONES32] if j % 3 == 0 else []
+                sketches.append(_sk(rng.choice(pool, size=per - len(ones), replace=False).tolist() + ones))
+                assert len(sketches[-1]) == per
+        else:
+            members = int(rng.integers(2, 6))
+            for i in range(members):
+                held = rng.choice(pool, size=int(rng.integers(0, 4)), replace=False).tolist()
+                held += [int(pool[0])] if i == c % members else []
+                held += [ONES32] if (c + i) % 5 == 0 else []
+                sketches.append(_sk(held))
+        labels += [first] * (len(sketches) - first)
+    return sketches, labels
+
+
+def many_block_layout(num_cu):
+    """many_block's two clusters of BLOCK_TALL_MEMBERS members: one in a workgroup's second turn behind an ordinary cluster, one in
+    the first turn in front of one"""
+    grid = api.PAN_BLOCK_WGS_PER_CU * num_cu
+    return {"clusters": grid + 37, "grid": grid, "tall": (5 + grid, 11)}
+
+
+def many_block(num_cu):
+    """PAN_BLOCK_WGS_PER_CU * num_cu + 37 clusters over a pool of BLOCK_POOL values, all on the workgroup path: 2 to 4 members that
+    together hold 513 to 2 048 records (clusters 1 and 2 exactly those), and two clusters of 1 100 members of whom 100 hold 15
+    hashes: more members than the path's LDS histogram has entries"""
+    lay = many_block_layout(num_cu)
+    rng = np.random.default_rng(71)
+    pool = _pool(70, BLOCK_POOL)
+    lo, hi = api.PAN_WAVE_RECORDS + 1, api.PAN_BLOCK_RECORDS
+    sketches, labels = [], []
+    for c in range(lay["clusters"]):
+        first = len(sketches)
+        if c in lay["tall"]:
+            for j in range(BLOCK_TALL_MEMBERS):
+                at = 1 + 14 * ((j // 11) % 49)
+                sketches.append(_sk([pool[0]] + pool[at:at + 14].tolist() if j % 11 == 0 else []))
+        else:
+            records = lo if c == 1 else hi if c == 2 else int(rng.integers(1100, hi + 1)) if c % 7 == 0 else int(rng.integers(lo, 1100))
+            members = max(int(rng.integers(2, 5)), -(-records // 600))
+            for i in range(members):
+                per = records // members + (1 if i < records % members else 0)
+                sketches.append(_sk(rng.choice(pool, size=per, replace=False)))
+                assert len(sketches[-1]) == per
+        labels += [first] * (len(sketches) - first)
+    return sketches, labels
+
+
+BINS_MEMBERS = 1100
+BINS_COUNTS = (1, 2, 1025, 1025, 1025, 1026, 1026, 1026, 1027, 1099, 1099, BINS_MEMBERS)  # PAN_SWEEP_BINS + 1 is the last count with a bin
+BINS_RUN, BINS_HOMES = 5, 40  # the 64-slot run of the table the twelve hashes live in, and how far into it their probes start
+
+
+def past_the_bins(width):
+    """one arena cluster of 1 100 members and twelve hashes, hash k held by the members 0 .. BINS_COUNTS[k] - 1: the counts on
+    either side of the sweep's last bin, equal and different ones past it, in one wave of one tile.  The twelve values start
+    their probes in the first BINS_HOMES slots of one 64-aligned run of the table (api.pan_slot), so wherever linear probing puts
+    them, they stay in that run."""
+    lg = api.pan_table_log2(sum(BINS_COUNTS))
+    assert lg is not None and BINS_HOMES + len(BINS_COUNTS) <= 64
+    vals = np.arange(1, 2_000_000, dtype=np.uint64)
+    keys = vals if width == 4 else widen(vals)
+    with np.errstate(over="ignore"):
+        slots = (keys * np.uint64(api.PAN_MULT)) >> np.uint64(64 - lg)
+    held = vals[((slots >> np.uint64(6)) == np.uint64(BINS_RUN)) & ((slots & np.uint64(63)) < np.uint64(BINS_HOMES))][:len(BINS_COUNTS)]
+    assert len(held) == len(BINS_COUNTS)
+    for v in held.tolist():
+        key = v if width == 4 else int(widen([v])[0])
+        assert api.pan_slot(key, lg) >> 6 == BINS_RUN and api.pan_slot(key, lg) & 63 < BINS_HOMES
+    return [_sk(v for v, f in zip(held.tolist(), BINS_COUNTS) if i < f) for i in range(BINS_MEMBERS)], [0] * BINS_MEMBERS

@@ -10,6 +10,7 @@ NONE = 0xFFFFFFFF
 # mirrors of rabbittclust_amd/csrc/rtc_quality.h (tests/test_cpu_quality.py holds them against api's and the header's)
 WAVE_ROW, WAVE_SLOTS, BLOCK_ROW, BLOCK_SLOTS, GLOBAL_LOG2_MIN = 128, 256, 1024, 2048, 6
 WAVE, WORKGROUP, GLOBAL = 1, 2, 4
+WGS_PER_CU = {WAVE: 32, WORKGROUP: 4, GLOBAL: 8}  # SIL_WAVE_ / SIL_BLOCK_ / SIL_GLOBAL_WGS_PER_CU: a path's grid, a row a workgroup and turn
 
 _CACHE = {}
 
@@ -184,6 +185,40 @@ def singletons(n=30):
     rng = np.random.default_rng(78)
     edges = [(u, v, int(rng.integers(0, ONE + 1))) for u in range(n) for v in range(u) if rng.random() < 0.3]
     return n, edges, np.arange(n, dtype=np.int64)
+
+
+def _circulant(n, reach, seed):
+    """Vertex x is listed with x + 1 .. x + reach (mod n), the orientation alternating: every row has 2 reach entries.  q takes
+    eight values, so sums and means tie; the labels are nine scattered ids, and every 41st vertex is unclustered.  The rows of a
+    path stand in vertex order, so with a grid of G workgroups, workgroup b meets the b-th, (b + G)-th, ... clustered vertex:
+    rows over the same nine clusters, one after the other in the same table."""
+    assert n > 2 * reach
+    rng = np.random.default_rng(seed)
+    ids = np.sort(rng.choice(n, size=9, replace=False))
+    labels = ids[rng.integers(0, 9, size=n)].astype(np.int64)
+    labels[40::41] = -1
+    q = ((rng.integers(0, 8, size=(n, reach)) + 1) * (ONE // 16)).tolist()
+    edges = []
+    for x in range(n):
+        for k in range(1, reach + 1):
+            y = (x + k) % n
+            edges.append((x, y, q[x][k - 1]) if (x + k) % 2 else (y, x, q[x][k - 1]))
+    return n, edges, labels
+
+
+def many_short_rows(num_cu):
+    """32 num_cu + 501 vertices with rows of 6 entries: more rows than the wave path's grid, and than the global path's under
+    RTC_SIL_GLOBAL=1"""
+    if ("short", num_cu) not in _CACHE:
+        _CACHE[("short", num_cu)] = _circulant(WGS_PER_CU[WAVE] * num_cu + 501, 3, 2400)
+    return _CACHE[("short", num_cu)]
+
+
+def many_long_rows(num_cu):
+    """4 num_cu + 77 vertices with rows of 130 entries, just past WAVE_ROW: more rows than the workgroup path's grid"""
+    if ("long", num_cu) not in _CACHE:
+        _CACHE[("long", num_cu)] = _circulant(WGS_PER_CU[WORKGROUP] * num_cu + 77, (WAVE_ROW + 2) // 2, 2401)
+    return _CACHE[("long", num_cu)]
 
 
 # ---- sketches for rtc_cluster_quality ----------------------------------------------------------------------------------------

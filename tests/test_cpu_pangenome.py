@@ -211,7 +211,7 @@ def test_path_boundaries_are_the_headers():
     text = open(os.path.join(ROOT, "rabbittclust_amd", "csrc", "rtc_pan.h")).read()
     got = {k: int(v, 0) for k, v in re.findall(r"(PAN_[A-Z0-9_]+) = (0x[0-9A-Fa-f]+|\d+)", text)}
     for name in ("PAN_WAVE_RECORDS", "PAN_WAVE_SLOTS", "PAN_WAVE_HIST", "PAN_BLOCK_RECORDS", "PAN_BLOCK_SLOTS", "PAN_BLOCK_HIST", "PAN_GLOBAL_LOG2_MIN",
-                 "PAN_GLOBAL_WGS_PER_CU", "PAN_SLOT_BYTES", "PAN_MEMBER_BYTES", "PAN_CLUSTER_BYTES", "PAN_MULT", "PAN_GROWTH_POINTS"):
+                 "PAN_GLOBAL_WGS_PER_CU", "PAN_WAVE_WGS_PER_CU", "PAN_BLOCK_WGS_PER_CU", "PAN_SWEEP_BINS", "PAN_SLOT_BYTES", "PAN_MEMBER_BYTES", "PAN_CLUSTER_BYTES", "PAN_MULT", "PAN_GROWTH_POINTS"):
         assert got[name] == getattr(api, name), name
     assert "PAN_EMPTY = ~0ull" in text and api.PAN_EMPTY == (1 << 64) - 1
     assert (api.PAN_PATH_WAVE, api.PAN_PATH_BLOCK, api.PAN_PATH_GLOBAL) == (1, 2, 4)

@@ -125,6 +125,8 @@ def test_path_boundaries_are_the_headers():
                        ("SIL_GLOBAL_LOG2_MIN", S.GLOBAL_LOG2_MIN)):
         assert got[name] == mine == getattr(api, name), name
     assert (api.SIL_PATH_WAVE, api.SIL_PATH_WORKGROUP, api.SIL_PATH_GLOBAL) == (S.WAVE, S.WORKGROUP, S.GLOBAL)
+    assert (got["SIL_WAVE_WGS_PER_CU"], got["SIL_BLOCK_WGS_PER_CU"], got["SIL_GLOBAL_WGS_PER_CU"]) == (S.WGS_PER_CU[S.WAVE], S.WGS_PER_CU[S.WORKGROUP],
+                                                                                                     S.WGS_PER_CU[S.GLOBAL])
     # no table is more than half full, and the LDS tables fit four workgroups a CU beside each other
     assert S.WAVE_SLOTS >= 2 * S.WAVE_ROW and S.BLOCK_SLOTS >= 2 * S.BLOCK_ROW and 4 * 16 * S.BLOCK_SLOTS <= 160 * 1024
     assert [S.table_log2(x) for x in (1, 128, 129, 1024, 1025, 2048, 2049)] == [8, 8, 11, 11, 12, 12, 13]
@@ -170,6 +172,76 @@ def test_sets_hold_their_cases():
     assert (int(rec[9]["a_den"]), int(rec[9]["far_q"]), int(rec[9]["near_q"]), int(rec[9]["near_cluster"])) == (0, 0, ONE // 8, 2)
     without = R.silhouette(n, [e for e in edges if 10 not in e[:2]], labels)
     assert without.tobytes() == rec.tobytes()  # the unclustered vertex's records change nothing
+
+
+def _row_tables(n, edges, labels):
+    """what the row kernel gathers of every clustered vertex with a row: (cluster -> [listed neighbours, sum of q], far, near)"""
+    rows = {}
+    for u, v, q in edges:
+        for x, y in ((u, v), (v, u)):
+            if labels[x] < 0:
+                continue
+            tab, far, near = rows.setdefault(x, ({}, 0, (ONE, NONE)))
+            if labels[y] < 0:
+                continue  # the entry stands in the row; its neighbour is a member of nothing
+            d = int(labels[y])
+            slot = tab.setdefault(d, [0, 0])
+            slot[0] += 1
+            slot[1] += q
+            rows[x] = (tab, max(far, q) if d == labels[x] else far, near if d == labels[x] else min(near, (q, d)))
+    return rows
+
+
+def _record_of(tab, far, near, c, size, clustered):
+    """sil_rule's sweep and finish over a gathered table, as (a_num, b_num, a_den, b_den, b_cluster, far_q, near_q, near_cluster)"""
+    n_c = int(size[c])
+    cnt_c, sum_c = tab.get(c, (0, 0))
+    best = None
+    for d, (cnt, total) in tab.items():
+        if d == c:
+            continue
+        n_d = int(size[d])
+        s_d = total + (n_d - cnt) * ONE
+        if best is None or s_d * best[1] < best[0] * n_d or (s_d * best[1] == best[0] * n_d and d < best[2]):
+            best = (s_d, n_d, d)
+    if best is None or not best[0] < best[1] * ONE:
+        best = (ONE, 1, NONE) if clustered > n_c else (0, 0, NONE)
+    return (sum_c + (n_c - 1 - cnt_c) * ONE, best[0], n_c - 1, best[1], best[2], ONE if cnt_c < n_c - 1 else far, near[0], near[1])
+
+
+@pytest.mark.parametrize("num_cu", [64, 256, 304])
+def test_the_row_grids_take_a_second_turn(num_cu):
+    """many_short_rows and many_long_rows (tests/test_gpu_quality.py runs them): more rows on a path than row_kernel's grid there
+    has workgroups, and a row gathered on top of the table of the row its workgroup scored a turn earlier gives another record"""
+    for build, all_global, path in ((S.many_short_rows, False, S.WAVE), (S.many_short_rows, True, S.GLOBAL), (S.many_long_rows, False, S.WORKGROUP)):
+        n, edges, labels = build(num_cu)
+        deg = _row_lengths(n, edges)
+        assert set(deg.tolist()) == ({6} if build is S.many_short_rows else {S.WAVE_ROW + 2})
+        assert len(set(q for _, _, q in edges)) == 8 and len(set(labels[labels >= 0].tolist())) == 9 and (labels < 0).sum() == n // 41
+        listed = [x for x in range(n) if labels[x] >= 0]  # the path's list: every clustered vertex has a row, all of one length
+        assert {S.path_of(int(deg[x]), all_global) for x in listed} == {path}
+        grid = min(len(listed), S.WGS_PER_CU[path] * num_cu)
+        assert grid == S.WGS_PER_CU[path] * num_cu < len(listed)
+        rows = _row_tables(n, edges, labels)
+        want = R.silhouette(n, edges, labels)
+        size = np.bincount(labels[labels >= 0], minlength=n)
+        clustered = int((labels >= 0).sum())
+        differ = 0
+        for i, x in enumerate(listed):
+            tab, far, near = rows[x]
+            clean = _record_of(tab, far, near, int(labels[x]), size, clustered)
+            assert clean == tuple(int(want[x][f]) for f in R.FIELDS), x  # the model with a cleared table is the restatement
+            if i < grid:
+                continue
+            stale = {d: list(v) for d, v in rows[listed[i - grid]][0].items()}
+            for d, (cnt, total) in tab.items():
+                slot = stale.setdefault(d, [0, 0])
+                slot[0] += cnt
+                slot[1] += total
+            differ += _record_of(stale, far, near, int(labels[x]), size, clustered) != clean
+        assert 10 * differ >= 9 * (len(listed) - grid), (differ, len(listed) - grid)
+    n, edges, labels = S.many_long_rows(num_cu)
+    assert (labels >= 0).sum() < S.WGS_PER_CU[S.GLOBAL] * num_cu  # under RTC_SIL_GLOBAL=1 the long rows stay within one turn
 
 
 def test_the_large_set_needs_128_bits():

@@ -1,6 +1,6 @@
 """clust-mst --quality on the GPU: rtc_silhouette record for record, all eight fields, against the restatement (tests/refquality.py)
 on the sets of tests/quality_sets.py -- rows at the path boundaries, tables whose probe chains wrap, the arithmetic's edges, means
-that need 128 bits -- with and without RTC_SIL_GLOBAL=1; rtc_cluster_quality against brute force over all pairs of sketches; and
+that need 128 bits, more rows than a path's grid has workgroups -- with and without RTC_SIL_GLOBAL=1; rtc_cluster_quality against brute force over all pairs of sketches; and
 the command line end to end."""
 import ctypes as C
 import functools
@@ -9,6 +9,7 @@ import math
 import os
 import struct
 import subprocess
+import time
 
 import numpy as np
 import pytest
@@ -98,6 +99,28 @@ def test_tables_with_shared_home_slots_and_wrapping_chains(ctx, switch, log2_slo
     n, edges, labels, want = _want("colliding_star", log2_slots)
     assert int(want[n - 1]["b_cluster"]) != NONE
     _run_both(ctx, switch, n, edges, labels, want, ("colliding_star", log2_slots))
+
+
+@pytest.mark.parametrize("name", ["many_short_rows", "many_long_rows"])
+def test_a_workgroup_scores_a_second_row(ctx, switch, name):
+    """more rows on a path than row_kernel's grid there has workgroups (tests/test_cpu_quality.py: a table, a count array or a wave
+    slot left from the turn before would show): short rows on the wave path and, under RTC_SIL_GLOBAL=1, the global one; rows of
+    130 entries on the workgroup path"""
+    num_cu = ctx.num_cu()
+    t0 = time.perf_counter()
+    n, edges, labels, want = _want(name, num_cu)
+    t1 = time.perf_counter()
+    _run_both(ctx, switch, n, edges, labels, want, name)
+    t2 = time.perf_counter()
+    rows = _expected_rows(n, edges, labels, False)  # _run_both held the counters of both calls to these
+    assert ctx.silhouette_counters()["global_rows"] == sum(rows.values())  # the last call: every row on the global path
+    print("%s: n %d, %d records, rows %s, all on the global path %d; set and restatement %.2f s, both GPU calls with their checks %.3f s"
+          % (name, n, len(edges), rows, sum(rows.values()), t1 - t0, t2 - t1))
+    if name == "many_short_rows":
+        assert rows[S.WAVE] > S.WGS_PER_CU[S.WAVE] * num_cu and rows[S.WORKGROUP] == rows[S.GLOBAL] == 0
+        assert rows[S.WAVE] > S.WGS_PER_CU[S.GLOBAL] * num_cu  # the rows of the global path under RTC_SIL_GLOBAL=1
+    else:
+        assert rows[S.WORKGROUP] > S.WGS_PER_CU[S.WORKGROUP] * num_cu and rows[S.WAVE] == rows[S.GLOBAL] == 0
 
 
 @pytest.mark.parametrize("name", ["arithmetic", "one_cluster", "singletons"])
